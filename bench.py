@@ -5,6 +5,12 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
            --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --cpu-only                      # BASELINE config 1: ViT-Tiny raster, batch 32, host cores only
+    python bench.py --full                          # + per-kernel roofline figures, CPU baseline, RCCL figures
+    python bench.py --dump-outputs DIR              # + loss, parameters and gradients of the last timed step as .npy
+
+A plain run sets up, warms up, times the steps and prints the line; everything else it can measure (HIP-event timing of
+the kernels and the roofline figures built on it, the CPU baseline, the RCCL exposed-time and bandwidth figures) runs only
+with --full.
 
 Default workload (BASELINE.json configs[2] / [3]): ViT-B/16 at 224x224, Hilbert pixel order
 (HilbertEmbedding1D(224, 256, 3, 768) + VisionTransformer1D(depth 12, heads 12, mlp 3072,
@@ -13,7 +19,7 @@ Default workload (BASELINE.json configs[2] / [3]): ViT-B/16 at 224x224, Hilbert 
 forward -> soft-target CE -> backward -> (gradient all-reduce) -> clip 1.0 -> AdamW.
 Prints ONE JSON line on rank 0 (contract in the task statement).
 
-What the line's roofline numbers are, so that they can be recomputed from profiles/ alone:
+What the line's roofline numbers are (--full), so that they can be recomputed from profiles/ alone:
   * `roofline`      the dominant kernel FAMILY of the step: all instantiations of the persistent 8-phase GEMM
                     `gemm8p_kernel<NI, MASK, P2>` (every forward and dX GEMM).  achieved = sum of 2MNK over the family's
                     launches in the timed region / sum of their HIP-event durations (events on the launching stream);
@@ -25,7 +31,7 @@ What the line's roofline numbers are, so that they can be recomputed from profil
                     bytes/s of 8 TB/s -- at N = 196, hd = 64 attention is below the ridge, i.e. HBM-bound), the fused
                     gather + patch-embed kernels (both bounds) and the whole step.
   * `cpu_baseline`  the oracle's fp32 PyTorch-CPU restatement of the reference path timed on the host cores
-                    (rank 0 at N = 1 only): BASELINE.md §3 -- 1 warm-up + 3 timed steps, all cores of the box's share.
+                    (--full, rank 0 at N = 1 only): BASELINE.md §3 -- 1 warm-up + 3 timed steps, all cores of the box's share.
 """
 import argparse
 import json
@@ -167,6 +173,38 @@ def frac_entry(rec, bound_flops=True, bytes_per_launch=None):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, model):
+    """What a caller of the timed step receives after its last step: the loss, and every parameter and its gradient
+    (float32).  A tensor larger than the per-tensor cap contributes a fixed sample: seeded random positions, sorted, so
+    that two builds run with the same arguments write the same positions.  The cap is the largest power of two that keeps
+    the whole dump within DUMP_BYTES."""
+    import numpy as np
+    named = list(model.named_parameters())
+    tensors = [p for _, p in named] + [p.grad for _, p in named if p.grad is not None]
+    cap = 1 << 20
+    while 132 + sum(128 + 4 * min(t.numel(), cap) for t in tensors) > DUMP_BYTES:     # 128 B: an .npy header
+        cap //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    positions = {}
+    for name, p in named:
+        idx = None
+        if p.numel() > cap:
+            if p.numel() not in positions:
+                g = torch.Generator().manual_seed(1234)
+                positions[p.numel()] = torch.randperm(p.numel(), generator=g)[:cap].sort().values.to(p.device)
+            idx = positions[p.numel()]
+        for kind, t in (("param", p), ("grad", p.grad)):
+            if t is None:
+                continue
+            flat = t.detach().reshape(-1)
+            flat = flat if idx is None else flat[idx]
+            np.save(os.path.join(out_dir, f"{kind}.{name}.npy"), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -188,6 +226,12 @@ def main():
     ap.add_argument("--cpu-batch", type=int, default=0, help="CPU-baseline batch (default: BASELINE.md §3's per workload)")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--graph", action="store_true", help="replay the whole training step from one hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: HIP-event kernel timing and the roofline "
+                         "figures, the CPU baseline (N = 1), the RCCL exposed-time and bandwidth figures (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the loss, parameters and gradients of the last step to DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of the larger tensors, %d MB at most)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
     # Deadline: a run still going after this many seconds dumps every thread's Python stack to stderr and exits with
     # code 1 instead of holding the GPU lease (SFCVIT_BENCH_WATCHDOG; default for multi-rank runs: 900 s; 0 = off).
@@ -261,10 +305,10 @@ def main():
 
     for _ in range(args.warmup):
         loss = step()
-    timing = rank == 0 and not args.no_kernel_timing and not args.graph
+    timing = args.full and rank == 0 and not args.no_kernel_timing and not args.graph
     if timing:
         ops.TIMER = ops.KernelTimer(None if args.time_all_kernels else ("gemm ", "attn", "pe_", "tokens_gather"))
-    if reducer is not None:
+    if reducer is not None and args.full:
         reducer.reset_stats()
     sync()
     t0 = time.perf_counter()
@@ -284,7 +328,9 @@ def main():
     if not (loss_v == loss_v):
         raise SystemExit("loss is NaN")
 
-    rccl_stats = reducer.stats(args.steps) if reducer is not None else None     # collective calls inside: every rank
+    rccl_stats = reducer.stats(args.steps) if reducer is not None and args.full else None   # collective calls inside: every rank
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, model)
     if rank == 0:
         ms = dt / args.steps * 1e3
         value = world * batch * args.steps / dt
@@ -304,7 +350,7 @@ def main():
             "step_mfma_frac": round(value / world * flops_img / 1e12 / PEAK_BF16_TFLOPS, 4),
             "final_loss": round(loss_v, 4),
         }
-        if world > 1:
+        if rccl_stats is not None:
             out["rccl"] = dict(rccl_stats, backend=backend, world_size=dist.get_world_size())
         if kern:
             tsteps = len(range(0, args.steps, max(1, args.time_every)))     # steps whose launches carried event pairs
@@ -377,7 +423,7 @@ def main():
             out["kernel_timing"] = (f"HIP events around every launch of the GEMMs / attention / patch embed in {tsteps} of the "
                                     f"{args.steps} timed steps")
             out["gemm_ms_per_step"] = round(all_g["ms_total"] / tsteps, 3)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_batch or cbatch, args.cpu_steps)
         print(json.dumps(out), flush=True)
     if world > 1:
