@@ -211,7 +211,15 @@ typedef struct sfcvit_gemm_args {
                               both operands are k-contiguous and the shape sits on its tile grid, else the LDS-DMA
                               ring kernel, else the generic 128 x 128 kernel); 1 = generic only; 4 / 6 / 7 = ring
                               kernel (heuristic / 256 x 128 / 256 x 256); 8 / 9 / 10 = persistent kernel with
-                              256- / 224- / 192-row tiles (EINVAL when not eligible) */
+                              256- / 224- / 192-row tiles (EINVAL when not eligible); SFCVIT_GEMM_* below */
+#define SFCVIT_GEMM_AUTO 0
+#define SFCVIT_GEMM_GENERIC 1
+#define SFCVIT_GEMM_RING 4
+#define SFCVIT_GEMM_RING_256x128 6
+#define SFCVIT_GEMM_RING_256x256 7
+#define SFCVIT_GEMM_P8_256 8
+#define SFCVIT_GEMM_P8_224 9
+#define SFCVIT_GEMM_P8_192 10
     float dropout_p;       /* > 0: after act, before residual: v = keep(m, n) ? v / (1 - p) : 0 (nn.Dropout, training) */
     uint32_t dropout_seed;
     float dact_scale;      /* multiplies v together with dact (0 = 1): 1/(1-p) of a dropout that followed the ReLU */

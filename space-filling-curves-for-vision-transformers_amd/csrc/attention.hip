@@ -17,7 +17,6 @@
 //       dV^T += dO^T P, dK^T += Q^T dS   A: tr-reads of dO / Q   B: P / dS accumulators
 //   backward, dQ kernel    (wave = 16 queries, loop over 64-key blocks in LDS)
 //       S^T = K Q^T, dP^T = V dO^T ; dQ^T += K^T dS^T  (A: tr-read of K, B: dS^T)
-#include <cstdlib>
 #include "attention_common.h"
 #include "common_host.h"
 
@@ -299,48 +298,35 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_q_kernel(const sfcvit_attn_a
     store_rows(dbase, ld, q, q < N, dq, 1.f, lane);
 }
 
-int check_args(const sfcvit_attn_args *a, const char *what, bool bwd) {
-    if (!a || !a->qkv || !a->out || !a->lse) return fail(SFCVIT_EINVAL, "%s: null pointer", what);
-    if (bwd && (!a->dout || !a->dqkv || !a->delta)) return fail(SFCVIT_EINVAL, "%s: null pointer", what);
-    if (a->hd != 64 && a->hd != 128 && a->hd != 192 && a->hd != 256)
-        return fail(SFCVIT_EINVAL, "%s: head dim %d not supported (64, 128, 192, 256)", what, a->hd);
-    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return fail(SFCVIT_EINVAL, "%s: dropout_p=%g out of [0, 1)", what, a->dropout_p);
-    if (a->B <= 0 || a->N <= 0 || a->H <= 0 || a->B > 65535 || a->H > 65535)
-        return fail(SFCVIT_EINVAL, "%s: B=%d N=%d H=%d", what, a->B, a->N, a->H);
-    if (!aligned16(a->qkv) || !aligned16(a->out) || (bwd && (!aligned16(a->dout) || !aligned16(a->dqkv))))
-        return fail(SFCVIT_EINVAL, "%s: tensors must be 16-byte aligned", what);
-    return SFCVIT_OK;
-}
-
 }  // namespace
 
-// attention_seq.hip: whole-sequence kernels; return -1 when N is too long for them.
-int attn_seq_fwd(const sfcvit_attn_args &a, hipStream_t s);
-int attn_seq_bwd(const sfcvit_attn_args &a, hipStream_t s);
-// attention_bwd_fused.hip: dK, dV and dQ in one pass (head dim 64, N <= 224); -1 when not eligible.
-int attn_seq_bwd_fused(const sfcvit_attn_args &a, int dq_sums, hipStream_t s);
-// attention_wide.hip: head dims 128 / 192 / 256; return -1 for head dim 64.
-int attn_wide_fwd(const sfcvit_attn_args &a, hipStream_t s);
-int attn_wide_bwd(const sfcvit_attn_args &a, hipStream_t s);
-// attention_long.hip: forward with K / V of the whole sequence resident, head dim 64, 256 < N <= 608; -1 otherwise.
-int attn_long_fwd(const sfcvit_attn_args &a, hipStream_t s);
-int attn_long_bwd(const sfcvit_attn_args &a, hipStream_t s);
+// The plan's launchers (dispatch.cpp): attention_seq.hip, attention_bwd_fused.hip, attention_wide.hip, attention_long.hip.
+int attn_seq_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
+int attn_seq_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
+int attn_seq_bwd_fused(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
+int attn_wide_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
+int attn_wide_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
+int attn_long_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
+int attn_long_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
 
 }  // namespace sfcvit
 
 using namespace sfcvit;
 
 extern "C" int sfcvit_attention_fwd(const sfcvit_attn_args *a, void *stream) {
-    if (int rc = check_args(a, "attention_fwd", false)) return rc;
-    if (int rc = attn_wide_fwd(*a, static_cast<hipStream_t>(stream)); rc >= 0) return rc;
-    if (int rc = attn_seq_fwd(*a, static_cast<hipStream_t>(stream)); rc >= 0) return rc;
-    const char *el = getenv("SFCVIT_ATTN_LONG");             // "0": tiled kernel for every N > 256 (A/B, tests); read per call
-    if (!(el && el[0] == '0'))
-        if (int rc = attn_long_fwd(*a, static_cast<hipStream_t>(stream)); rc >= 0) return rc;
-    dim3 grid((a->N + BLK - 1) / BLK, a->H, a->B);
-    note_attn_kernel("attn_fwd_kernel");
-    hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(THREADS), 0, static_cast<hipStream_t>(stream), *a);
-    return check_launch("attention_fwd");
+    if (!a) return fail(SFCVIT_EINVAL, "attention_fwd: null pointer");
+    const AttnPlan p = attn_fwd_plan(*a, read_knobs(KNOBS_ATTN_FWD));
+    if (p.err) return fail(p.err, "%s", p.msg);
+    note_attn_kernel(p);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (p.family) {
+    case AttnFamily::WIDE: return attn_wide_fwd(p, *a, s);
+    case AttnFamily::SEQ: return attn_seq_fwd(p, *a, s);
+    case AttnFamily::LONG: return attn_long_fwd(p, *a, s);
+    default:
+        hipLaunchKernelGGL(attn_fwd_kernel, dim3(p.grid, a->H, a->B), dim3(THREADS), 0, s, *a);
+        return check_launch("attention_fwd");
+    }
 }
 
 extern "C" int64_t sfcvit_attention_colsum_workspace(int B, int N, int H, int hd) {
@@ -353,63 +339,51 @@ extern "C" int64_t sfcvit_attention_colsum_workspace(int B, int N, int H, int hd
 }
 
 extern "C" int sfcvit_attention_bwd(const sfcvit_attn_args *a, void *stream) {
-    if (int rc = check_args(a, "attention_bwd", true)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int D3 = 3 * a->H * a->hd;
+    if (!a) return fail(SFCVIT_EINVAL, "attention_bwd: null pointer");
+    const AttnPlan p = attn_bwd_plan(*a, device_cu_count(), read_knobs(KNOBS_ATTN_BWD));
+    if (p.err) return fail(p.err, "%s", p.msg);
     if (a->colsum_out && (!a->colsum_part || a->colsum_part_bytes < sfcvit_attention_colsum_workspace(a->B, a->N, a->H, a->hd)))
         return fail(SFCVIT_EINVAL, "attention_bwd: colsum_out needs colsum_part of sfcvit_attention_colsum_workspace bytes");
-    {   // one pass: dK, dV, dQ, delta and the column sums from a single evaluation of P and dS (hd = 64, N <= 224)
-        const char *env = getenv("SFCVIT_ATTN_BWD_FUSED");       // "0": the two-kernel form (A/B measurements, tests)
-        if (!(env && env[0] == '0')) {
-            sfcvit_attn_args f = *a;
-            if (!a->colsum_out) f.colsum_part = nullptr;
-            // The column sums of dK and dV leave the kernel as 128 floats per item (its key waves hold whole columns).  Those of
-            // dQ come from the key waves as well since round 4: sum_q dQ[q, :] = scale sum_k (sum_q dS[q, k]) K[k, :], one add
-            // per score in the loop and a 16 x 64 product per wave after it.  (Round 3 took them from the two dQ waves -- per-chunk
-            // lane reductions + LDS read-modify-writes on the waves a step waits for, +37 us per launch -- and therefore
-            // defaulted to a separate 16-us pass over the Q third of dqkv, which SFCVIT_ATTN_DQSUM=pass still selects: A/B.)
-            const char *dq = getenv("SFCVIT_ATTN_DQSUM");
-            const int dq_in_kernel = !(dq && dq[0] == 'p');
-            if (int rc = attn_seq_bwd_fused(f, dq_in_kernel, s); rc >= 0) {
-                if (rc || !a->colsum_out) return rc;
-                if (dq_in_kernel) return launch_colsum_reduce(a->colsum_part, a->B, D3, a->colsum_out, a->colsum_bf16, stream);
-                // K | V thirds from the kernel's partial rows, the Q third (columns 0 .. D-1 of dqkv) from its own pass; disjoint
-                // outputs and disjoint partial regions, so the two reductions may run in one deferred batch
-                const int Dq = a->H * a->hd;
-                char *outp = static_cast<char *>(a->colsum_out);
-                if (int rc2 = reduce_cols(a->colsum_part + Dq, a->B, D3, D3 - Dq, outp + size_t(Dq) * (a->colsum_bf16 ? 2 : 4), a->colsum_bf16, stream))
-                    return rc2;
-                const int64_t head = int64_t(a->B) * D3 * int64_t(sizeof(float));
-                return sfcvit_colsum(a->dqkv, a->B * a->N, Dq, D3, a->colsum_out, a->colsum_bf16, a->colsum_part + size_t(a->B) * D3,
-                                     a->colsum_part_bytes - head, stream);
-            }
-        }
+    note_attn_kernel(p);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    sfcvit_attn_args f = *a;
+    if (!a->colsum_out) f.colsum_part = nullptr;        // the kernels that write partial rows take a null colsum_part as "none"
+    int rc = SFCVIT_OK;
+    if (p.family != AttnFamily::FUSED && p.family != AttnFamily::LONG) {   // these compute delta themselves
+        const int64_t groups = int64_t(a->B) * a->N * a->H;
+        hipLaunchKernelGGL(attn_delta_kernel, dim3(unsigned((groups * 8 + THREADS - 1) / THREADS)), dim3(THREADS), 0, s,
+                           static_cast<const uint16_t *>(a->dout), static_cast<const uint16_t *>(a->out), a->delta, a->B, a->N, a->H, a->hd);
+        if ((rc = check_launch("attention_bwd delta"))) return rc;
     }
-    {   // sequence-resident kernels (hd = 64, 256 < N <= 608): delta comes out of their dQ kernel, the column sums too
-        const char *el = getenv("SFCVIT_ATTN_LONG");         // "0": tiled kernels for every N > 256 (A/B, tests)
-        if (!(el && el[0] == '0')) {
-            sfcvit_attn_args f = *a;
-            if (!a->colsum_out) f.colsum_part = nullptr;
-            if (int rc = attn_long_bwd(f, s); rc >= 0) {
-                if (rc || !a->colsum_out) return rc;
-                return launch_colsum_reduce(a->colsum_part, a->B, D3, a->colsum_out, a->colsum_bf16, stream);
-            }
-        }
+    switch (p.family) {
+    case AttnFamily::FUSED: rc = attn_seq_bwd_fused(p, f, s); break;
+    case AttnFamily::LONG: rc = attn_long_bwd(p, f, s); break;
+    case AttnFamily::WIDE: rc = attn_wide_bwd(p, *a, s); break;
+    case AttnFamily::SEQ: rc = attn_seq_bwd(p, *a, s); break;
+    case AttnFamily::TILED: {
+        const dim3 grid(p.grid, a->H, a->B);
+        hipLaunchKernelGGL(attn_bwd_kv_kernel, grid, dim3(THREADS), 0, s, *a);
+        if ((rc = check_launch("attention_bwd kv"))) break;
+        hipLaunchKernelGGL(attn_bwd_q_kernel, grid, dim3(THREADS), 0, s, *a);
+        rc = check_launch("attention_bwd q");
+        break;
     }
-    const int rc_rest = [&]() -> int {
-    const int64_t groups = int64_t(a->B) * a->N * a->H;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3(unsigned((groups * 8 + THREADS - 1) / THREADS)), dim3(THREADS), 0, s,
-                       static_cast<const uint16_t *>(a->dout), static_cast<const uint16_t *>(a->out), a->delta, a->B, a->N, a->H, a->hd);
-    if (int rc = check_launch("attention_bwd delta")) return rc;
-    if (int rc = attn_wide_bwd(*a, s); rc >= 0) return rc;
-    if (int rc = attn_seq_bwd(*a, s); rc >= 0) return rc;
-    dim3 grid((a->N + BLK - 1) / BLK, a->H, a->B);
-    note_attn_kernel("attn_bwd_kv_kernel");
-    hipLaunchKernelGGL(attn_bwd_kv_kernel, grid, dim3(THREADS), 0, s, *a);
-    if (int rc = check_launch("attention_bwd kv")) return rc;
-    hipLaunchKernelGGL(attn_bwd_q_kernel, grid, dim3(THREADS), 0, s, *a);
-    return check_launch("attention_bwd q");
-    }();
-    if (rc_rest || !a->colsum_out) return rc_rest;
-    return sfcvit_colsum(a->dqkv, a->B * a->N, D3, D3, a->colsum_out, a->colsum_bf16, a->colsum_part, a->colsum_part_bytes, stream);
+    }
+    if (rc) return rc;
+    const int D3 = 3 * a->H * a->hd, Dq = a->H * a->hd;
+    switch (p.colsum) {
+    case Colsum::NONE: return SFCVIT_OK;
+    case Colsum::PARTIALS: return launch_colsum_reduce(a->colsum_part, a->B, D3, a->colsum_out, a->colsum_bf16, stream);
+    case Colsum::PASS:
+        return sfcvit_colsum(a->dqkv, a->B * a->N, D3, D3, a->colsum_out, a->colsum_bf16, a->colsum_part, a->colsum_part_bytes, stream);
+    case Colsum::PARTIALS_QPASS: break;
+    }
+    // K | V thirds from the kernel's partial rows, the Q third (columns 0 .. D-1 of dqkv) from its own pass; disjoint outputs
+    // and disjoint partial regions, so the two reductions may run in one deferred batch
+    char *outp = static_cast<char *>(a->colsum_out);
+    if ((rc = reduce_cols(a->colsum_part + Dq, a->B, D3, D3 - Dq, outp + size_t(Dq) * (a->colsum_bf16 ? 2 : 4), a->colsum_bf16, stream)))
+        return rc;
+    const int64_t head = int64_t(a->B) * D3 * int64_t(sizeof(float));
+    return sfcvit_colsum(a->dqkv, a->B * a->N, Dq, D3, a->colsum_out, a->colsum_bf16, a->colsum_part + size_t(a->B) * D3,
+                         a->colsum_part_bytes - head, stream);
 }

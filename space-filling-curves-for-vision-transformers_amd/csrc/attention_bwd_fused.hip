@@ -33,7 +33,6 @@
 //   * rows >= N: the DMA fills them with copies of row N - 1 (finite); padded queries get lse = +inf (P = dS = 0), padded
 //     keys get dS = 0 before the exchange and their dK / dV rows are not stored; exchange rows of keys >= 16 nf are
 //     zeroed once.
-#include <algorithm>
 #include "attention_common.h"
 #include "common_host.h"
 
@@ -43,10 +42,7 @@ namespace {
 using namespace attn;
 
 constexpr int FT = 1024, FWAVES = 16, FMAXC = 7;   // threads, waves, 32-row chunks (N <= 224)
-constexpr int FUSED_ROW_BYTES = 4 * 128 + 2 * 64 + 6 * 4;    // LDS bytes per padded sequence row: Q, dO, two K images; dS exchange x 2; two sets of lse / delta / row key
-constexpr int FUSED_CS_BYTES = 16 * 128 * 4;                   // column-sum staging [FWAVES][dK | dV][64] floats
-constexpr int FUSED_POST_BYTES = 8192;                       // own scratch: the [32][64] partial dK / dV of a shared fragment (+ as much again for short sequences, whose K image is too small for the column-sum staging)
-constexpr int FUSED_EXTRA = 256 + 64 + 14 * 64 * 4;          // (256 spare) + two item records (3 pointers each, 8-byte slots) + the key waves' shares of the dQ column sums [14][64]
+static_assert(FUSED_MAX_N == 32 * FMAXC, "dispatch.h");   // FUSED_*: the LDS layout (dispatch.h)
 
 // tools/attn_isa_budget.py compiles this file with -DSFCVIT_ISA_MARKERS and buckets the instructions between the marks
 #ifdef SFCVIT_ISA_MARKERS
@@ -537,48 +533,23 @@ __global__ __launch_bounds__(FT) void attn_seq_bwd_fused_kernel(const sfcvit_att
     }
 }
 
-constexpr int FUSED_MAX_N = 32 * FMAXC;
-constexpr int FUSED_MAX_LDS = FUSED_MAX_N * FUSED_ROW_BYTES + FUSED_EXTRA + FUSED_POST_BYTES;
-
 template <int NFC, bool DROP>
-int launch_fused(const sfcvit_attn_args &a, int npad, size_t lds, int grid, int round, int per, int ticks, int dq_sums, hipStream_t s) {
-    static const int nt = [] { const char *e = getenv("SFCVIT_ATTN_NT"); return e ? atoi(e) : 0; }();
-    static const int fixed = [] { const char *e = getenv("SFCVIT_ATTN_BWD_QUEUE"); return e && e[0] == '0'; }();     // "0": fixed stride (A/B)
-    unsigned *qcnt = nullptr;
-    if (!fixed && grid < a.B * a.H) {
-        unsigned *slot = stream_counters(s);
-        if (slot) qcnt = slot + 12;
-    }
+int launch(const AttnPlan &p, const sfcvit_attn_args &a, unsigned *qcnt, hipStream_t s) {
     if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&attn_seq_bwd_fused_kernel<NFC, DROP>), FUSED_MAX_LDS, "attention_bwd_fused attribute")) return rc;
-    hipLaunchKernelGGL((attn_seq_bwd_fused_kernel<NFC, DROP>), dim3(grid), dim3(FT), lds, s, a, npad, round, per, ticks, dq_sums, a.B * a.H, nt & 1, qcnt);
+    hipLaunchKernelGGL((attn_seq_bwd_fused_kernel<NFC, DROP>), dim3(p.grid), dim3(FT), p.lds, s, a, p.npad, p.round, p.per, p.ticks, p.dq_sums,
+                       a.B * a.H, p.nt, qcnt);
     return check_launch("attention_bwd_fused");
 }
 
 }  // namespace
 
-// -1: not eligible (the caller falls back to the two-kernel form); else a status.
-int attn_seq_bwd_fused(const sfcvit_attn_args &a, int dq_sums, hipStream_t s) {
-    if (a.hd != HD || a.N > FUSED_MAX_N) return -1;
-    const int npad = (a.N + 31) / 32 * 32;
-    const bool nf13 = (a.N + 15) / 16 == 13, drop = a.dropout_p > 0.f;
-    const size_t lds = size_t(npad) * FUSED_ROW_BYTES + FUSED_EXTRA + FUSED_POST_BYTES + (npad * 128 >= FUSED_CS_BYTES ? 0 : FUSED_CS_BYTES);
-    // One workgroup per CU walking the (batch, head) items with the next one staged behind the current (kernel header);
-    // SFCVIT_ATTN_BWD_PERSIST=0: one workgroup per item, i.e. the kernel of rounds 2-3 (A/B).
-    const int items = a.B * a.H, cus = device_cu_count();
-    const char *pe = getenv("SFCVIT_ATTN_BWD_PERSIST");
-    const int grid = (cus > 0 && !(pe && pe[0] == '0')) ? std::min(items, cus) : items;
-    // Start-up stagger (attention_common.h): every workgroup opens with a 117 KiB load burst and they all take the same time,
-    // so launched together they stay in lockstep.  Two slots 4.5 us apart: 270.8 -> 257.1 us at ViT-B / 256 with one workgroup
-    // per item (3 or 4 slots, 2-8 us: 255.6-258.6).  SFCVIT_ATTN_STAGGER_BWD = "slots,ticks" (10 ns) overrides; "1,0" = off.
-    // The persistent form (round 4) pays the burst once per 12 items and its workgroups drift apart on their own: the stagger
-    // costs it 5 us (227.6 vs 222.7 us, profiles/r4/attention_bench_r4.txt), so it is on for one-workgroup-per-item launches only.
-    int slots = grid < items ? 1 : 2, ticks = 450;
-    if (const char *e = getenv("SFCVIT_ATTN_STAGGER_BWD")) sscanf(e, "%d,%d", &slots, &ticks);
-    if (slots < 1) slots = 1;
-    const int round = 256, per = (round + slots - 1) / slots;
-    note_attn_kernel("attn_seq_bwd_fused_kernel<%d, %s>", nf13 ? 13 : 0, drop ? "true" : "false");
-    if (nf13) return drop ? launch_fused<13, true>(a, npad, lds, grid, round, per, ticks, dq_sums, s) : launch_fused<13, false>(a, npad, lds, grid, round, per, ticks, dq_sums, s);
-    return drop ? launch_fused<0, true>(a, npad, lds, grid, round, per, ticks, dq_sums, s) : launch_fused<0, false>(a, npad, lds, grid, round, per, ticks, dq_sums, s);
+// The plan's one-pass backward (dispatch.cpp attn_bwd_plan): one workgroup per CU walking the (batch, head) items with the
+// next one staged behind the current (kernel header), items dealt from the stream's counters when p.queue.
+int attn_seq_bwd_fused(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s) {
+    unsigned *slot = p.queue ? stream_counters(s) : nullptr;
+    unsigned *qcnt = slot ? slot + 12 : nullptr;
+    if (p.inst == 13) return p.drop ? launch<13, true>(p, a, qcnt, s) : launch<13, false>(p, a, qcnt, s);
+    return p.drop ? launch<0, true>(p, a, qcnt, s) : launch<0, false>(p, a, qcnt, s);
 }
 
 #ifdef SFCVIT_ATTN_TRACE

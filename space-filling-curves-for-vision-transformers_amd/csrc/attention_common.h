@@ -3,13 +3,14 @@
 #pragma once
 #include "../../include/sfcvit.h"
 #include "device_common.h"
+#include "dispatch.h"
 
 namespace sfcvit {
 namespace attn {
 
-constexpr int HD = 64;
+constexpr int HD = ATTN_HD;
 constexpr int THREADS = 256;
-constexpr int BLK = 64;                 // rows (keys or queries) per LDS block
+constexpr int BLK = ATTN_BLK;           // rows (keys or queries) per LDS block
 constexpr int IMG_BYTES = BLK * HD * 2;  // 8 KiB
 
 // [64 rows][64 cols] bf16 image for transposed reads only: 32-B chunk ^ ((row >> 1) & 3).

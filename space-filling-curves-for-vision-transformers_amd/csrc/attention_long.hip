@@ -21,7 +21,6 @@ using namespace attn;
 
 constexpr int LT = 768, LW = LT / 64;   // 12 waves
 constexpr int CKF = 12;                 // key fragments per softmax chunk
-constexpr int LONG_MAX_N = 608;         // 2 images x 608 rows x 128 B = 152 KiB
 
 typedef const __attribute__((address_space(1))) void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
@@ -376,33 +375,24 @@ __global__ __launch_bounds__(LT) void attn_long_bwd_q_kernel(const sfcvit_attn_a
     if (a.colsum_part) wg_colsum(csq, smem, a.colsum_part + size_t(b) * 3 * D + h * HD, tid);
 }
 
-constexpr int LONG_MAX_LDS = 2 * ((LONG_MAX_N + 31) / 32 * 32) * 128 + 3 * ((LONG_MAX_N + 31) / 32 * 32) * 4;
-
 }  // namespace
 
-// -1: not eligible; else a status.  a.delta is written here (dQ kernel) and read by the dK/dV kernel.
-int attn_long_bwd(const sfcvit_attn_args &a, hipStream_t s) {
-    if (a.hd != HD || a.N <= 256 || a.N > LONG_MAX_N) return -1;
-    const int npad = (a.N + 31) / 32 * 32;
+// The plan's sequence-resident kernels (dispatch.cpp, head dim 64, 256 < N <= 608).  Backward: the dQ kernel writes a.delta,
+// the dK / dV kernel reads it.
+int attn_long_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s) {
     for (const void *k : {reinterpret_cast<const void *>(&attn_long_bwd_kv_kernel), reinterpret_cast<const void *>(&attn_long_bwd_q_kernel)})
         if (int rc = raise_lds_limit(k, LONG_MAX_LDS, "attention_long attribute")) return rc;
-    note_attn_kernel("attn_long_bwd_kv_kernel");
-    hipLaunchKernelGGL(attn_long_bwd_q_kernel, dim3(a.H, a.B), dim3(LT), size_t(2 * npad * 128), s, a, npad);
+    hipLaunchKernelGGL(attn_long_bwd_q_kernel, dim3(a.H, a.B), dim3(LT), p.lds, s, a, p.npad);
     if (int rc = check_launch("attention_long_bwd q")) return rc;
-    hipLaunchKernelGGL(attn_long_bwd_kv_kernel, dim3(a.H, a.B), dim3(LT), size_t(2 * npad * 128 + 3 * npad * 4), s, a, npad);
+    hipLaunchKernelGGL(attn_long_bwd_kv_kernel, dim3(a.H, a.B), dim3(LT), p.lds2, s, a, p.npad);
     return check_launch("attention_long_bwd kv");
 }
 
-// -1: not eligible (the caller takes the tiled kernel); else a status.
-int attn_long_fwd(const sfcvit_attn_args &a, hipStream_t s) {
-    if (a.hd != HD || a.N <= 256 || a.N > LONG_MAX_N) return -1;
-    const int npad = (a.N + 31) / 32 * 32;
-    const int lds = 2 * npad * 128;
+int attn_long_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s) {
     for (const void *k : {reinterpret_cast<const void *>(&attn_long_fwd_kernel<0>), reinterpret_cast<const void *>(&attn_long_fwd_kernel<36>)})
-        if (int rc = raise_lds_limit(k, 2 * ((LONG_MAX_N + 31) / 32 * 32) * 128, "attention_long attribute")) return rc;
-    note_attn_kernel("attn_long_fwd_kernel<%d>", npad == 576 ? 36 : 0);
-    if (npad == 576) hipLaunchKernelGGL(attn_long_fwd_kernel<36>, dim3(a.H, a.B), dim3(LT), lds, s, a, npad);
-    else hipLaunchKernelGGL(attn_long_fwd_kernel<0>, dim3(a.H, a.B), dim3(LT), lds, s, a, npad);
+        if (int rc = raise_lds_limit(k, 2 * LONG_NPAD_MAX * 128, "attention_long attribute")) return rc;
+    if (p.inst == 36) hipLaunchKernelGGL(attn_long_fwd_kernel<36>, dim3(a.H, a.B), dim3(LT), p.lds, s, a, p.npad);
+    else hipLaunchKernelGGL(attn_long_fwd_kernel<0>, dim3(a.H, a.B), dim3(LT), p.lds, s, a, p.npad);
     return check_launch("attention_long_fwd");
 }
 

@@ -335,9 +335,6 @@ __global__ __launch_bounds__(THREADS, 3) void attn_seq_bwd_q_kernel(const sfcvit
     }
 }
 
-constexpr int SEQ_MAX_N = 256;
-constexpr int SEQ_MAX_LDS = 2 * SEQ_MAX_N * 128 + 3 * SEQ_MAX_N * 4;
-
 int set_lds_limit() {
     for (const void *k : {reinterpret_cast<const void *>(&attn_seq_fwd_kernel<0, false>), reinterpret_cast<const void *>(&attn_seq_fwd_kernel<0, true>),
                           reinterpret_cast<const void *>(&attn_seq_fwd_kernel<13, false>), reinterpret_cast<const void *>(&attn_seq_fwd_kernel<13, true>),
@@ -349,34 +346,25 @@ int set_lds_limit() {
 
 }  // namespace
 
-int attn_seq_fwd(const sfcvit_attn_args &a, hipStream_t s) {
-    if (a.N > SEQ_MAX_N) return -1;
+// The plan's whole-sequence kernels (dispatch.cpp): forward, or the backward's dK / dV kernel then its dQ kernel.
+int attn_seq_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s) {
     if (int rc = set_lds_limit()) return rc;
-    const int npad = (a.N + 15) / 16 * 16;
-    const int nf = (a.N + 15) / 16;
-    const bool drop = a.dropout_p > 0.f;
-    note_attn_kernel("attn_seq_fwd_kernel<%d, %s>", nf == 13 ? 13 : 0, drop ? "true" : "false");
     const dim3 grid(a.H, a.B), block(THREADS);
-    const size_t lds = size_t(2 * npad * 128);
-    if (nf == 13 && drop) hipLaunchKernelGGL((attn_seq_fwd_kernel<13, true>), grid, block, lds, s, a, npad);
-    else if (nf == 13) hipLaunchKernelGGL((attn_seq_fwd_kernel<13, false>), grid, block, lds, s, a, npad);
-    else if (drop) hipLaunchKernelGGL((attn_seq_fwd_kernel<0, true>), grid, block, lds, s, a, npad);
-    else hipLaunchKernelGGL((attn_seq_fwd_kernel<0, false>), grid, block, lds, s, a, npad);
+    if (p.inst == 13 && p.drop) hipLaunchKernelGGL((attn_seq_fwd_kernel<13, true>), grid, block, p.lds, s, a, p.npad);
+    else if (p.inst == 13) hipLaunchKernelGGL((attn_seq_fwd_kernel<13, false>), grid, block, p.lds, s, a, p.npad);
+    else if (p.drop) hipLaunchKernelGGL((attn_seq_fwd_kernel<0, true>), grid, block, p.lds, s, a, p.npad);
+    else hipLaunchKernelGGL((attn_seq_fwd_kernel<0, false>), grid, block, p.lds, s, a, p.npad);
     return check_launch("attention_seq_fwd");
 }
 
-int attn_seq_bwd(const sfcvit_attn_args &a, hipStream_t s) {
-    if (a.N > SEQ_MAX_N) return -1;
+int attn_seq_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s) {
     if (int rc = set_lds_limit()) return rc;
-    const int npad = (a.N + 31) / 32 * 32;
-    const bool nf13 = (a.N + 15) / 16 == 13;
-    note_attn_kernel("attn_seq_bwd_kv_kernel<%d>", nf13 ? 13 : 0);
-    if (nf13) hipLaunchKernelGGL(attn_seq_bwd_kv_kernel<13>, dim3(a.H, a.B), dim3(THREADS), size_t(2 * npad * 128 + 3 * npad * 4), s, a, npad);
-    else hipLaunchKernelGGL(attn_seq_bwd_kv_kernel<0>, dim3(a.H, a.B), dim3(THREADS), size_t(2 * npad * 128 + 3 * npad * 4), s, a, npad);
+    const dim3 grid(a.H, a.B), block(THREADS);
+    if (p.inst == 13) hipLaunchKernelGGL(attn_seq_bwd_kv_kernel<13>, grid, block, p.lds, s, a, p.npad);
+    else hipLaunchKernelGGL(attn_seq_bwd_kv_kernel<0>, grid, block, p.lds, s, a, p.npad);
     if (int rc = check_launch("attention_seq_bwd kv")) return rc;
-    const int npad16 = (a.N + 15) / 16 * 16;
-    if (nf13) hipLaunchKernelGGL(attn_seq_bwd_q_kernel<13>, dim3(a.H, a.B), dim3(THREADS), size_t(2 * npad16 * 128), s, a, npad16);
-    else hipLaunchKernelGGL(attn_seq_bwd_q_kernel<0>, dim3(a.H, a.B), dim3(THREADS), size_t(2 * npad16 * 128), s, a, npad16);
+    if (p.inst == 13) hipLaunchKernelGGL(attn_seq_bwd_q_kernel<13>, grid, block, p.lds2, s, a, p.npad2);
+    else hipLaunchKernelGGL(attn_seq_bwd_q_kernel<0>, grid, block, p.lds2, s, a, p.npad2);
     return check_launch("attention_seq_bwd q");
 }
 

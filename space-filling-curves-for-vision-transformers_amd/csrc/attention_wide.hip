@@ -301,55 +301,36 @@ __global__ __launch_bounds__(THREADS) void attn_wide_bwd_q_kernel(const sfcvit_a
     }
 }
 
-constexpr int LDS_LIMIT = 160 * 1024;
-
 template <int S>
-int launch_fwd(const sfcvit_attn_args &a, int npad, size_t lds, hipStream_t s) {
-    if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&attn_wide_fwd_kernel<S>), LDS_LIMIT, "attention_wide attribute")) return rc;
-    note_attn_kernel("attn_wide_fwd_kernel<%d>", S);
-    hipLaunchKernelGGL(attn_wide_fwd_kernel<S>, dim3(a.H, a.B), dim3(THREADS), lds, s, a, npad);
+int launch_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s) {
+    if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&attn_wide_fwd_kernel<S>), ATTN_LDS_LIMIT, "attention_wide attribute")) return rc;
+    hipLaunchKernelGGL(attn_wide_fwd_kernel<S>, dim3(a.H, a.B), dim3(THREADS), p.lds, s, a, p.npad);
     return check_launch("attention_wide_fwd");
 }
 
 template <int S>
-int launch_bwd(const sfcvit_attn_args &a, int npad, size_t lds_kv, size_t lds_q, hipStream_t s) {
+int launch_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s) {
     for (const void *k : {reinterpret_cast<const void *>(&attn_wide_bwd_kv_kernel<S>), reinterpret_cast<const void *>(&attn_wide_bwd_q_kernel<S>)})
-        if (int rc = raise_lds_limit(k, LDS_LIMIT, "attention_wide attribute")) return rc;
-    note_attn_kernel("attn_wide_bwd_kv_kernel<%d>", S);
-    hipLaunchKernelGGL(attn_wide_bwd_kv_kernel<S>, dim3(a.H, a.B), dim3(THREADS), lds_kv, s, a, npad);
+        if (int rc = raise_lds_limit(k, ATTN_LDS_LIMIT, "attention_wide attribute")) return rc;
+    hipLaunchKernelGGL(attn_wide_bwd_kv_kernel<S>, dim3(a.H, a.B), dim3(THREADS), p.lds, s, a, p.npad);
     if (int rc = check_launch("attention_wide_bwd kv")) return rc;
-    hipLaunchKernelGGL(attn_wide_bwd_q_kernel<S>, dim3(a.H, a.B), dim3(THREADS), lds_q, s, a, npad);
+    hipLaunchKernelGGL(attn_wide_bwd_q_kernel<S>, dim3(a.H, a.B), dim3(THREADS), p.lds2, s, a, p.npad);
     return check_launch("attention_wide_bwd q");
 }
 
 }  // namespace
 
-// Head dims 128 / 192 / 256.  -1: not this path's business (hd == 64); otherwise a status (EINVAL with a message when
-// the sequence does not fit the LDS).
-int attn_wide_fwd(const sfcvit_attn_args &a, hipStream_t s) {
-    if (a.hd == 64) return -1;
-    const int S = a.hd / 64;
-    if (a.hd % 64 || S < 2 || S > 4) return fail(SFCVIT_EINVAL, "attention: head dim %d not supported (64, 128, 192, 256)", a.hd);
-    const int npad = (a.N + 31) / 32 * 32;
-    const size_t lds = size_t(2) * S * npad * 128;
-    if (a.N > 256 || lds > size_t(LDS_LIMIT))
-        return fail(SFCVIT_EINVAL, "attention: head dim %d with N = %d needs %zu KiB of LDS (limit 160); only head dim 64 has a tiled kernel", a.hd, a.N, lds >> 10);
-    if (S == 2) return launch_fwd<2>(a, npad, lds, s);
-    if (S == 3) return launch_fwd<3>(a, npad, lds, s);
-    return launch_fwd<4>(a, npad, lds, s);
+// The plan's head-dim 128 / 192 / 256 kernels (dispatch.cpp; S = p.inst = hd / 64).
+int attn_wide_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s) {
+    if (p.inst == 2) return launch_fwd<2>(p, a, s);
+    if (p.inst == 3) return launch_fwd<3>(p, a, s);
+    return launch_fwd<4>(p, a, s);
 }
 
-int attn_wide_bwd(const sfcvit_attn_args &a, hipStream_t s) {
-    if (a.hd == 64) return -1;
-    const int S = a.hd / 64;
-    if (a.hd % 64 || S < 2 || S > 4) return fail(SFCVIT_EINVAL, "attention: head dim %d not supported (64, 128, 192, 256)", a.hd);
-    const int npad = (a.N + 31) / 32 * 32;
-    const size_t lds_q = size_t(2) * S * npad * 128, lds_kv = lds_q + size_t(3) * npad * 4;
-    if (a.N > 256 || lds_kv > size_t(LDS_LIMIT))
-        return fail(SFCVIT_EINVAL, "attention: head dim %d with N = %d needs %zu KiB of LDS (limit 160); only head dim 64 has a tiled kernel", a.hd, a.N, lds_kv >> 10);
-    if (S == 2) return launch_bwd<2>(a, npad, lds_kv, lds_q, s);
-    if (S == 3) return launch_bwd<3>(a, npad, lds_kv, lds_q, s);
-    return launch_bwd<4>(a, npad, lds_kv, lds_q, s);
+int attn_wide_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s) {
+    if (p.inst == 2) return launch_bwd<2>(p, a, s);
+    if (p.inst == 3) return launch_bwd<3>(p, a, s);
+    return launch_bwd<4>(p, a, s);
 }
 
 }  // namespace sfcvit

@@ -1,14 +1,59 @@
 #include "common_host.h"
 
 #include <hip/hip_runtime.h>
+#include <atomic>
+#include <cstdlib>
 #include <mutex>
 
 namespace sfcvit {
 namespace {
 thread_local char g_err[512] = "";
-thread_local int g_gemm[5] = {0, 0, 0, 0, 0};
+thread_local GemmPlan g_gemm;
+thread_local bool g_gemm_noted = false;
 thread_local char g_attn[96] = "none";
 thread_local char g_rowwise[96] = "none";
+}
+
+int env_int(const char *name, int def) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : def;
+}
+
+char env_first(const char *name) {
+    const char *e = getenv(name);
+    return e ? e[0] : 0;
+}
+
+int env_pair(const char *name, int *a, int *b) {
+    const char *e = getenv(name);
+    const int n = e ? sscanf(e, "%d,%d", a, b) : 0;
+    return n > 0 ? n : 0;
+}
+
+Knobs read_knobs(KnobScope scope) {
+    static const Knobs once = [] {
+        Knobs k;
+        k.gemm_walk = env_int("SFCVIT_GEMM_WALK", -1);
+        k.attn_bwd_queue = !env_off("SFCVIT_ATTN_BWD_QUEUE");
+        k.attn_nt = env_int("SFCVIT_ATTN_NT", 0);
+        return k;
+    }();
+    Knobs k = once;
+    if (scope == KNOBS_GEMM) {
+        k.gemm_2phase = !env_off("SFCVIT_GEMM_2PHASE");
+        env_pair("SFCVIT_GEMM_STAGGER", &k.gemm_stagger_slots, &k.gemm_stagger_ticks);
+        k.reserve_cus = env_int("SFCVIT_RESERVE_CUS", 0);
+        return k;
+    }
+    k.attn_long = !env_off("SFCVIT_ATTN_LONG");
+    if (scope == KNOBS_ATTN_BWD) {
+        k.attn_bwd_fused = !env_off("SFCVIT_ATTN_BWD_FUSED");
+        k.attn_dq_in_kernel = env_first("SFCVIT_ATTN_DQSUM") != 'p';
+        k.attn_bwd_persist = !env_off("SFCVIT_ATTN_BWD_PERSIST");
+        int slots = 0;
+        if (env_pair("SFCVIT_ATTN_STAGGER_BWD", &slots, &k.attn_stagger_ticks)) k.attn_stagger_slots = slots < 1 ? 1 : slots;
+    }
+    return k;
 }
 
 void note_rowwise_kernel(const char *fmt, ...) {
@@ -18,18 +63,11 @@ void note_rowwise_kernel(const char *fmt, ...) {
     va_end(ap);
 }
 
-void note_attn_kernel(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_attn, sizeof(g_attn), fmt, ap);
-    va_end(ap);
-}
+void note_attn_kernel(const AttnPlan &p) { kernel_name(p, g_attn, sizeof(g_attn)); }
 
-bool gemm_fused_colsum() { return g_gemm[0] == 1 && (g_gemm[2] & 16); }
-bool gemm_fused_actmask() { return g_gemm[0] == 1 && (g_gemm[2] & 32); }
-
-void note_gemm_kernel(int family, int a, int b, int c, int d) {
-    g_gemm[0] = family; g_gemm[1] = a; g_gemm[2] = b; g_gemm[3] = c; g_gemm[4] = d;
+void note_gemm_kernel(const GemmPlan &p) {
+    g_gemm = p;
+    g_gemm_noted = true;
 }
 
 int fail(int code, const char *fmt, ...) {
@@ -61,17 +99,20 @@ int raise_lds_limit(const void *kernel, int bytes, const char *what) {
     return SFCVIT_OK;
 }
 
-// Compute units of the current device (cached per device); 0 if it cannot be told.
+// Compute units of the current device (cached per device; threads that race on the first call store the same value); 0 if
+// it cannot be told.
 int device_cu_count() {
-    static int cus[64];
+    static std::atomic<int> cus[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (!cus[dev]) {
+    int n = cus[dev].load(std::memory_order_relaxed);
+    if (!n) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-        cus[dev] = prop.multiProcessorCount;
+        n = prop.multiProcessorCount;
+        cus[dev].store(n, std::memory_order_relaxed);
     }
-    return cus[dev];
+    return n;
 }
 
 int check_launch(const char *what) {
@@ -87,16 +128,9 @@ extern "C" int sfcvit_abi_version(void) { return SFCVIT_ABI_VERSION; }
 extern "C" const char *sfcvit_last_error(void) { return sfcvit::g_err; }
 
 extern "C" int sfcvit_last_gemm_kernel(char *buf, int n) {
-    using sfcvit::g_gemm;
     if (!buf || n <= 0) return SFCVIT_EINVAL;
-    const char *tf[2] = {"false", "true"};
-    switch (g_gemm[0]) {
-    case 1: snprintf(buf, size_t(n), "gemm8p_kernel<%d, %d, %s>", g_gemm[1], g_gemm[2], tf[g_gemm[3] & 1]); break;
-    case 2: snprintf(buf, size_t(n), "gemm8p_km_kernel<%s>", tf[g_gemm[1] & 1]); break;
-    case 3: snprintf(buf, size_t(n), "gemm256_kernel<%s, %s, %d, %s>", tf[g_gemm[1] & 1], tf[g_gemm[2] & 1], g_gemm[3], tf[g_gemm[4] & 1]); break;
-    case 4: snprintf(buf, size_t(n), "gemm_kernel<%s, %s, %s>", tf[g_gemm[1] & 1], tf[g_gemm[2] & 1], tf[g_gemm[3] & 1]); break;
-    default: snprintf(buf, size_t(n), "none"); break;
-    }
+    if (sfcvit::g_gemm_noted) sfcvit::kernel_name(sfcvit::g_gemm, buf, size_t(n));
+    else snprintf(buf, size_t(n), "none");
     return SFCVIT_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <cstdio>
 
 #include "../../include/sfcvit.h"
+#include "dispatch.h"
 
 namespace sfcvit {
 
@@ -25,16 +26,12 @@ unsigned *stream_counters(void *stream);
 // Opt a kernel into `bytes` of dynamic LDS on the current device (once per kernel and device; 0 or an error code).
 int raise_lds_limit(const void *kernel, int bytes, const char *what);
 
-// Which GEMM kernel the calling thread's last sfcvit_gemm launched (sfcvit_last_gemm_kernel formats it as the symbol
-// rocprofv3 shows): family 1 gemm8p_kernel<a, b, c>, 2 gemm8p_km_kernel<a>, 3 gemm256_kernel<a, b, c, d>, 4 gemm_kernel<a, b, c>.
-void note_gemm_kernel(int family, int a = 0, int b = 0, int c = 0, int d = 0);
-// Which attention kernel the calling thread's last sfcvit_attention_fwd / _bwd launched (its main kernel, named as
-// rocprofv3 names it); fmt is printf-style.
-void note_attn_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+// The plan whose main kernel the calling thread's last sfcvit_gemm / sfcvit_attention_fwd / _bwd launched
+// (sfcvit_last_gemm_kernel / sfcvit_last_attn_kernel name it as rocprofv3 does).
+void note_gemm_kernel(const GemmPlan &p);
+void note_attn_kernel(const AttnPlan &p);
 // Which row-wise kernel the calling thread's last sfcvit_layernorm_bwd* launched (sfcvit_last_rowwise_kernel).
 void note_rowwise_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-bool gemm_fused_colsum();     // the kernel noted last was the 8-phase kernel with column sums in its epilogue
-bool gemm_fused_actmask();    // ... with the activation bit mask written (act) or read (dact) by its epilogue
 
 // rowwise.hip: out[n] = sum over `nparts` rows of part[nparts][N] in a fixed order; out fp32 or bf16.
 int launch_colsum_reduce(const float *part, int nparts, int N, void *out, int out_bf16, void *stream);

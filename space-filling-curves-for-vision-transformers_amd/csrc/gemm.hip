@@ -123,11 +123,26 @@ __global__ __launch_bounds__(256) void splitk_reduce(const float *__restrict__ w
     }
 }
 
+template <bool A_KM, bool B_KM>
+void launch_gemm_kernel(const sfcvit_gemm_args &g, bool heavy, int grid, int k_per_split, int splits, hipStream_t s) {
+    if (heavy) hipLaunchKernelGGL((gemm_kernel<A_KM, B_KM, true>), dim3(grid), dim3(THREADS), 4 * TILE_BYTES, s, g, k_per_split, splits);
+    else hipLaunchKernelGGL((gemm_kernel<A_KM, B_KM, false>), dim3(grid), dim3(THREADS), 4 * TILE_BYTES, s, g, k_per_split, splits);
+}
+
+// The generic kernel: `grid` workgroups over `splits` k-ranges of k_per_split rows.
+int launch_generic(const sfcvit_gemm_args &g, bool a_km, bool b_km, bool heavy, int grid, int k_per_split, int splits, hipStream_t s) {
+    if (a_km && b_km) launch_gemm_kernel<true, true>(g, heavy, grid, k_per_split, splits, s);
+    else if (a_km) launch_gemm_kernel<true, false>(g, heavy, grid, k_per_split, splits, s);
+    else if (b_km) launch_gemm_kernel<false, true>(g, heavy, grid, k_per_split, splits, s);
+    else launch_gemm_kernel<false, false>(g, heavy, grid, k_per_split, splits, s);
+    return check_launch("gemm");
+}
+
 }  // namespace
 
-int gemm256_dispatch(const sfcvit_gemm_args &a, int splits, int k_per_split, hipStream_t s);   // gemm256.hip
-int gemm8p_dispatch(const sfcvit_gemm_args &a, int splits, hipStream_t s);                        // gemm8p.hip
-int gemm8p_km_dispatch(const sfcvit_gemm_args &a, int splits_req, int *splits_used, int *k_done, hipStream_t s);
+int gemm256_launch(const GemmPlan &p, const sfcvit_gemm_args &a, hipStream_t s);     // gemm256.hip
+int gemm8p_launch(const GemmPlan &p, const sfcvit_gemm_args &a, hipStream_t s);      // gemm8p.hip
+int gemm8p_km_launch(const GemmPlan &p, const sfcvit_gemm_args &a, hipStream_t s);
 
 }  // namespace sfcvit
 
@@ -144,128 +159,60 @@ extern "C" int64_t sfcvit_gemm_colsum_workspace(int M, int N) {
     return fused > separate ? fused : separate;
 }
 
-static int gemm_impl(const sfcvit_gemm_args *a, void *stream);
-
+// Validate and plan (dispatch.cpp), launch the plan's kernels, then its post passes.
 extern "C" int sfcvit_gemm(const sfcvit_gemm_args *a, void *stream) {
     using namespace sfcvit;
-    if (a && a->colsum_out) {
+    if (!a) return fail(SFCVIT_EINVAL, "gemm: null operand");
+    if (a->colsum_out) {
         if (a->c_is_f32 || a->splitk > 1) return fail(SFCVIT_EINVAL, "gemm: colsum_out needs a bf16 C and no split-K");
         if (!a->workspace || a->workspace_bytes < sfcvit_gemm_colsum_workspace(a->M, a->N) || !aligned16(a->workspace))
             return fail(SFCVIT_EINVAL, "gemm: colsum_out needs sfcvit_gemm_colsum_workspace(M, N) bytes of workspace");
     }
-    if (a && a->actmask) {
-        if (a->N % 16 || a->ld_actmask % 2 || a->ld_actmask * 8 < a->N || (reinterpret_cast<uintptr_t>(a->actmask) & 1))
-            return fail(SFCVIT_EINVAL, "gemm: actmask needs N %% 16 == 0, an even ld_actmask >= N / 8 and 2-byte alignment");
-        if (a->act != SFCVIT_ACT_RELU && a->dact != SFCVIT_ACT_RELU)
-            return fail(SFCVIT_EINVAL, "gemm: actmask goes with act = RELU (written) or dact = RELU (read)");
-        if (a->c_is_f32 || a->splitk > 1) return fail(SFCVIT_EINVAL, "gemm: actmask not with fp32 C or split-K");
-    }
-    if (int rc = gemm_impl(a, stream)) return rc;
-    if (a->actmask && a->act == SFCVIT_ACT_RELU && !gemm_fused_actmask()) {      // the kernel that ran does not write the bits
-        const int64_t nv = int64_t(a->M) * (a->N / 16);
-        hipLaunchKernelGGL(relu_bits_kernel, dim3(unsigned((nv + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           static_cast<const uint16_t *>(a->c), a->ldc, a->M, a->N, static_cast<uint8_t *>(a->actmask), a->ld_actmask);
-        if (int rc = check_launch("gemm actmask pass")) return rc;
-    }
-    if (a->colsum_out && !gemm_fused_colsum())   // the kernel that ran had no fused column sums: one pass over the stored C
-        return sfcvit_colsum(a->c, a->M, a->N, a->ldc, a->colsum_out, a->colsum_bf16, a->workspace, a->workspace_bytes, stream);
-    return SFCVIT_OK;
-}
-
-static int gemm_impl(const sfcvit_gemm_args *a, void *stream) {
-    using namespace sfcvit;
-    if (!a || !a->a || !a->b || !a->c) return fail(SFCVIT_EINVAL, "gemm: null operand");
-    if (a->M <= 0 || a->N <= 0 || a->K <= 0) return fail(SFCVIT_EINVAL, "gemm: M=%d N=%d K=%d", a->M, a->N, a->K);
-    // 16-byte vectors along the contiguous dimension of every operand.
-    if (a->K % 8 != 0 && (!a->a_kmajor || !a->b_kmajor))
-        return fail(SFCVIT_EINVAL, "gemm: K=%d must be a multiple of 8 for a k-contiguous operand", a->K);
-    if (a->a_kmajor && a->M % 8 != 0) return fail(SFCVIT_EINVAL, "gemm: M=%d must be a multiple of 8 for k-major A", a->M);
-    if ((a->b_kmajor && a->N % 8 != 0) || a->N % 4 != 0)
-        return fail(SFCVIT_EINVAL, "gemm: N=%d must be a multiple of 4 (8 for k-major B)", a->N);
-    if (a->lda % 8 || a->ldb % 8 || a->ldc % 4) return fail(SFCVIT_EINVAL, "gemm: lda=%d ldb=%d ldc=%d alignment", a->lda, a->ldb, a->ldc);
-    if (!aligned16(a->a) || !aligned16(a->b) || !aligned16(a->c)) return fail(SFCVIT_EINVAL, "gemm: operands must be 16-byte aligned");
-    if (a->residual && (a->ldr % 4 || (reinterpret_cast<uintptr_t>(a->residual) & 7)))
-        return fail(SFCVIT_EINVAL, "gemm: residual alignment");
-    if ((a->aux_in || a->aux_out) && a->ldaux % 4) return fail(SFCVIT_EINVAL, "gemm: ldaux=%d alignment", a->ldaux);
-    if (a->dact != SFCVIT_ACT_NONE && !a->aux_in) return fail(SFCVIT_EINVAL, "gemm: dact needs aux_in");
-    if (a->act < 0 || a->act > 2 || a->dact < 0 || a->dact > 2) return fail(SFCVIT_EINVAL, "gemm: bad act/dact");
-    if (a->bias && (reinterpret_cast<uintptr_t>(a->bias) & 7)) return fail(SFCVIT_EINVAL, "gemm: bias alignment");
-    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return fail(SFCVIT_EINVAL, "gemm: dropout_p=%g out of [0, 1)", a->dropout_p);
-    int splits = a->splitk < 1 ? 1 : a->splitk;
-    const int ktiles = (a->K + BK - 1) / BK;
-    if (splits > ktiles) splits = ktiles;
-    const int out_tiles = ((a->N + BN - 1) / BN) * ((a->M + BM - 1) / BM);
-    const bool per_xcd = splits > 1 && out_tiles < 64;          // one set of k-ranges per XCD (see gemm_kernel)
-    if (per_xcd) splits = (splits + 7) / 8 * 8;
-    int k_per_split = ((ktiles + splits - 1) / splits) * BK;
-    if (!per_xcd) splits = (a->K + k_per_split - 1) / k_per_split;   // drop empty trailing ranges
-    if (splits > 1) {
-        if (a->bias || a->residual || a->aux_out || a->act || a->dact || a->dropout_p > 0.f)
-            return fail(SFCVIT_EINVAL, "gemm: split-K supports no epilogue");
-        const int64_t need = int64_t(splits) * a->M * a->N * int64_t(sizeof(float));
-        if (!a->workspace || a->workspace_bytes < need || !aligned16(a->workspace))
-            return fail(SFCVIT_EINVAL, "gemm: split-K workspace too small (%lld bytes needed; use sfcvit_gemm_workspace)", (long long)need);
-    }
-
+    const GemmPlan p = gemm_plan(*a, device_cu_count(), read_knobs(KNOBS_GEMM));
+    if (p.err) return fail(p.err, "%s", p.msg);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (a->force_generic == 0 || (a->force_generic >= 8 && a->force_generic <= 10)) {
-        int p8 = gemm8p_dispatch(*a, splits, s);
-        if (p8 >= 0) return p8;
-        int used = 0, k_done = 0;
-        p8 = gemm8p_km_dispatch(*a, splits, &used, &k_done, s);
-        if (p8 > 0) return p8;
-        if (p8 == 0 && k_done < a->K) {
-            // the last K % 128 rows of both k-major operands: one more fp32 slab from the generic kernel, summed with the
-            // others in the same fixed order
-            sfcvit_gemm_args t = *a;
-            t.a = static_cast<const uint16_t *>(a->a) + size_t(k_done) * a->lda;
-            t.b = static_cast<const uint16_t *>(a->b) + size_t(k_done) * a->ldb;
-            t.K = a->K - k_done;
-            t.c = static_cast<float *>(a->workspace) + size_t(used) * a->M * a->N;
-            t.ldc = a->N;
-            t.c_is_f32 = 1;
-            t.splitk = 1;
-            t.workspace = nullptr;
-            t.workspace_bytes = 0;
-            t.force_generic = 1;
-            if (int rc = gemm_impl(&t, stream)) return rc;
-            {   // what ran is the 8-phase weight-gradient kernel (+ its tail)
-                const char *e = getenv("SFCVIT_GEMM_2PHASE");
-                note_gemm_kernel(2, !(e && e[0] == '0'));
-            }
-            used++;
-        }
-        if (p8 == 0) {
-            const int64_t nvec = int64_t(a->M) * (a->N / 4);
-            hipLaunchKernelGGL(splitk_reduce, dim3(unsigned((nvec + 255) / 256)), dim3(256), 0, s,
-                               static_cast<const float *>(a->workspace), used, a->M, a->N, a->c, a->ldc, a->c_is_f32);
-            return check_launch("gemm splitk_reduce");
-        }
-        if (a->force_generic != 0) return fail(SFCVIT_EINVAL, "gemm: shape / options not eligible for the persistent 8-phase kernel");
+    note_gemm_kernel(p);
+    int rc = SFCVIT_OK;
+    switch (p.family) {
+    case GemmFamily::P8: rc = gemm8p_launch(p, *a, s); break;
+    case GemmFamily::P8_KM: rc = gemm8p_km_launch(p, *a, s); break;
+    case GemmFamily::RING: rc = gemm256_launch(p, *a, s); break;
+    case GemmFamily::GENERIC: rc = launch_generic(*a, p.a_km, p.b_km, p.heavy, p.grid, p.k_per_split, p.splits, s); break;
     }
-    const int big = (a->force_generic == 1) ? -1 : gemm256_dispatch(*a, splits, k_per_split, s);
-    if (big > 0) return big;
-    dim3 grid(((a->N + BN - 1) / BN) * ((a->M + BM - 1) / BM) * splits), block(THREADS);
-    const size_t lds = 4 * TILE_BYTES;
-    const bool heavy = a->act == SFCVIT_ACT_GELU || a->dact == SFCVIT_ACT_GELU;
-#define SFCVIT_GO(AK, BK)                                                                                   \
-    do {                                                                                                    \
-        if (heavy) hipLaunchKernelGGL((gemm_kernel<AK, BK, true>), grid, block, lds, s, *a, k_per_split, splits);   \
-        else hipLaunchKernelGGL((gemm_kernel<AK, BK, false>), grid, block, lds, s, *a, k_per_split, splits);        \
-    } while (0)
-    if (big != 0) note_gemm_kernel(4, a->a_kmajor != 0, a->b_kmajor != 0, heavy);
-    if (big == 0) {
-    } else if (!a->a_kmajor && !a->b_kmajor) SFCVIT_GO(false, false);
-    else if (!a->a_kmajor && a->b_kmajor) SFCVIT_GO(false, true);
-    else if (a->a_kmajor && !a->b_kmajor) SFCVIT_GO(true, false);
-    else SFCVIT_GO(true, true);
-#undef SFCVIT_GO
-    if (int rc = check_launch("gemm")) return rc;
-    if (splits > 1) {
+    if (rc) return rc;
+    if (p.tail_slab >= 0) {
+        // the last K % 128 rows of both k-major operands: one more fp32 slab from the generic kernel, summed with the
+        // others in the same fixed order
+        sfcvit_gemm_args t = *a;
+        t.a = static_cast<const uint16_t *>(a->a) + size_t(p.k_done) * a->lda;
+        t.b = static_cast<const uint16_t *>(a->b) + size_t(p.k_done) * a->ldb;
+        t.K = a->K - p.k_done;
+        t.c = static_cast<float *>(a->workspace) + size_t(p.tail_slab) * a->M * a->N;
+        t.ldc = a->N;
+        t.c_is_f32 = 1;
+        t.splitk = 1;
+        t.workspace = nullptr;
+        t.workspace_bytes = 0;
+        t.force_generic = SFCVIT_GEMM_GENERIC;
+        const int tiles = ((a->N + BN - 1) / BN) * ((a->M + BM - 1) / BM);
+        if ((rc = launch_generic(t, true, true, false, tiles, (t.K + BK - 1) / BK * BK, 1, s))) return rc;
+    }
+    if (p.colsum_parts &&
+        (rc = launch_colsum_reduce(static_cast<const float *>(a->workspace), p.colsum_parts, a->N, a->colsum_out, a->colsum_bf16, s)))
+        return rc;
+    if (p.reduce_slabs) {
         const int64_t nvec = int64_t(a->M) * (a->N / 4);
         hipLaunchKernelGGL(splitk_reduce, dim3(unsigned((nvec + 255) / 256)), dim3(256), 0, s,
-                           static_cast<const float *>(a->workspace), splits, a->M, a->N, a->c, a->ldc, a->c_is_f32);
-        return check_launch("gemm splitk_reduce");
+                           static_cast<const float *>(a->workspace), p.reduce_slabs, a->M, a->N, a->c, a->ldc, a->c_is_f32);
+        if ((rc = check_launch("gemm splitk_reduce"))) return rc;
     }
+    if (p.actmask_pass) {
+        const int64_t nv = int64_t(a->M) * (a->N / 16);
+        hipLaunchKernelGGL(relu_bits_kernel, dim3(unsigned((nv + 255) / 256)), dim3(256), 0, s,
+                           static_cast<const uint16_t *>(a->c), a->ldc, a->M, a->N, static_cast<uint8_t *>(a->actmask), a->ld_actmask);
+        if ((rc = check_launch("gemm actmask pass"))) return rc;
+    }
+    if (p.colsum_pass)
+        return sfcvit_colsum(a->c, a->M, a->N, a->ldc, a->colsum_out, a->colsum_bf16, a->workspace, a->workspace_bytes, stream);
     return SFCVIT_OK;
 }

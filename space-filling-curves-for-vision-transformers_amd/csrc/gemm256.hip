@@ -189,52 +189,28 @@ __global__ __launch_bounds__(Cfg<BN_>::T, 2) void gemm256_kernel(const sfcvit_ge
 }
 
 template <bool A_KM, bool B_KM, int BN_, bool HEAVY>
-int launch1(const sfcvit_gemm_args &a, int splits, int k_per_split, hipStream_t s) {
+int launch(const GemmPlan &p, const sfcvit_gemm_args &a, hipStream_t s) {
     constexpr size_t lds = Cfg<BN_>::LDS;
     if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm256_kernel<A_KM, B_KM, BN_, HEAVY>), int(lds), "gemm256 attribute"))
         return rc;
-    dim3 grid((a.M / 256) * (a.N / BN_), 1, splits), block(Cfg<BN_>::T);
-    note_gemm_kernel(3, A_KM, B_KM, BN_, HEAVY);
-    hipLaunchKernelGGL((gemm256_kernel<A_KM, B_KM, BN_, HEAVY>), grid, block, lds, s, a, k_per_split);
+    hipLaunchKernelGGL((gemm256_kernel<A_KM, B_KM, BN_, HEAVY>), dim3(p.grid, 1, p.splits), dim3(Cfg<BN_>::T), lds, s, a, p.k_per_split);
     return check_launch("gemm256");
 }
 
-template <bool A_KM, bool B_KM, int BN_>
-int launch(const sfcvit_gemm_args &a, int splits, int k_per_split, hipStream_t s) {
-    if (a.act == SFCVIT_ACT_GELU || a.dact == SFCVIT_ACT_GELU) return launch1<A_KM, B_KM, BN_, true>(a, splits, k_per_split, s);
-    return launch1<A_KM, B_KM, BN_, false>(a, splits, k_per_split, s);
+template <bool A_KM, bool B_KM>
+int launch_bn(const GemmPlan &p, const sfcvit_gemm_args &a, hipStream_t s) {
+    if (p.bn == 256) return p.heavy ? launch<A_KM, B_KM, 256, true>(p, a, s) : launch<A_KM, B_KM, 256, false>(p, a, s);
+    return p.heavy ? launch<A_KM, B_KM, 128, true>(p, a, s) : launch<A_KM, B_KM, 128, false>(p, a, s);
 }
 
 }  // namespace
 
-// Called by sfcvit_gemm after argument validation.  Returns -1 when the shape is not
-// eligible (caller falls back to the generic kernel), else a status code.
-int gemm256_dispatch(const sfcvit_gemm_args &a, int splits, int k_per_split, hipStream_t s) {
-    if (a.M % 256 || a.N % 128 || a.K % 32 || k_per_split % 32) return -1;
-    // BN = 256 unless that leaves the last round of workgroups mostly idle on 256 CUs.
-    bool bn256 = a.N % 256 == 0;
-    if (bn256) {
-        const long t = long(a.M / 256) * (a.N / 256) * splits;
-        const long rounds = (t + 255) / 256;
-        if (t < 200 || double(t) / double(rounds * 256) < 0.85) bn256 = false;
-    }
-    // Measured on the ViT-B shapes (tools/bench_gemm.py, profiles/r1): the 256 x 128 two-workgroup
-    // configuration wins when both operands are k-contiguous (forward GEMMs: 730-880 TFLOP/s vs
-    // 650-760 generic, 650-820 for 256 x 256); with a k-major operand (dX, dW: transposed LDS reads,
-    // twice the LDS instructions) the generic kernel's 128 x 128 tiles are as fast or faster.
-    if (a.force_generic == 0) {
-        if (a.a_kmajor || a.b_kmajor) return -1;
-        bn256 = false;
-    }
-    if (a.force_generic == 6) bn256 = false;             // tests / benchmarking: force the 256 x 128 configuration
-    if (a.force_generic == 7 && a.N % 256 == 0) bn256 = true;
-#define SFCVIT_GO(AK, BK)                                                                          \
-    return bn256 ? launch<AK, BK, 256>(a, splits, k_per_split, s) : launch<AK, BK, 128>(a, splits, k_per_split, s)
-    if (!a.a_kmajor && !a.b_kmajor) SFCVIT_GO(false, false);
-    if (!a.a_kmajor && a.b_kmajor) SFCVIT_GO(false, true);
-    if (a.a_kmajor && !a.b_kmajor) SFCVIT_GO(true, false);
-    SFCVIT_GO(true, true);
-#undef SFCVIT_GO
+// The plan's ring kernel (dispatch.cpp plan_ring).
+int gemm256_launch(const GemmPlan &p, const sfcvit_gemm_args &a, hipStream_t s) {
+    if (p.a_km && p.b_km) return launch_bn<true, true>(p, a, s);
+    if (p.a_km) return launch_bn<true, false>(p, a, s);
+    if (p.b_km) return launch_bn<false, true>(p, a, s);
+    return launch_bn<false, false>(p, a, s);
 }
 
 }  // namespace sfcvit

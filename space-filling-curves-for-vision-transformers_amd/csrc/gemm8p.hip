@@ -40,8 +40,8 @@
 //     the instruction cache punished a runtime option tree).  Wave group 1 runs its epilogue before, group 0 after
 //     the tile's last barrier: both run concurrently instead of one after the other.
 //
-// Anything not eligible (k-major operands, split-K, GELU / aux_out / fp32 output, shapes off the tile grid) returns
-// -1 from gemm8p_dispatch and takes the older kernels (gemm256.hip, gemm.hip).
+// Anything not eligible (k-major operands, split-K, GELU / aux_out / fp32 output, shapes off the tile grid)
+// is not planned onto it (dispatch.cpp plan_p8) and takes the older kernels (gemm256.hip, gemm.hip).
 #include "common_host.h"
 #include "gemm_core.h"
 #include <mutex>
@@ -57,9 +57,10 @@ namespace p8 {
 
 constexpr int T = 512, HALF = 16384, KTB = 65536, LDS_BYTES = 2 * KTB;
 // gemm8p_kernel's LDS beyond the ring: the 4-entry tile ring, one [16][128 B] store patch per wave, the bias vector
-constexpr int LDS_TQ = LDS_BYTES, LDS_PATCH = LDS_TQ + 64, LDS_BIAS = LDS_PATCH + 8 * 2048, LDS_MAX = 160 * 1024;
-constexpr int BIAS_MAX_N = (LDS_MAX - LDS_BIAS) / 2;
-enum { RELU = 1, DROP = 2, RES = 4, DACT = 8, CSUM = 16, BITS = 32 };   // BITS: sfcvit_gemm_args.actmask written (RELU) / read (DACT)
+constexpr int LDS_TQ = LDS_BYTES, LDS_PATCH = LDS_TQ + 64, LDS_BIAS = LDS_PATCH + 8 * 2048, LDS_MAX = P8_LDS_MAX;
+static_assert(LDS_BIAS == P8_LDS_BIAS, "dispatch.h prices the bias vector at this offset");
+// BITS: sfcvit_gemm_args.actmask written (RELU) / read (DACT)
+enum { RELU = P8_RELU, DROP = P8_DROP, RES = P8_RES, DACT = P8_DACT, CSUM = P8_CSUM, BITS = P8_BITS };
 
 typedef const __attribute__((address_space(1))) void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
@@ -889,35 +890,17 @@ __global__ __launch_bounds__(T) void gemm8p_km_kernel(const sfcvit_gemm_args g, 
 struct DeviceState {
     unsigned *pool = nullptr;
     int next = 0;
-    int cus = 0;
     std::unordered_map<hipStream_t, unsigned *> per_stream;
 };
 constexpr int MAX_DEVICES = 64, SLOTS = 1024, SLOT_UINTS = 16;
 std::mutex g_mu;
 DeviceState g_dev[MAX_DEVICES];
 
-DeviceState *device_state() {              // the CURRENT device's state (g_mu held by the caller)
+unsigned *queue_counters(hipStream_t s) {
+    std::lock_guard<std::mutex> lock(g_mu);
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return nullptr;
     DeviceState *d = &g_dev[dev];
-    if (!d->cus) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return nullptr;
-        d->cus = prop.multiProcessorCount;
-    }
-    return d;
-}
-
-int device_cus() {
-    std::lock_guard<std::mutex> lock(g_mu);
-    DeviceState *d = device_state();
-    return d ? d->cus : 0;
-}
-
-unsigned *queue_counters(hipStream_t s) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    DeviceState *d = device_state();
-    if (!d) return nullptr;
     auto it = d->per_stream.find(s);
     if (it != d->per_stream.end()) return it->second;
     if (!d->pool) {
@@ -934,63 +917,35 @@ unsigned *queue_counters(hipStream_t s) {
 }
 
 template <int NI, int MASK>
-int launch(const sfcvit_gemm_args &a, int grid, hipStream_t s) {
+int launch(const GemmPlan &p, const sfcvit_gemm_args &a, unsigned *counters, hipStream_t s) {
     const int LDS_TOTAL = LDS_BIAS + (a.bias ? a.N * 2 : 0);
-    unsigned *counters = queue_counters(s);
-    if (!counters) return fail(SFCVIT_ELAUNCH, "gemm8p: could not allocate the tile-queue counters");
-    // the two-phase k-tile schedule is the default; SFCVIT_GEMM_2PHASE=0 selects the four-phase one (A/B in one process)
-    const char *e = getenv("SFCVIT_GEMM_2PHASE");
-    note_gemm_kernel(1, NI, MASK, !(e && e[0] == '0'));
-    // Start-up stagger: the 32 workgroups of an XCD start in 4 groups 2 us apart.  Uniform tiles keep the 256 workgroups of a
-    // launch in lockstep, so all of them reach their epilogue in the same microsecond and 33 MB of C hit the memory system at
-    // once (the epilogue section of the first tiles of a launch takes 10 000 clocks, 5 600 once the workgroups have drifted
-    // apart: profiles/r3/gemm8p_ktile_trace.txt); the tile queue absorbs the late starts (late workgroups draw fewer tiles).
-    // Measured alone, M = 50 176 (tools/gemm_lab/ab_two_phase.py with AB_STAGGER): QKV 148.9 -> 141.7 us, out-proj 74.4 ->
-    // 68.6, linear1 233.7 -> 230.9, linear2 208.0 -> 205.3, linear2 dX 225.8 -> 221.4, linear1 dX 206.6 -> 203.1, in_proj dX
-    // 162.0 -> 161.6; training step 33.26-33.38 -> 32.86-32.89 ms (three alternating pairs of runs on one box).
-    // SFCVIT_GEMM_STAGGER="slots,ticks" (10 ns) overrides; "1,0" = off.
-    // Tile walk: column windows of 6 tiles for the wide GEMMs (N >= 1 792).  An XCD's 32 concurrent tiles are then ~5 row tiles x
-    // 6 column tiles instead of ~3 x 9-12, i.e. 11 distinct operand panels instead of 12-15: memory-side fetch of the N = 3 072 /
-    // 2 304 forward GEMMs 427 -> 263 MB per launch, L2 hit rate 0.56 -> 0.63, time unchanged (profiles/r4/gemm_tile_walk_ab.txt).
-    // SFCVIT_GEMM_WALK = window width, 0 = row-major walk (round 3).
-    static const int walk_env = [] { const char *w = getenv("SFCVIT_GEMM_WALK"); return w ? atoi(w) : -1; }();
-    const int walk = walk_env >= 0 ? walk_env : (a.N / 256 > 6 ? 6 : 0);
-    int stag_slots = 4, stag_ticks = 200;
-    if (const char *st = getenv("SFCVIT_GEMM_STAGGER")) sscanf(st, "%d,%d", &stag_slots, &stag_ticks);
-    if (stag_slots < 1) stag_slots = 1;
-    {   // a launch whose workgroups draw one tile each has no lockstep to break: the delay would only lengthen it
-        const long ntiles = long((a.M + 32 * NI - 1) / (32 * NI)) * (a.N / 256);
-        if (ntiles < 2L * grid) stag_ticks = 0;
-    }
-    if (!(e && e[0] == '0')) {
+    if (p.p2) {
         if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm8p_kernel<NI, MASK, true>), LDS_MAX, "gemm8p attribute")) return rc;
-        hipLaunchKernelGGL((gemm8p_kernel<NI, MASK, true>), dim3(grid), dim3(T), LDS_TOTAL, s, a, counters, stag_slots, stag_ticks, walk);
-        const int rc = check_launch("gemm8p");
-        if (rc) (void)hipMemsetAsync(counters, 0, SLOT_UINTS * sizeof(unsigned), s);
-        return rc;
+        hipLaunchKernelGGL((gemm8p_kernel<NI, MASK, true>), dim3(p.grid), dim3(T), LDS_TOTAL, s, a, counters, p.stag_slots, p.stag_ticks, p.walk);
+    } else {
+        if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm8p_kernel<NI, MASK>), LDS_MAX, "gemm8p attribute")) return rc;
+        hipLaunchKernelGGL((gemm8p_kernel<NI, MASK>), dim3(p.grid), dim3(T), LDS_TOTAL, s, a, counters, p.stag_slots, p.stag_ticks, p.walk);
     }
-    if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm8p_kernel<NI, MASK>), LDS_MAX, "gemm8p attribute")) return rc;
-    hipLaunchKernelGGL((gemm8p_kernel<NI, MASK>), dim3(grid), dim3(T), LDS_TOTAL, s, a, counters, stag_slots, stag_ticks, walk);
     const int rc = check_launch("gemm8p");
     if (rc) (void)hipMemsetAsync(counters, 0, SLOT_UINTS * sizeof(unsigned), s);   // a launch that did not run leaves no debt
     return rc;
 }
 
 template <int NI>
-int launch_mask(const sfcvit_gemm_args &a, int mask, int grid, hipStream_t s) {
-    switch (mask) {
-    case 0: return launch<NI, 0>(a, grid, s);
-    case RES: return launch<NI, RES>(a, grid, s);
-    case DROP | RES: return launch<NI, DROP | RES>(a, grid, s);
-    case RELU: return launch<NI, RELU>(a, grid, s);
-    case RELU | DROP: return launch<NI, RELU | DROP>(a, grid, s);
-    case DACT: return launch<NI, DACT>(a, grid, s);
-    case DACT | CSUM: return launch<NI, DACT | CSUM>(a, grid, s);
-    case RELU | BITS: return launch<NI, RELU | BITS>(a, grid, s);
-    case RELU | DROP | BITS: return launch<NI, RELU | DROP | BITS>(a, grid, s);
-    case DACT | BITS: return launch<NI, DACT | BITS>(a, grid, s);
-    case DACT | CSUM | BITS: return launch<NI, DACT | CSUM | BITS>(a, grid, s);
-    default: return -1;
+int launch_mask(const GemmPlan &p, const sfcvit_gemm_args &a, unsigned *counters, hipStream_t s) {
+    switch (p.mask) {                            // the epilogues dispatch.cpp plan_p8 admits
+    case 0: return launch<NI, 0>(p, a, counters, s);
+    case RES: return launch<NI, RES>(p, a, counters, s);
+    case DROP | RES: return launch<NI, DROP | RES>(p, a, counters, s);
+    case RELU: return launch<NI, RELU>(p, a, counters, s);
+    case RELU | DROP: return launch<NI, RELU | DROP>(p, a, counters, s);
+    case DACT: return launch<NI, DACT>(p, a, counters, s);
+    case DACT | CSUM: return launch<NI, DACT | CSUM>(p, a, counters, s);
+    case RELU | BITS: return launch<NI, RELU | BITS>(p, a, counters, s);
+    case RELU | DROP | BITS: return launch<NI, RELU | DROP | BITS>(p, a, counters, s);
+    case DACT | BITS: return launch<NI, DACT | BITS>(p, a, counters, s);
+    case DACT | CSUM | BITS: return launch<NI, DACT | CSUM | BITS>(p, a, counters, s);
+    default: return fail(SFCVIT_EINVAL, "gemm8p: no kernel for epilogue mask %d", p.mask);
     }
 }
 
@@ -1001,100 +956,29 @@ int launch_mask(const sfcvit_gemm_args &a, int mask, int grid, hipStream_t s) {
 // other persistent kernels of the library: attention_bwd_fused.hip deals its items from words 12-13.  nullptr: none to be had.
 unsigned *stream_counters(void *stream) { return p8::queue_counters(static_cast<hipStream_t>(stream)); }
 
-// Weight-gradient form (both operands k-major, split-K into the workspace slabs).  Returns -1 when not eligible,
-// else a status; *splits_used = number of slabs written (the caller runs the ordered reduction over them).
-// k need not be a multiple of 128 (k = batch x tokens: 19 600 rows at batch 100): the kernel takes the largest multiple,
-// *k_done says how far it got, and the caller adds the remaining < 128 rows as one more slab (a slab is kept free for it).
-int gemm8p_km_dispatch(const sfcvit_gemm_args &a, int splits_req, int *splits_used, int *k_done, hipStream_t s) {
+// The plan's persistent kernel (dispatch.cpp plan_p8).
+int gemm8p_launch(const GemmPlan &p, const sfcvit_gemm_args &a, hipStream_t s) {
     using namespace p8;
-    if (!a.a_kmajor || !a.b_kmajor || splits_req < 2) return -1;
-    if (a.M % 256 || a.N % 256 || a.K < 256 || a.lda % 8 || a.ldb % 8) return -1;
-    const int cus = device_cus();
-    if (!cus) return -1;
-    const int Kb = a.K / 128 * 128, tail = a.K - Kb;
-    const int tiles = (a.M / 256) * (a.N / 256), KT = Kb / 64;
-    // SFCVIT_RESERVE_CUS=n (read per call): leave n CUs out of the split, for nodes where collectives run beside backward -- a
-    // launch of one workgroup per CU takes twice as long when it does not fit on the CUs that are free
-    int reserve = 0;
-    if (const char *rv = getenv("SFCVIT_RESERVE_CUS")) reserve = atoi(rv);
-    if (reserve < 0 || reserve > cus / 2) reserve = 0;
-    int splits = (cus - reserve) / tiles;                         // one workgroup per CU
-    if (splits > splits_req) splits = splits_req;
-    const int64_t slabs_avail = a.workspace_bytes / (int64_t(a.M) * a.N * int64_t(sizeof(float))) - (tail ? 1 : 0);
-    if (splits > slabs_avail) splits = int(slabs_avail);
-    if (splits < 2) return -1;
-    int kps = ((KT + splits - 1) / splits + 1) / 2 * 2;           // k-tiles per split, even
-    splits = (KT + kps - 1) / kps;
-    if (splits < 2) return -1;
+    unsigned *counters = queue_counters(s);
+    if (!counters) return fail(SFCVIT_ELAUNCH, "gemm8p: could not allocate the tile-queue counters");
+    if (p.ni == 8) return launch_mask<8>(p, a, counters, s);
+    if (p.ni == 7) return launch_mask<7>(p, a, counters, s);
+    return launch_mask<6>(p, a, counters, s);
+}
+
+// The plan's weight-gradient kernel (dispatch.cpp plan_p8_km) over the first p.k_done rows of K.
+int gemm8p_km_launch(const GemmPlan &p, const sfcvit_gemm_args &a, hipStream_t s) {
+    using namespace p8;
     sfcvit_gemm_args body = a;
-    body.K = Kb;
-    const char *e = getenv("SFCVIT_GEMM_2PHASE");              // "0": the four-phase k-tile schedule (A/B in one process)
-    note_gemm_kernel(2, !(e && e[0] == '0'));
-    if (e && e[0] == '0') {
-        if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm8p_km_kernel<false>), LDS_BYTES, "gemm8p_km attribute")) return rc;
-        hipLaunchKernelGGL(gemm8p_km_kernel<false>, dim3((tiles * splits + 7) / 8 * 8), dim3(T), LDS_BYTES, s, body, kps, splits);
-    } else {
+    body.K = p.k_done;
+    if (p.p2) {
         if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm8p_km_kernel<true>), LDS_BYTES, "gemm8p_km attribute")) return rc;
-        hipLaunchKernelGGL(gemm8p_km_kernel<true>, dim3((tiles * splits + 7) / 8 * 8), dim3(T), LDS_BYTES, s, body, kps, splits);
+        hipLaunchKernelGGL(gemm8p_km_kernel<true>, dim3(p.grid), dim3(T), LDS_BYTES, s, body, p.k_per_split, p.splits);
+    } else {
+        if (int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm8p_km_kernel<false>), LDS_BYTES, "gemm8p_km attribute")) return rc;
+        hipLaunchKernelGGL(gemm8p_km_kernel<false>, dim3(p.grid), dim3(T), LDS_BYTES, s, body, p.k_per_split, p.splits);
     }
-    *splits_used = splits;
-    *k_done = Kb;
     return check_launch("gemm8p_km");
 }
 
-// Called by sfcvit_gemm after argument validation.  -1 = not eligible (the caller tries the older kernels).
-int gemm8p_dispatch(const sfcvit_gemm_args &a, int splits, hipStream_t s) {
-    using namespace p8;
-    if (a.a_kmajor || a.b_kmajor || splits != 1 || a.c_is_f32 || a.aux_out) return -1;
-    if (a.act == SFCVIT_ACT_GELU || a.dact == SFCVIT_ACT_GELU) return -1;
-    if (a.N % 256 || a.K % 128 || a.K < 256 || a.lda % 8 || a.ldb % 8 || a.ldc % 8) return -1;
-    if (a.lda >= (1 << 21) || a.ldb >= (1 << 21)) return -1;       // 32-bit byte offsets within a tile
-    if (a.M / 192 >= 32768 || a.N / 256 >= 65536) return -1;       // (row tile, column tile) packed into one int
-    if (a.residual && (a.ldr % 8 || (reinterpret_cast<uintptr_t>(a.residual) & 15))) return -1;
-    if (a.dact && (a.ldaux % 8 || (reinterpret_cast<uintptr_t>(a.aux_in) & 15))) return -1;
-    if (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15)) return -1;
-    int mask = 0;
-    if (a.act == SFCVIT_ACT_RELU) mask |= RELU;
-    if (a.dropout_p > 0.f) mask |= DROP;
-    if (a.residual) mask |= RES;
-    if (a.dact == SFCVIT_ACT_RELU) mask |= DACT;
-    if (a.colsum_out) mask |= CSUM;                          // built with DACT only; other combinations fall back
-    if (a.actmask && (mask & (RELU | DACT)) && !(mask & RES)) mask |= BITS;   // with RELU + RES the bits come from the pass over C
-    if ((mask & DACT) && a.bias) return -1;                  // the DACT variants leave the bias out (register room)
-    if (a.bias && a.N > BIAS_MAX_N) return -1;               // the bias vector lives in LDS
-    const int cus = device_cus() / 8 * 8;
-    if (cus < 8) return -1;
-    // Tile height: the one whose rounds of tiles cost least.  A tile's time is not proportional to its rows: the stamped
-    // k-tile (profiles/r3/gemm8p_ktile_trace.txt) takes 2 663 clocks at 256 rows and 2 487 at 224 (0.934, not 0.875) -- the
-    // per-section hand-off does not shrink with the tile; 192 rows extrapolated.  With these weights N = 3 072 at M = 50 176
-    // takes 256-row tiles (10 rounds x 1 000 < 11 x 934; measured 234 vs 238 us and 219 vs 226 us), N = 768 stays at 224.
-    const int nt = a.N / 256;
-    long best = -1;
-    int ni = 0;
-    // Any M >= one tile: a height that does not divide M makes the last row tile overlap its predecessor (kernel header),
-    // which costs that tile's share of recomputed rows, i.e. it is priced as one more tile.  The overlapping tile reads
-    // residual / aux_in rows another workgroup may be storing to if C aliases them: refused then.
-    const bool aliased = a.c == a.residual || a.c == a.aux_in;
-    for (int cand : {8, 7, 6}) {
-        if (a.M < 32 * cand || (a.M % (32 * cand) && aliased)) continue;
-        const long tiles = long((a.M + 32 * cand - 1) / (32 * cand)) * nt;
-        const long cost = ((tiles + cus - 1) / cus) * (cand == 8 ? 1000 : cand == 7 ? 934 : 870);
-        if (best < 0 || cost < best) { best = cost; ni = cand; }
-    }
-    if (!ni) return -1;
-    if (a.force_generic == 8) { if (a.M < 256 || (a.M % 256 && aliased)) return -1; ni = 8; }    // tests: pin the 256-row tile
-    if (a.force_generic == 9) { if (a.M < 224 || (a.M % 224 && aliased)) return -1; ni = 7; }    // tests: pin the 224-row tile
-    if (a.force_generic == 10) { if (a.M < 192 || (a.M % 192 && aliased)) return -1; ni = 6; }   // tests: pin the 192-row tile
-    const int nparts = 2 * ((a.M + 32 * ni - 1) / (32 * ni));            // CSUM: one partial row per (row tile, wave group)
-    if (mask & CSUM) {
-        const int64_t need = int64_t(nparts) * a.N * int64_t(sizeof(float));
-        if (!a.workspace || a.workspace_bytes < need || (reinterpret_cast<uintptr_t>(a.workspace) & 15)) return -1;
-    }
-    const int rc = ni == 8 ? launch_mask<8>(a, mask, cus, s) : ni == 7 ? launch_mask<7>(a, mask, cus, s) : launch_mask<6>(a, mask, cus, s);
-    if (rc == 0 && (mask & CSUM))
-        return launch_colsum_reduce(static_cast<const float *>(a.workspace), nparts, a.N, a.colsum_out, a.colsum_bf16, s);
-    return rc;
-}
-
 }  // namespace sfcvit
-

@@ -8,11 +8,12 @@
 #pragma once
 #include "../../include/sfcvit.h"
 #include "device_common.h"
+#include "dispatch.h"
 
 namespace sfcvit {
 namespace gemm_core {
 
-constexpr int BM = 128, BN = 128, BK = 64;
+constexpr int BM = GEN_TILE, BN = GEN_TILE, BK = GEN_BK;   // dispatch.h
 constexpr int THREADS = 256;
 constexpr int TILE_BYTES = 128 * 64 * 2;  // one operand tile
 

@@ -1,7 +1,8 @@
 // Sanitizer driver for the HOST-ONLY code of libsfcvit_hip.so ("Race detection / sanitizers": GPU ASan is not
 // available on this pool, so the native host code gets a CPU-side -fsanitize=address,undefined build of its own):
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
-//   host part), the error path of common.cpp.  Every output buffer is a heap block of EXACTLY the documented size, so that
+//   host part), the error path of common.cpp, and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid,
+//   splits and post passes each GEMM / attention shape of the benchmarked models gets).  Every output buffer is a heap block of EXACTLY the documented size, so that
 // an off-by-one in a generator or in the descriptor writer is a heap-buffer-overflow report instead of silent corruption.
 // Built and run by `make asan` (tests/test_host_cpu.py::test_host_code_is_clean_under_address_sanitizer).  No GPU call.
 #include <cstdint>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../../include/sfcvit.h"
+#include "../dispatch.h"
 
 static int g_fail = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { std::fprintf(stderr, "host_check: " __VA_ARGS__); std::fprintf(stderr, " (%s:%d)\n", __FILE__, __LINE__); g_fail++; } } while (0)
@@ -22,6 +24,235 @@ static bool is_permutation(const int32_t *t, int n2) {
         seen[t[i]] = 1;
     }
     return true;
+}
+
+// ---- kernel selection (dispatch.cpp), cus = 256 as on the MI355X; the plans read no pointer, so fake aligned ones serve ----
+using namespace sfcvit;
+static void *ptr(int i) { return reinterpret_cast<void *>(uintptr_t(0x100000) * uintptr_t(i + 1)); }
+
+struct G {                  // one sfcvit_gemm call as sfcvit.ops makes it
+    int M, N, K, akm, bkm, fg;
+    unsigned epi;           // E_* below
+    int splitk;
+    const char *name;       // expected kernel_name, or an error message prefix when it starts with "gemm:"
+    int grid, splits, post; // expected grid / splits (0: not checked); post: P_* bits that must be on (all others off)
+};
+enum { E_BIAS = 1, E_RES = 2, E_DROP = 4, E_RELU = 8, E_DACT = 16, E_CSUM = 32, E_BITS = 64, E_GELU = 128 };
+enum { P_PARTS = 1, P_REDUCE = 2, P_ACTMASK = 4, P_COLSUM = 8, P_TAIL = 16 };
+
+static sfcvit_gemm_args gemm_args(const G &g) {
+    sfcvit_gemm_args a{};
+    a.a = ptr(0); a.b = ptr(1); a.c = ptr(2);
+    a.M = g.M; a.N = g.N; a.K = g.K;
+    a.lda = g.akm ? g.M : g.K; a.ldb = g.bkm ? g.N : g.K; a.ldc = g.N;
+    a.a_kmajor = g.akm; a.b_kmajor = g.bkm;
+    a.force_generic = g.fg;
+    a.splitk = g.splitk;
+    if (g.splitk > 1) { a.workspace = ptr(3); a.workspace_bytes = int64_t((g.splitk + 7) / 8 * 8) * g.M * g.N * 4; }
+    if (g.epi & E_BIAS) a.bias = ptr(4);
+    if (g.epi & E_RES) { a.residual = ptr(5); a.ldr = g.N; }
+    if (g.epi & E_DROP) { a.dropout_p = 0.1f; a.dropout_seed = 7; }
+    if (g.epi & E_RELU) a.act = SFCVIT_ACT_RELU;
+    if (g.epi & E_GELU) a.act = SFCVIT_ACT_GELU;
+    if (g.epi & E_DACT) { a.dact = SFCVIT_ACT_RELU; a.aux_in = ptr(6); a.ldaux = g.N; a.dact_scale = 1.f / 0.9f; }
+    if (g.epi & E_CSUM) { a.colsum_out = ptr(7); a.workspace = ptr(3); a.workspace_bytes = int64_t(1) << 30; }
+    if (g.epi & E_BITS) { a.actmask = ptr(8); a.ld_actmask = g.N / 8; }
+    return a;
+}
+
+static void check_gemm(const G &g, const Knobs &k, const char *what) {
+    const sfcvit_gemm_args a = gemm_args(g);
+    const GemmPlan p = gemm_plan(a, 256, k);
+    if (!std::strncmp(g.name, "gemm:", 5)) {
+        CHECK(p.err == SFCVIT_EINVAL && std::strstr(p.msg, g.name), "%s: want error '%s', got %d '%s'", what, g.name, p.err, p.msg);
+        return;
+    }
+    char name[96];
+    kernel_name(p, name, sizeof(name));
+    CHECK(p.err == SFCVIT_OK && !std::strcmp(name, g.name), "%s: want %s, got %s (%s)", what, g.name, name, p.msg);
+    if (g.grid) CHECK(p.grid == g.grid, "%s: grid %d, want %d", what, p.grid, g.grid);
+    if (g.splits) CHECK(p.splits == g.splits, "%s: splits %d, want %d", what, p.splits, g.splits);
+    const int post = (p.colsum_parts ? P_PARTS : 0) | (p.reduce_slabs ? P_REDUCE : 0) | (p.actmask_pass ? P_ACTMASK : 0) |
+                     (p.colsum_pass ? P_COLSUM : 0) | (p.tail_slab >= 0 ? P_TAIL : 0);
+    CHECK(post == g.post, "%s: post passes %#x, want %#x", what, post, g.post);
+}
+
+static void check_dispatch() {
+    const Knobs dflt;
+    // ViT-B/16 @ 224, batch 256 (M = 256 x 196 tokens), training (dropout 0.1) -- the benched step
+    const int M = 50176;
+    const G vit_b[] = {
+        {M, 2304, 768, 0, 0, 0, E_BIAS, 1, "gemm8p_kernel<8, 0, true>", 256, 1, 0},                               // in_proj
+        {M, 768, 768, 0, 0, 0, E_BIAS | E_RES | E_DROP, 1, "gemm8p_kernel<7, 6, true>", 256, 1, 0},              // out_proj
+        {M, 3072, 768, 0, 0, 0, E_BIAS | E_RELU | E_DROP | E_BITS, 1, "gemm8p_kernel<8, 35, true>", 256, 1, 0},   // linear1
+        {M, 768, 3072, 0, 0, 0, E_BIAS | E_RES | E_DROP, 1, "gemm8p_kernel<7, 6, true>", 256, 1, 0},             // linear2
+        {M, 3072, 768, 0, 0, 0, E_DACT | E_CSUM | E_BITS, 1, "gemm8p_kernel<8, 56, true>", 256, 1, P_PARTS},      // linear2 dX (+ db1)
+        {M, 768, 3072, 0, 0, 0, E_RES, 1, "gemm8p_kernel<7, 4, true>", 256, 1, 0},                               // linear1 dX
+        {M, 768, 768, 0, 0, 0, 0, 1, "gemm8p_kernel<7, 0, true>", 256, 1, 0},                                    // out_proj dX
+        {M, 768, 2304, 0, 0, 0, E_RES, 1, "gemm8p_kernel<7, 4, true>", 256, 1, 0},                               // in_proj dX
+        {2304, 768, M, 1, 1, 0, 0, 9, "gemm8p_km_kernel<true>", 248, 9, P_REDUCE},                                // dW in_proj
+        {768, 768, M, 1, 1, 0, 0, 28, "gemm8p_km_kernel<true>", 256, 28, P_REDUCE},                              // dW out_proj
+        {3072, 768, M, 1, 1, 0, 0, 7, "gemm8p_km_kernel<true>", 256, 7, P_REDUCE},                               // dW linear1
+        {768, 3072, M, 1, 1, 0, 0, 7, "gemm8p_km_kernel<true>", 256, 7, P_REDUCE},                               // dW linear2
+        // eval / no dropout
+        {M, 768, 768, 0, 0, 0, E_BIAS | E_RES, 1, "gemm8p_kernel<7, 4, true>", 256, 1, 0},
+        {M, 3072, 768, 0, 0, 0, E_BIAS | E_RELU | E_BITS, 1, "gemm8p_kernel<8, 33, true>", 256, 1, 0},
+        {M, 3072, 768, 0, 0, 0, E_BIAS | E_RELU, 1, "gemm8p_kernel<8, 1, true>", 256, 1, 0},
+        // RELU + RES has no persistent epilogue: the ring kernel, and the bits from a pass over C
+        {M, 768, 768, 0, 0, 0, E_RES | E_RELU | E_BITS, 1, "gemm256_kernel<false, false, 128, false>", 1176, 1, P_ACTMASK},
+        // batch 64 (M = 64 x 196), the shape the GPU tests assert (test_dropout_gpu BENCHED_KERNELS, test_parity_gpu
+        // vit_b_hilbert224_b64; both ignore the tile height): 224-row tiles at N = 2 304 / 3 072, 192-row at N = 768
+        {12544, 2304, 768, 0, 0, 0, E_BIAS, 1, "gemm8p_kernel<7, 0, true>", 256, 1, 0},
+        {12544, 768, 768, 0, 0, 0, E_BIAS | E_RES | E_DROP, 1, "gemm8p_kernel<6, 6, true>", 256, 1, 0},
+        {12544, 3072, 768, 0, 0, 0, E_BIAS | E_RELU | E_DROP | E_BITS, 1, "gemm8p_kernel<7, 35, true>", 256, 1, 0},
+        {12544, 3072, 768, 0, 0, 0, E_BIAS | E_RELU | E_BITS, 1, "gemm8p_kernel<7, 33, true>", 256, 1, 0},
+        {12544, 3072, 768, 0, 0, 0, E_DACT | E_CSUM | E_BITS, 1, "gemm8p_kernel<7, 56, true>", 256, 1, P_PARTS},
+        {12544, 768, 3072, 0, 0, 0, E_RES, 1, "gemm8p_kernel<6, 4, true>", 256, 1, 0},
+        {12544, 768, 768, 0, 0, 0, 0, 1, "gemm8p_kernel<6, 0, true>", 256, 1, 0},
+        {2304, 768, 12544, 1, 1, 0, 0, 9, "gemm8p_km_kernel<true>", 248, 9, P_REDUCE},
+        // the head (rank 64, 1 536 outputs, 1 000 classes): off the persistent kernels
+        {M, 64, 768, 0, 0, 0, 0, 1, "gemm_kernel<false, false, false>", 392, 1, 0},                              // h = z W_emb^T
+        {256, 1536, 12544, 0, 0, 0, 0, 8, "gemm256_kernel<false, false, 128, false>", 12, 8, P_REDUCE},         // y1
+        {256, 1000, 1536, 0, 0, 0, E_BIAS, 1, "gemm_kernel<false, false, false>", 16, 1, 0},                     // logits
+        {1000, 1536, 256, 1, 1, 0, 0, 1, "gemm_kernel<true, true, false>", 96, 1, 0},                            // dW classifier
+        {256, 1536, 1000, 0, 1, 0, 0, 1, "gemm_kernel<false, true, false>", 24, 1, 0},                           // d(a)
+        {1536, 12544, 256, 1, 1, 0, 0, 1, "gemm_kernel<true, true, false>", 0, 1, 0},                            // dW_seq
+        {256, 12544, 1536, 0, 1, 0, 0, 1, "gemm_kernel<false, true, false>", 0, 1, 0},                           // dh
+        {64, 768, M, 1, 1, 0, 0, 56, "gemm_kernel<true, true, false>", 336, 56, P_REDUCE},                       // dW_emb
+        {M, 768, 64, 0, 0, 0, 0, 1, "gemm256_kernel<false, false, 128, false>", 1176, 1, 0},                     // dz
+        // ViT-Tiny widths (D = 192, MLP 768, 4 tokens at 32 px): no persistent-kernel shape
+        {1024, 576, 192, 0, 0, 0, E_BIAS, 1, "gemm_kernel<false, false, false>", 0, 1, 0},                       // in_proj
+        {1024, 768, 192, 0, 0, 0, E_BIAS | E_RELU, 1, "gemm256_kernel<false, false, 128, false>", 24, 1, 0},    // linear1
+        {1024, 768, 192, 0, 0, 0, E_BIAS | E_GELU, 1, "gemm256_kernel<false, false, 128, true>", 24, 1, 0},     // GELU epilogue
+        // weight gradient with K % 128 != 0 (batch 100): the last 16 rows as one more slab
+        {768, 768, 19600, 1, 1, 0, 0, 28, "gemm8p_km_kernel<true>", 0, 26, P_REDUCE | P_TAIL},
+        // every force_generic value
+        {M, 768, 768, 0, 0, SFCVIT_GEMM_GENERIC, 0, 1, "gemm_kernel<false, false, false>", 2352, 1, 0},
+        {M, 768, 768, 0, 0, SFCVIT_GEMM_RING, 0, 1, "gemm256_kernel<false, false, 128, false>", 1176, 1, 0},
+        {M, 2304, 768, 0, 0, SFCVIT_GEMM_RING, 0, 1, "gemm256_kernel<false, false, 256, false>", 1764, 1, 0},
+        {M, 2304, 768, 0, 0, SFCVIT_GEMM_RING_256x128, 0, 1, "gemm256_kernel<false, false, 128, false>", 3528, 1, 0},
+        {M, 768, 768, 0, 0, SFCVIT_GEMM_RING_256x256, 0, 1, "gemm256_kernel<false, false, 256, false>", 588, 1, 0},
+        {M, 768, 768, 0, 1, SFCVIT_GEMM_RING, 0, 1, "gemm256_kernel<false, true, 128, false>", 0, 1, 0},
+        {M, 768, 768, 0, 0, SFCVIT_GEMM_P8_256, 0, 1, "gemm8p_kernel<8, 0, true>", 256, 1, 0},
+        {M, 768, 768, 0, 0, SFCVIT_GEMM_P8_224, 0, 1, "gemm8p_kernel<7, 0, true>", 256, 1, 0},
+        {M, 768, 768, 0, 0, SFCVIT_GEMM_P8_192, 0, 1, "gemm8p_kernel<6, 0, true>", 256, 1, 0},
+        {2304, 768, M, 1, 1, SFCVIT_GEMM_P8_256, 0, 9, "gemm8p_km_kernel<true>", 248, 9, P_REDUCE},
+        {M, 64, 768, 0, 0, SFCVIT_GEMM_P8_256, 0, 1, "gemm: shape / options not eligible for the persistent 8-phase kernel", 0, 0, 0},
+        {M, 768, 768, 0, 0, SFCVIT_GEMM_AUTO, E_GELU | E_BIAS, 1, "gemm256_kernel<false, false, 128, true>", 0, 1, 0},
+        // argument checks
+        {M, 768, 770, 0, 0, 0, 0, 1, "gemm: K=770 must be a multiple of 8", 0, 0, 0},
+        {M, 768, 768, 0, 0, 0, E_BIAS, 4, "gemm: split-K supports no epilogue", 0, 0, 0},
+    };
+    char what[64];
+    for (const G &g : vit_b) {
+        std::snprintf(what, sizeof(what), "gemm %dx%dx%d fg %d epi %#x", g.M, g.N, g.K, g.fg, g.epi);
+        check_gemm(g, dflt, what);
+    }
+    {   // SFCVIT_GEMM_2PHASE=0: the four-phase schedule of both persistent forms
+        Knobs k;
+        k.gemm_2phase = false;
+        check_gemm({M, 768, 768, 0, 0, 0, 0, 1, "gemm8p_kernel<7, 0, false>", 256, 1, 0}, k, "2PHASE=0 gemm8p");
+        check_gemm({2304, 768, M, 1, 1, 0, 0, 9, "gemm8p_km_kernel<false>", 248, 9, P_REDUCE}, k, "2PHASE=0 km");
+    }
+    {   // persistent GEMM: tile walk, start-up stagger and SFCVIT_GEMM_WALK / _STAGGER / SFCVIT_RESERVE_CUS
+        auto plan = [](const G &g, const Knobs &k) { return gemm_plan(gemm_args(g), 256, k); };
+        const G qkv = {M, 2304, 768, 0, 0, 0, E_BIAS, 1, "", 0, 0, 0}, proj = {M, 768, 768, 0, 0, 0, 0, 1, "", 0, 0, 0};
+        const G one_tile = {256, 256, 256, 0, 0, 0, 0, 1, "", 0, 0, 0}, dwo = {768, 768, M, 1, 1, 0, 0, 28, "", 0, 0, 0};
+        GemmPlan p = plan(qkv, dflt);
+        CHECK(p.walk == 6 && p.stag_slots == 4 && p.stag_ticks == 200, "qkv: walk %d stagger %d,%d", p.walk, p.stag_slots, p.stag_ticks);
+        p = plan(proj, dflt);
+        CHECK(p.walk == 0 && p.stag_slots == 4 && p.stag_ticks == 200, "out_proj: walk %d stagger %d,%d", p.walk, p.stag_slots, p.stag_ticks);
+        p = plan(one_tile, dflt);
+        CHECK(p.stag_ticks == 0, "one tile per workgroup: stagger ticks %d", p.stag_ticks);
+        Knobs k;
+        k.gemm_walk = 0;
+        k.gemm_stagger_slots = 0;
+        k.gemm_stagger_ticks = 100;
+        p = plan(qkv, k);
+        CHECK(p.walk == 0 && p.stag_slots == 1 && p.stag_ticks == 100, "WALK=0 STAGGER=0,100: walk %d stagger %d,%d", p.walk, p.stag_slots, p.stag_ticks);
+        k = Knobs();
+        k.reserve_cus = 16;                                     // 240 CUs / 9 tiles: 26 k-ranges of 32 k-tiles -> 25
+        p = plan(dwo, k);
+        CHECK(p.splits == 25 && p.k_per_split == 32 && p.grid == 232, "RESERVE_CUS=16: splits %d kps %d grid %d", p.splits, p.k_per_split, p.grid);
+        k.reserve_cus = 200;                                    // more than half the CUs: ignored
+        p = plan(dwo, k);
+        CHECK(p.splits == 28 && p.k_per_split == 28 && p.grid == 256, "RESERVE_CUS=200: splits %d kps %d grid %d", p.splits, p.k_per_split, p.grid);
+    }
+    {   // null operand: the message the Python test reads
+        sfcvit_gemm_args a{};
+        const GemmPlan p = gemm_plan(a, 256, dflt);
+        CHECK(p.err == SFCVIT_EINVAL && std::strstr(p.msg, "null"), "gemm null operand: %d '%s'", p.err, p.msg);
+    }
+
+    // attention: (B, N, H, hd, p, bwd, knobs) -> kernel
+    struct A { int B, N, H, hd; float p; bool bwd; int knob; const char *name; Colsum colsum; };
+    enum { K_NONE, K_LONG0, K_FUSED0, K_DQPASS, K_PERSIST0 };
+    const A attn[] = {
+        {256, 196, 12, 64, 0.1f, false, K_NONE, "attn_seq_fwd_kernel<13, true>", Colsum::NONE},            // ViT-B / 256
+        {256, 196, 12, 64, 0.f, false, K_NONE, "attn_seq_fwd_kernel<13, false>", Colsum::NONE},
+        {256, 196, 12, 64, 0.1f, true, K_NONE, "attn_seq_bwd_fused_kernel<13, true>", Colsum::PARTIALS},
+        {64, 196, 12, 64, 0.1f, false, K_NONE, "attn_seq_fwd_kernel<13, true>", Colsum::NONE},              // batch 64
+        {64, 196, 12, 64, 0.1f, true, K_NONE, "attn_seq_bwd_fused_kernel<13, true>", Colsum::PARTIALS},
+        {256, 196, 12, 64, 0.f, true, K_NONE, "attn_seq_bwd_fused_kernel<13, false>", Colsum::PARTIALS},
+        {256, 196, 12, 64, 0.1f, true, K_DQPASS, "attn_seq_bwd_fused_kernel<13, true>", Colsum::PARTIALS_QPASS},
+        {256, 196, 12, 64, 0.1f, true, K_FUSED0, "attn_seq_bwd_kv_kernel<13>", Colsum::PASS},
+        {64, 576, 16, 64, 0.1f, false, K_NONE, "attn_long_fwd_kernel<36>", Colsum::NONE},                  // ViT-L/16 @ 384
+        {64, 576, 16, 64, 0.1f, true, K_NONE, "attn_long_bwd_kv_kernel", Colsum::PARTIALS},
+        {64, 577, 16, 64, 0.1f, false, K_NONE, "attn_long_fwd_kernel<0>", Colsum::NONE},
+        {64, 576, 16, 64, 0.1f, false, K_LONG0, "attn_fwd_kernel", Colsum::NONE},
+        {64, 576, 16, 64, 0.1f, true, K_LONG0, "attn_bwd_kv_kernel", Colsum::PASS},
+        {256, 4, 3, 64, 0.1f, false, K_NONE, "attn_seq_fwd_kernel<0, true>", Colsum::NONE},               // ViT-Tiny @ 32
+        {256, 4, 3, 64, 0.1f, true, K_NONE, "attn_seq_bwd_fused_kernel<0, true>", Colsum::PARTIALS},
+        {8, 240, 4, 64, 0.f, true, K_NONE, "attn_seq_bwd_kv_kernel<0>", Colsum::PASS},                     // 224 < N <= 256
+        {8, 1024, 4, 64, 0.f, false, K_NONE, "attn_fwd_kernel", Colsum::NONE},                             // N > 608: tiled
+        {8, 1024, 4, 64, 0.f, true, K_NONE, "attn_bwd_kv_kernel", Colsum::PASS},
+        {8, 196, 4, 128, 0.f, false, K_NONE, "attn_wide_fwd_kernel<2>", Colsum::NONE},                      // wide head dims
+        {8, 196, 4, 128, 0.1f, true, K_NONE, "attn_wide_bwd_kv_kernel<2>", Colsum::PASS},
+        {8, 128, 4, 192, 0.f, false, K_NONE, "attn_wide_fwd_kernel<3>", Colsum::NONE},
+        {8, 128, 4, 256, 0.f, true, K_NONE, "attn_wide_bwd_kv_kernel<4>", Colsum::PASS},
+        {8, 196, 4, 192, 0.f, false, K_NONE, "attention: head dim 192 with N = 196 needs 168 KiB of LDS", Colsum::NONE},
+        {8, 196, 4, 256, 0.f, true, K_NONE, "attention: head dim 256 with N = 196 needs 226 KiB of LDS", Colsum::NONE},
+        {8, 300, 4, 128, 0.f, false, K_NONE, "attention: head dim 128 with N = 300 needs", Colsum::NONE},
+        {8, 196, 4, 96, 0.f, false, K_NONE, "attention_fwd: head dim 96 not supported", Colsum::NONE},
+    };
+    for (const A &t : attn) {
+        sfcvit_attn_args a{};
+        a.qkv = ptr(0); a.out = ptr(1); a.lse = static_cast<float *>(ptr(2));
+        a.dout = ptr(3); a.dqkv = ptr(4); a.delta = static_cast<float *>(ptr(5));
+        a.B = t.B; a.N = t.N; a.H = t.H; a.hd = t.hd; a.dropout_p = t.p;
+        if (t.bwd) { a.colsum_out = ptr(6); a.colsum_part = static_cast<float *>(ptr(7)); a.colsum_part_bytes = int64_t(1) << 40; }
+        Knobs k;
+        k.attn_long = t.knob != K_LONG0;
+        k.attn_bwd_fused = t.knob != K_FUSED0;
+        k.attn_dq_in_kernel = t.knob != K_DQPASS;
+        k.attn_bwd_persist = t.knob != K_PERSIST0;
+        const AttnPlan p = t.bwd ? attn_bwd_plan(a, 256, k) : attn_fwd_plan(a, k);
+        std::snprintf(what, sizeof(what), "attention %s B %d N %d H %d hd %d", t.bwd ? "bwd" : "fwd", t.B, t.N, t.H, t.hd);
+        if (!std::strncmp(t.name, "attention", 9)) {
+            CHECK(p.err == SFCVIT_EINVAL && std::strstr(p.msg, t.name), "%s: want error '%s', got %d '%s'", what, t.name, p.err, p.msg);
+            continue;
+        }
+        char name[96];
+        kernel_name(p, name, sizeof(name));
+        CHECK(p.err == SFCVIT_OK && !std::strcmp(name, t.name), "%s: want %s, got %s (%s)", what, t.name, name, p.msg);
+        CHECK(p.colsum == t.colsum, "%s: column-sum mode %d, want %d", what, int(p.colsum), int(t.colsum));
+    }
+    {   // the one-pass backward's grid, queue and stagger: persistent (one workgroup per CU, items from the counters, no
+        // stagger) and one workgroup per item (SFCVIT_ATTN_BWD_PERSIST=0: two slots)
+        sfcvit_attn_args a{};
+        a.qkv = ptr(0); a.out = ptr(1); a.lse = static_cast<float *>(ptr(2));
+        a.dout = ptr(3); a.dqkv = ptr(4); a.delta = static_cast<float *>(ptr(5));
+        a.B = 256; a.N = 196; a.H = 12; a.hd = 64; a.dropout_p = 0.1f;
+        AttnPlan p = attn_bwd_plan(a, 256, dflt);
+        CHECK(p.grid == 256 && p.queue && p.per == 256 && p.ticks == 450 && p.npad == 224 && p.dq_sums == 1,
+              "fused bwd: grid %d queue %d per %d ticks %d npad %d", p.grid, p.queue, p.per, p.ticks, p.npad);
+        CHECK(p.lds == size_t(224) * FUSED_ROW_BYTES + FUSED_EXTRA + FUSED_POST_BYTES, "fused bwd: lds %zu", p.lds);
+        CHECK(p.colsum == Colsum::NONE, "fused bwd without colsum_out: mode %d", int(p.colsum));
+        Knobs k;
+        k.attn_bwd_persist = false;
+        p = attn_bwd_plan(a, 256, k);
+        CHECK(p.grid == 3072 && !p.queue && p.per == 128, "fused bwd, PERSIST=0: grid %d queue %d per %d", p.grid, p.queue, p.per);
+    }
 }
 
 int main() {
@@ -90,6 +321,7 @@ int main() {
         CHECK(sfcvit_tile_descriptors(nullptr, 4, 256, 32, out, 64) < 0, "tile descriptors: null accepted");
     }
     CHECK(sfcvit_abi_version() == SFCVIT_ABI_VERSION, "abi version");
+    check_dispatch();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     std::printf("host_check ok\n");
     return 0;

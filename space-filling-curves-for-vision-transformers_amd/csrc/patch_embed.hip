@@ -455,7 +455,7 @@ extern "C" int sfcvit_tokens_gather_tiles(const void *x, const int32_t *pix, con
     const auto *xp = static_cast<const float *>(x);
     auto *tp = static_cast<uint16_t *>(tokens);
     const int HW = H * W;
-    static const int upw = [] { const char *e = getenv("SFCVIT_GATHER_U"); return e && atoi(e) == 2 ? 2 : 1; }();   // images per wave (A/B: 2 = fewer, longer workgroups)
+    static const int upw = env_int("SFCVIT_GATHER_U", 1) == 2 ? 2 : 1;   // images per wave (A/B: 2 = fewer, longer workgroups)
     const dim3 grid((N + 1) / 2, (B + 4 * upw - 1) / (4 * upw));
     if (grid.y > 65535) return fail(SFCVIT_EINVAL, "tokens_gather_tiles: batch %d too large", B);
     const uint32_t wmagic = uint32_t((uint64_t(1) << 32) / uint32_t(W)) + 1;
@@ -465,7 +465,7 @@ extern "C" int sfcvit_tokens_gather_tiles(const void *x, const int32_t *pix, con
     // shares HBM with the gather (75.8 us against 42.1 us with clean caches; a plain fp32 -> bf16 cast of the image suffers
     // the same: 69 vs 37 us).  Streaming loads do not allocate: 46.0 us; with streaming stores 43.2 us alone, 44.0 us in
     // the step (profiles/r4/gather_ab.txt).  SFCVIT_GATHER_NT=0..3 for the A/B.
-    static const int nt = [] { const char *e = getenv("SFCVIT_GATHER_NT"); return e ? atoi(e) : 3; }();
+    static const int nt = env_int("SFCVIT_GATHER_NT", 3);
 #define TILES(CC, NTV) do { if (upw == 2) hipLaunchKernelGGL((tokens_gather_tiles_kernel<CC, NTV, 2>), grid, dim3(TG_THREADS), lds, s, xp, pix, order, origin, tp, B, HW, W, wmagic, N); \
                             else hipLaunchKernelGGL((tokens_gather_tiles_kernel<CC, NTV, 1>), grid, dim3(TG_THREADS), lds, s, xp, pix, order, origin, tp, B, HW, W, wmagic, N); } while (0)
 #define TILES_C(CC) do { if (nt == 1) TILES(CC, 1); else if (nt == 2) TILES(CC, 2); else if (nt == 3) TILES(CC, 3); else TILES(CC, 0); } while (0)

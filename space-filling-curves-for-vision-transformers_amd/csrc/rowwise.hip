@@ -454,7 +454,7 @@ __global__ __launch_bounds__(RED_THREADS) void ln_bwd_reduce(const float *__rest
 // SFCVIT_LN_COLS=0: the 16-byte-vector kernel also at D = 768 / 1 024 (A/B in tools/bench_rowwise.py; at D = 1 024, ViT-L, the
 // float-pair form gains 2-6 %: 45.3 -> 44.6 us, with dropout output 61.4 -> 57.9 us at M = 36 864)
 bool ln_bwd_cols(int D) {
-    static const bool on = [] { const char *e = getenv("SFCVIT_LN_COLS"); return !(e && e[0] == '0'); }();
+    static const bool on = !env_off("SFCVIT_LN_COLS");
     return on && (D == 768 || D == 1024);
 }
 
@@ -463,7 +463,7 @@ bool ln_bwd_cols(int D) {
 // of the latter (with dropout output and column sums 70.3 / 77.2 and 59.0 / 57.3).
 int ln_bwd_blocks(int M, int D) {
     const int want = (M + WAVES - 1) / WAVES;
-    static const int env = [] { const char *e = getenv("SFCVIT_LN_BLOCKS"); return e ? atoi(e) : 0; }();   // tuning knob
+    static const int env = env_int("SFCVIT_LN_BLOCKS", 0);   // tuning knob
     const int cap = env > 0 ? env : (ln_bwd_cols(D) && D == 768 ? 768 : 512);    // (D = 1 024: 179-194 registers, two waves per SIMD)
     return want < cap ? want : cap;
 }
@@ -858,7 +858,7 @@ extern "C" int sfcvit_layernorm_fwd(const void *x, const void *gamma, const void
     const auto *gp = static_cast<const uint16_t *>(gamma);
     const auto *bp = static_cast<const uint16_t *>(beta);
     auto *yp = static_cast<uint16_t *>(y);
-    static const int two_rows = [] { const char *e = getenv("SFCVIT_LN_FWD_TWO_ROWS"); return e ? atoi(e) : 1; }();
+    static const int two_rows = env_int("SFCVIT_LN_FWD_TWO_ROWS", 1);
     if (two_rows && (D == 768 || D == 1024) && M >= 4096) {
         const dim3 grid2((M + 2 * WAVES - 1) / (2 * WAVES));
         if (D == 768) hipLaunchKernelGGL(ln_fwd2_kernel<3>, grid2, block, 0, s, xp, gp, bp, yp, mean, rstd, M, D, eps);
@@ -1127,7 +1127,7 @@ extern "C" int sfcvit_adamw_step(const sfcvit_adamw_args *a, void *stream) {
     const float bc2 = 1.f - powf(a->beta2, float(a->step));
     if (!aligned16(a->param) || !aligned16(a->master) || !aligned16(a->grad) || !aligned16(a->m) || !aligned16(a->v))
         return fail(SFCVIT_EINVAL, "adamw: buffers must be 16-byte aligned");
-    static const int nt = [] { const char *e = getenv("SFCVIT_ADAMW_NT"); return e ? atoi(e) & 3 : 3; }();
+    static const int nt = env_int("SFCVIT_ADAMW_NT", 3) & 3;
 #define ADAMW(NT) hipLaunchKernelGGL(adamw_kernel<NT>, dim3(grid_for((a->n + 7) / 8)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *a, bc1, 1.f / sqrtf(bc2))
     if (nt == 3) ADAMW(3); else if (nt == 2) ADAMW(2); else if (nt == 1) ADAMW(1); else ADAMW(0);
 #undef ADAMW

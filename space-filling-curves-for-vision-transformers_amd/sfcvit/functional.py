@@ -416,7 +416,7 @@ def attention(qkv, n_heads):
 
 
 def _fast_gemm_shape(M, N, K):
-    """Shapes the persistent 8-phase GEMM takes (csrc/gemm8p.hip: gemm8p_dispatch)."""
+    """Shapes the persistent 8-phase GEMM takes (csrc/dispatch.cpp: plan_p8)."""
     return M >= 192 and N % 256 == 0 and K % 128 == 0 and K >= 256
 
 

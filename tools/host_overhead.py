@@ -13,7 +13,7 @@ import bench  # noqa: E402
 from sfcvit.training import FusedAdamW, mixup_soft_targets, train_step  # noqa: E402
 
 workload = sys.argv[1] if len(sys.argv) > 1 else "vit_b16_224_hilbert"
-img, patch, D, depth, heads, mlp, classes, batch = bench.WORKLOADS[workload]
+tok, img, patch, D, depth, heads, mlp, classes, batch, _ = bench.WORKLOADS[workload]
 model = bench.build(workload, 0.1).to("cuda", dtype=torch.bfloat16).train()
 opt = FusedAdamW(model.parameters(), lr=3e-4, weight_decay=5e-5)
 x = torch.randn(batch, 3, img, img, device="cuda")
