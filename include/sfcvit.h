@@ -347,6 +347,17 @@ int64_t sfcvit_attention_colsum_workspace(int B, int N, int H, int hd);
 
 int sfcvit_attention_fwd(const sfcvit_attn_args *a, void *stream);
 int sfcvit_attention_bwd(const sfcvit_attn_args *a, void *stream);
+/* The same for any sequence length: head dims 128 / 192 / 256 whose whole sequence does not fit one CU's LDS (N > 256,
+ * or 192 / 160 for hd 192 / 256), where sfcvit_attention_fwd / _bwd refuse, run on streaming kernels that loop over
+ * 64-row blocks (attn_wide_stream_*); every other shape runs exactly what sfcvit_attention_fwd / _bwd run.  Column sums
+ * (colsum_out) work as there. */
+int sfcvit_attention_fwd_any(const sfcvit_attn_args *a, void *stream);
+int sfcvit_attention_bwd_any(const sfcvit_attn_args *a, void *stream);
+/* HOST: the plan of sfcvit_attention_fwd (bwd = 0) / _bwd (bwd != 0), or of their _any forms (any_length != 0), for
+ * these arguments and the current environment switches, without touching a device: writes the name of the main kernel
+ * (as sfcvit_last_attn_kernel would report it) into buf and returns SFCVIT_OK, or returns the refusal's code with the
+ * message in sfcvit_last_error().  Tensors are checked for null / alignment only, never read. */
+int sfcvit_attention_plan(const sfcvit_attn_args *a, int bwd, int any_length, char *buf, int n);
 /* HOST: name of the main kernel the calling thread's last sfcvit_attention_fwd / _bwd launched, as rocprofv3 prints it
  * (e.g. "attn_seq_bwd_fused_kernel<13, true>"): tests assert through it that a shape ran on the production kernel. */
 int sfcvit_last_attn_kernel(char *buf, int n);

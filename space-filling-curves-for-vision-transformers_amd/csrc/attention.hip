@@ -300,7 +300,8 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_q_kernel(const sfcvit_attn_a
 
 }  // namespace
 
-// The plan's launchers (dispatch.cpp): attention_seq.hip, attention_bwd_fused.hip, attention_wide.hip, attention_long.hip.
+// The plan's launchers (dispatch.cpp): attention_seq.hip, attention_bwd_fused.hip, attention_wide.hip, attention_long.hip,
+// attention_wide_stream.hip.
 int attn_seq_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
 int attn_seq_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
 int attn_seq_bwd_fused(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
@@ -308,25 +309,49 @@ int attn_wide_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
 int attn_wide_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
 int attn_long_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
 int attn_long_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
+int attn_wide_stream_fwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
+int attn_wide_stream_bwd(const AttnPlan &p, const sfcvit_attn_args &a, hipStream_t s);
 
-}  // namespace sfcvit
+namespace {
 
-using namespace sfcvit;
+constexpr int PLAN_CUS = 256;                    // sfcvit_attention_plan: MI355X's CU count (only the name is reported)
 
-extern "C" int sfcvit_attention_fwd(const sfcvit_attn_args *a, void *stream) {
+int attention_fwd(const sfcvit_attn_args *a, void *stream, bool any_length) {
     if (!a) return fail(SFCVIT_EINVAL, "attention_fwd: null pointer");
-    const AttnPlan p = attn_fwd_plan(*a, read_knobs(KNOBS_ATTN_FWD));
+    const AttnPlan p = attn_fwd_plan(*a, read_knobs(KNOBS_ATTN_FWD), any_length);
     if (p.err) return fail(p.err, "%s", p.msg);
     note_attn_kernel(p);
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (p.family) {
     case AttnFamily::WIDE: return attn_wide_fwd(p, *a, s);
+    case AttnFamily::STREAM: return attn_wide_stream_fwd(p, *a, s);
     case AttnFamily::SEQ: return attn_seq_fwd(p, *a, s);
     case AttnFamily::LONG: return attn_long_fwd(p, *a, s);
     default:
         hipLaunchKernelGGL(attn_fwd_kernel, dim3(p.grid, a->H, a->B), dim3(THREADS), 0, s, *a);
         return check_launch("attention_fwd");
     }
+}
+
+int attention_bwd(const sfcvit_attn_args *a, void *stream, bool any_length);
+
+}  // namespace
+}  // namespace sfcvit
+
+using namespace sfcvit;
+
+extern "C" int sfcvit_attention_fwd(const sfcvit_attn_args *a, void *stream) { return attention_fwd(a, stream, false); }
+extern "C" int sfcvit_attention_fwd_any(const sfcvit_attn_args *a, void *stream) { return attention_fwd(a, stream, true); }
+extern "C" int sfcvit_attention_bwd(const sfcvit_attn_args *a, void *stream) { return attention_bwd(a, stream, false); }
+extern "C" int sfcvit_attention_bwd_any(const sfcvit_attn_args *a, void *stream) { return attention_bwd(a, stream, true); }
+
+extern "C" int sfcvit_attention_plan(const sfcvit_attn_args *a, int bwd, int any_length, char *buf, int n) {
+    if (!a || !buf || n <= 0) return fail(SFCVIT_EINVAL, "attention_plan: null pointer");
+    const AttnPlan p = bwd ? attn_bwd_plan(*a, PLAN_CUS, read_knobs(KNOBS_ATTN_BWD), any_length != 0)
+                           : attn_fwd_plan(*a, read_knobs(KNOBS_ATTN_FWD), any_length != 0);
+    if (p.err) return fail(p.err, "%s", p.msg);
+    kernel_name(p, buf, size_t(n));
+    return SFCVIT_OK;
 }
 
 extern "C" int64_t sfcvit_attention_colsum_workspace(int B, int N, int H, int hd) {
@@ -338,9 +363,12 @@ extern "C" int64_t sfcvit_attention_colsum_workspace(int B, int N, int H, int hd
     return fused > generic ? fused : generic;
 }
 
-extern "C" int sfcvit_attention_bwd(const sfcvit_attn_args *a, void *stream) {
+namespace sfcvit {
+namespace {
+
+int attention_bwd(const sfcvit_attn_args *a, void *stream, bool any_length) {
     if (!a) return fail(SFCVIT_EINVAL, "attention_bwd: null pointer");
-    const AttnPlan p = attn_bwd_plan(*a, device_cu_count(), read_knobs(KNOBS_ATTN_BWD));
+    const AttnPlan p = attn_bwd_plan(*a, device_cu_count(), read_knobs(KNOBS_ATTN_BWD), any_length);
     if (p.err) return fail(p.err, "%s", p.msg);
     if (a->colsum_out && (!a->colsum_part || a->colsum_part_bytes < sfcvit_attention_colsum_workspace(a->B, a->N, a->H, a->hd)))
         return fail(SFCVIT_EINVAL, "attention_bwd: colsum_out needs colsum_part of sfcvit_attention_colsum_workspace bytes");
@@ -359,6 +387,7 @@ extern "C" int sfcvit_attention_bwd(const sfcvit_attn_args *a, void *stream) {
     case AttnFamily::FUSED: rc = attn_seq_bwd_fused(p, f, s); break;
     case AttnFamily::LONG: rc = attn_long_bwd(p, f, s); break;
     case AttnFamily::WIDE: rc = attn_wide_bwd(p, *a, s); break;
+    case AttnFamily::STREAM: rc = attn_wide_stream_bwd(p, *a, s); break;
     case AttnFamily::SEQ: rc = attn_seq_bwd(p, *a, s); break;
     case AttnFamily::TILED: {
         const dim3 grid(p.grid, a->H, a->B);
@@ -387,3 +416,6 @@ extern "C" int sfcvit_attention_bwd(const sfcvit_attn_args *a, void *stream) {
     return sfcvit_colsum(a->dqkv, a->B * a->N, Dq, D3, a->colsum_out, a->colsum_bf16, a->colsum_part + size_t(a->B) * D3,
                          a->colsum_part_bytes - head, stream);
 }
+
+}  // namespace
+}  // namespace sfcvit

@@ -1,4 +1,6 @@
-// Whole-sequence attention for head dims 128 / 192 / 256 (= 64 S, S = 2..4), N <= 256.
+// Whole-sequence attention for head dims 128 / 192 / 256 (= 64 S, S = 2..4), as long as the whole sequence fits one
+// CU's LDS: N <= 256 / 192 / 160.  Longer sequences run on the streaming kernels of attention_wide_stream.hip (through
+// sfcvit_attention_fwd_any / _bwd_any); sfcvit_attention_fwd / _bwd refuse them.
 //
 // The reference's own script builds VisionTransformer1D(embed_dim 768, n_heads 4) -- head dim 192 (main.py:276-282);
 // T / B / L all use 64, which attention_seq.hip and attention.hip are tuned for.  These kernels are the same

@@ -46,6 +46,7 @@ Knobs read_knobs(KnobScope scope) {
         return k;
     }
     k.attn_long = !env_off("SFCVIT_ATTN_LONG");
+    k.attn_wide_stream = env_int("SFCVIT_ATTN_WIDE_STREAM", 0) != 0;
     if (scope == KNOBS_ATTN_BWD) {
         k.attn_bwd_fused = !env_off("SFCVIT_ATTN_BWD_FUSED");
         k.attn_dq_in_kernel = env_first("SFCVIT_ATTN_DQSUM") != 'p';

@@ -237,26 +237,35 @@ int check_attn(AttnPlan &p, const sfcvit_attn_args &a, const char *what) {
     return p.err;
 }
 
-// Head dims 128 / 192 / 256: whole sequence in LDS, no tiled form.
-void plan_wide(AttnPlan &p, const sfcvit_attn_args &a) {
+// Head dims 128 / 192 / 256: whole sequence in LDS; the default entry points refuse what does not fit.  any_length calls
+// stream 64-row blocks instead (attention_wide_stream.hip) where it does not fit, or always with SFCVIT_ATTN_WIDE_STREAM=1.
+void plan_wide(AttnPlan &p, const sfcvit_attn_args &a, const Knobs &k, bool any_length) {
     p.family = AttnFamily::WIDE;
     p.inst = a.hd / ATTN_HD;
     p.npad = p.npad2 = (a.N + 31) / 32 * 32;
     p.lds = wide_lds(p.inst, p.npad, p.bwd);                     // bwd: the dK / dV kernel, then the dQ kernel
     p.lds2 = p.bwd ? wide_lds(p.inst, p.npad, false) : 0;
-    if (a.N > SEQ_MAX_N || p.lds > size_t(ATTN_LDS_LIMIT))
+    const bool fits = a.N <= SEQ_MAX_N && p.lds <= size_t(ATTN_LDS_LIMIT);
+    if (any_length && (!fits || k.attn_wide_stream)) {
+        p.family = AttnFamily::STREAM;
+        p.npad = p.npad2 = 0;
+        p.lds = stream_lds(p.inst, p.bwd);
+        p.lds2 = p.bwd ? stream_lds(p.inst, false) : 0;
+        p.grid = (a.N + ATTN_BLK - 1) / ATTN_BLK;
+    } else if (!fits) {
         refuse(p, SFCVIT_EINVAL, "attention: head dim %d with N = %d needs %zu KiB of LDS (limit 160); only head dim 64 has a tiled kernel",
                a.hd, a.N, p.lds >> 10);
+    }
 }
 
 }  // namespace
 
-AttnPlan attn_fwd_plan(const sfcvit_attn_args &a, const Knobs &k) {
+AttnPlan attn_fwd_plan(const sfcvit_attn_args &a, const Knobs &k, bool any_length) {
     AttnPlan p;
     if (check_attn(p, a, "attention_fwd")) return p;
     p.drop = a.dropout_p > 0.f;
     if (a.hd != ATTN_HD) {
-        plan_wide(p, a);
+        plan_wide(p, a, k, any_length);
     } else if (a.N <= SEQ_MAX_N) {
         p.family = AttnFamily::SEQ;
         p.npad = (a.N + 15) / 16 * 16;
@@ -274,7 +283,7 @@ AttnPlan attn_fwd_plan(const sfcvit_attn_args &a, const Knobs &k) {
     return p;
 }
 
-AttnPlan attn_bwd_plan(const sfcvit_attn_args &a, int cus, const Knobs &k) {
+AttnPlan attn_bwd_plan(const sfcvit_attn_args &a, int cus, const Knobs &k, bool any_length) {
     AttnPlan p;
     p.bwd = true;
     if (check_attn(p, a, "attention_bwd")) return p;              // (sfcvit_attention_bwd checks colsum_part's size next)
@@ -316,7 +325,7 @@ AttnPlan attn_bwd_plan(const sfcvit_attn_args &a, int cus, const Knobs &k) {
         p.lds2 = size_t(2 * p.npad * 128 + 3 * p.npad * 4);
         if (a.colsum_out) p.colsum = Colsum::PARTIALS;
     } else if (a.hd != ATTN_HD) {                                   // these need the delta pass first
-        plan_wide(p, a);
+        plan_wide(p, a, k, any_length);
     } else if (a.N <= SEQ_MAX_N) {
         p.family = AttnFamily::SEQ;
         p.inst = (a.N + 15) / 16 == 13 ? 13 : 0;
@@ -355,6 +364,9 @@ void kernel_name(const AttnPlan &p, char *buf, size_t n) {
         break;
     case AttnFamily::TILED: snprintf(buf, n, p.bwd ? "attn_bwd_kv_kernel" : "attn_fwd_kernel"); break;
     case AttnFamily::FUSED: snprintf(buf, n, "attn_seq_bwd_fused_kernel<%d, %s>", p.inst, drop); break;
+    case AttnFamily::STREAM:
+        snprintf(buf, n, p.bwd ? "attn_wide_stream_bwd_kv_kernel<%d>" : "attn_wide_stream_fwd_kernel<%d>", p.inst);
+        break;
     }
 }
 

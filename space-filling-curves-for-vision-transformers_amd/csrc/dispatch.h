@@ -14,6 +14,8 @@
 //     SFCVIT_ATTN_DQSUM        kernel   "pass": dQ column sums from a separate pass over dqkv
 //     SFCVIT_ATTN_BWD_PERSIST  1        "0": one workgroup per (batch, head) item in the one-pass backward
 //     SFCVIT_ATTN_STAGGER_BWD  1 / 2,450  "slots,ticks" of the one-pass backward (persistent / one item per workgroup)
+//     SFCVIT_ATTN_WIDE_STREAM  0        "1": streaming kernels for every any-length call with head dim > 64, also where the
+//                                       whole-sequence kernels fit (A/B timing, small-N tests)
 //   read once per process
 //     SFCVIT_GEMM_WALK         6 if N >= 1792, else 0  tile-walk window width of the persistent GEMM; 0 = row-major
 //     SFCVIT_ATTN_BWD_QUEUE    1        "0": fixed item stride in the persistent attention backward
@@ -53,6 +55,8 @@ constexpr int FUSED_EXTRA = 256 + 64 + 14 * 64 * 4;          // (256 spare) + tw
 constexpr int FUSED_MAX_LDS = FUSED_MAX_N * FUSED_ROW_BYTES + FUSED_EXTRA + FUSED_POST_BYTES;
 // head dims 128 / 192 / 256 (S = hd / 64): Q | K or K | V images of the whole sequence, + lse / delta / row key (dK / dV kernel)
 constexpr size_t wide_lds(int S, int npad, bool kv) { return size_t(2) * S * npad * 128 + (kv ? size_t(3) * npad * 4 : 0); }
+// head dims 128 / 192 / 256, any N (attention_wide_stream.hip): one 64-row block of K | V or Q | dO, + lse / delta / row key
+constexpr size_t stream_lds(int S, bool kv) { return wide_lds(S, ATTN_BLK, kv); }
 
 // ---- switches ----
 struct Knobs {
@@ -64,6 +68,7 @@ struct Knobs {
     bool attn_dq_in_kernel = true;                           // SFCVIT_ATTN_DQSUM
     bool attn_bwd_persist = true;                            // SFCVIT_ATTN_BWD_PERSIST
     int attn_stagger_slots = 0, attn_stagger_ticks = 450;    // SFCVIT_ATTN_STAGGER_BWD (slots 0: the plan's default)
+    bool attn_wide_stream = false;                           // SFCVIT_ATTN_WIDE_STREAM
     int gemm_walk = -1;                                      // SFCVIT_GEMM_WALK (-1: the plan's default)
     bool attn_bwd_queue = true;                              // SFCVIT_ATTN_BWD_QUEUE
     int attn_nt = 0;                                         // SFCVIT_ATTN_NT
@@ -103,7 +108,7 @@ struct GemmPlan : PlanStatus {
 GemmPlan gemm_plan(const sfcvit_gemm_args &a, int cus, const Knobs &k);
 
 // ---- attention ----
-enum class AttnFamily : unsigned char { WIDE, SEQ, LONG, TILED, FUSED };
+enum class AttnFamily : unsigned char { WIDE, SEQ, LONG, TILED, FUSED, STREAM };
 enum class Colsum : unsigned char { NONE, PARTIALS, PARTIALS_QPASS, PASS };
 struct AttnPlan : PlanStatus {
     AttnFamily family = AttnFamily::TILED;
@@ -111,13 +116,15 @@ struct AttnPlan : PlanStatus {
     int inst = 0;                                            // template instance: NFC (13 / 36 / 0) or, wide, S = hd / 64
     int npad = 0, npad2 = 0;                                 // padded rows of the (first, second) kernel
     size_t lds = 0, lds2 = 0;                                // dynamic LDS of the (first, second) kernel
-    int grid = 0;                                            // FUSED: workgroups; TILED: query / key blocks
+    int grid = 0;                                            // FUSED: workgroups; TILED, STREAM: query / key blocks
     bool queue = false;                                      // FUSED: items dealt from the stream's counters
     int round = 0, per = 0, ticks = 0, nt = 0, dq_sums = 0;  // FUSED: stagger, nontemporal DMA, dQ column sums in the kernel
     Colsum colsum = Colsum::NONE;                            // bwd: where the column sums of dqkv come from
 };
-AttnPlan attn_fwd_plan(const sfcvit_attn_args &a, const Knobs &k);
-AttnPlan attn_bwd_plan(const sfcvit_attn_args &a, int cus, const Knobs &k);
+// any_length (sfcvit_attention_fwd_any / _bwd_any): head dims 128 / 192 / 256 run on the STREAM kernels where the
+// whole-sequence ones would refuse for LDS (or always, with SFCVIT_ATTN_WIDE_STREAM=1); every other plan is unchanged.
+AttnPlan attn_fwd_plan(const sfcvit_attn_args &a, const Knobs &k, bool any_length = false);
+AttnPlan attn_bwd_plan(const sfcvit_attn_args &a, int cus, const Knobs &k, bool any_length = false);
 
 // The symbol of the plan's main kernel, e.g. "gemm8p_kernel<7, 35, true>" or "attn_seq_bwd_fused_kernel<13, true>".
 void kernel_name(const GemmPlan &p, char *buf, size_t n);

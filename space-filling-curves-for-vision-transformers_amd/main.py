@@ -69,7 +69,7 @@ def main():
     ap.add_argument("--levels", type=int, nargs="+", default=[16, 4, 1])
     ap.add_argument("--embed-dim", type=int, default=256)
     ap.add_argument("--depth", type=int, default=8)             # main.py:276-282
-    ap.add_argument("--heads", type=int, default=4)             # head dim 768 / 4 = 192 (attention_wide.hip)
+    ap.add_argument("--heads", type=int, default=4)             # head dim 768 / 4 = 192, any image size (attention_wide.hip up to N = 192, attention_wide_stream.hip beyond)
     ap.add_argument("--mlp-dim", type=int, default=512)
     ap.add_argument("--classes", type=int, default=10)
     ap.add_argument("--batch-size", type=int, default=512)      # main.py:228

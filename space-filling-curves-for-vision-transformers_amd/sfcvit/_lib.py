@@ -104,6 +104,9 @@ SIGNATURES = {
     "sfcvit_dropout_mask": (c_int, [c_void_p, c_int64, c_int, c_float, ctypes.c_uint32, c_void_p]),
     "sfcvit_attention_fwd": (c_int, [ctypes.POINTER(AttnArgs), c_void_p]),
     "sfcvit_attention_bwd": (c_int, [ctypes.POINTER(AttnArgs), c_void_p]),
+    "sfcvit_attention_fwd_any": (c_int, [ctypes.POINTER(AttnArgs), c_void_p]),
+    "sfcvit_attention_bwd_any": (c_int, [ctypes.POINTER(AttnArgs), c_void_p]),
+    "sfcvit_attention_plan": (c_int, [ctypes.POINTER(AttnArgs), c_int, c_int, ctypes.c_char_p, c_int]),
     "sfcvit_attention_colsum_workspace": (c_int64, [c_int, c_int, c_int, c_int]),
     "sfcvit_gelu_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "sfcvit_gelu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -378,7 +378,7 @@ class _Attention(Function):
     @staticmethod
     def forward(ctx, qkv, n_heads, scale):
         qkv = _c(qkv)
-        out, lse = ops.attention_fwd(qkv, n_heads, scale=scale)
+        out, lse = ops.attention_fwd(qkv, n_heads, scale=scale, any_length=True)
         ctx.save_for_backward(qkv, out, lse)
         ctx.n_heads, ctx.scale = n_heads, scale
         return out
@@ -386,7 +386,7 @@ class _Attention(Function):
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
-        return ops.attention_bwd(qkv, out, lse, _c(dout), ctx.n_heads, scale=ctx.scale), None, None
+        return ops.attention_bwd(qkv, out, lse, _c(dout), ctx.n_heads, scale=ctx.scale, any_length=True), None, None
 
 
 def _head_padding(D, n_heads):
@@ -479,7 +479,7 @@ class _EncoderLayer(Function):
         sa, s1_, sf, s2_ = seeds
         x2 = _c(x).view(B * N, D)
         qkv = ops.gemm(x2, in_w, bias=in_b)
-        o, lse = ops.attention_fwd(qkv.view(B, N, 3 * Da), n_heads, p, sa, scale=scale)
+        o, lse = ops.attention_fwd(qkv.view(B, N, 3 * Da), n_heads, p, sa, scale=scale, any_length=True)
         s1 = ops.gemm(o.view(B * N, Da), out_w, bias=out_b, residual=x2, dropout_p=p, dropout_seed=s1_)
         x1, mean1, rstd1 = ops.layernorm_fwd(s1, n1_w, n1_b, eps)
         # The dX GEMM through ReLU + dropout needs only the sign pattern of h: a bit matrix written by linear1's epilogue
@@ -543,7 +543,7 @@ class _EncoderLayer(Function):
         # the in_proj bias gradient (column sums of dqkv) comes out of the attention backward itself
         bi_slot = _slot(in_b)
         dqkv, dbi = ops.attention_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), ctx.n_heads, p, sa,
-                                      colsum=bi_slot if bi_slot is not None else True, scale=ctx.scale)
+                                      colsum=bi_slot if bi_slot is not None else True, scale=ctx.scale, any_length=True)
         dqkv = dqkv.view(B * N, 3 * Da)
         if bi_slot is None:
             dbi = dbi.to(_BF16)

@@ -417,8 +417,9 @@ SUPPORTED_HEAD_DIMS = (64, 128, 192, 256)
 
 
 def _attn_dims(D3, n_heads):
-    """(D, head dim) of a packed q|k|v projection; the kernels exist for head dims 64 (any N) and 128 / 192 / 256
-    (whole-sequence kernels: N <= 288 / 192 / 128)."""
+    """(D, head dim) of a packed q|k|v projection; the kernels exist for head dims 64 (any N) and 128 / 192 / 256 (any N
+    with any_length=True: whole-sequence kernels up to N = 256 / 192 / 160, streaming kernels beyond; without it those
+    limits are refusals)."""
     if D3 % 3 or (D3 // 3) % n_heads:
         raise ValueError(f"attention: packed width {D3} is not 3 * n_heads * head_dim for n_heads = {n_heads}")
     D = D3 // 3
@@ -437,8 +438,9 @@ def padded_head_dim(hd):
     return None
 
 
-def attention_fwd(qkv, n_heads, dropout_p=0.0, dropout_seed=0, scale=None):
-    """qkv [B, N, 3*D] bf16 -> out [B, N, D] bf16, lse [B, H, N] fp32.  scale: softmax scale, default 1 / sqrt(head dim)."""
+def attention_fwd(qkv, n_heads, dropout_p=0.0, dropout_seed=0, scale=None, any_length=False):
+    """qkv [B, N, 3*D] bf16 -> out [B, N, D] bf16, lse [B, H, N] fp32.  scale: softmax scale, default 1 / sqrt(head dim).
+    any_length: head dims 128 / 192 / 256 at any N (sfcvit_attention_fwd_any); otherwise the whole-sequence limits hold."""
     _need(qkv, _BF16, "attention qkv", 3)
     B, N, D3 = qkv.shape
     D, hd = _attn_dims(D3, n_heads)
@@ -450,14 +452,16 @@ def attention_fwd(qkv, n_heads, dropout_p=0.0, dropout_seed=0, scale=None):
     a.dropout_p, a.dropout_seed = dropout_p, dropout_seed
     if dropout_p > 0.0 and STEP_STATE is not None:
         a.seed_off = STEP_STATE.data_ptr()
+    fn = lib.sfcvit_attention_fwd_any if any_length else lib.sfcvit_attention_fwd
     check(_launch("attn_fwd_kernel", 4.0 * B * n_heads * N * N * hd,
-                  lambda: lib.sfcvit_attention_fwd(ctypes.byref(a), _stream())), "sfcvit_attention_fwd")
+                  lambda: fn(ctypes.byref(a), _stream())), "sfcvit_attention_fwd" + ("_any" if any_length else ""))
     return out, lse
 
 
-def attention_bwd(qkv, out, lse, dout, n_heads, dropout_p=0.0, dropout_seed=0, colsum=None, scale=None):
+def attention_bwd(qkv, out, lse, dout, n_heads, dropout_p=0.0, dropout_seed=0, colsum=None, scale=None, any_length=False):
     """-> dqkv [, column sums of dqkv over all B * N rows = the in_proj bias gradient: colsum=True -> fp32 [3D] (new
-    tensor), or a bf16 [3D] tensor to write into (e.g. a slot of the flat gradient buffer)]."""
+    tensor), or a bf16 [3D] tensor to write into (e.g. a slot of the flat gradient buffer)].  any_length: as in
+    attention_fwd (sfcvit_attention_bwd_any)."""
     _need(dout, _BF16, "attention dout", 3)
     B, N, D3 = qkv.shape
     D, hd = _attn_dims(D3, n_heads)
@@ -480,8 +484,9 @@ def attention_bwd(qkv, out, lse, dout, n_heads, dropout_p=0.0, dropout_seed=0, c
         a.colsum_part, a.colsum_part_bytes = ws.data_ptr(), nbytes
         a.colsum_out, a.colsum_bf16 = cs.data_ptr(), int(cs.dtype == _BF16)
     with _Deferring([colsum] if cs is not None and colsum is not True else [], [ws] if cs is not None else []):
+        fn = lib.sfcvit_attention_bwd_any if any_length else lib.sfcvit_attention_bwd
         check(_launch("attn_bwd", 10.0 * B * n_heads * N * N * hd,
-                      lambda: lib.sfcvit_attention_bwd(ctypes.byref(a), _stream())), "sfcvit_attention_bwd")
+                      lambda: fn(ctypes.byref(a), _stream())), "sfcvit_attention_bwd" + ("_any" if any_length else ""))
     return dqkv if cs is None else (dqkv, cs)
 
 
