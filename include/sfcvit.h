@@ -131,6 +131,50 @@ int sfcvit_tokens_gather_tiles(const void *x, const int32_t *pix, const int32_t 
 int sfcvit_patch_embed_bwd(const sfcvit_patch_embed_args *a, void *stream);
 
 /* ------------------------------------------------------------------------
+ * MixUp / CutMix on the device
+ *   replaces mixup_data / cutmix_data (src/training/train.py:7-47) and the soft-target construction + accuracy
+ *   bookkeeping of train_with_mixup_or_cutmix (train.py:148-172).
+ *
+ * One batch's mix is described by two DEVICE buffers, so that a captured graph picks up new values on every replay:
+ *   perm  int32[B]: the partner image of each image (the reference's `idx`).  An entry outside [0, B) means "no
+ *         partner" (the image itself): no kernel reads outside the batch whatever the buffer holds.
+ *   rec   eight 32-bit words, 16-byte aligned:
+ *         [0] mode: 0 = none, 1 = MixUp, 2 = CutMix
+ *         [1] r0 [2] r1 [3] c0 [4] c1: the CutMix box [r0, r1) x [c0, c1) on tensor dims 2 and 3
+ *         [5] lam  [6] 1 - lam: fp32 bit patterns; 1 - lam is formed on the host in double and rounded once, which is
+ *             what torch does with the Python scalar `1 - lam`
+ *         [7] reserved (0)
+ *   The reference's quirk is kept: rand_bbox derives bbx* from W and bby* from H, and cutmix_data then applies bbx to
+ *   dim 2 (rows) and bby to dim 3 (columns) (train.py:41-42).  The record stores the box AS IT IS APPLIED -- r = bbx,
+ *   c = bby -- not as it is named.
+ * Per pixel of image b, with q = perm[b]:
+ *   MixUp   fadd(fmul(lam, x[b]), fmul(1 - lam, x[q])): three separately rounded fp32 operations, never a fused
+ *           multiply-add (bit-identical to torch's lam * x + (1 - lam) * x[idx])
+ *   CutMix  x[q] inside the box, x[b] outside; the source is the un-mixed batch, so cycles in perm are exact
+ *   mode 0  x[b]
+ * Images are fp32.
+ * ---------------------------------------------------------------------- */
+/* sfcvit_tokens_gather / sfcvit_tokens_gather_tiles with the mix applied on the way to bf16: tokens[b * N + n][kk * C + c] =
+ * bf16(mix(x)[b, c, pix[n][kk]]) -- one more read of the image, no extra pass, and backward (which keeps the tokens) is
+ * unchanged.  origin != NULL: the 16 x 16-tile kernel (P must be 256 and the arguments those of sfcvit_tokens_gather_tiles;
+ * a wave loads the partner's lines next to the image's own, and a tile pair the box does not touch loads no partner);
+ * origin == NULL: the per-pixel kernels (any P; ld as in sfcvit_tokens_gather).  Mode 0 gives the unmixed gather's bits. */
+int sfcvit_tokens_gather_mix(const void *x, const int32_t *pix, const int32_t *order, const int32_t *origin, const int32_t *perm,
+                             const uint32_t *rec, int B, int C, int H, int W, int N, int P, void *tokens, int ld, void *stream);
+/* out[B, C, H, W] = the mixed batch (fp32 in and out): one read of x[b] and x[perm[b]], one write, 16-byte accesses when
+ * H * W % 4 == 0.  For the paths that never materialise tokens (the fused gather-GEMM kernels, the hierarchical kernel, the
+ * Conv2d-weight tokenizers, altvit).  out must not overlap x. */
+int sfcvit_mix_images(const void *x, const int32_t *perm, const uint32_t *rec, void *out, int B, int C, int H, int W, void *stream);
+/* sfcvit_soft_ce on the targets lam * onehot(y_a) + (1 - lam) * onehot(y_b) without building them: y_a, y_b int64 [B]
+ * (device), lam / 1 - lam from rec (mode 0: lam = 1).  Same max / sum-of-exponentials loop as sfcvit_soft_ce, so the same
+ * lse; where y_a == y_b the single target is fadd(lam, 1 - lam), as the dense row holds.  loss_rows, dlogits (may be NULL)
+ * as in sfcvit_soft_ce.  hit_rows (fp32 [B] or NULL) = lam * (argmax == y_a) + (1 - lam) * (argmax == y_b), the lowest
+ * index winning ties: per row, no atomics, so an epoch's sum is the same from run to run.  A label outside [0, C) is a
+ * label without a target: it adds nothing to loss, gradient or hits, and nothing is read or written through it. */
+int sfcvit_soft_ce_pair(const void *logits, const int64_t *y_a, const int64_t *y_b, const uint32_t *rec, float *loss_rows,
+                        void *dlogits, float *hit_rows, int B, int C, int ld, float gscale, void *stream);
+
+/* ------------------------------------------------------------------------
  * Fused hierarchical tokenizer, forward
  *   replaces HierarchicalHilbertEmbedding.forward (src/tokenizers/multiscale/multi_hilbert.py:31-40) and its
  *   siblings multi_morton.py / multi_moore.py / multi_peano.py / multi_onion.py / multi_zigzag.py (same lines) when

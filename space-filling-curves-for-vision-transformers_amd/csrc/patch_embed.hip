@@ -15,6 +15,7 @@
 // (D*K bf16, L2-resident); dW is permuted back by the split-K reduction.
 #include "common_host.h"
 #include "gemm_core.h"
+#include "mix.h"
 
 namespace sfcvit {
 namespace {
@@ -267,20 +268,35 @@ namespace sfcvit {
 namespace {
 constexpr int GT = 256, GIMG = 8;
 
-template <bool XBF16>
+// MIX: image b is mixed with image perm[b] as the record says (mix.h) on the way to bf16; fp32 images only.
+template <bool XBF16, bool MIX>
 __global__ __launch_bounds__(GT) void tokens_gather_kernel(const void *__restrict__ x, const int32_t *__restrict__ pix,
-                                                           uint16_t *__restrict__ tokens, int B, int C, int HW, int N, int P, int ld) {
+                                                           uint16_t *__restrict__ tokens, int B, int C, int HW, int N, int P, int ld,
+                                                           int W, const int32_t *__restrict__ perm, const uint32_t *__restrict__ rec) {
+    static_assert(!(XBF16 && MIX), "a mix needs fp32 images");
     extern __shared__ __attribute__((aligned(16))) char smem_g[];
     uint16_t *row = reinterpret_cast<uint16_t *>(smem_g);                 // [ld]
     const int n = blockIdx.x, b0 = blockIdx.y * GIMG, tid = threadIdx.x, K = P * C;
+    MixRec mr{};
+    if constexpr (MIX) mr = load_mix_rec(rec);
     for (int i = K + tid; i < ld; i += GT) row[i] = 0;                     // padding columns
     for (int b = b0; b < min(B, b0 + GIMG); b++) {
         const size_t img = size_t(b) * C * HW;
+        size_t imq = img;
+        if constexpr (MIX) imq = size_t(mix_partner(perm, b, B)) * C * HW;
         for (int kk = tid; kk < P; kk += GT) {
             const int off = pix[size_t(n) * P + kk];
+            const int pr = MIX ? off / W : 0, pc = MIX ? off - pr * W : 0;
+            const bool partner = MIX && mix_needs_partner(mr, pr, pc), inside = MIX && in_box(mr, pr, pc);
             for (int c = 0; c < C; c++) {
                 const size_t src = img + size_t(c) * HW + off;
-                row[kk * C + c] = XBF16 ? static_cast<const uint16_t *>(x)[src] : f2bf(static_cast<const float *>(x)[src]);
+                if constexpr (MIX) {
+                    const float a = static_cast<const float *>(x)[src];
+                    const float bq = partner ? static_cast<const float *>(x)[imq + size_t(c) * HW + off] : 0.f;
+                    row[kk * C + c] = f2bf(mix_px(mr, a, bq, inside));
+                } else {
+                    row[kk * C + c] = XBF16 ? static_cast<const uint16_t *>(x)[src] : f2bf(static_cast<const float *>(x)[src]);
+                }
             }
         }
         __syncthreads();
@@ -295,10 +311,12 @@ __global__ __launch_bounds__(GT) void tokens_gather_kernel(const void *__restric
 // rows are 64 bytes of fp32, half a 128-byte line whose other half belongs to the tile next to it; with one token per
 // workgroup every line of the image was fetched twice (62 us at ViT-B / 256 images: 154 MB of image read as 308).  The
 // caller orders the tokens by their lowest pixel offset, which puts horizontal neighbours side by side.
-template <bool XBF16, int CMAX>
+template <bool XBF16, int CMAX, bool MIX>
 __global__ __launch_bounds__(2 * GT) void tokens_gather_p256_kernel(const void *__restrict__ x, const int32_t *__restrict__ pix,
                                                                     const int32_t *__restrict__ order, uint16_t *__restrict__ tokens,
-                                                                    int B, int C, int HW, int N, int P, int ld) {
+                                                                    int B, int C, int HW, int N, int P, int ld,
+                                                                    int W, const int32_t *__restrict__ perm, const uint32_t *__restrict__ rec) {
+    static_assert(!(XBF16 && MIX), "a mix needs fp32 images");
     extern __shared__ __attribute__((aligned(16))) char smem_g[];
     const int half = threadIdx.x >> 8, tid = threadIdx.x & (GT - 1);
     const int slot = 2 * blockIdx.x + half;
@@ -310,13 +328,40 @@ __global__ __launch_bounds__(2 * GT) void tokens_gather_p256_kernel(const void *
     uint16_t v[GIMG][CMAX];
     if (live && tid < P) {
         const int off = pix[size_t(n) * P + tid];
+        if constexpr (MIX) {
+            // the partner's pixel rides along with the image's own: all loads of the GIMG images in flight, then combined
+            const MixRec mr = load_mix_rec(rec);
+            const int pr = off / W, pc = off - pr * W;
+            const bool partner = mix_needs_partner(mr, pr, pc), inside = in_box(mr, pr, pc);   // per pixel: a CutMix box cuts through tokens
+            float a[GIMG][CMAX], bq[GIMG][CMAX];
 #pragma unroll
-        for (int i = 0; i < GIMG; i++) {
-            if (i < nb) {
-                const size_t img = size_t(b0 + i) * C * HW + off;
+            for (int i = 0; i < GIMG; i++) {
+                if (i < nb) {
+                    const size_t img = size_t(b0 + i) * C * HW + off;
+                    const size_t imq = size_t(mix_partner(perm, b0 + i, B)) * C * HW + off;
 #pragma unroll
-                for (int c = 0; c < CMAX; c++)
-                    if (c < C) v[i][c] = XBF16 ? static_cast<const uint16_t *>(x)[img + size_t(c) * HW] : f2bf(static_cast<const float *>(x)[img + size_t(c) * HW]);
+                    for (int c = 0; c < CMAX; c++)
+                        if (c < C) {
+                            a[i][c] = static_cast<const float *>(x)[img + size_t(c) * HW];
+                            bq[i][c] = partner ? static_cast<const float *>(x)[imq + size_t(c) * HW] : 0.f;
+                        }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < GIMG; i++)
+                if (i < nb)
+#pragma unroll
+                    for (int c = 0; c < CMAX; c++)
+                        if (c < C) v[i][c] = f2bf(mix_px(mr, a[i][c], bq[i][c], inside));
+        } else {
+#pragma unroll
+            for (int i = 0; i < GIMG; i++) {
+                if (i < nb) {
+                    const size_t img = size_t(b0 + i) * C * HW + off;
+#pragma unroll
+                    for (int c = 0; c < CMAX; c++)
+                        if (c < C) v[i][c] = XBF16 ? static_cast<const uint16_t *>(x)[img + size_t(c) * HW] : f2bf(static_cast<const float *>(x)[img + size_t(c) * HW]);
+                }
             }
         }
 #pragma unroll
@@ -354,11 +399,15 @@ __global__ __launch_bounds__(2 * GT) void tokens_gather_p256_kernel(const void *
 // 132 registers).
 constexpr int TG_THREADS = 256;
 
-template <int C, int NT, int U>
+// MIX: the wave loads the same lines of image perm[b] next to those of b and combines them in registers before pack2bf
+// (mix.h): MixUp everywhere, CutMix per pixel -- row and column follow from `line`, `chunk` and the tile origin -- and a
+// tile pair that the box does not touch (or mode 0) issues no partner loads at all: the test is wave-uniform.
+template <int C, int NT, int U, bool MIX>
 __global__ __launch_bounds__(TG_THREADS) void tokens_gather_tiles_kernel(const float *__restrict__ x, const int32_t *__restrict__ pix,
                                                                          const int32_t *__restrict__ order, const int32_t *__restrict__ origin,
                                                                          uint16_t *__restrict__ tokens, int B, int HW, int W,
-                                                                         uint32_t wmagic, int N) {
+                                                                         uint32_t wmagic, int N,
+                                                                         const int32_t *__restrict__ perm, const uint32_t *__restrict__ rec) {
     extern __shared__ __attribute__((aligned(16))) char smem_g[];
     uint16_t *pos = reinterpret_cast<uint16_t *>(smem_g);                  // [2 tokens][256 curve pixels] -> pixel of the pair image
     constexpr int UNIT = C * 16 * 64;                                      // bytes of one bf16 pair image
@@ -379,6 +428,22 @@ __global__ __launch_bounds__(TG_THREADS) void tokens_gather_tiles_kernel(const f
     const int chunk = lane & 7, lt = chunk >> 2;
     const size_t src0 = size_t(lt ? o1 : o0) + 4 * (chunk & 3);
     f32x4 v[U][2 * C];
+    // MIX: pixel (row, col) of this lane's vector i is (trow + (line & 15), tcol + e), e = 0..3; `partner` is the same
+    // for every lane of the workgroup (record and tile origins are)
+    MixRec mr{};
+    int trow = 0, tcol = 0;
+    bool partner = false;
+    if constexpr (MIX) {
+        mr = load_mix_rec(rec);
+        const int oo = lt ? o1 : o0;
+        trow = oo / W;
+        tcol = oo - trow * W + 4 * (chunk & 3);
+        const int ra = o0 / W, ca = o0 - ra * W, rb = o1 / W, cb = o1 - rb * W;
+        partner = mr.mode == 1u ||
+                  (mr.mode == 2u && ((ra < mr.r1 && ra + 16 > mr.r0 && ca < mr.c1 && ca + 16 > mr.c0) ||
+                                     (rb < mr.r1 && rb + 16 > mr.r0 && cb < mr.c1 && cb + 16 > mr.c0)));
+    }
+    f32x4 vq[MIX ? U : 1][MIX ? 2 * C : 1];
 #pragma unroll
     for (int u = 0; u < U; u++) {
         if (b0 + u < B) {
@@ -388,6 +453,32 @@ __global__ __launch_bounds__(TG_THREADS) void tokens_gather_tiles_kernel(const f
                 const int line = 8 * i + (lane >> 3);
                 const f32x4 *src = reinterpret_cast<const f32x4 *>(im + size_t(line >> 4) * HW + size_t(line & 15) * W);
                 v[u][i] = (NT & 1) ? __builtin_nontemporal_load(src) : *src;
+            }
+            if constexpr (MIX) {
+                if (partner) {
+                    const float *iq = x + size_t(mix_partner(perm, b0 + u, B)) * C * HW + src0;
+#pragma unroll
+                    for (int i = 0; i < 2 * C; i++) {
+                        const int line = 8 * i + (lane >> 3);
+                        const f32x4 *src = reinterpret_cast<const f32x4 *>(iq + size_t(line >> 4) * HW + size_t(line & 15) * W);
+                        vq[u][i] = (NT & 1) ? __builtin_nontemporal_load(src) : *src;
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (MIX) {
+        if (partner) {
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                if (b0 + u < B) {
+#pragma unroll
+                    for (int i = 0; i < 2 * C; i++) {
+                        const int row = trow + ((8 * i + (lane >> 3)) & 15);
+#pragma unroll
+                        for (int e = 0; e < 4; e++) v[u][i][e] = mix_px(mr, v[u][i][e], vq[u][i][e], in_box(mr, row, tcol + e));
+                    }
+                }
             }
         }
     }
@@ -442,22 +533,27 @@ __global__ __launch_bounds__(TG_THREADS) void tokens_gather_tiles_kernel(const f
 }  // namespace
 }  // namespace sfcvit
 
-extern "C" int sfcvit_tokens_gather_tiles(const void *x, const int32_t *pix, const int32_t *order, const int32_t *origin, int B, int C,
-                                          int H, int W, int N, void *tokens, int ld, void *stream) {
-    using namespace sfcvit;
-    if (!x || !pix || !origin || !tokens) return fail(SFCVIT_EINVAL, "tokens_gather_tiles: null pointer");
+namespace sfcvit {
+namespace {
+
+// perm / rec: the batch mix (both or neither); `what` names the entry point in messages.
+int gather_tiles_impl(const char *what, const void *x, const int32_t *pix, const int32_t *order, const int32_t *origin,
+                      const int32_t *perm, const uint32_t *rec, int B, int C, int H, int W, int N, void *tokens, int ld, void *stream) {
+    if (!x || !pix || !origin || !tokens) return fail(SFCVIT_EINVAL, "%s: null pointer", what);
     if (B <= 0 || C < 1 || C > 4 || H <= 0 || W <= 0 || N <= 0 || int64_t(N) * 256 != int64_t(H) * W || (W & 7) || (H & 15))
-        return fail(SFCVIT_EINVAL, "tokens_gather_tiles: B=%d C=%d H=%d W=%d N=%d (1 <= C <= 4, W %% 8 == 0, H %% 16 == 0, N * 256 == H * W)", B, C, H, W, N);
-    if (ld != 256 * C) return fail(SFCVIT_EINVAL, "tokens_gather_tiles: ld=%d (must be 256 * C = %d)", ld, 256 * C);
-    if (!aligned16(x) || !aligned16(tokens)) return fail(SFCVIT_EINVAL, "tokens_gather_tiles: x and tokens must be 16-byte aligned");
-    if (int64_t(16) * W * W >= (int64_t(1) << 32)) return fail(SFCVIT_EINVAL, "tokens_gather_tiles: W=%d too wide", W);
+        return fail(SFCVIT_EINVAL, "%s: B=%d C=%d H=%d W=%d N=%d (1 <= C <= 4, W %% 8 == 0, H %% 16 == 0, N * 256 == H * W)", what, B, C, H, W, N);
+    if (ld != 256 * C) return fail(SFCVIT_EINVAL, "%s: ld=%d (must be 256 * C = %d)", what, ld, 256 * C);
+    if (!aligned16(x) || !aligned16(tokens)) return fail(SFCVIT_EINVAL, "%s: x and tokens must be 16-byte aligned", what);
+    if (int64_t(16) * W * W >= (int64_t(1) << 32)) return fail(SFCVIT_EINVAL, "%s: W=%d too wide", what, W);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const auto *xp = static_cast<const float *>(x);
     auto *tp = static_cast<uint16_t *>(tokens);
     const int HW = H * W;
-    static const int upw = env_int("SFCVIT_GATHER_U", 1) == 2 ? 2 : 1;   // images per wave (A/B: 2 = fewer, longer workgroups)
+    // images per wave (A/B: 2 = fewer, longer workgroups); the mixing form holds twice the lines and exists for 1 only
+    static const int upw_env = env_int("SFCVIT_GATHER_U", 1) == 2 ? 2 : 1;
+    const int upw = perm ? 1 : upw_env;
     const dim3 grid((N + 1) / 2, (B + 4 * upw - 1) / (4 * upw));
-    if (grid.y > 65535) return fail(SFCVIT_EINVAL, "tokens_gather_tiles: batch %d too large", B);
+    if (grid.y > 65535) return fail(SFCVIT_EINVAL, "%s: batch %d too large", what, B);
     const uint32_t wmagic = uint32_t((uint64_t(1) << 32) / uint32_t(W)) + 1;
     const size_t lds = 1024 + size_t(4 * upw) * C * 1024;
     // nontemporal loads (1) and stores (2).  The gather is the first kernel of a step: L2 and the memory-side cache are full
@@ -466,8 +562,8 @@ extern "C" int sfcvit_tokens_gather_tiles(const void *x, const int32_t *pix, con
     // the same: 69 vs 37 us).  Streaming loads do not allocate: 46.0 us; with streaming stores 43.2 us alone, 44.0 us in
     // the step (profiles/r4/gather_ab.txt).  SFCVIT_GATHER_NT=0..3 for the A/B.
     static const int nt = env_int("SFCVIT_GATHER_NT", 3);
-#define TILES(CC, NTV) do { if (upw == 2) hipLaunchKernelGGL((tokens_gather_tiles_kernel<CC, NTV, 2>), grid, dim3(TG_THREADS), lds, s, xp, pix, order, origin, tp, B, HW, W, wmagic, N); \
-                            else hipLaunchKernelGGL((tokens_gather_tiles_kernel<CC, NTV, 1>), grid, dim3(TG_THREADS), lds, s, xp, pix, order, origin, tp, B, HW, W, wmagic, N); } while (0)
+#define TILES_K(CC, NTV, UU, MX) hipLaunchKernelGGL((tokens_gather_tiles_kernel<CC, NTV, UU, MX>), grid, dim3(TG_THREADS), lds, s, xp, pix, order, origin, tp, B, HW, W, wmagic, N, perm, rec)
+#define TILES(CC, NTV) do { if (perm) TILES_K(CC, NTV, 1, true); else if (upw == 2) TILES_K(CC, NTV, 2, false); else TILES_K(CC, NTV, 1, false); } while (0)
 #define TILES_C(CC) do { if (nt == 1) TILES(CC, 1); else if (nt == 2) TILES(CC, 2); else if (nt == 3) TILES(CC, 3); else TILES(CC, 0); } while (0)
     switch (C) {
     case 1: TILES_C(1); break;
@@ -477,34 +573,67 @@ extern "C" int sfcvit_tokens_gather_tiles(const void *x, const int32_t *pix, con
     }
 #undef TILES_C
 #undef TILES
-    return check_launch("tokens_gather_tiles");
+#undef TILES_K
+    return check_launch(what);
+}
+
+// W is only read by the mixing kernels (pixel offset -> row, column).
+int gather_impl(const char *what, const void *x, int x_is_bf16, const int32_t *pix, const int32_t *order, const int32_t *perm,
+                const uint32_t *rec, int B, int C, int HW, int W, int N, int P, void *tokens, int ld, void *stream) {
+    if (!x || !pix || !tokens) return fail(SFCVIT_EINVAL, "%s: null pointer", what);
+    if (B <= 0 || C <= 0 || HW <= 0 || N <= 0 || P <= 0 || int64_t(N) * P != HW)
+        return fail(SFCVIT_EINVAL, "%s: B=%d C=%d HW=%d N=%d P=%d (N * P must equal H * W)", what, B, C, HW, N, P);
+    if (ld < P * C || ld % 8 || ld > 32768) return fail(SFCVIT_EINVAL, "%s: ld=%d (>= P * C = %d, multiple of 8, <= 32768)", what, ld, P * C);
+    if (!aligned16(tokens)) return fail(SFCVIT_EINVAL, "%s: tokens must be 16-byte aligned", what);
+    const dim3 grid(N, (B + GIMG - 1) / GIMG);
+    if (grid.y > 65535) return fail(SFCVIT_EINVAL, "%s: batch %d too large", what, B);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto *tp = static_cast<uint16_t *>(tokens);
+    if (P <= GT && C <= 4 && size_t(2) * GIMG * ld * 2 <= 64 * 1024) {
+        const dim3 grid2((N + 1) / 2, grid.y);
+        const size_t lds = size_t(2) * GIMG * ld * 2;
+        if (perm)
+            hipLaunchKernelGGL((tokens_gather_p256_kernel<false, 4, true>), grid2, dim3(2 * GT), lds, s, x, pix, order, tp, B, C, HW, N, P, ld, W, perm, rec);
+        else if (x_is_bf16)
+            hipLaunchKernelGGL((tokens_gather_p256_kernel<true, 4, false>), grid2, dim3(2 * GT), lds, s, x, pix, order, tp, B, C, HW, N, P, ld, W, perm, rec);
+        else
+            hipLaunchKernelGGL((tokens_gather_p256_kernel<false, 4, false>), grid2, dim3(2 * GT), lds, s, x, pix, order, tp, B, C, HW, N, P, ld, W, perm, rec);
+        return check_launch(what);
+    }
+    if (perm)
+        hipLaunchKernelGGL((tokens_gather_kernel<false, true>), grid, dim3(GT), size_t(ld) * 2, s, x, pix, tp, B, C, HW, N, P, ld, W, perm, rec);
+    else if (x_is_bf16)
+        hipLaunchKernelGGL((tokens_gather_kernel<true, false>), grid, dim3(GT), size_t(ld) * 2, s, x, pix, tp, B, C, HW, N, P, ld, W, perm, rec);
+    else
+        hipLaunchKernelGGL((tokens_gather_kernel<false, false>), grid, dim3(GT), size_t(ld) * 2, s, x, pix, tp, B, C, HW, N, P, ld, W, perm, rec);
+    return check_launch(what);
+}
+
+}  // namespace
+}  // namespace sfcvit
+
+extern "C" int sfcvit_tokens_gather_tiles(const void *x, const int32_t *pix, const int32_t *order, const int32_t *origin, int B, int C,
+                                          int H, int W, int N, void *tokens, int ld, void *stream) {
+    return sfcvit::gather_tiles_impl("tokens_gather_tiles", x, pix, order, origin, nullptr, nullptr, B, C, H, W, N, tokens, ld, stream);
 }
 
 extern "C" int sfcvit_tokens_gather(const void *x, int x_is_bf16, const int32_t *pix, const int32_t *order, int B, int C, int HW, int N,
                                     int P, void *tokens, int ld, void *stream) {
+    return sfcvit::gather_impl("tokens_gather", x, x_is_bf16, pix, order, nullptr, nullptr, B, C, HW, 0, N, P, tokens, ld, stream);
+}
+
+extern "C" int sfcvit_tokens_gather_mix(const void *x, const int32_t *pix, const int32_t *order, const int32_t *origin,
+                                        const int32_t *perm, const uint32_t *rec, int B, int C, int H, int W, int N, int P,
+                                        void *tokens, int ld, void *stream) {
     using namespace sfcvit;
-    if (!x || !pix || !tokens) return fail(SFCVIT_EINVAL, "tokens_gather: null pointer");
-    if (B <= 0 || C <= 0 || HW <= 0 || N <= 0 || P <= 0 || int64_t(N) * P != HW)
-        return fail(SFCVIT_EINVAL, "tokens_gather: B=%d C=%d HW=%d N=%d P=%d (N * P must equal H * W)", B, C, HW, N, P);
-    if (ld < P * C || ld % 8 || ld > 32768) return fail(SFCVIT_EINVAL, "tokens_gather: ld=%d (>= P * C = %d, multiple of 8, <= 32768)", ld, P * C);
-    if (!aligned16(tokens)) return fail(SFCVIT_EINVAL, "tokens_gather: tokens must be 16-byte aligned");
-    const dim3 grid(N, (B + GIMG - 1) / GIMG);
-    if (grid.y > 65535) return fail(SFCVIT_EINVAL, "tokens_gather: batch %d too large", B);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (P <= GT && C <= 4 && size_t(2) * GIMG * ld * 2 <= 64 * 1024) {
-        const dim3 grid2((N + 1) / 2, grid.y);
-        const size_t lds = size_t(2) * GIMG * ld * 2;
-        if (x_is_bf16)
-            hipLaunchKernelGGL((tokens_gather_p256_kernel<true, 4>), grid2, dim3(2 * GT), lds, s, x, pix, order, static_cast<uint16_t *>(tokens), B, C, HW, N, P, ld);
-        else
-            hipLaunchKernelGGL((tokens_gather_p256_kernel<false, 4>), grid2, dim3(2 * GT), lds, s, x, pix, order, static_cast<uint16_t *>(tokens), B, C, HW, N, P, ld);
-        return check_launch("tokens_gather");
+    if (!perm || !rec) return fail(SFCVIT_EINVAL, "tokens_gather_mix: null perm / rec (the unmixed gather is sfcvit_tokens_gather)");
+    if (H <= 0 || W <= 0 || int64_t(H) * W > 0x7fffffff) return fail(SFCVIT_EINVAL, "tokens_gather_mix: H=%d W=%d", H, W);
+    if (!aligned16(x)) return fail(SFCVIT_EINVAL, "tokens_gather_mix: x must be 16-byte aligned");
+    if (origin) {
+        if (P != 256) return fail(SFCVIT_EINVAL, "tokens_gather_mix: P=%d with a tile origin table (16 x 16 tiles: P = 256)", P);
+        return gather_tiles_impl("tokens_gather_mix", x, pix, order, origin, perm, rec, B, C, H, W, N, tokens, ld, stream);
     }
-    if (x_is_bf16)
-        hipLaunchKernelGGL(tokens_gather_kernel<true>, grid, dim3(GT), size_t(ld) * 2, s, x, pix, static_cast<uint16_t *>(tokens), B, C, HW, N, P, ld);
-    else
-        hipLaunchKernelGGL(tokens_gather_kernel<false>, grid, dim3(GT), size_t(ld) * 2, s, x, pix, static_cast<uint16_t *>(tokens), B, C, HW, N, P, ld);
-    return check_launch("tokens_gather");
+    return gather_impl("tokens_gather_mix", x, 0, pix, order, perm, rec, B, C, H * W, W, N, P, tokens, ld, stream);
 }
 
 extern "C" int64_t sfcvit_patch_embed_workspace(int B, int C, int N, int P, int D, int bwd) {

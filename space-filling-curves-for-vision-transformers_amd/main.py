@@ -26,7 +26,7 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from sfcvit.models.vit import VisionTransformer1D                                  # noqa: E402
 import sfcvit.tokenizers as T                                                       # noqa: E402
-from sfcvit.training import FusedAdamW, GradReducer, GraphedTrainStep, SoftTargetCrossEntropy, WarmupCosine   # noqa: E402
+from sfcvit.training import BatchMix, FusedAdamW, GradReducer, GraphedTrainStep, SoftTargetCrossEntropy, WarmupCosine   # noqa: E402
 from sfcvit.training.loops import evaluate, train_with_mixup_or_cutmix             # noqa: E402
 
 
@@ -91,6 +91,9 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="replay every training step from one hipGraph (the reference's torch.compile(model, "
                          "mode='reduce-overhead'), main.py:284, for the whole step); single process")
+    ap.add_argument("--device-mix", action="store_true",
+                    help="MixUp / CutMix on the device: the batch is mixed inside the tokenizer's gather and the loss taken "
+                         "from the label pair (same seeded draws); with --graph the augmentation is part of the replayed step")
     a = ap.parse_args()
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
@@ -158,12 +161,19 @@ def main():
     graphed = None
     if a.graph:
         model.train()
-        graphed = GraphedTrainStep(model, torch.zeros(per_rank, 3, a.img_size, a.img_size, device=device),
-                                   torch.zeros(per_rank, a.classes, device=device), optimizer, scheduler, reducer=reducer)
+        images0 = torch.zeros(per_rank, 3, a.img_size, a.img_size, device=device)
+        if a.device_mix:
+            graphed = GraphedTrainStep(model, images0, None, optimizer, scheduler, reducer=reducer,
+                                       mix=BatchMix(per_rank, device),
+                                       labels=(torch.zeros(per_rank, dtype=torch.int64, device=device),
+                                               torch.zeros(per_rank, dtype=torch.int64, device=device)))
+        else:
+            graphed = GraphedTrainStep(model, images0, torch.zeros(per_rank, a.classes, device=device), optimizer, scheduler,
+                                       reducer=reducer)
 
     for epoch in range(start_epoch, a.epochs):
         tr_loss, tr_acc = train_with_mixup_or_cutmix(model, train_loader, train_criterion, optimizer, scheduler,
-                                                     device, reducer=reducer, graphed=graphed)
+                                                     device, reducer=reducer, graphed=graphed, device_mix=a.device_mix)
         te_loss, te_acc = evaluate(model, test_loader, test_criterion, device)
         if world > 1:                                  # equal shards per rank: the global figures are the rank means
             t = torch.tensor([tr_loss, tr_acc, te_loss, te_acc], device=device, dtype=torch.float64)

@@ -80,6 +80,11 @@ SIGNATURES = {
     "sfcvit_hier_resample_concat_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sfcvit_tokens_gather_tiles": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "sfcvit_tokens_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "sfcvit_tokens_gather_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                         c_int, c_void_p, c_int, c_void_p]),
+    "sfcvit_mix_images": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "sfcvit_soft_ce_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_float, c_void_p]),
     "sfcvit_reduce_defer": (c_int, [c_int]),
     "sfcvit_reduce_pending": (c_int, []),
     "sfcvit_reduce_flush": (c_int, [c_void_p]),

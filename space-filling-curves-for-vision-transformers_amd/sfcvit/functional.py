@@ -127,9 +127,9 @@ class _PatchEmbed2(Function):
     the persistent GEMMs at 950-1 150 TFLOP/s -- what the reference does (hilbert_embedding1D.py:36-43), minus its reshape copy."""
 
     @staticmethod
-    def forward(ctx, x, pix, w, b, desc, order):
+    def forward(ctx, x, pix, w, b, desc, order, mix=None):
         B, (N, P) = x.shape[0], pix.shape
-        tokens = ops.gather_tokens(_c(x), pix, desc, order)
+        tokens = ops.gather_tokens(_c(x), pix, desc, order, mix)      # mix: MixUp / CutMix inside the gather; backward sees tokens only
         ctx.save_for_backward(tokens, w)
         ctx.small = (b,)
         return ops.gemm(tokens, w, bias=b).view(B, N, w.shape[0])
@@ -139,7 +139,7 @@ class _PatchEmbed2(Function):
         tokens, w = ctx.saved_tensors
         dy2 = _c(dy).view(-1, dy.shape[-1])
         b = ctx.small[0]
-        return None, None, _wgrad(dy2, tokens, w), (_bgrad(dy2, b) if b is not None else None), None, None
+        return None, None, _wgrad(dy2, tokens, w), (_bgrad(dy2, b) if b is not None else None), None, None, None
 
 
 class _PatchEmbed(Function):
@@ -182,16 +182,30 @@ def pe_two_stage(x, pix, D):
     return PE_TWO_STAGE and K % 8 == 0 and 2.0 * x.shape[0] * pix.shape[0] * K * D >= 4e9
 
 
-def patch_embed(x, pix, weight, bias, desc=None, order=None):
-    """Curve gather + patchify + projection: x [B,C,H,W] (fp32 or bf16) -> [B,N,D] bf16.
-    desc = ops.TileDesc of the pixel table (tokens are 16 x 16 tiles / 256-pixel strips) or None: picks the tile gather
-    kernel (and the fused kernels of SFCVIT_PE_FUSED=1); order = ops.gather_order of the table on the device, or None."""
+def mix_images(x, mix):
+    """The MixUp / CutMix'd image batch (fp32, one pass: ops.mix_images), for the tokenizers that do not materialise
+    tokens.  Images receive no gradient; mix = None returns x."""
+    if mix is None:
+        return x
     if _traced():
         from . import library
-        return library.patch_embed(x, pix, _bf(weight), _bf(bias), desc)
+        return library.mix_images(x, mix)
+    return ops.mix_images(x.detach(), mix)
+
+
+def patch_embed(x, pix, weight, bias, desc=None, order=None, mix=None):
+    """Curve gather + patchify + projection: x [B,C,H,W] (fp32 or bf16) -> [B,N,D] bf16.
+    desc = ops.TileDesc of the pixel table (tokens are 16 x 16 tiles / 256-pixel strips) or None: picks the tile gather
+    kernel (and the fused kernels of SFCVIT_PE_FUSED=1); order = ops.gather_order of the table on the device, or None.
+    mix = a sfcvit.training.BatchMix or None: MixUp / CutMix of the batch, inside the gather where tokens are
+    materialised (gather + GEMM), as one pass over the image in front of the fused kernels otherwise (they re-gather
+    from the saved image in backward and so need the mixed one)."""
+    if _traced():
+        from . import library
+        return library.patch_embed(mix_images(x, mix), pix, _bf(weight), _bf(bias), desc)
     if pe_two_stage(x, pix, weight.shape[0]):
-        return _PatchEmbed2.apply(x, pix, _bf(weight), _bf(bias), desc, order)
-    return _PatchEmbed.apply(x, pix, _bf(weight), _bf(bias), desc)
+        return _PatchEmbed2.apply(x, pix, _bf(weight), _bf(bias), desc, order, mix)
+    return _PatchEmbed.apply(mix_images(x, mix), pix, _bf(weight), _bf(bias), desc)
 
 
 class _ResampleConcat(Function):
@@ -671,6 +685,28 @@ def soft_target_cross_entropy(logits, targets):
     return _SoftCE.apply(_bf(logits), targets)
 
 
+class _PairCE(Function):
+    @staticmethod
+    def forward(ctx, logits, y_a, y_b, mix):
+        B, C = logits.shape
+        rows, dl, hits = ops.soft_ce_pair(_c(logits), _c(y_a), _c(y_b), mix, C, 1.0 / B)
+        ctx.save_for_backward(dl)
+        ctx.mark_non_differentiable(hits)
+        return rows.mean(), hits
+
+    @staticmethod
+    def backward(ctx, g, _ghits):
+        (dl,) = ctx.saved_tensors
+        return dl * g.to(dl.dtype), None, None, None
+
+
+def mixed_target_cross_entropy(logits, y_a, y_b, mix):
+    """soft_target_cross_entropy on lam * onehot(y_a) + (1 - lam) * onehot(y_b) without building the targets: lam comes
+    from the batch mix's device record, the labels are int64 [B] on the device.  -> (loss, hit_rows) with
+    hit_rows[b] = lam * (argmax == y_a) + (1 - lam) * (argmax == y_b), the loop's accuracy bookkeeping (train.py:171)."""
+    return _PairCE.apply(_bf(logits), y_a, y_b, mix)
+
+
 # ----------------------------------------------------------------------------
 # torch.compile (main.py:284 wraps the model in torch.compile(mode="reduce-overhead")).  The blocks a VisionTransformer{,1D}
 # is made of -- patch_embed, mixer_block, encoder_layer, predictor_head, soft_target_cross_entropy -- are registered as
@@ -679,6 +715,6 @@ def soft_target_cross_entropy(logits, targets):
 # (used by the hierarchical tokenizers, altvit and MultiLayerPredictor(n_layers > 2)) stay opaque: Dynamo breaks the graph
 # around each and runs it as written.
 # ----------------------------------------------------------------------------
-for _name in ("hier_tokenizer", "linear", "layer_norm", "gelu", "gelu_dropout", "attention"):
+for _name in ("mixed_target_cross_entropy", "hier_tokenizer", "linear", "layer_norm", "gelu", "gelu_dropout", "attention"):
     globals()[_name] = torch.compiler.disable(globals()[_name], recursive=True)
 del _name

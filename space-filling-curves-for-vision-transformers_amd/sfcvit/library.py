@@ -124,6 +124,22 @@ def _pe_backward(ctx, dy, _dxs):
 patch_embed_op.register_autograd(_pe_backward, setup_context=_pe_setup)
 
 
+# mix_images: the MixUp / CutMix'd image batch in front of patch_embed (images receive no gradient: none is registered)
+class _MixView:
+    def __init__(self, perm, rec):
+        self.perm, self.rec = perm, rec
+
+
+@torch.library.custom_op("sfcvit::mix_images", mutates_args=())
+def mix_images_op(x: Tensor, perm: Tensor, rec: Tensor) -> Tensor:
+    return ops.mix_images(x, _MixView(perm, rec))
+
+
+@mix_images_op.register_fake
+def _(x, perm, rec):
+    return x.new_empty(x.shape, dtype=torch.float32)
+
+
 # the two-stage form (functional._PatchEmbed2: gather, then the projection on the GEMM kernels): y, tokens
 @torch.library.custom_op("sfcvit::patch_embed2", mutates_args=())
 def patch_embed2_op(x: Tensor, pix: Tensor, w: Tensor, b: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
@@ -400,6 +416,10 @@ def patch_embed(x, pix, weight, bias, desc):
         return torch.ops.sfcvit.patch_embed2(x.contiguous(), pix, weight, bias)[0]
     meta = [desc.mode, desc.ncls, *desc.cnt] if desc is not None else []
     return torch.ops.sfcvit.patch_embed(x, pix, weight, bias, desc.dev if desc is not None else None, meta)[0]
+
+
+def mix_images(x, mix):
+    return torch.ops.sfcvit.mix_images(x, mix.perm, mix.rec)
 
 
 def mixer_block(x, ln_w, ln_b, w1, b1, w2, b2, eps):

@@ -67,8 +67,8 @@ class HilbertPatchEmbedding(nn.Module):
         # the class's private integer recursion equals the src/curves Hilbert order on power-of-two grids
         self.hilbert_indices = torch.from_numpy(curve_table(hilbert_curve, self.grid_h)).long()
 
-    def forward(self, x):
-        x = _patches(x, self.patch_height, self.patch_width)[:, self.hilbert_indices.to(x.device)]
+    def forward(self, x, mix=None):
+        x = _patches(F.mix_images(x, mix), self.patch_height, self.patch_width)[:, self.hilbert_indices.to(x.device)]
         x = F.layer_norm(x, self.layernorm1.weight, self.layernorm1.bias, self.layernorm1.eps)
         x = F.linear(x, self.linear.weight, self.linear.bias)
         return F.layer_norm(x, self.layernorm2.weight, self.layernorm2.bias, self.layernorm2.eps)
@@ -146,7 +146,8 @@ class SimpleViT(_PooledViT):
         self.to_latent = nn.Identity()
         self.linear_head = nn.Linear(dim, num_classes)
 
-    def forward(self, img):
+    def forward(self, img, mix=None):
+        img = F.mix_images(img, mix)
         pat, ln1, lin, ln2 = self.to_patch_embedding
         x = F.layer_norm(pat(img), ln1.weight, ln1.bias, ln1.eps)
         x = F.layer_norm(F.linear(x, lin.weight, lin.bias), ln2.weight, ln2.bias, ln2.eps)
@@ -185,5 +186,5 @@ class HilbertViT(_PooledViT):
         self.to_latent = nn.Identity()
         self.linear_head = nn.Linear(dim, num_classes)
 
-    def forward(self, img):
-        return self._encode(self.to_patch_embedding(img))
+    def forward(self, img, mix=None):
+        return self._encode(self.to_patch_embedding(F.mix_images(img, mix)))

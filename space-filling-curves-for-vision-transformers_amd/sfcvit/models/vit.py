@@ -143,8 +143,9 @@ class VisionTransformer(nn.Module):
         self.mlp_head = MultiLayerPredictor(embed_dim, self.patch_embed.n_patches, n_layers=2,
                                             num_classes=num_classes, dropout_p=head_dropout_p)
 
-    def forward(self, x):
-        x = self.patch_embed(x)
+    def forward(self, x, mix=None):
+        """mix: a sfcvit.training.BatchMix applied to the image batch by the tokenizer, or None."""
+        x = self.patch_embed(x) if mix is None else self.patch_embed(x, mix=mix)
         x = self.encoder(x)
         return self.mlp_head(x)
 
@@ -165,8 +166,9 @@ class VisionTransformer1D(nn.Module):
         self.mlp_head = MultiLayerPredictor(embed_dim, self.patch_embed.n_patches, n_layers=2,
                                             dropout_p=head_dropout_p, num_classes=num_classes)
 
-    def forward(self, x):
-        x = self.patch_embed(x)
+    def forward(self, x, mix=None):
+        """mix: a sfcvit.training.BatchMix applied to the image batch by the tokenizer, or None."""
+        x = self.patch_embed(x) if mix is None else self.patch_embed(x, mix=mix)
         x = self.mlp_mixer(x)
         x = self.encoder(x)
         return self.mlp_head(x)

@@ -583,19 +583,43 @@ def gather_order(pix_host):
     return np.argsort(pix_host.min(axis=1), kind="stable").astype(np.int32)
 
 
-def gather_tokens(x, pix, desc=None, order=None):
+def _mix_ptrs(mix, x, name):
+    """(perm, rec) pointers of a batch mix (sfcvit.training.BatchMix, or anything with int32 `perm` [B] and `rec` [8] on
+    x's device) after checking them against the image batch."""
+    if x.dtype != torch.float32:
+        raise TypeError(f"{name}: a mix needs an fp32 image batch (what a loader delivers), got {x.dtype}; "
+                        "mixing a bf16 batch is not supported")
+    perm = _need(mix.perm, torch.int32, f"{name} mix.perm", 1)
+    rec = _need(mix.rec, torch.int32, f"{name} mix.rec", 1)
+    if perm.numel() != x.shape[0] or rec.numel() != 8:
+        raise ValueError(f"{name}: mix is for a batch of {perm.numel()} images (rec of {rec.numel()} words), "
+                         f"the batch has {x.shape[0]}")
+    return _p(perm), _p(rec)
+
+
+def gather_tokens(x, pix, desc=None, order=None, mix=None):
     """x [B,C,H,W] fp32/bf16, pix [N,P] int32 (device) -> tokens [B*N, P*C (rounded up to 8)] bf16 in the reference's
     feature order kk * C + c: the A operand of the projection GEMM and of its weight gradient.
     desc: TileDesc of the table or None; order: device int32 [N] from gather_order() or None (tokens paired as numbered).
-    16 x 16 tiles of an fp32 image go to sfcvit_tokens_gather_tiles, everything else to sfcvit_tokens_gather."""
+    16 x 16 tiles of an fp32 image go to sfcvit_tokens_gather_tiles, everything else to sfcvit_tokens_gather.
+    mix: a batch mix (sfcvit.training.BatchMix) applied on the way to bf16 (sfcvit_tokens_gather_mix: MixUp / CutMix of
+    image b with image mix.perm[b], fp32 images only); None = the plain gather."""
     N, P = pix.shape
     a = _pe_args(x, pix, N, P, 8)
     ld = (P * a.C + 7) // 8 * 8
-    tokens = torch.empty((a.B * N, ld), device=x.device, dtype=_BF16)
     if order is not None:
         _need(order, torch.int32, "gather order", 1)
-    if GATHER_TILES and desc is not None and desc.mode == 1 and P == 256 and a.C <= 4 and x.dtype == torch.float32:
-        origin = desc.dev[16 + N:16 + 2 * N]
+    tiles = GATHER_TILES and desc is not None and desc.mode == 1 and P == 256 and a.C <= 4 and x.dtype == torch.float32
+    origin = desc.dev[16 + N:16 + 2 * N] if tiles else None
+    if mix is not None:
+        perm, rec = _mix_ptrs(mix, x, "gather_tokens")
+        tokens = torch.empty((a.B * N, ld), device=x.device, dtype=_BF16)
+        check(_launch("tokens_gather", 0.0, lambda: lib.sfcvit_tokens_gather_mix(_p(x), _p(pix), _p(order), _p(origin), perm, rec, a.B, a.C,
+                                                                               x.shape[2], x.shape[3], N, P, _p(tokens), ld, _stream())),
+              "sfcvit_tokens_gather_mix")
+        return tokens
+    tokens = torch.empty((a.B * N, ld), device=x.device, dtype=_BF16)
+    if tiles:
         check(_launch("tokens_gather", 0.0, lambda: lib.sfcvit_tokens_gather_tiles(_p(x), _p(pix), _p(order), _p(origin), a.B, a.C, x.shape[2],
                                                                                  x.shape[3], N, _p(tokens), ld, _stream())),
               "sfcvit_tokens_gather_tiles")
@@ -603,6 +627,21 @@ def gather_tokens(x, pix, desc=None, order=None):
     check(_launch("tokens_gather", 0.0, lambda: lib.sfcvit_tokens_gather(_p(x), a.x_is_bf16, _p(pix), _p(order), a.B, a.C, a.HW, N, P,
                                                                        _p(tokens), ld, _stream())), "sfcvit_tokens_gather")
     return tokens
+
+
+def mix_images(x, mix):
+    """x [B,C,H,W] fp32 -> the mixed batch (new tensor, fp32): MixUp / CutMix of image b with image mix.perm[b] as
+    mix.rec says, one pass (sfcvit_mix_images).  For the tokenizers that do not go through gather_tokens."""
+    if not x.is_cuda:
+        raise _lib.SfcvitError(f"mix_images: the HIP path needs a CUDA (ROCm) tensor, got device {x.device}; there is no CPU fallback")
+    if x.dim() != 4:
+        raise ValueError(f"mix_images x: expected [B,C,H,W], got shape {tuple(x.shape)}")
+    perm, rec = _mix_ptrs(mix, x, "mix_images")
+    x = _need(x if x.is_contiguous() else x.contiguous(), torch.float32, "mix_images x", 4)
+    B, C, H, W = x.shape
+    out = torch.empty_like(x)
+    check(_launch("mix_images", 0.0, lambda: lib.sfcvit_mix_images(_p(x), perm, rec, _p(out), B, C, H, W, _stream())), "sfcvit_mix_images")
+    return out
 
 
 def patch_embed_fwd(x, pix, w, bias, desc=None):
@@ -745,6 +784,25 @@ def soft_ce(logits, targets, n_classes, gscale):
     check(lib.sfcvit_soft_ce(_p(logits), _p(targets), _p(loss_rows), _p(dlogits), B, n_classes, ld, gscale, _stream()),
           "sfcvit_soft_ce")
     return loss_rows, dlogits
+
+
+def soft_ce_pair(logits, y_a, y_b, mix, n_classes, gscale):
+    """logits bf16 [B, ld] (first n_classes columns are classes), y_a / y_b int64 [B] (device), mix: the batch mix whose
+    record holds lam -> loss_rows fp32 [B], dlogits bf16 [B, ld] (times gscale), hit_rows fp32 [B]
+    (lam * (argmax == y_a) + (1 - lam) * (argmax == y_b)): sfcvit_soft_ce_pair."""
+    _need(logits, _BF16, "soft_ce_pair logits", 2)
+    _need(y_a, torch.int64, "soft_ce_pair y_a", 1)
+    _need(y_b, torch.int64, "soft_ce_pair y_b", 1)
+    rec = _need(mix.rec, torch.int32, "soft_ce_pair mix.rec", 1)
+    B, ld = logits.shape
+    if y_a.numel() != B or y_b.numel() != B or rec.numel() != 8:
+        raise ValueError(f"soft_ce_pair: {B} rows of logits, {y_a.numel()} / {y_b.numel()} labels, rec of {rec.numel()} words")
+    loss_rows = torch.empty(B, device=logits.device, dtype=torch.float32)
+    hit_rows = torch.empty(B, device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits)
+    check(lib.sfcvit_soft_ce_pair(_p(logits), _p(y_a), _p(y_b), _p(rec), _p(loss_rows), _p(dlogits), _p(hit_rows), B, n_classes, ld,
+                                  gscale, _stream()), "sfcvit_soft_ce_pair")
+    return loss_rows, dlogits, hit_rows
 
 
 def sumsq_accum(g, out):

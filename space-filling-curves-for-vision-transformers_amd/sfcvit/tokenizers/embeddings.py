@@ -88,7 +88,8 @@ class _FusedTokenizer(BasePatchEmbedding):
 
     _static_order = True            # False: the token order changes from call to call (RandomEmbedding): nothing to prebuild
 
-    def forward(self, x):
+    def forward(self, x, mix=None):
+        """mix: a sfcvit.training.BatchMix (MixUp / CutMix of the batch on the device) or None."""
         img = self._geom[0]
         if x.dim() != 4 or x.shape[2] != img or x.shape[3] != img:
             raise ValueError(f"expected [B, C, {img}, {img}] input, got {tuple(x.shape)}")
@@ -100,7 +101,7 @@ class _FusedTokenizer(BasePatchEmbedding):
             pix = self._pix
         else:
             pix = self._pix_table(x.device)
-        return F.patch_embed(x, pix, self.proj.weight, self.proj.bias, self._desc, self._order)
+        return F.patch_embed(x, pix, self.proj.weight, self.proj.bias, self._desc, self._order, mix)
 
 
 class _Curve1D(_FusedTokenizer):
@@ -233,13 +234,13 @@ class _Conv2dTokenizer(_FusedTokenizer):
     def _flat_table(self):
         return None
 
-    def forward(self, x):
+    def forward(self, x, mix=None):
         img = self._geom[0]
         if x.dim() != 4 or x.shape[2] != img or x.shape[3] != img:
             raise ValueError(f"expected [B, C, {img}, {img}] input, got {tuple(x.shape)}")
         w = self.proj.weight
         w2 = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
-        return F.patch_embed(x, self._pix_table(x.device), w2, self.proj.bias)
+        return F.patch_embed(F.mix_images(x, mix), self._pix_table(x.device), w2, self.proj.bias)
 
 
 class ZigzagEmbedding(_Conv2dTokenizer):
@@ -263,10 +264,10 @@ class RandomEmbedding(_Conv2dTokenizer):
     (drawn from torch's CPU generator, as in the reference)."""
     _static_order = False
 
-    def forward(self, x):
+    def forward(self, x, mix=None):
         self._perm = torch.randperm(self.n_patches)
         self._pix_key = None                     # a new order every call: never reuse the cached pixel table
-        return super().forward(x)
+        return super().forward(x, mix)
 
     def _flat_table(self):
         return self._perm

@@ -54,7 +54,8 @@ class _Hierarchical(nn.Module):
             self._fuse_key = key
         return self._fuse_ok
 
-    def forward(self, x, one_kernel=None):
+    def forward(self, x, one_kernel=None, mix=None):
+        x = F.mix_images(x, mix)                     # every level reads the same mixed batch: mixed once, in one pass
         if self._fusable(x):
             img = self.levels[0]._geom[0]
             if x.dim() != 4 or x.shape[2] != img or x.shape[3] != img:

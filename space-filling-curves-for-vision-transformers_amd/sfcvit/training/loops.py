@@ -76,13 +76,69 @@ def train_with_scheduler(model, train_loader, criterion, optimizer, scheduler, d
     return _plain_epoch(model, train_loader, criterion, optimizer, scheduler, device)
 
 
+def _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_alpha, cutmix_alpha, mix_prob, reducer, graphed):
+    """train_with_mixup_or_cutmix(device_mix=True): the same draws, but the batch is mixed where the tokenizer reads it
+    (model(images, mix=bm)) and the loss / accuracy come from the label pair (F.mixed_target_cross_entropy)."""
+    from .. import functional as F
+    from .mix import BatchMix
+    model.train()
+    total_loss = torch.zeros((), device=device)
+    total_correct = torch.zeros((), device=device)
+    total_samples = 0
+    mixes = {}                                       # one record per batch size (the last batch of an epoch may be short)
+    for images, labels in train_loader:
+        images, labels = images.to(device), labels.to(device)
+        B, (H, W) = images.size(0), images.shape[2:]
+        if graphed is not None and graphed.mix is not None and images.shape == graphed.images.shape:
+            bm = graphed.mix.draw(H, W, mixup_alpha, cutmix_alpha, mix_prob)
+            graphed.images.copy_(images)
+            graphed.labels[0].copy_(labels)
+            torch.index_select(labels, 0, bm.idx, out=graphed.labels[1])
+            loss = graphed()
+            total_correct += graphed.hits.sum()
+            total_loss += loss.float() * B
+            total_samples += B
+            continue
+        bm = mixes.get(B)
+        if bm is None:
+            bm = mixes[B] = BatchMix(B, images.device)
+        bm.draw(H, W, mixup_alpha, cutmix_alpha, mix_prob)
+        y_a, y_b = labels, labels[bm.idx]
+        if hasattr(optimizer, "begin_step"):
+            optimizer.begin_step()
+        optimizer.zero_grad()
+        if reducer is not None:
+            reducer.begin_step()
+        outputs = model(images, mix=bm)
+        loss, hits = F.mixed_target_cross_entropy(outputs, y_a, y_b, bm)
+        loss.backward()
+        if reducer is not None:
+            reducer.finish()
+        if not isinstance(optimizer, FusedAdamW):
+            torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0, foreach=False)
+        optimizer.step()
+        if scheduler is not None:
+            scheduler.step()
+        total_correct += hits.sum()
+        total_loss += loss.detach().float() * B
+        total_samples += B
+    return float(total_loss) / total_samples, float(total_correct) / total_samples
+
+
 def train_with_mixup_or_cutmix(model, train_loader, criterion, optimizer, scheduler, device,
-                               mixup_alpha=0.2, cutmix_alpha=1.0, mix_prob=0.5, reducer=None, graphed=None):
+                               mixup_alpha=0.2, cutmix_alpha=1.0, mix_prob=0.5, reducer=None, graphed=None, device_mix=False):
     """train.py:133-178.  `optimizer` is a FusedAdamW (clip inside) or any torch optimizer.
     graphed: a sfcvit.training.GraphedTrainStep built on this model / optimizer / scheduler with static buffers of the
     loader's batch shape -- the step (forward, soft-target CE, backward, clip, AdamW, scheduler) is then one hipGraph
     replay per batch (what main.py:284's torch.compile(mode="reduce-overhead") is after); batches of another size run
-    eagerly."""
+    eagerly.
+    device_mix: MixUp / CutMix on the device (sfcvit.training.BatchMix): the same seeded draws, the batch mixed inside
+    the tokenizer's gather and the loss / accuracy taken from the label pair; `criterion` is not called (the loss is
+    soft-target cross entropy, as main.py's).  With a GraphedTrainStep(mix=..., labels=...) the augmentation is part
+    of the replayed step."""
+    if device_mix:
+        return _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_alpha, cutmix_alpha, mix_prob,
+                                 reducer, graphed)
     model.train()
     total_loss = torch.zeros((), device=device)
     total_correct = torch.zeros((), device=device)

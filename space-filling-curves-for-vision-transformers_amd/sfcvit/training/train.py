@@ -29,7 +29,9 @@ class GraphedTrainStep:
     by one; a replay is one call.
 
     `images` / `targets` are STATIC buffers: copy each new batch into them (`.copy_`) before calling; `.logits` is the
-    static output of the last replay (accuracy bookkeeping of the epoch loops).  Needs the
+    static output of the last replay (accuracy bookkeeping of the epoch loops).  With `mix=BatchMix` and
+    `labels=(y_a, y_b)` (static int64 buffers) the step mixes the raw batch itself (model(images, mix=mix) + the
+    label-pair loss; `targets` may be None) and `.hits` is the static per-row hit count of the last replay.  Needs the
     optimizer's device-resident step state (dropout seeds and Adam's step count would otherwise be frozen into the
     graph as by-value kernel arguments).  Shapes, model mode (train / eval) and dropout rates are fixed at capture.
     Data parallelism: pass `reducer=GradReducer(optimizer, overlap=False)`; the step is then TWO graphs -- forward +
@@ -40,9 +42,17 @@ class GraphedTrainStep:
     `preserve_state` (default) parameters, optimizer moments, step count and scheduler position are put back
     afterwards, so that a training script that switches to the graphed step trains exactly as before."""
 
-    def __init__(self, model, images, targets, optimizer, scheduler=None, warmup=3, preserve_state=True, reducer=None):
+    def __init__(self, model, images, targets, optimizer, scheduler=None, warmup=3, preserve_state=True, reducer=None,
+                 mix=None, labels=None):
         self.model, self.images, self.targets, self.opt, self.sched = model, images, targets, optimizer, scheduler
         self.logits = None
+        # device-side MixUp / CutMix: the captured step is model(images, mix=mix) + the label-pair loss; `images` then holds
+        # the RAW batch, `labels` = static int64 (y_a, y_b), and the augmentation changes with mix.draw() between replays
+        self.mix, self.labels, self.hits = mix, labels, None
+        if (mix is None) != (labels is None):
+            raise ValueError("GraphedTrainStep: mix= and labels= (static y_a, y_b) go together")
+        if mix is None and targets is None:
+            raise ValueError("GraphedTrainStep: targets may only be None with mix= and labels=")
         self.reducer = reducer
         if reducer is not None and reducer.overlap:
             raise ValueError("GraphedTrainStep needs GradReducer(optimizer, overlap=False): hooks cannot run inside a graph replay")
@@ -78,8 +88,12 @@ class GraphedTrainStep:
     def _fwd_bwd(self):
         self.opt.begin_step()
         self.opt.zero_grad()
-        logits = self.model(self.images)
-        loss = F.soft_target_cross_entropy(logits, self.targets)
+        if self.mix is not None:
+            logits = self.model(self.images, mix=self.mix)
+            loss, self.hits = F.mixed_target_cross_entropy(logits, self.labels[0], self.labels[1], self.mix)
+        else:
+            logits = self.model(self.images)
+            loss = F.soft_target_cross_entropy(logits, self.targets)
         loss.backward()
         if self.reducer is not None and self.opt.flat_grad is not None:
             self.opt.adopt_all()                      # every gradient in the flat buffer before the collectives read it
