@@ -175,6 +175,63 @@ int sfcvit_soft_ce_pair(const void *logits, const int64_t *y_a, const int64_t *y
                         void *dlogits, float *hit_rows, int B, int C, int ld, float gscale, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Train / test image transforms on the device: uint8 batch in, normalized images out
+ *   replaces the per-sample transform stack of the reference's loaders (main.py:169-188):
+ *     train  RandomResizedCrop(size) -> RandomHorizontalFlip -> ColorJitter(0.4, 0.4, 0.4, 0.1) -> ToImage /
+ *            ToDtype(float32, scale=True) -> RandomErasing(p=0.2) -> Normalize(mean, std)
+ *     test   ToDtype -> Normalize
+ *   in two steps: a HOST draw of one 16-word record per image (plain C++, no HIP), and ONE capturable launch that
+ *   reads the uint8 batch [B, C, H, W] and the device copy of the records and writes the augmented, scaled,
+ *   normalized batch [B, C, S, S] (fp32 or bf16).
+ *
+ * Record, 16 words of 32 bits per image:
+ *   [0]      flags: bit 0 flip, bit 1 erase, bits 2-5 = brightness / contrast / saturation / hue enabled
+ *   [1..4]   crop top, left, h, w (ints, inside the H x W source)
+ *   [5]      jitter order: four 2-bit fields, field i = the op applied i-th (0 brightness, 1 contrast, 2 saturation,
+ *            3 hue), a permutation of 0..3
+ *   [6..9]   brightness, contrast, saturation, hue factors (fp32 bit patterns)
+ *   [10..13] erase top, left, h, w on the S x S OUTPUT grid
+ *   [14..15] 0
+ * Every random number of the draw is a pure function of (seed, step, sample_base + b, draw index), so a sample's
+ * record does not depend on batch size, rank or call order (csrc/augment.cpp states the stream).
+ * ---------------------------------------------------------------------- */
+#define SFCVIT_AUG_WORDS 16
+#define SFCVIT_AUG_FLAGS 0
+#define SFCVIT_AUG_CROP 1
+#define SFCVIT_AUG_ORDER 5
+#define SFCVIT_AUG_FACTORS 6
+#define SFCVIT_AUG_ERASE 10
+#define SFCVIT_AUG_FLIP_BIT 1u
+#define SFCVIT_AUG_ERASE_BIT 2u
+#define SFCVIT_AUG_JITTER_SHIFT 2     /* flags bit (2 + op) = op enabled */
+#define SFCVIT_AUG_ORDER_IDENTITY 0xE4u
+
+typedef struct sfcvit_augment_cfg {
+    int32_t S;            /* output size (S x S); the apply needs S >= H and S >= W (upsampling or identity) */
+    int32_t crop;         /* draw a RandomResizedCrop box (0 = the whole image) */
+    int32_t flip;         /* draw a horizontal flip with probability 1/2 */
+    int32_t out_is_bf16;  /* output dtype of the apply: 0 fp32, 1 bf16 (round to nearest even) */
+    double scale[2];      /* crop: area fraction range, torchvision's default (0.08, 1) */
+    double ratio[2];      /* crop: aspect range, default (3/4, 4/3) */
+    double brightness, contrast, saturation, hue;   /* ColorJitter ranges; 0 disables the op */
+    double erase_p;       /* RandomErasing probability; 0 disables it (area 0.02-0.33 of S x S, aspect 0.3-3.3) */
+    float mean[3], std[3]; /* Normalize, per channel (the apply refuses a zero std) */
+} sfcvit_augment_cfg;
+
+/* HOST. Fills rec_host[B * 16] for samples sample_base .. sample_base + B - 1 of step `step`.  Every switch off
+ * (a zeroed cfg with S = H = W) gives the test transform's record: flags 0, the whole image, identity order. */
+int sfcvit_augment_draw(uint32_t *rec_host, int B, int H, int W, const sfcvit_augment_cfg *cfg, uint64_t seed, uint64_t step,
+                        int64_t sample_base);
+/* x uint8 [B, C, H, W], rec_dev the device copy of the records, out [B, C, S, S] fp32 or bf16; cfg is a HOST pointer
+ * read before the call returns.  Per output pixel, in fp32 on v / 255: bilinear crop + resize (align_corners = False,
+ * taps inside the crop box, the output column mirrored under flip), the jitter ops in the record's order (contrast
+ * blends with the image's gray mean AS IT STANDS before that op: a per-image reduction in a fixed order, so two runs
+ * give the same bits), the erase box set to 0, (x - mean) / std.  1 <= C <= 3, and C == 3 when a colour op is enabled.
+ * A record that was never filled in is clamped into the image: no read leaves the batch whatever the buffer holds. */
+int sfcvit_augment_apply(const uint8_t *x, const uint32_t *rec_dev, void *out, int B, int C, int H, int W,
+                         const sfcvit_augment_cfg *cfg, void *stream);
+
+/* ------------------------------------------------------------------------
  * Fused hierarchical tokenizer, forward
  *   replaces HierarchicalHilbertEmbedding.forward (src/tokenizers/multiscale/multi_hilbert.py:31-40) and its
  *   siblings multi_morton.py / multi_moore.py / multi_peano.py / multi_onion.py / multi_zigzag.py (same lines) when

@@ -26,15 +26,17 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from sfcvit.models.vit import VisionTransformer1D                                  # noqa: E402
 import sfcvit.tokenizers as T                                                       # noqa: E402
-from sfcvit.training import BatchMix, FusedAdamW, GradReducer, GraphedTrainStep, SoftTargetCrossEntropy, WarmupCosine   # noqa: E402
+from sfcvit.training import BatchMix, DeviceAugment, FusedAdamW, GradReducer, GraphedTrainStep, SoftTargetCrossEntropy, WarmupCosine   # noqa: E402
 from sfcvit.training.loops import evaluate, train_with_mixup_or_cutmix             # noqa: E402
 
 
 class SyntheticLoader:
-    """CIFAR-shaped random batches, regenerated deterministically every epoch."""
+    """CIFAR-shaped random batches, regenerated deterministically every epoch.  uint8=True (--device-augment): raw
+    [0, 255] images, as a dataset holds them before any transform."""
 
-    def __init__(self, n, batch, img, classes, seed, device):
+    def __init__(self, n, batch, img, classes, seed, device, uint8=False):
         self.n, self.batch, self.img, self.classes, self.seed, self.device = n, batch, img, classes, seed, device
+        self.uint8 = uint8
         self.dataset = range(n)
 
     def __len__(self):
@@ -43,6 +45,10 @@ class SyntheticLoader:
     def __iter__(self):
         g = torch.Generator(device=self.device).manual_seed(self.seed)
         for _ in range(len(self)):
+            if self.uint8:
+                yield (torch.randint(0, 256, (self.batch, 3, self.img, self.img), device=self.device, generator=g, dtype=torch.uint8),
+                       torch.randint(0, self.classes, (self.batch,), device=self.device, generator=g))
+                continue
             yield (torch.randn(self.batch, 3, self.img, self.img, device=self.device, generator=g),
                    torch.randint(0, self.classes, (self.batch,), device=self.device, generator=g))
 
@@ -94,6 +100,12 @@ def main():
     ap.add_argument("--device-mix", action="store_true",
                     help="MixUp / CutMix on the device: the batch is mixed inside the tokenizer's gather and the loss taken "
                          "from the label pair (same seeded draws); with --graph the augmentation is part of the replayed step")
+    ap.add_argument("--device-augment", action="store_true",
+                    help="the reference's transform stack (RandomResizedCrop, flip, ColorJitter, RandomErasing, Normalize; "
+                         "main.py:169-188) on the device: the loaders then yield raw uint8 batches [B, 3, H, W]; works with "
+                         "--device-mix and --graph")
+    ap.add_argument("--mean", type=float, nargs=3, default=[0.4914, 0.4822, 0.4465])      # main.py:176-177 (CIFAR)
+    ap.add_argument("--std", type=float, nargs=3, default=[0.2023, 0.1994, 0.2010])
     a = ap.parse_args()
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
@@ -116,7 +128,7 @@ def main():
         # The reference builds its loaders inline (main.py:169-230: torchvision CIFAR-10 + v2 transforms, DataLoader with
         # 16 workers).  That pipeline is the caller's; this is the hook for it: `pkg.mod:fn` names a factory
         #     fn(batch_size=, img_size=, classes=, rank=, world=, seed=) -> (train_loader, test_loader)
-        # returning iterables of (images [B, 3, H, W] float, labels [B] int64) with __len__, on any device (the loops move
+        # returning iterables of (images [B, 3, H, W] float -- raw uint8 under --device-augment --, labels [B] int64) with __len__, on any device (the loops move
         # every batch to the GPU, src/training/train.py:144-145), each rank's own shard, every batch of `batch_size` rows.
         import importlib
         mod, _, fn = a.data_module.partition(":")
@@ -130,8 +142,15 @@ def main():
             print("no --data-module given (the reference's torchvision CIFAR-10 pipeline, main.py:169-230, is not part of "
                   "this package" + ("" if have_tv else " and torchvision is not installed") + "): using --synthetic data")
             a.synthetic = True
-        train_loader = SyntheticLoader(a.train_size // world, per_rank, a.img_size, a.classes, seed + 1 + rank, device)
-        test_loader = SyntheticLoader(a.test_size // world, per_rank, a.img_size, a.classes, seed + 1001 + rank, device)
+        train_loader = SyntheticLoader(a.train_size // world, per_rank, a.img_size, a.classes, seed + 1 + rank, device,
+                                       uint8=a.device_augment)
+        test_loader = SyntheticLoader(a.test_size // world, per_rank, a.img_size, a.classes, seed + 1001 + rank, device,
+                                      uint8=a.device_augment)
+    augment = test_transform = None
+    if a.device_augment:
+        augment = DeviceAugment(per_rank, a.img_size, a.img_size, mean=a.mean, std=a.std, seed=seed, device=device)
+        augment.sample_base = rank * per_rank          # one draw stream per sample index, whatever the rank layout
+        test_transform = DeviceAugment.test_transform(per_rank, a.img_size, a.img_size, mean=a.mean, std=a.std, device=device)
 
     patch_embed = build_tokenizer(a)
     model = VisionTransformer1D(patch_embed=patch_embed, depth=a.depth, n_heads=a.heads, mlp_dim=a.mlp_dim,
@@ -156,6 +175,8 @@ def main():
             # ours: {"n": steps taken}; the reference's LambdaLR (transformers' cosine schedule): {"last_epoch": steps taken}
             scheduler.n = ssd.get("n", ssd.get("last_epoch", start_epoch * len(train_loader)))
             optimizer.lr = scheduler.lr_at(scheduler.n)
+            if augment is not None and ck.get("augment_state_dict"):
+                augment.load_state_dict(ck["augment_state_dict"])       # the draw stream goes on where it stopped
     os.makedirs(a.checkpoint_dir, exist_ok=True)
     ckpt = os.path.join(a.checkpoint_dir, f"checkpoint_{a.tokenizer}.pt")
     graphed = None
@@ -173,8 +194,9 @@ def main():
 
     for epoch in range(start_epoch, a.epochs):
         tr_loss, tr_acc = train_with_mixup_or_cutmix(model, train_loader, train_criterion, optimizer, scheduler,
-                                                     device, reducer=reducer, graphed=graphed, device_mix=a.device_mix)
-        te_loss, te_acc = evaluate(model, test_loader, test_criterion, device)
+                                                     device, reducer=reducer, graphed=graphed, device_mix=a.device_mix,
+                                                     augment=augment)
+        te_loss, te_acc = evaluate(model, test_loader, test_criterion, device, transform=test_transform)
         if world > 1:                                  # equal shards per rank: the global figures are the rank means
             t = torch.tensor([tr_loss, tr_acc, te_loss, te_acc], device=device, dtype=torch.float64)
             dist.all_reduce(t)
@@ -186,7 +208,8 @@ def main():
                 best = te_acc
                 torch.save({"epoch": epoch, "model_state_dict": model.state_dict(),
                             "optimizer_state_dict": optimizer.state_dict() if optimizer.master is not None else {},
-                            "scheduler_state_dict": {"n": scheduler.n}, "train_loss": tr_loss, "train_acc": tr_acc,
+                            "scheduler_state_dict": {"n": scheduler.n},
+                            "augment_state_dict": augment.state_dict() if augment is not None else {}, "train_loss": tr_loss, "train_acc": tr_acc,
                             "test_loss": te_loss, "test_acc": te_acc}, ckpt)      # main.py:345-354 keys
     if world > 1:
         dist.destroy_process_group()

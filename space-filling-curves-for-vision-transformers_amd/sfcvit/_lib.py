@@ -58,6 +58,19 @@ class AdamWArgs(ctypes.Structure):
                 ("step", c_int32), ("dev_state", c_void_p)]
 
 
+class AugmentCfg(ctypes.Structure):
+    _fields_ = [("S", c_int32), ("crop", c_int32), ("flip", c_int32), ("out_is_bf16", c_int32),
+                ("scale", ctypes.c_double * 2), ("ratio", ctypes.c_double * 2),
+                ("brightness", ctypes.c_double), ("contrast", ctypes.c_double), ("saturation", ctypes.c_double),
+                ("hue", ctypes.c_double), ("erase_p", ctypes.c_double),
+                ("mean", c_float * 3), ("std", c_float * 3)]
+
+
+# record layout of the device image transforms (the SFCVIT_AUG_* constants of include/sfcvit.h)
+AUG_WORDS, AUG_FLAGS, AUG_CROP, AUG_ORDER, AUG_FACTORS, AUG_ERASE = 16, 0, 1, 5, 6, 10
+AUG_FLIP_BIT, AUG_ERASE_BIT, AUG_JITTER_SHIFT, AUG_ORDER_IDENTITY = 1, 2, 2, 0xE4
+
+
 # name -> (restype, argtypes); every symbol include/sfcvit.h declares.
 SIGNATURES = {
     "sfcvit_abi_version": (c_int, []),
@@ -85,6 +98,8 @@ SIGNATURES = {
     "sfcvit_mix_images": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "sfcvit_soft_ce_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                     c_float, c_void_p]),
+    "sfcvit_augment_draw": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(AugmentCfg), ctypes.c_uint64, ctypes.c_uint64, c_int64]),
+    "sfcvit_augment_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(AugmentCfg), c_void_p]),
     "sfcvit_reduce_defer": (c_int, [c_int]),
     "sfcvit_reduce_pending": (c_int, []),
     "sfcvit_reduce_flush": (c_int, [c_void_p]),

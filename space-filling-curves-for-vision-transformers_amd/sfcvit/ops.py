@@ -786,6 +786,43 @@ def soft_ce(logits, targets, n_classes, gscale):
     return loss_rows, dlogits
 
 
+def augment_draw(rec, H, W, cfg, seed, step, sample_base=0):
+    """Fill rec (int32 [B, 16], HOST tensor, contiguous) with the transform records of samples sample_base .. + B - 1 of
+    step `step` (sfcvit_augment_draw: plain host code, no GPU).  cfg: _lib.AugmentCfg."""
+    if rec.is_cuda or rec.dtype != torch.int32 or rec.dim() != 2 or rec.size(1) != _lib.AUG_WORDS or not rec.is_contiguous():
+        raise ValueError(f"augment_draw rec: expected a contiguous host int32 [B, {_lib.AUG_WORDS}] tensor, got "
+                         f"{rec.dtype} {tuple(rec.shape)} on {rec.device}")
+    check(lib.sfcvit_augment_draw(_p(rec), rec.size(0), int(H), int(W), ctypes.byref(cfg), int(seed) & (2 ** 64 - 1),
+                                  int(step) & (2 ** 64 - 1), int(sample_base)), "sfcvit_augment_draw")
+    return rec
+
+
+def augment_apply(u8, rec, cfg, out=None):
+    """u8 uint8 [B, C, H, W] + rec int32 [B, 16] (device copy of augment_draw's records) -> the transformed batch
+    [B, C, S, S], fp32 or bf16 as cfg.out_is_bf16 says (sfcvit_augment_apply: one launch).  out: write there instead of
+    allocating (a GraphedTrainStep's static image buffer, say)."""
+    if not u8.is_cuda:
+        raise _lib.SfcvitError(f"augment_apply: the HIP path needs a CUDA (ROCm) tensor, got device {u8.device}; there is no CPU fallback")
+    if u8.dim() != 4:
+        raise ValueError(f"augment_apply u8: expected [B,C,H,W], got shape {tuple(u8.shape)}")
+    u8 = _need(u8 if u8.is_contiguous() else u8.contiguous(), torch.uint8, "augment_apply u8", 4)
+    rec = _need(rec, torch.int32, "augment_apply rec", 2)
+    B, C, H, W = u8.shape
+    if tuple(rec.shape) != (B, _lib.AUG_WORDS):
+        raise ValueError(f"augment_apply: rec is {tuple(rec.shape)} for a batch of {B} images (expected [{B}, {_lib.AUG_WORDS}])")
+    dtype = _BF16 if cfg.out_is_bf16 else torch.float32
+    S = int(cfg.S)
+    if out is None:
+        out = torch.empty((B, C, S, S), dtype=dtype, device=u8.device)
+    else:
+        _need(out, dtype, "augment_apply out", 4)
+        if tuple(out.shape) != (B, C, S, S):
+            raise ValueError(f"augment_apply out: expected {(B, C, S, S)}, got {tuple(out.shape)}")
+    check(_launch("augment_apply", 0.0, lambda: lib.sfcvit_augment_apply(_p(u8), _p(rec), _p(out), B, C, H, W, ctypes.byref(cfg),
+                                                                          _stream())), "sfcvit_augment_apply")
+    return out
+
+
 def soft_ce_pair(logits, y_a, y_b, mix, n_classes, gscale):
     """logits bf16 [B, ld] (first n_classes columns are classes), y_a / y_b int64 [B] (device), mix: the batch mix whose
     record holds lam -> loss_rows fp32 [B], dlogits bf16 [B, ld] (times gscale), hit_rows fp32 [B]

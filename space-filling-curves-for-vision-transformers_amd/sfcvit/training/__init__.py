@@ -2,3 +2,4 @@ from .optim import FlatGradBuffer, FusedAdamW, WarmupCosine, WarmupCosineSchedul
 from .train import GraphedTrainStep, SoftTargetCrossEntropy, mixup_soft_targets, train_step  # noqa: F401
 from .distributed import GradReducer  # noqa: F401
 from .mix import BatchMix  # noqa: F401
+from .augment import DeviceAugment  # noqa: F401

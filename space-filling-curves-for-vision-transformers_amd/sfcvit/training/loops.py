@@ -44,12 +44,25 @@ def mixup_criterion(criterion, pred, y_a, y_b, lam):
     return lam * criterion(pred, y_a) + (1 - lam) * criterion(pred, y_b)
 
 
-def _plain_epoch(model, train_loader, criterion, optimizer, scheduler, device):
+def _augmented(images, augment, graphed=None):
+    """augment= (a sfcvit.training.DeviceAugment): the loader's batch is the raw uint8 one; draw this step's records and
+    transform it on the device -- straight into the graphed step's static image buffer when the result fits it."""
+    augment.draw()
+    dst = None
+    if graphed is not None and graphed.images.dtype == augment.out_dtype and \
+            tuple(graphed.images.shape) == (images.size(0), images.size(1), augment.size, augment.size):
+        dst = graphed.images
+    return augment(images, out=dst)
+
+
+def _plain_epoch(model, train_loader, criterion, optimizer, scheduler, device, augment=None):
     model.train()
     total_loss = torch.zeros((), device=device)
     correct = torch.zeros((), device=device)
     for images, labels in train_loader:
         images, labels = images.to(device), labels.to(device)
+        if augment is not None:
+            images = _augmented(images, augment)
         if hasattr(optimizer, "begin_step"):
             optimizer.begin_step()
         optimizer.zero_grad()
@@ -65,18 +78,19 @@ def _plain_epoch(model, train_loader, criterion, optimizer, scheduler, device):
     return float(total_loss) / n, float(correct) / n
 
 
-def train(model, train_loader, criterion, optimizer, device):
+def train(model, train_loader, criterion, optimizer, device, augment=None):
     """train.py:57-77: hard labels, no scheduler.  The reference does not clip here: construct
-    FusedAdamW(..., max_grad_norm=None) for the same behaviour."""
-    return _plain_epoch(model, train_loader, criterion, optimizer, None, device)
+    FusedAdamW(..., max_grad_norm=None) for the same behaviour.  augment: see train_with_mixup_or_cutmix."""
+    return _plain_epoch(model, train_loader, criterion, optimizer, None, device, augment)
 
 
-def train_with_scheduler(model, train_loader, criterion, optimizer, scheduler, device):
+def train_with_scheduler(model, train_loader, criterion, optimizer, scheduler, device, augment=None):
     """train.py:102-130: as `train` with a per-step scheduler."""
-    return _plain_epoch(model, train_loader, criterion, optimizer, scheduler, device)
+    return _plain_epoch(model, train_loader, criterion, optimizer, scheduler, device, augment)
 
 
-def _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_alpha, cutmix_alpha, mix_prob, reducer, graphed):
+def _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_alpha, cutmix_alpha, mix_prob, reducer, graphed,
+                      augment=None):
     """train_with_mixup_or_cutmix(device_mix=True): the same draws, but the batch is mixed where the tokenizer reads it
     (model(images, mix=bm)) and the loss / accuracy come from the label pair (F.mixed_target_cross_entropy)."""
     from .. import functional as F
@@ -88,10 +102,13 @@ def _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_a
     mixes = {}                                       # one record per batch size (the last batch of an epoch may be short)
     for images, labels in train_loader:
         images, labels = images.to(device), labels.to(device)
+        if augment is not None:
+            images = _augmented(images, augment, graphed if graphed is not None and graphed.mix is not None else None)
         B, (H, W) = images.size(0), images.shape[2:]
         if graphed is not None and graphed.mix is not None and images.shape == graphed.images.shape:
             bm = graphed.mix.draw(H, W, mixup_alpha, cutmix_alpha, mix_prob)
-            graphed.images.copy_(images)
+            if images is not graphed.images:
+                graphed.images.copy_(images)
             graphed.labels[0].copy_(labels)
             torch.index_select(labels, 0, bm.idx, out=graphed.labels[1])
             loss = graphed()
@@ -126,7 +143,8 @@ def _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_a
 
 
 def train_with_mixup_or_cutmix(model, train_loader, criterion, optimizer, scheduler, device,
-                               mixup_alpha=0.2, cutmix_alpha=1.0, mix_prob=0.5, reducer=None, graphed=None, device_mix=False):
+                               mixup_alpha=0.2, cutmix_alpha=1.0, mix_prob=0.5, reducer=None, graphed=None, device_mix=False,
+                               augment=None):
     """train.py:133-178.  `optimizer` is a FusedAdamW (clip inside) or any torch optimizer.
     graphed: a sfcvit.training.GraphedTrainStep built on this model / optimizer / scheduler with static buffers of the
     loader's batch shape -- the step (forward, soft-target CE, backward, clip, AdamW, scheduler) is then one hipGraph
@@ -135,16 +153,22 @@ def train_with_mixup_or_cutmix(model, train_loader, criterion, optimizer, schedu
     device_mix: MixUp / CutMix on the device (sfcvit.training.BatchMix): the same seeded draws, the batch mixed inside
     the tokenizer's gather and the loss / accuracy taken from the label pair; `criterion` is not called (the loss is
     soft-target cross entropy, as main.py's).  With a GraphedTrainStep(mix=..., labels=...) the augmentation is part
-    of the replayed step."""
+    of the replayed step.
+    augment: a sfcvit.training.DeviceAugment -- the loader then yields the raw uint8 batches [B, C, H, W] and the
+    reference's transform stack (main.py:169-188) runs on the device in front of the mix, one launch per batch; with a
+    device-mix GraphedTrainStep the result is written straight into its static image buffer.  None = float batches, as
+    before."""
     if device_mix:
         return _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_alpha, cutmix_alpha, mix_prob,
-                                 reducer, graphed)
+                                 reducer, graphed, augment)
     model.train()
     total_loss = torch.zeros((), device=device)
     total_correct = torch.zeros((), device=device)
     total_samples = 0
     for images, labels in train_loader:
         images, labels = images.to(device), labels.to(device)
+        if augment is not None:
+            images = _augmented(images, augment)
         if np.random.rand() < mix_prob:
             images, y_a, y_b, lam = mixup_data(images, labels, alpha=mixup_alpha)
         else:
@@ -184,8 +208,9 @@ def train_with_mixup_or_cutmix(model, train_loader, criterion, optimizer, schedu
     return float(total_loss) / total_samples, float(total_correct) / total_samples
 
 
-def evaluate(model, test_loader, criterion, device):
-    """train.py:80-99."""
+def evaluate(model, test_loader, criterion, device, transform=None):
+    """train.py:80-99.  transform: a DeviceAugment.test_transform (any callable on the device batch) -- the loader then
+    yields raw uint8 batches."""
     model.eval()
     total_loss = torch.zeros((), device=device)
     correct = torch.zeros((), device=device)
@@ -193,6 +218,8 @@ def evaluate(model, test_loader, criterion, device):
     with torch.no_grad():
         for images, labels in test_loader:
             images, labels = images.to(device), labels.to(device)
+            if transform is not None:
+                images = transform(images)
             outputs = model(images)
             total_loss += criterion(outputs.float(), labels) * images.size(0)
             correct += (outputs.argmax(dim=1) == labels).sum()
