@@ -464,6 +464,41 @@ int sfcvit_attention_plan(const sfcvit_attn_args *a, int bwd, int any_length, ch
 int sfcvit_last_attn_kernel(char *buf, int n);
 
 /* ------------------------------------------------------------------------
+ * Attention maps and attention-distance statistics
+ *   replaces the `(output, [attn_weights per layer])` path of CustomTransformerEncoderLayer / CustomTransformerEncoder
+ *   (src/models/vit.py:48-174, commented out there; average_attn_weights=False) and the need_weights=True branch of
+ *   multi_head_attention_forward (torch:nn/functional.py), which leaves the fused SDPA path and materialises
+ *   [B, H, N, N] per layer.
+ *
+ * Both entry points take the packed projection and the lse that sfcvit_attention_fwd / _fwd_any wrote for it (the
+ * log-sum-exp of the scaled scores; it does not depend on dropout) and rebuild
+ *     P[i, j] = exp(scale * q_i . k_j - lse[i])
+ * in one pass over 64-key blocks: no row maximum, no online softmax, LDS use independent of N.  Any N >= 1, head dims
+ * 64 / 128 / 192 / 256.  No atomics: every output element is written once by one lane after sums in a fixed order, so
+ * two runs give the same bits.
+ * ---------------------------------------------------------------------- */
+typedef struct sfcvit_attn_probe_args {
+    const void *qkv;       /* [B, N, 3*H*hd] bf16 (sfcvit_attn_args.qkv) */
+    const float *lse;      /* [B, H, N] fp32, as written by the attention forward */
+    int32_t B, N, H, hd;
+    float scale;           /* the forward's softmax scale; finite, nonzero */
+    /* sfcvit_attention_probs */
+    void *probs;           /* head_mean = 0: [B, H, N, N]; head_mean = 1: [B, N, N] = the mean over heads, summed in head
+                              order in fp32 and multiplied by 1/H once (average_attn_weights=True) */
+    int32_t probs_is_bf16; /* 0: fp32, 1: bf16 (round to nearest even) */
+    int32_t head_mean;
+    /* sfcvit_attention_stats: per query row, each [B, H, N] fp32 or NULL = skip (at least one must be given) */
+    const float *pos;      /* [N, 2] fp32 (row, col) of each token's centre in the image; needed by dist_rows only */
+    float *dist_rows;      /* sum_j P[i, j] * ||pos_i - pos_j||_2 : attention distance in image space */
+    float *seq_rows;       /* sum_j P[i, j] * |i - j|             : attention distance along the token sequence (the curve) */
+    float *ent_rows;       /* sum_j P[i, j] * (lse_i - s_ij)      : entropy in nats (a term with P = 0 adds 0) */
+    float *mass_rows;      /* sum_j P[i, j]                       : ~1; how well these scores agree with the forward's lse */
+} sfcvit_attn_probe_args;
+/* Rows are written with 16-byte stores when N % 4 == 0 (fp32) / N % 8 == 0 (bf16), element by element otherwise. */
+int sfcvit_attention_probs(const sfcvit_attn_probe_args *a, void *stream);
+int sfcvit_attention_stats(const sfcvit_attn_probe_args *a, void *stream);
+
+/* ------------------------------------------------------------------------
  * Elementwise / loss / optimizer
  * ---------------------------------------------------------------------- */
 /* y = gelu_erf(x) (nn.GELU in MultiLayerPredictor, vit.py:308); bf16, n elements. */

@@ -30,6 +30,7 @@ int raise_lds_limit(const void *kernel, int bytes, const char *what);
 // (sfcvit_last_gemm_kernel / sfcvit_last_attn_kernel name it as rocprofv3 does).
 void note_gemm_kernel(const GemmPlan &p);
 void note_attn_kernel(const AttnPlan &p);
+void note_attn_kernel(const ProbePlan &p);      // sfcvit_attention_probs / _stats report through sfcvit_last_attn_kernel too
 // Which row-wise kernel the calling thread's last sfcvit_layernorm_bwd* launched (sfcvit_last_rowwise_kernel).
 void note_rowwise_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 

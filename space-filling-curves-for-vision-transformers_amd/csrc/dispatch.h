@@ -126,6 +126,19 @@ struct AttnPlan : PlanStatus {
 AttnPlan attn_fwd_plan(const sfcvit_attn_args &a, const Knobs &k, bool any_length = false);
 AttnPlan attn_bwd_plan(const sfcvit_attn_args &a, int cus, const Knobs &k, bool any_length = false);
 
+// ---- attention maps / statistics (attention_probe.cpp plans, attention_probe.hip launches) ----
+constexpr int PROBE_POS_BYTES = 2 * ATTN_BLK * 4;            // stats kernel: (row, col) of the staged block's 64 keys
+struct ProbePlan : PlanStatus {
+    bool stats = false;                                      // sfcvit_attention_stats, else sfcvit_attention_probs
+    int inst = 0;                                            // S = hd / 64
+    bool mean = false;                                       // map kernel: heads summed inside the workgroup
+    int blocks = 0;                                          // 64-row blocks along N (queries; the map kernel: keys too)
+    int grid_z = 0;                                          // stats: B (y = H); map: B, or B * H without head_mean
+    size_t lds = 0;                                          // one 64-key block of K (+ its positions)
+};
+ProbePlan attn_probe_plan(const sfcvit_attn_probe_args &a, bool stats);
+void kernel_name(const ProbePlan &p, char *buf, size_t n);
+
 // The symbol of the plan's main kernel, e.g. "gemm8p_kernel<7, 35, true>" or "attn_seq_bwd_fused_kernel<13, true>".
 void kernel_name(const GemmPlan &p, char *buf, size_t n);
 void kernel_name(const AttnPlan &p, char *buf, size_t n);

@@ -77,6 +77,70 @@ static void check_gemm(const G &g, const Knobs &k, const char *what) {
     CHECK(post == g.post, "%s: post passes %#x, want %#x", what, post, g.post);
 }
 
+// attention maps / statistics (attention_probe.cpp): accepted argument sets with their kernel and launch geometry, and the
+// refusals of include/sfcvit.h
+static void check_probe() {
+    auto base = [](int B, int N, int H, int hd) {
+        sfcvit_attn_probe_args a{};
+        a.qkv = ptr(0); a.lse = static_cast<float *>(ptr(1));
+        a.B = B; a.N = N; a.H = H; a.hd = hd; a.scale = 0.125f;
+        return a;
+    };
+    char name[96];
+    {
+        sfcvit_attn_probe_args a = base(256, 196, 12, 64);
+        a.probs = ptr(2);
+        ProbePlan p = attn_probe_plan(a, false);
+        kernel_name(p, name, sizeof(name));
+        CHECK(p.err == SFCVIT_OK && !std::strcmp(name, "attn_probe_map_kernel<1, false>") && p.blocks == 4 && p.grid_z == 3072 && p.lds == 8192,
+              "probe map: %s blocks %d z %d lds %zu (%s)", name, p.blocks, p.grid_z, p.lds, p.msg);
+        a.head_mean = 1; a.probs_is_bf16 = 1; a.hd = 256; a.N = 577;
+        p = attn_probe_plan(a, false);
+        kernel_name(p, name, sizeof(name));
+        CHECK(p.err == SFCVIT_OK && !std::strcmp(name, "attn_probe_map_kernel<4, true>") && p.blocks == 10 && p.grid_z == 256 && p.lds == 32768,
+              "probe mean map: %s blocks %d z %d lds %zu (%s)", name, p.blocks, p.grid_z, p.lds, p.msg);
+        a.head_mean = 0; a.B = 8192;                                 // B * H maps beyond the launch grid
+        CHECK(attn_probe_plan(a, false).err == SFCVIT_EINVAL, "probe map: B * H = 98304 accepted");
+        a = base(1, 1, 1, 128);
+        a.mass_rows = static_cast<float *>(ptr(3));
+        p = attn_probe_plan(a, true);
+        kernel_name(p, name, sizeof(name));
+        CHECK(p.err == SFCVIT_OK && !std::strcmp(name, "attn_probe_stats_kernel<2>") && p.blocks == 1 && p.grid_z == 1 && p.lds == 2 * 8192 + 512,
+              "probe stats: %s blocks %d z %d lds %zu (%s)", name, p.blocks, p.grid_z, p.lds, p.msg);
+        a.pos = static_cast<float *>(ptr(4)); a.dist_rows = static_cast<float *>(ptr(5));
+        CHECK(attn_probe_plan(a, true).err == SFCVIT_OK, "probe stats with pos + dist_rows refused");
+    }
+    for (int stats = 0; stats < 2; stats++) {
+        auto full = [&](int B, int N, int H, int hd) {
+            sfcvit_attn_probe_args a = base(B, N, H, hd);
+            a.probs = ptr(2); a.pos = static_cast<float *>(ptr(4)); a.dist_rows = static_cast<float *>(ptr(5));
+            return a;
+        };
+        auto refused = [&](const sfcvit_attn_probe_args &a, const char *frag, const char *what) {
+            const ProbePlan p = attn_probe_plan(a, stats != 0);
+            CHECK(p.err == SFCVIT_EINVAL && std::strstr(p.msg, frag), "probe %d %s: want '%s', got %d '%s'", stats, what, frag, p.err, p.msg);
+        };
+        CHECK(attn_probe_plan(full(2, 65, 3, 192), stats != 0).err == SFCVIT_OK, "probe %d: valid arguments refused", stats);
+        sfcvit_attn_probe_args a = full(2, 65, 3, 64);
+        a.qkv = nullptr; refused(a, "null", "null qkv");
+        a = full(2, 65, 3, 64); a.lse = nullptr; refused(a, "null", "null lse");
+        refused(full(2, 65, 3, 48), "head dim 48 not supported", "hd 48");
+        refused(full(2, 0, 3, 64), "N=0", "N = 0");
+        refused(full(0, 65, 3, 64), "B=0", "B = 0");
+        a = full(2, 65, 3, 64); a.qkv = reinterpret_cast<void *>(uintptr_t(0x100008)); refused(a, "aligned", "misaligned qkv");
+        a = full(2, 65, 3, 64); a.scale = 0.f; refused(a, "scale", "scale 0");
+        if (stats) {
+            a = full(2, 65, 3, 64); a.dist_rows = nullptr; refused(a, "every output is NULL", "no output");
+            a = full(2, 65, 3, 64); a.pos = nullptr; refused(a, "needs pos", "dist_rows without pos");
+            a = full(2, 65, 3, 64); a.dist_rows = reinterpret_cast<float *>(uintptr_t(0x600004)); refused(a, "aligned", "misaligned output");
+        } else {
+            a = full(2, 65, 3, 64); a.probs = nullptr; refused(a, "null", "null probs");
+            a = full(2, 65, 3, 64); a.probs = reinterpret_cast<void *>(uintptr_t(0x300002)); refused(a, "aligned", "misaligned probs");
+            a = full(2, 65, 3, 64); a.head_mean = 2; refused(a, "must be 0 or 1", "head_mean 2");
+        }
+    }
+}
+
 static void check_dispatch() {
     const Knobs dflt;
     // ViT-B/16 @ 224, batch 256 (M = 256 x 196 tokens), training (dropout 0.1) -- the benched step
@@ -253,6 +317,7 @@ static void check_dispatch() {
         p = attn_bwd_plan(a, 256, k);
         CHECK(p.grid == 3072 && !p.queue && p.per == 128, "fused bwd, PERSIST=0: grid %d queue %d per %d", p.grid, p.queue, p.per);
     }
+    check_probe();
 }
 
 int main() {

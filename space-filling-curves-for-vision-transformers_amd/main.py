@@ -104,6 +104,9 @@ def main():
                     help="the reference's transform stack (RandomResizedCrop, flip, ColorJitter, RandomErasing, Normalize; "
                          "main.py:169-188) on the device: the loaders then yield raw uint8 batches [B, 3, H, W]; works with "
                          "--device-mix and --graph")
+    ap.add_argument("--attention-report", default=None, metavar="FILE",
+                    help="after building (or resuming) the model, measure one test batch with sfcvit.analysis.attention_report "
+                         "and write per-layer, per-head batch means of attention distance (image and curve) and entropy as JSON")
     ap.add_argument("--mean", type=float, nargs=3, default=[0.4914, 0.4822, 0.4465])      # main.py:176-177 (CIFAR)
     ap.add_argument("--std", type=float, nargs=3, default=[0.2023, 0.1994, 0.2010])
     a = ap.parse_args()
@@ -177,6 +180,18 @@ def main():
             optimizer.lr = scheduler.lr_at(scheduler.n)
             if augment is not None and ck.get("augment_state_dict"):
                 augment.load_state_dict(ck["augment_state_dict"])       # the draw stream goes on where it stopped
+    if a.attention_report and rank == 0:
+        import json
+        from sfcvit.analysis import attention_report, report_summary
+        images, _ = next(iter(test_loader))
+        images = images.to(device)
+        if test_transform is not None:
+            images = test_transform(images)
+        summary = report_summary(attention_report(model, images))
+        summary.update(tokenizer=a.tokenizer, img_size=a.img_size, heads=a.heads, batch=int(images.shape[0]))
+        with open(a.attention_report, "w") as f:
+            json.dump(summary, f, indent=1)
+        print(f"attention report: {len(summary['layers'])} layers -> {a.attention_report}")
     os.makedirs(a.checkpoint_dir, exist_ok=True)
     ckpt = os.path.join(a.checkpoint_dir, f"checkpoint_{a.tokenizer}.pt")
     graphed = None

@@ -50,6 +50,14 @@ class AttnArgs(ctypes.Structure):
                 ("colsum_part", c_void_p), ("colsum_part_bytes", c_int64), ("colsum_out", c_void_p), ("colsum_bf16", c_int32)]
 
 
+class AttnProbeArgs(ctypes.Structure):
+    _fields_ = [("qkv", c_void_p), ("lse", c_void_p),
+                ("B", c_int32), ("N", c_int32), ("H", c_int32), ("hd", c_int32), ("scale", c_float),
+                ("probs", c_void_p), ("probs_is_bf16", c_int32), ("head_mean", c_int32),
+                ("pos", c_void_p), ("dist_rows", c_void_p), ("seq_rows", c_void_p), ("ent_rows", c_void_p),
+                ("mass_rows", c_void_p)]
+
+
 class AdamWArgs(ctypes.Structure):
     _fields_ = [("param", c_void_p), ("master", c_void_p), ("grad", c_void_p), ("m", c_void_p),
                 ("v", c_void_p), ("sumsq", c_void_p), ("n", c_int64),
@@ -128,6 +136,8 @@ SIGNATURES = {
     "sfcvit_attention_bwd_any": (c_int, [ctypes.POINTER(AttnArgs), c_void_p]),
     "sfcvit_attention_plan": (c_int, [ctypes.POINTER(AttnArgs), c_int, c_int, ctypes.c_char_p, c_int]),
     "sfcvit_attention_colsum_workspace": (c_int64, [c_int, c_int, c_int, c_int]),
+    "sfcvit_attention_probs": (c_int, [ctypes.POINTER(AttnProbeArgs), c_void_p]),
+    "sfcvit_attention_stats": (c_int, [ctypes.POINTER(AttnProbeArgs), c_void_p]),
     "sfcvit_gelu_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "sfcvit_gelu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sfcvit_soft_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

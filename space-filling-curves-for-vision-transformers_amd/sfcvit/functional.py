@@ -487,7 +487,9 @@ class _EncoderLayer(Function):
     identity.  Masks are functions of (seed, element index), regenerated in backward."""
 
     @staticmethod
-    def forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale):
+    def launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale):
+        """The forward's kernel launches, every intermediate returned (forward saves them; encoder_layer_probe reads the
+        attention inputs out of the same sequence, so what it carries on is what forward computes)."""
         B, N, D = x.shape
         Da = in_w.shape[0] // 3                             # attention width: D, or n_heads * padded head dim (encoder_layer)
         sa, s1_, sf, s2_ = seeds
@@ -503,6 +505,13 @@ class _EncoderLayer(Function):
         h = ops.gemm(x1, w1, bias=b1, act=ops.ACT_RELU, dropout_p=p, dropout_seed=sf, actmask=hbits)
         s2 = ops.gemm(h, w2, bias=b2, residual=x1, dropout_p=p, dropout_seed=s2_)
         y, mean2, rstd2 = ops.layernorm_fwd(s2, n2_w, n2_b, eps)
+        return x2, qkv, o, lse, s1, mean1, rstd1, x1, hbits, h, s2, y, mean2, rstd2
+
+    @staticmethod
+    def forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale):
+        B, N, D = x.shape
+        x2, qkv, o, lse, s1, mean1, rstd1, x1, hbits, h, s2, y, mean2, rstd2 = _EncoderLayer.launches(
+            x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale)
         ctx.hbits = hbits
         ctx.save_for_backward(x2, qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2,
                               in_w, out_w, n1_w, w1, w2, n2_w)
@@ -568,13 +577,9 @@ class _EncoderLayer(Function):
         return (dx.view(B, N, D), dwi, dbi, dwo, dbo, dg1, dbt1, dw1, db1, dw2, db2, dg2, dbt2, None, None, None, None, None)
 
 
-def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5,
-                  dropout_p=0.0):
-    """dropout_p > 0 = training-mode nn.TransformerEncoderLayer (fresh masks every call).
-    A head dim the attention kernels do not have (embed_dim / n_heads = 32, 48, 96, ...) runs on the next one that
-    exists: in_proj's rows and out_proj's columns are zero-padded per head (differentiable torch plumbing on the
-    weights, 3 D^2 elements -- not on the activations), so q, k, v come out of the projection GEMM already padded, the
-    padded columns add nothing to q k^T or p v, and out_proj ignores them; the softmax scale stays 1 / sqrt(head dim)."""
+def _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads):
+    """bf16 arguments of _EncoderLayer and its softmax scale (None = 1 / sqrt(kernel head dim)), the per-head zero
+    padding of encoder_layer applied."""
     args = [_bf(t) for t in (x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b)]
     D = args[0].shape[-1]
     hd, hp = _head_padding(D, n_heads)
@@ -586,6 +591,28 @@ def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w,
             args[2] = pad(args[2].reshape(3, n_heads, hd), (0, hp - hd)).reshape(3 * n_heads * hp)
         args[3] = pad(args[3].reshape(D, n_heads, hd), (0, hp - hd)).reshape(D, n_heads * hp)
         scale = 1.0 / math.sqrt(hd)
+    return args, scale
+
+
+def encoder_layer_probe(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5):
+    """The eval-mode (dropout 0) encoder layer with its attention inputs exposed: (y, qkv [B, N, 3 * H * kernel head dim],
+    lse [B, H, N], softmax scale or None).  Same launches as encoder_layer(dropout_p=0): y has its bits.  For
+    sfcvit.analysis; no autograd graph is built."""
+    with torch.no_grad():
+        args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
+        B, N, D = args[0].shape
+        t = _EncoderLayer.launches(*args, n_heads, eps, 0.0, (0, 0, 0, 0), scale)
+        return t[11].view(B, N, D), t[1].view(B, N, -1), t[3], scale
+
+
+def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5,
+                  dropout_p=0.0):
+    """dropout_p > 0 = training-mode nn.TransformerEncoderLayer (fresh masks every call).
+    A head dim the attention kernels do not have (embed_dim / n_heads = 32, 48, 96, ...) runs on the next one that
+    exists: in_proj's rows and out_proj's columns are zero-padded per head (differentiable torch plumbing on the
+    weights, 3 D^2 elements -- not on the activations), so q, k, v come out of the projection GEMM already padded, the
+    padded columns add nothing to q k^T or p v, and out_proj ignores them; the softmax scale stays 1 / sqrt(head dim)."""
+    args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
     if _traced():
         from . import library      # (dropout seeds are drawn inside the op: nothing data-dependent in the traced graph)
         return library.encoder_layer(args, n_heads, eps, float(dropout_p), scale)

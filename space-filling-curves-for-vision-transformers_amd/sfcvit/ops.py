@@ -490,6 +490,69 @@ def attention_bwd(qkv, out, lse, dout, n_heads, dropout_p=0.0, dropout_seed=0, c
     return dqkv if cs is None else (dqkv, cs)
 
 
+def _probe_args(qkv, lse, n_heads, scale, what):
+    _need(qkv, _BF16, f"{what} qkv", 3)
+    _need(lse, torch.float32, f"{what} lse", 3)
+    B, N, D3 = qkv.shape
+    D, hd = _attn_dims(D3, n_heads)
+    if tuple(lse.shape) != (B, n_heads, N):
+        raise ValueError(f"{what}: lse must be [B, H, N] = {(B, n_heads, N)}, got {tuple(lse.shape)}")
+    a = _lib.AttnProbeArgs()
+    a.qkv, a.lse = qkv.data_ptr(), lse.data_ptr()
+    a.B, a.N, a.H, a.hd, a.scale = B, N, n_heads, hd, (1.0 / math.sqrt(hd) if scale is None else float(scale))
+    return a, B, N, hd
+
+
+def attention_probs(qkv, lse, n_heads, scale=None, head_mean=False, dtype=torch.float32, out=None):
+    """The attention map softmax(scale q k^T) rebuilt from the packed projection and the lse attention_fwd returned for it
+    (same scale): [B, H, N, N], or with head_mean the mean over heads [B, N, N] (nn.MultiheadAttention's
+    average_attn_weights=True).  dtype: torch.float32 or torch.bfloat16.  out: a contiguous tensor of that shape and dtype
+    to write into."""
+    a, B, N, hd = _probe_args(qkv, lse, n_heads, scale, "attention_probs")
+    if dtype not in (torch.float32, _BF16):
+        raise TypeError(f"attention_probs: dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+    shape = (B, N, N) if head_mean else (B, n_heads, N, N)
+    if out is None:
+        out = torch.empty(shape, device=qkv.device, dtype=dtype)
+    elif tuple(_need(out, dtype, "attention_probs out").shape) != shape:
+        raise ValueError(f"attention_probs out: expected shape {shape}, got {tuple(out.shape)}")
+    a.probs, a.probs_is_bf16, a.head_mean = out.data_ptr(), int(dtype == _BF16), int(bool(head_mean))
+    check(_launch("attn_probe_map", 2.0 * B * n_heads * N * N * hd,
+                  lambda: lib.sfcvit_attention_probs(ctypes.byref(a), _stream())), "sfcvit_attention_probs")
+    return out
+
+
+ATTENTION_STATS = ("distance", "sequence_distance", "entropy", "mass")
+
+
+def attention_stats(qkv, lse, n_heads, pos=None, scale=None, out=None):
+    """Per query row, without forming the N x N map: a dict of [B, H, N] fp32 tensors
+         "distance"           sum_j P_ij ||pos_i - pos_j||   (only with pos: [N, 2] fp32 token centres, analysis.token_positions)
+         "sequence_distance"  sum_j P_ij |i - j|
+         "entropy"            -sum_j P_ij ln P_ij            (nats)
+         "mass"               sum_j P_ij                     (~1: these scores against the forward's lse)
+    out: dict name -> contiguous fp32 [B, H, N] tensor to write into (missing names are allocated)."""
+    a, B, N, hd = _probe_args(qkv, lse, n_heads, scale, "attention_stats")
+    if pos is not None:
+        if tuple(_need(pos, torch.float32, "attention_stats pos", 2).shape) != (N, 2):
+            raise ValueError(f"attention_stats: pos must be [N, 2] = {(N, 2)}, got {tuple(pos.shape)}")
+        a.pos = pos.data_ptr()
+    res = {}
+    for name, field in zip(ATTENTION_STATS, ("dist_rows", "seq_rows", "ent_rows", "mass_rows")):
+        if name == "distance" and pos is None:
+            continue
+        t = (out or {}).get(name)
+        if t is None:
+            t = torch.empty((B, n_heads, N), device=qkv.device, dtype=torch.float32)
+        elif tuple(_need(t, torch.float32, f"attention_stats out[{name}]").shape) != (B, n_heads, N):
+            raise ValueError(f"attention_stats out[{name}]: expected shape {(B, n_heads, N)}, got {tuple(t.shape)}")
+        setattr(a, field, t.data_ptr())
+        res[name] = t
+    check(_launch("attn_probe_stats", 2.0 * B * n_heads * N * N * hd,
+                  lambda: lib.sfcvit_attention_stats(ctypes.byref(a), _stream())), "sfcvit_attention_stats")
+    return res
+
+
 # ----------------------------------------------------------------------------
 # tokenizer
 # ----------------------------------------------------------------------------
