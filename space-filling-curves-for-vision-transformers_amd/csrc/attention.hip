@@ -33,15 +33,15 @@ __global__ __launch_bounds__(THREADS) void attn_fwd_kernel(const sfcvit_attn_arg
     char *kimg = smem, *vimg = smem + IMG_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.z, h = blockIdx.y, N = a.N, D = a.H * HD, ld = 3 * D;
-    const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * HD;
-    const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
+    const HeadView hv = head_view(a, b, h, HD);
+    const uint16_t *qp = hv.qp, *kp = hv.kp, *vp = hv.vp;
     const int q0 = blockIdx.x * BLK + wave * 16;
     const float scale = a.scale;
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
     const float dsc = 1.f / (1.f - a.dropout_p);
     // mask row of this lane's query
-    const uint32_t drk = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(q0 + (lane & 15)));
+    const uint32_t drk = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), b, a.H, h, N, q0 + (lane & 15));
 
     bf16x8 qf[2];
     qf[0] = global_frag(qp, ld, q0, N, 0, lane);
@@ -112,9 +112,9 @@ __global__ __launch_bounds__(THREADS) void attn_fwd_kernel(const sfcvit_attn_arg
     mfma_fence();
     const float l_tot = group_sum(l_run);
     const int q = q0 + (lane & 15);
-    uint16_t *out = static_cast<uint16_t *>(a.out) + size_t(b) * N * D + h * HD;
+    uint16_t *out = hv.rows(a.out);
     store_rows(out, D, q, q < N, o, 1.f / l_tot, lane);
-    if (q < N && lane < 16) a.lse[(size_t(b) * a.H + h) * N + q] = m_run + __logf(l_tot);
+    if (q < N && lane < 16) a.lse[bh_row(b, a.H, h, N, q)] = m_run + __logf(l_tot);
 }
 
 // ---------------------------------------------------------------------------
@@ -160,14 +160,13 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_kv_kernel(const sfcvit_attn_
     const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * HD;
     const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
     const uint16_t *dop = static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * HD;
-    const float *lse = a.lse + (size_t(b) * a.H + h) * N, *del = a.delta + (size_t(b) * a.H + h) * N;
+    const float *lse = a.lse + bh_row(b, a.H, h, N, 0), *del = a.delta + bh_row(b, a.H, h, N, 0);
     const int key0 = blockIdx.x * BLK + wave * 16;
     const float scale = a.scale;
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
     const float dsc = 1.f / (1.f - a.dropout_p);
     const int dkey = key0 + (lane & 15);
-    const uint64_t dbh = (uint64_t(b) * a.H + h) * uint64_t(N);
 
     bf16x8 kf[2], vf[2];
 #pragma unroll
@@ -208,7 +207,7 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_kv_kernel(const sfcvit_attn_
                     float keep = 1.f;
                     if (drop) {
                         bool k0b, k1b;
-                        drop_keep2(drop_row_key(eff_seed(a.dropout_seed, a.seed_off), dbh + uint64_t(q0 + ql)), uint32_t(dkey >> 1), dth, k0b, k1b);
+                        drop_keep2(mask_row_key(eff_seed(a.dropout_seed, a.seed_off), b, a.H, h, N, q0 + ql), uint32_t(dkey >> 1), dth, k0b, k1b);
                         keep = ((dkey & 1) ? k1b : k0b) ? dsc : 0.f;
                     }
                     p[t][r] = pv * keep;                                   // dropped probabilities feed dV
@@ -240,18 +239,18 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_q_kernel(const sfcvit_attn_a
     char *kimg = smem, *vimg = smem + IMG_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.z, h = blockIdx.y, N = a.N, D = a.H * HD, ld = 3 * D;
-    const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * HD;
-    const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
-    const uint16_t *dop = static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * HD;
+    const HeadView hv = head_view(a, b, h, HD);
+    const uint16_t *qp = hv.qp, *kp = hv.kp, *vp = hv.vp;
+    const uint16_t *dop = hv.rows(a.dout);
     const int q0 = blockIdx.x * BLK + wave * 16;
     const int q = q0 + (lane & 15);
     const float scale = a.scale;
-    const float lse_q = q < N ? a.lse[(size_t(b) * a.H + h) * N + q] : 0.f;
-    const float del_q = q < N ? a.delta[(size_t(b) * a.H + h) * N + q] : 0.f;
+    const float lse_q = q < N ? a.lse[bh_row(b, a.H, h, N, q)] : 0.f;
+    const float del_q = q < N ? a.delta[bh_row(b, a.H, h, N, q)] : 0.f;
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
     const float dsc = 1.f / (1.f - a.dropout_p);
-    const uint32_t drk = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(q));
+    const uint32_t drk = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), b, a.H, h, N, q);
 
     bf16x8 qf[2], dof[2];
 #pragma unroll
@@ -283,8 +282,7 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_q_kernel(const sfcvit_attn_a
                 // s[r] = S^T[key = k0 + 16kfi + 4g + r][q]; keys >= N have K = V = 0 and add nothing
                 float keep[4] = {1.f, 1.f, 1.f, 1.f};
                 if (drop) drop_keep4(drk, k0 + 16 * kfi + 4 * (lane >> 4), dth, dsc, keep);
-#pragma unroll
-                for (int r = 0; r < 4; r++) ds[t][r] = __expf(s[r] * scale - lse_q) * (dp[r] * keep[r] - del_q) * scale;
+                ds[t] = ds_from_scores<false>(s, dp, splat4(lse_q), splat4(del_q), keep, scale, scale);
             }
             const bf16x8 dsf = pack_frag(ds[0], ds[1]);
 #pragma unroll
@@ -293,7 +291,7 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_q_kernel(const sfcvit_attn_a
                                                                  dq[hf], 0, 0, 0);
         }
     }
-    uint16_t *dbase = static_cast<uint16_t *>(a.dqkv) + size_t(b) * N * ld + h * HD;
+    uint16_t *dbase = hv.packed(a.dqkv);
     mfma_fence();
     store_rows(dbase, ld, q, q < N, dq, 1.f, lane);
 }

@@ -51,26 +51,12 @@ static_assert(FUSED_MAX_N == 32 * FMAXC, "dispatch.h");   // FUSED_*: the LDS la
 #define ISA_MARK(name) do { } while (0)
 #endif
 
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
 #ifdef SFCVIT_ATTN_TRACE
 __device__ unsigned long long g_attn_trace[512];
 #define ATRACE(i) do { if (blockIdx.x == 5 && threadIdx.x == 0 && (i) < 512) g_attn_trace[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define ATRACE(i) do {} while (0)
 #endif
-
-// Stage npad rows x 64 cols (128-B rows) into a kc image by LDS-DMA; the bank swizzle goes on the SOURCE chunk
-// (the DMA writes lane-linear); rows >= N copy row N - 1.
-__device__ __forceinline__ void dma_rows(char *img, const uint16_t *__restrict__ src, int ld, int N, int npad, int tid, int nt = 0) {
-    for (int p = tid; p < npad * 8; p += FT) {
-        const int row = p >> 3, cs = p & 7;
-        const int c = cs ^ kc_swz(row);
-        const uint16_t *g = src + size_t(min(row, N - 1)) * ld + c * 8;
-        if (nt) __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(img + p * 16), 16, 0, 2);      // nt: read once, do not allocate
-        else __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(img + p * 16), 16, 0, 0);
-    }
-}
 
 // dS^T exchange image: [key rows][32 queries] bf16, 64-B rows; the two 32-B halves (query fragment 0 / 1 of the chunk)
 // are swapped on rows with (row >> 2) & 1 set, which makes both the 8-byte writes of a key wave and the transposed
@@ -113,7 +99,7 @@ __global__ __launch_bounds__(FT) void attn_seq_bwd_fused_kernel(const sfcvit_att
     const int tsel = !split ? -1 : wave == nf - 1 ? 0 : wave == nf ? 1 : -1;   // -1: both query fragments of a chunk
     const bool is_key = wave < nf || (split && wave == nf), is_dq = wave >= FWAVES - 2;
     const uint32_t dth = drop_thresh(a.dropout_p);
-    const float scale = a.scale, c2 = a.scale * 1.4426950408889634f;
+    const float scale = a.scale, c2 = a.scale * LOG2E;
     // (lane offsets of the fragment reads are rebuilt inside key_step / dq_step from an opaque lane id: hoisted here they
     // were spilled and reloaded every step)
     const float dsc = 1.f / (1.f - a.dropout_p);
@@ -140,12 +126,12 @@ __global__ __launch_bounds__(FT) void attn_seq_bwd_fused_kernel(const sfcvit_att
                 opiece[i] = nt ? __builtin_nontemporal_load(op) : *op;
             }
         }
-        const float *lse = a.lse + (size_t(b) * a.H + h) * N;
+        const float *lse = a.lse + bh_row(b, a.H, h, N, 0);
         float *lse_w = reinterpret_cast<float *>(small);
         uint32_t *rkey_w = reinterpret_cast<uint32_t *>(small) + 2 * npad;
         for (int i = tid; i < npad; i += FT) {
-            lse_w[i] = i < N ? lse[i] * 1.4426950408889634f : INFINITY;   // padded queries: p = exp2(-inf) = 0
-            rkey_w[i] = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(i));
+            lse_w[i] = lse_log2(lse, i, i < N, INFINITY);   // padded queries: p = exp2(-inf) = 0
+            rkey_w[i] = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), b, a.H, h, N, i);
         }
     };
     // delta[q] = sum_c dO[q][c] O[q][c]: 8 products per thread and piece, summed over the 8 lanes that share a row
@@ -174,14 +160,15 @@ __global__ __launch_bounds__(FT) void attn_seq_bwd_fused_kernel(const sfcvit_att
     // LDS-DMA in flight, puts `s_waitcnt vmcnt(0)` in front of every transposed LDS read and every use of an ordinary load
     // -- each wave would wait for its prefetch at the top of the step that is supposed to hide it.  The kernel waits
     // itself: vmcnt(0) in front of the barrier that ends the step (dma_wait).
+    // ("m0" clobber: hipcc warns that M0 is reserved -- it manages M0 for its own LDS-DMA builtin, hence the declaration.)
     const uint32_t lds_base = uint32_t(uintptr_t((lptr_t)smem));
     auto dma_piece = [&](const char *img, const uint16_t *src, int sld, int p) __attribute__((always_inline)) {
         const int row = p >> 3, cs = p & 7;
         const int c = cs ^ kc_swz(row);
         const uint16_t *gp = src + size_t(min(row, N - 1)) * sld + c * 8;
         const uint32_t m0v = __builtin_amdgcn_readfirstlane(lds_base + uint32_t(img - smem) + uint32_t(p) * 16u);
-        if (nt) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt" ::"v"(gp), "s"(m0v) : "memory");
-        else asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gp), "s"(m0v) : "memory");
+        if (nt) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt" ::"v"(gp), "s"(m0v) : "m0", "memory");
+        else asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gp), "s"(m0v) : "m0", "memory");
     };
     auto dma_wait = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
 
@@ -204,9 +191,9 @@ __global__ __launch_bounds__(FT) void attn_seq_bwd_fused_kernel(const sfcvit_att
         const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * HD;
         fetch_item(item, small0);
         if (tid == 0) write_record(item, rec0);
-        dma_rows(qimg, base, ld, N, npad, tid, nt);
-        dma_rows(doimg, static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * HD, D, N, npad, tid, nt);
-        dma_rows(kimg0, base + D, ld, N, npad, tid, nt);
+        dma_rows<FT, true>(qimg, base, ld, N, npad, tid, nt);
+        dma_rows<FT, true>(doimg, static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * HD, D, N, npad, tid, nt);
+        dma_rows<FT, true>(kimg0, base + D, ld, N, npad, tid, nt);
         {   // exchange rows no key wave writes (keys 16 nf .. npad - 1), both halves of the double buffer; written once
             const int nz = (npad - 16 * nf) * 4;         // 16-byte pieces per half
             for (int i = tid; i < 2 * nz; i += FT) {

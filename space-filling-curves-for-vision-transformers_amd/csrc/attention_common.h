@@ -1,5 +1,9 @@
-// Shared device helpers of the attention kernels (attention.hip: tiled, any N;
-// attention_seq.hip: whole sequence resident in LDS, N <= 256).
+// Shared device code of the attention kernels (attention*.hip).  The kernels differ in residency, wave count, chunking
+// and pipelining; what they must agree on lives here: the LDS images and their fragment reads (one 128-byte-row image per
+// 64 head columns, the "kc" swizzle of device_common.h; stage64 / dma_rows fill them), the dropout mask's row numbering
+// (bh_row / mask_row_key: every row key of every kernel is made there, so backward regenerates the forward's mask),
+// LOG2E, and -- in the kernels whose compiled code they left unchanged -- HeadView, lse_log2 and ds_from_scores.  MFMA
+// orientations: attention.hip's header; fence rule between an MFMA and its accumulators' first reader: device_common.h.
 #pragma once
 #include "../../include/sfcvit.h"
 #include "device_common.h"
@@ -168,6 +172,64 @@ __device__ __forceinline__ void drop_keep4(uint32_t row_key, int key0, uint32_t 
 #pragma unroll
     for (int r = 0; r < 4; r++) keep[r] = k[r] ? sc : 0.f;
 }
+
+// Index of query `row` of (b, h) in the [B, H, N] arrays lse / delta -- and the number of its row in the dropout mask.
+__device__ __forceinline__ uint64_t bh_row(int b, int H, int h, int N, int row) { return (uint64_t(b) * H + h) * uint64_t(N) + uint64_t(row); }
+// Key of mask row number bh_row(b, H, h, N, row).  The overloads are equivalent: a kernel passes (b, H, h, N, row), or names
+// row0 = bh_row(.., 0) once and passes row0 + row.  Which one is schedule-sensitive (where the row number merges with the
+// lse / delta addresses): do not unify them without comparing the compiled kernels.
+__device__ __forceinline__ uint32_t mask_row_key(uint32_t seed, uint64_t row_number) { return drop_row_key(seed, row_number); }
+__device__ __forceinline__ uint32_t mask_row_key(uint32_t seed, int b, int H, int h, int N, int row) { return mask_row_key(seed, bh_row(b, H, h, N, row)); }
+constexpr float LOG2E = 1.4426950408889634f;       // exp(x * scale) = exp2(x * scale * LOG2E)
+// lse[i] * log2(e); rows past the sequence get `pad`: +inf for a keys-major kernel's queries (P = 0), 0 for the lane's own query.
+template <class Index>
+__device__ __forceinline__ float lse_log2(const float *lse, Index i, bool valid, float pad) { return valid ? lse[i] * LOG2E : pad; }
+
+// `npad` rows x 64 cols of a [N, ld] matrix into an LDS image by LDS-DMA (global_load_lds_dwordx4: asynchronous, no
+// staging registers), by a workgroup of WG_THREADS threads.  The DMA writes lane-linear (slot p = tid + WG_THREADS i at LDS byte 16 p),
+// so the image's bank swizzle is applied to the SOURCE column chunk.  Rows >= N are filled with a copy of row N - 1
+// (finite values); every consumer masks them: keys >= N get probability / dS = 0, queries >= N get lse = +inf.
+typedef const __attribute__((address_space(1))) void *gptr_t;
+typedef __attribute__((address_space(3))) void *lptr_t;
+// ALLOW_NT: honour the run-time non-temporal switch `nt` (fused backward); a plain defaulted argument changed the other kernels.
+template <int WG_THREADS, bool ALLOW_NT = false>
+__device__ __forceinline__ void dma_rows(char *img, const uint16_t *__restrict__ src, int ld, int N, int npad, int tid, int nt = 0) {
+    for (int p = tid; p < npad * 8; p += WG_THREADS) {
+        const int row = p >> 3, cs = p & 7;
+        const int c = cs ^ kc_swz(row);
+        const uint16_t *g = src + size_t(min(row, N - 1)) * ld + c * 8;
+        if (ALLOW_NT && nt) __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(img + p * 16), 16, 0, 2);      // nt: read once, do not allocate
+        else __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(img + p * 16), 16, 0, 0);
+    }
+}
+
+// One (batch, head) of qkv [B, N, 3 D] (q | k | v thirds, D = H hd), out / dout [B, N, D] (rows) and dqkv (packed like qkv).
+// Holds values, never a reference to the kernel's argument block; the other bases are formed where they are asked for.
+struct HeadView {
+    int b, h, hd, N, D, ld;
+    const uint16_t *qp, *kp, *vp;      // row stride ld
+    __device__ __forceinline__ uint16_t *packed(void *p) const { return static_cast<uint16_t *>(p) + size_t(b) * N * ld + h * hd; }   // row stride ld
+    __device__ __forceinline__ uint16_t *rows(void *p) const { return static_cast<uint16_t *>(p) + size_t(b) * N * D + h * hd; }       // row stride D
+    __device__ __forceinline__ const uint16_t *rows(const void *p) const { return static_cast<const uint16_t *>(p) + size_t(b) * N * D + h * hd; }
+};
+template <class Args>
+__device__ __forceinline__ HeadView head_view(const Args &a, int b, int h, int hd) {
+    const int N = a.N, D = a.H * hd, ld = 3 * D;
+    const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * hd;
+    return HeadView{b, h, hd, N, D, ld, base, base + D, base + 2 * D};
+}
+// The backward core of the dQ kernels: ds[r] = P[r] (dP[r] keep[r] - delta[r]) scale, P[r] = exp(s[r] c - lse[r]).  EXP2 = false:
+// c = scale, lse as saved; true: c = scale log2(e), lse pre-scaled.  (The dK / dV loops, which also need P keep, changed
+// their instruction streams with it and keep the spelled-out form.)
+template <bool EXP2>
+__device__ __forceinline__ f32x4 ds_from_scores(const f32x4 &s, const f32x4 &dp, const f32x4 &lse, const f32x4 &delta, const float (&keep)[4],
+                                                float c, float scale) {
+    f32x4 ds;
+#pragma unroll
+    for (int r = 0; r < 4; r++) ds[r] = (EXP2 ? fast_exp2(s[r] * c - lse[r]) : __expf(s[r] * c - lse[r])) * (dp[r] * keep[r] - delta[r]) * scale;
+    return ds;
+}
+__device__ __forceinline__ f32x4 splat4(float v) { return f32x4{v, v, v, v}; }
 
 }  // namespace attn
 }  // namespace sfcvit

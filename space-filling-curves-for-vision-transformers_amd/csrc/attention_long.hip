@@ -7,10 +7,8 @@
 // SIMD hides none of the exp / reduction latency between the MFMA bursts.  Here the workgroup is 12 waves (3 per SIMD;
 // 36 query fragments at N = 576 = exactly 3 per wave) and a wave's score row is cut into chunks of 12 key fragments
 // (192 keys: 48 accumulator registers) with the online-softmax rescale between chunks -- 3 rescales per row at
-// N = 576, against 9 in the tiled kernel.  No barrier after the staging.  MFMA orientations, LDS images and the
-// dropout mask are those of attention_seq.hip / attention.hip (S^T = K Q^T with K rows from LDS, O^T += V^T P^T with
-// V^T by ds_read_b64_tr_b16 and the exp'd accumulators as the B operand), so backward (attention.hip) regenerates the
-// same mask from (seed, row, key).
+// N = 576, against 9 in the tiled kernel.  No barrier after the staging.  MFMA orientations: attention.hip's header; LDS
+// images, stager and the dropout mask's row keys: attention_common.h.
 #include "attention_common.h"
 #include "common_host.h"
 
@@ -22,19 +20,6 @@ using namespace attn;
 constexpr int LT = 768, LW = LT / 64;   // 12 waves
 constexpr int CKF = 12;                 // key fragments per softmax chunk
 
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
-
-template <bool VT>
-__device__ __forceinline__ void dma_long(char *img, const uint16_t *__restrict__ src, int ld, int N, int npad, int tid) {
-    for (int p = tid; p < npad * 8; p += LT) {           // rows >= N: copies of row N - 1 (finite; their keys are masked)
-        const int row = p >> 3, cs = p & 7;
-        const int c = cs ^ kc_swz(row);        // "kc" and "vt" images share one swizzle now (device_common.h)
-        const uint16_t *g = src + size_t(min(row, N - 1)) * ld + c * 8;
-        __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(img + p * 16), 16, 0, 0);
-    }
-}
-
 // NFP = padded key fragments (npad / 16, even) as a compile-time constant, 0 = run time.
 template <int NFP>
 __global__ __launch_bounds__(LT) void attn_long_fwd_kernel(const sfcvit_attn_args a, int npad) {
@@ -42,17 +27,17 @@ __global__ __launch_bounds__(LT) void attn_long_fwd_kernel(const sfcvit_attn_arg
     char *kimg = smem, *vimg = smem + npad * 128;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y, h = blockIdx.x, N = a.N, D = a.H * HD, ld = 3 * D;
-    const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * HD;
-    const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
-    uint16_t *out = static_cast<uint16_t *>(a.out) + size_t(b) * N * D + h * HD;
+    const HeadView hv = head_view(a, b, h, HD);
+    const uint16_t *qp = hv.qp, *kp = hv.kp, *vp = hv.vp;
+    uint16_t *out = hv.rows(a.out);
     const int nfp = NFP ? NFP : npad >> 4, nqf = (N + 15) >> 4;
     bf16x8 qfr[2];
     qfr[0] = global_frag(qp, ld, 16 * wave, N, 0, lane);           // first query fragment: its latency hides behind the staging
     qfr[1] = global_frag(qp, ld, 16 * wave, N, 1, lane);
-    dma_long<false>(kimg, kp, ld, N, npad, tid);
-    dma_long<true>(vimg, vp, ld, N, npad, tid);
+    dma_rows<LT>(kimg, kp, ld, N, npad, tid);
+    dma_rows<LT>(vimg, vp, ld, N, npad, tid);
     __syncthreads();                                               // LDS-DMA pending: hipcc drains vmcnt(0) here
-    const float c2 = a.scale * 1.4426950408889634f;               // exp(x * scale) = exp2(x * c2)
+    const float c2 = a.scale * LOG2E;               // exp(x * scale) = exp2(x * c2)
     const LaneOff lo = lane_offsets(lane);
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
@@ -64,7 +49,7 @@ __global__ __launch_bounds__(LT) void attn_long_fwd_kernel(const sfcvit_attn_arg
         bf16x8 qn[2];                                              // next fragment of this wave, in flight during this one
         qn[0] = global_frag(qp, ld, 16 * (qf + LW), N, 0, lane);
         qn[1] = global_frag(qp, ld, 16 * (qf + LW), N, 1, lane);
-        const uint32_t drk = drop_row_key(seed, (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(q));
+        const uint32_t drk = mask_row_key(seed, b, a.H, h, N, q);
         f32x4 acc[4];
 #pragma unroll
         for (int hf = 0; hf < 4; hf++) acc[hf] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -128,7 +113,7 @@ __global__ __launch_bounds__(LT) void attn_long_fwd_kernel(const sfcvit_attn_arg
         mfma_fence();
         const float l = group_sum(l_run);
         store_rows(out, D, q, q < N, acc, 1.f / l, lane);
-        if (q < N && lane < 16) a.lse[(size_t(b) * a.H + h) * N + q] = m_run * a.scale + __logf(l);
+        if (q < N && lane < 16) a.lse[bh_row(b, a.H, h, N, q)] = m_run * a.scale + __logf(l);
         qfr[0] = qn[0];
         qfr[1] = qn[1];
     }
@@ -178,24 +163,25 @@ __global__ __launch_bounds__(LT) void attn_long_bwd_kv_kernel(const sfcvit_attn_
     const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * HD;
     const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
     const uint16_t *dop = static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * HD;
-    const float *lse = a.lse + (size_t(b) * a.H + h) * N, *del = a.delta + (size_t(b) * a.H + h) * N;
+    const uint64_t row0 = bh_row(b, a.H, h, N, 0);
+    const float *lse = a.lse + row0, *del = a.delta + row0;
     bf16x8 kf[2], vf[2];
 #pragma unroll
     for (int kk = 0; kk < 2; kk++) {
         kf[kk] = global_frag(kp, ld, 16 * wave, N, kk, lane);
         vf[kk] = global_frag(vp, ld, 16 * wave, N, kk, lane);
     }
-    dma_long<false>(qimg, qp, ld, N, npad, tid);
-    dma_long<false>(doimg, dop, D, N, npad, tid);
+    dma_rows<LT>(qimg, qp, ld, N, npad, tid);
+    dma_rows<LT>(doimg, dop, D, N, npad, tid);
     const uint32_t seed = eff_seed(a.dropout_seed, a.seed_off);
     for (int i = tid; i < npad; i += LT) {
-        lse_s[i] = i < N ? lse[i] * 1.4426950408889634f : INFINITY;   // padded queries: p = exp2(-inf) = 0
+        lse_s[i] = lse_log2(lse, i, i < N, INFINITY);   // padded queries: p = exp2(-inf) = 0
         del_s[i] = i < N ? del[i] : 0.f;
-        rkey_s[i] = drop_row_key(seed, (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(i));
+        rkey_s[i] = mask_row_key(seed, row0 + uint64_t(i));
     }
     __syncthreads();
     const int nf = (N + 15) >> 4, nc = npad >> 5;
-    const float scale = a.scale, c2 = a.scale * 1.4426950408889634f;
+    const float scale = a.scale, c2 = a.scale * LOG2E;
     const LaneOff lo = lane_offsets(lane);
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
@@ -284,8 +270,8 @@ __global__ __launch_bounds__(LT) void attn_long_bwd_q_kernel(const sfcvit_attn_a
     const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
     const uint16_t *dop = static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * HD;
     const uint16_t *op = static_cast<const uint16_t *>(a.out) + size_t(b) * N * D + h * HD;
-    const float *lse = a.lse + (size_t(b) * a.H + h) * N;
-    float *del = a.delta + (size_t(b) * a.H + h) * N;
+    const float *lse = a.lse + bh_row(b, a.H, h, N, 0);
+    float *del = a.delta + bh_row(b, a.H, h, N, 0);
     // sum over the 64 head columns of dO * O for row (lane & 15): 16 products per lane, then over the 4 lane groups
     auto row_delta = [&](const bf16x8 (&x)[2], const bf16x8 (&y)[2]) __attribute__((always_inline)) {
         float t = 0.f;
@@ -299,7 +285,7 @@ __global__ __launch_bounds__(LT) void attn_long_bwd_q_kernel(const sfcvit_attn_a
     float lse_q;
     {
         const int qq = 16 * wave + (lane & 15);
-        lse_q = qq < N ? lse[qq] * 1.4426950408889634f : 0.f;
+        lse_q = lse_log2(lse, qq, qq < N, 0.f);
 #pragma unroll
         for (int kk = 0; kk < 2; kk++) {
             qfr[kk] = global_frag(qp, ld, 16 * wave, N, kk, lane);
@@ -307,11 +293,11 @@ __global__ __launch_bounds__(LT) void attn_long_bwd_q_kernel(const sfcvit_attn_a
             ofr[kk] = global_frag(op, D, 16 * wave, N, kk, lane);
         }
     }
-    dma_long<false>(kimg, kp, ld, N, npad, tid);
-    dma_long<false>(vimg, vp, ld, N, npad, tid);
+    dma_rows<LT>(kimg, kp, ld, N, npad, tid);
+    dma_rows<LT>(vimg, vp, ld, N, npad, tid);
     __syncthreads();
     const int nqf = (N + 15) >> 4, nc = npad >> 5;
-    const float scale = a.scale, c2 = a.scale * 1.4426950408889634f;
+    const float scale = a.scale, c2 = a.scale * LOG2E;
     const LaneOff lo = lane_offsets(lane);
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
@@ -323,7 +309,7 @@ __global__ __launch_bounds__(LT) void attn_long_bwd_q_kernel(const sfcvit_attn_a
     for (int qf = wave; qf < nqf; qf += LW) {
         const int q = 16 * qf + (lane & 15), qn = q + 16 * LW;
         bf16x8 qnx[2], donx[2], onx[2];                               // next fragment of this wave
-        const float lse_n = qn < N ? lse[qn] * 1.4426950408889634f : 0.f;
+        const float lse_n = lse_log2(lse, qn, qn < N, 0.f);
 #pragma unroll
         for (int kk = 0; kk < 2; kk++) {
             qnx[kk] = global_frag(qp, ld, 16 * (qf + LW), N, kk, lane);
@@ -332,12 +318,12 @@ __global__ __launch_bounds__(LT) void attn_long_bwd_q_kernel(const sfcvit_attn_a
         }
         const float del_q = row_delta(dof, ofr);                      // rows >= N: zero fragments -> 0
         if (q < N && lane < 16) del[q] = del_q;
-        const uint32_t drk = drop_row_key(seed, (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(q));
+        const uint32_t drk = mask_row_key(seed, b, a.H, h, N, q);
         f32x4 dq[4];
 #pragma unroll
         for (int hf = 0; hf < 4; hf++) dq[hf] = f32x4{0.f, 0.f, 0.f, 0.f};
         auto ds_frag = [&](int kfi) __attribute__((always_inline)) {
-            f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f}, ds;
+            f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < 2; kk++) {
                 sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kc_frag_at(kimg, 16 * kfi, lo.k[kk]), qfr[kk], sc, 0, 0, 0);
@@ -345,8 +331,7 @@ __global__ __launch_bounds__(LT) void attn_long_bwd_q_kernel(const sfcvit_attn_a
             }
             float keep[4] = {1.f, 1.f, 1.f, 1.f};
             if (drop) drop_keep4(drk, 16 * kfi + 4 * (lane >> 4), dth, dsc, keep);
-#pragma unroll
-            for (int r = 0; r < 4; r++) ds[r] = fast_exp2(sc[r] * c2 - lse_q) * (dp[r] * keep[r] - del_q) * scale;
+            f32x4 ds = ds_from_scores<true>(sc, dp, splat4(lse_q), splat4(del_q), keep, c2, scale);
             if (16 * kfi + 16 > N) {                                  // boundary / padding fragment: keys >= N carry no gradient
 #pragma unroll
                 for (int r = 0; r < 4; r++)

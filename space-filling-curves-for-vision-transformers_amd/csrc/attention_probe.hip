@@ -23,8 +23,6 @@ namespace {
 
 using namespace attn;
 
-constexpr float LOG2E = 1.4426950408889634f;
-
 // x[kf][r] = q . k - lse / scale for this wave's 16 queries (fragments qf) against the 64 keys staged in kimg
 template <int S>
 __device__ __forceinline__ void probe_scores(f32x4 (&x)[4], const char *kimg, const bf16x8 (&qf)[S][2], float c0, const LaneOff &lo) {
@@ -48,10 +46,10 @@ __global__ __launch_bounds__(THREADS) void attn_probe_stats_kernel(const sfcvit_
     float *prow = reinterpret_cast<float *>(smem + S * IMG_BYTES), *pcol = prow + BLK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, N = a.N, hd = 64 * S, D = a.H * hd, ld = 3 * D;
-    const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * hd;
-    const uint16_t *qp = base, *kp = base + D;
+    const HeadView hv = head_view(a, b, h, hd);
+    const uint16_t *qp = hv.qp, *kp = hv.kp;
     const int q0 = blockIdx.x * BLK + wave * 16, q = q0 + (lane & 15);
-    const size_t row = (size_t(b) * a.H + h) * size_t(N);
+    const size_t row = bh_row(b, a.H, h, N, 0);
     const float lse_q = q < N ? a.lse[row + q] : 0.f;
     const float c0 = -lse_q / a.scale, c2 = a.scale * LOG2E;
     const bool has_pos = a.pos != nullptr;
@@ -150,7 +148,7 @@ __global__ __launch_bounds__(THREADS) void attn_probe_map_kernel(const sfcvit_at
     for (int h = h_lo; h < h_hi; h++) {
         const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * hd;
         const uint16_t *qp = base, *kp = base + D;
-        const float lse_q = q < N ? a.lse[(size_t(b) * a.H + h) * size_t(N) + q] : 0.f;
+        const float lse_q = q < N ? a.lse[bh_row(b, a.H, h, N, 0) + q] : 0.f;
         bf16x8 qf[S][2];
         static_for<0, S>([&](auto ic) __attribute__((always_inline)) {
             constexpr int sl = decltype(ic)::value;

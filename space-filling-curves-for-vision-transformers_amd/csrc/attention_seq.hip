@@ -21,23 +21,6 @@ using namespace attn;
 constexpr int MAXF = 16;   // 16-row fragments per sequence (N <= 256)
 constexpr int MAXC = 8;    // 32-row chunks
 
-// Stage `npad` rows x 64 cols of a [N, ld] matrix into an LDS image by LDS-DMA
-// (global_load_lds_dwordx4: asynchronous, no staging registers).  The DMA writes lane-linear
-// (slot p = tid + 256*i at LDS byte 16*p), so the image's bank swizzle is applied to the SOURCE
-// column chunk.  Rows >= N are filled with a copy of row N-1 (finite values); every consumer
-// masks them: keys >= N get probability / dS = 0, queries >= N get lse = +inf.
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
-template <bool VT>
-__device__ __forceinline__ void dma_seq(char *img, const uint16_t *__restrict__ src, int ld, int N, int npad, int tid) {
-    for (int p = tid; p < npad * 8; p += THREADS) {     // npad % 32 == 16: the last trip is half a workgroup
-        const int row = p >> 3, cs = p & 7;
-        const int c = cs ^ kc_swz(row);        // "kc" and "vt" images share one swizzle now (device_common.h)
-        const uint16_t *g = src + size_t(min(row, N - 1)) * ld + c * 8;
-        __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(img + p * 16), 16, 0, 0);
-    }
-}
-
 // 16 rows x 16 cols transposed fragment for the 16-deep MFMA (the odd last 16 keys of a sequence padded to 16)
 __device__ __forceinline__ bf16x4 tr_frag16_at(const char *img, int r_lo, int lane_off) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((SFCVIT_LDS bf16x4 *)(img + r_lo * 128 + lane_off));
@@ -78,10 +61,10 @@ __global__ __launch_bounds__(THREADS, 3) void attn_seq_fwd_kernel(const sfcvit_a
         qfr[o][0] = global_frag(qp, ld, 16 * (wave + WAVES * o), N, 0, lane);
         qfr[o][1] = global_frag(qp, ld, 16 * (wave + WAVES * o), N, 1, lane);
     }
-    dma_seq<false>(kimg, kp, ld, N, npad, tid);
-    dma_seq<true>(vimg, vp, ld, N, npad, tid);
+    dma_rows<THREADS>(kimg, kp, ld, N, npad, tid);
+    dma_rows<THREADS>(vimg, vp, ld, N, npad, tid);
     __syncthreads();                                     // LDS-DMA pending: hipcc drains vmcnt(0) here
-    const float c2 = a.scale * 1.4426950408889634f;     // exp(x * scale) = exp2(x * c2)
+    const float c2 = a.scale * LOG2E;                    // exp(x * scale) = exp2(x * c2)
     const LaneOff lo = lane_offsets(lane);
     constexpr bool drop = DROP;
     const uint32_t dth = drop_thresh(a.dropout_p);
@@ -120,7 +103,7 @@ __global__ __launch_bounds__(THREADS, 3) void attn_seq_fwd_kernel(const sfcvit_a
         mx = group_max(mx);                              // max of the RAW scores (scale > 0)
         const float mc = mx * c2;
         float l = 0.f;
-        const uint32_t drk = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(q));
+        const uint32_t drk = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), b, a.H, h, N, q);
 #pragma unroll
         for (int kf = 0; kf < MAXF; kf++)
             if (kf < nf) {
@@ -160,7 +143,7 @@ __global__ __launch_bounds__(THREADS, 3) void attn_seq_fwd_kernel(const sfcvit_a
         }
         mfma_fence();
         store_rows(out, D, q, q < N, acc, 1.f / l, lane);
-        if (q < N && lane < 16) a.lse[(size_t(b) * a.H + h) * N + q] = mx * a.scale + __logf(l);
+        if (q < N && lane < 16) a.lse[bh_row(b, a.H, h, N, q)] = mx * a.scale + __logf(l);
     }
 }
 
@@ -176,7 +159,8 @@ __global__ __launch_bounds__(THREADS, 2) void attn_seq_bwd_kv_kernel(const sfcvi
     const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * HD;
     const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
     const uint16_t *dop = static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * HD;
-    const float *lse = a.lse + (size_t(b) * a.H + h) * N, *del = a.delta + (size_t(b) * a.H + h) * N;
+    const uint64_t row0 = bh_row(b, a.H, h, N, 0);
+    const float *lse = a.lse + row0, *del = a.delta + row0;
     bf16x8 kfr[MAXOWN][2], vfr[MAXOWN][2];          // this wave's key fragments, fetched before the staging
 #pragma unroll
     for (int o = 0; o < MAXOWN; o++)
@@ -185,16 +169,16 @@ __global__ __launch_bounds__(THREADS, 2) void attn_seq_bwd_kv_kernel(const sfcvi
             kfr[o][kk] = global_frag(kp, ld, 16 * (wave + WAVES * o), N, kk, lane);
             vfr[o][kk] = global_frag(vp, ld, 16 * (wave + WAVES * o), N, kk, lane);
         }
-    dma_seq<false>(qimg, qp, ld, N, npad, tid);
-    dma_seq<false>(doimg, dop, D, N, npad, tid);
+    dma_rows<THREADS>(qimg, qp, ld, N, npad, tid);
+    dma_rows<THREADS>(doimg, dop, D, N, npad, tid);
     for (int i = tid; i < npad; i += THREADS) {
-        lse_s[i] = i < N ? lse[i] * 1.4426950408889634f : INFINITY;   // padded queries: p = exp2(-inf) = 0
+        lse_s[i] = lse_log2(lse, i, i < N, INFINITY);                 // padded queries: p = exp2(-inf) = 0
         del_s[i] = i < N ? del[i] : 0.f;
-        rkey_s[i] = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(i));
+        rkey_s[i] = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), row0 + uint64_t(i));
     }
     __syncthreads();
     const int nf = NFC ? NFC : (N + 15) >> 4, nc = NFC ? ((NFC + 1) >> 1) : npad >> 5;   // npad = 32 nc here
-    const float scale = a.scale, c2 = a.scale * 1.4426950408889634f;
+    const float scale = a.scale, c2 = a.scale * LOG2E;
     const LaneOff lo = lane_offsets(lane);
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
@@ -259,32 +243,33 @@ __global__ __launch_bounds__(THREADS, 3) void attn_seq_bwd_q_kernel(const sfcvit
     char *kimg = smem, *vimg = smem + npad * 128;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y, h = blockIdx.x, N = a.N, D = a.H * HD, ld = 3 * D;
-    const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * HD;
-    const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
-    const uint16_t *dop = static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * HD;
+    const HeadView hv = head_view(a, b, h, HD);
+    const uint16_t *qp = hv.qp, *kp = hv.kp, *vp = hv.vp;
+    const uint16_t *dop = hv.rows(a.dout);
+    const uint64_t row0 = bh_row(b, a.H, h, N, 0);
     bf16x8 qfa[MAXOWN][2], dofa[MAXOWN][2];         // this wave's query fragments, fetched before the staging
     float lse_a[MAXOWN], del_a[MAXOWN];
 #pragma unroll
     for (int o = 0; o < MAXOWN; o++) {
         const int qq = 16 * (wave + WAVES * o) + (lane & 15);
-        lse_a[o] = qq < N ? a.lse[(size_t(b) * a.H + h) * N + qq] * 1.4426950408889634f : 0.f;
-        del_a[o] = qq < N ? a.delta[(size_t(b) * a.H + h) * N + qq] : 0.f;
+        lse_a[o] = qq < N ? a.lse[row0 + qq] * LOG2E : 0.f;
+        del_a[o] = qq < N ? a.delta[row0 + qq] : 0.f;
 #pragma unroll
         for (int kk = 0; kk < 2; kk++) {
             qfa[o][kk] = global_frag(qp, ld, 16 * (wave + WAVES * o), N, kk, lane);
             dofa[o][kk] = global_frag(dop, D, 16 * (wave + WAVES * o), N, kk, lane);
         }
     }
-    dma_seq<false>(kimg, kp, ld, N, npad, tid);
-    dma_seq<false>(vimg, vp, ld, N, npad, tid);
+    dma_rows<THREADS>(kimg, kp, ld, N, npad, tid);
+    dma_rows<THREADS>(vimg, vp, ld, N, npad, tid);
     __syncthreads();
     const int nf = NFC ? NFC : (N + 15) >> 4, nc = NFC ? (NFC >> 1) : npad >> 5;
-    const float scale = a.scale, c2 = a.scale * 1.4426950408889634f;
+    const float scale = a.scale, c2 = a.scale * LOG2E;
     const LaneOff lo = lane_offsets(lane);
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
     const float dsc = 1.f / (1.f - a.dropout_p);
-    uint16_t *dbase = static_cast<uint16_t *>(a.dqkv) + size_t(b) * N * ld + h * HD;
+    uint16_t *dbase = hv.packed(a.dqkv);
 
 #pragma unroll
     for (int o = 0; o < MAXOWN; o++) {
@@ -292,7 +277,7 @@ __global__ __launch_bounds__(THREADS, 3) void attn_seq_bwd_q_kernel(const sfcvit
         if (qf >= nf) break;                             // wave-uniform
         const int q = 16 * qf + (lane & 15);
         const float lse_q = lse_a[o], del_q = del_a[o];
-        const uint32_t drk = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(q));
+        const uint32_t drk = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), row0 + uint64_t(q));
         const bf16x8 (&qfr)[2] = qfa[o];
         const bf16x8 (&dof)[2] = dofa[o];
         f32x4 dq[4];
@@ -300,7 +285,7 @@ __global__ __launch_bounds__(THREADS, 3) void attn_seq_bwd_q_kernel(const sfcvit
         for (int hf = 0; hf < 4; hf++) dq[hf] = f32x4{0.f, 0.f, 0.f, 0.f};
         // dS of one 16-key fragment: exp2(s c2 - lse) (dP keep - delta) scale, keys >= N zeroed
         auto ds_frag = [&](int kfi) __attribute__((always_inline)) {
-            f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f}, ds;
+            f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < 2; kk++) {
                 s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kc_frag_at(kimg, 16 * kfi, lo.k[kk]), qfr[kk], s, 0, 0, 0);
@@ -308,8 +293,7 @@ __global__ __launch_bounds__(THREADS, 3) void attn_seq_bwd_q_kernel(const sfcvit
             }
             float keep[4] = {1.f, 1.f, 1.f, 1.f};
             if (drop) drop_keep4(drk, 16 * kfi + 4 * (lane >> 4), dth, dsc, keep);
-#pragma unroll
-            for (int r = 0; r < 4; r++) ds[r] = fast_exp2(s[r] * c2 - lse_q) * (dp[r] * keep[r] - del_q) * scale;
+            f32x4 ds = ds_from_scores<true>(s, dp, splat4(lse_q), splat4(del_q), keep, c2, scale);
             if (16 * kfi + 16 > N) {                     // boundary fragment: keys >= N carry no gradient
 #pragma unroll
                 for (int r = 0; r < 4; r++)

@@ -20,20 +20,6 @@ using namespace attn;
 
 constexpr int MAXF = 16, MAXC = 8, WAVES = THREADS / 64;
 
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
-
-// npad rows x 64 columns (one slice) of a [N, ld] matrix -> LDS image, by LDS-DMA (rows >= N copy row N-1).
-template <bool VT>
-__device__ __forceinline__ void dma_slice(char *img, const uint16_t *__restrict__ src, int ld, int N, int npad, int tid) {
-    for (int p = tid; p < npad * 8; p += THREADS) {
-        const int row = p >> 3, cs = p & 7;
-        const int c = cs ^ kc_swz(row);        // "kc" and "vt" images share one swizzle now (device_common.h)
-        const uint16_t *g = src + size_t(min(row, N - 1)) * ld + c * 8;
-        __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(img + p * 16), 16, 0, 0);
-    }
-}
-
 template <int S>
 __global__ __launch_bounds__(THREADS) void attn_wide_fwd_kernel(const sfcvit_attn_args a, int npad) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -47,11 +33,11 @@ __global__ __launch_bounds__(THREADS) void attn_wide_fwd_kernel(const sfcvit_att
     const int nf = npad >> 4, nc = npad >> 5, nqf = (N + 15) >> 4;   // key fragments (padded to 32 keys), query fragments
 #pragma unroll
     for (int sl = 0; sl < S; sl++) {
-        dma_slice<false>(kimg + sl * img, kp + 64 * sl, ld, N, npad, tid);
-        dma_slice<true>(vimg + sl * img, vp + 64 * sl, ld, N, npad, tid);
+        dma_rows<THREADS>(kimg + sl * img, kp + 64 * sl, ld, N, npad, tid);
+        dma_rows<THREADS>(vimg + sl * img, vp + 64 * sl, ld, N, npad, tid);
     }
     __syncthreads();
-    const float c2 = a.scale * 1.4426950408889634f;
+    const float c2 = a.scale * LOG2E;
     const LaneOff lo = lane_offsets(lane);
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
@@ -91,7 +77,7 @@ __global__ __launch_bounds__(THREADS) void attn_wide_fwd_kernel(const sfcvit_att
         mx = group_max(mx);
         const float mc = mx * c2;
         float l = 0.f;
-        const uint32_t drk = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(q));
+        const uint32_t drk = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), b, a.H, h, N, q);
 #pragma unroll
         for (int kf = 0; kf < MAXF; kf++)
             if (kf < nf) {
@@ -126,7 +112,7 @@ __global__ __launch_bounds__(THREADS) void attn_wide_fwd_kernel(const sfcvit_att
         mfma_fence();
 #pragma unroll
         for (int sl = 0; sl < S; sl++) store_rows(out + 64 * sl, D, q, q < N, acc[sl], 1.f / l, lane);
-        if (q < N && lane < 16) a.lse[(size_t(b) * a.H + h) * N + q] = mx * a.scale + __logf(l);
+        if (q < N && lane < 16) a.lse[bh_row(b, a.H, h, N, q)] = mx * a.scale + __logf(l);
     }
 }
 
@@ -143,20 +129,21 @@ __global__ __launch_bounds__(THREADS) void attn_wide_bwd_kv_kernel(const sfcvit_
     const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * hd;
     const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
     const uint16_t *dop = static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * hd;
-    const float *lse = a.lse + (size_t(b) * a.H + h) * N, *del = a.delta + (size_t(b) * a.H + h) * N;
+    const uint64_t row0 = bh_row(b, a.H, h, N, 0);
+    const float *lse = a.lse + row0, *del = a.delta + row0;
 #pragma unroll
     for (int sl = 0; sl < S; sl++) {
-        dma_slice<false>(qimg + sl * img, qp + 64 * sl, ld, N, npad, tid);
-        dma_slice<false>(doimg + sl * img, dop + 64 * sl, D, N, npad, tid);
+        dma_rows<THREADS>(qimg + sl * img, qp + 64 * sl, ld, N, npad, tid);
+        dma_rows<THREADS>(doimg + sl * img, dop + 64 * sl, D, N, npad, tid);
     }
     for (int i = tid; i < npad; i += THREADS) {
-        lse_s[i] = i < N ? lse[i] * 1.4426950408889634f : INFINITY;
+        lse_s[i] = lse_log2(lse, i, i < N, INFINITY);
         del_s[i] = i < N ? del[i] : 0.f;
-        rkey_s[i] = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(i));
+        rkey_s[i] = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), row0 + uint64_t(i));
     }
     __syncthreads();
     const int nf = (N + 15) >> 4, nc = npad >> 5;          // npad % 32 == 0 here
-    const float scale = a.scale, c2 = a.scale * 1.4426950408889634f;
+    const float scale = a.scale, c2 = a.scale * LOG2E;
     const LaneOff lo = lane_offsets(lane);
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
@@ -238,12 +225,12 @@ __global__ __launch_bounds__(THREADS) void attn_wide_bwd_q_kernel(const sfcvit_a
     const uint16_t *dop = static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * hd;
 #pragma unroll
     for (int sl = 0; sl < S; sl++) {
-        dma_slice<false>(kimg + sl * img, kp + 64 * sl, ld, N, npad, tid);
-        dma_slice<false>(vimg + sl * img, vp + 64 * sl, ld, N, npad, tid);
+        dma_rows<THREADS>(kimg + sl * img, kp + 64 * sl, ld, N, npad, tid);
+        dma_rows<THREADS>(vimg + sl * img, vp + 64 * sl, ld, N, npad, tid);
     }
     __syncthreads();
     const int nf = (N + 15) >> 4, nc = npad >> 5;          // npad % 32 == 0 here
-    const float scale = a.scale, c2 = a.scale * 1.4426950408889634f;
+    const float scale = a.scale, c2 = a.scale * LOG2E;
     const LaneOff lo = lane_offsets(lane);
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
@@ -251,9 +238,9 @@ __global__ __launch_bounds__(THREADS) void attn_wide_bwd_q_kernel(const sfcvit_a
     uint16_t *dbase = static_cast<uint16_t *>(a.dqkv) + size_t(b) * N * ld + h * hd;
     for (int qf = wave; qf < nf; qf += WAVES) {
         const int q = 16 * qf + (lane & 15);
-        const float lse_q = q < N ? a.lse[(size_t(b) * a.H + h) * N + q] * 1.4426950408889634f : 0.f;
-        const float del_q = q < N ? a.delta[(size_t(b) * a.H + h) * N + q] : 0.f;
-        const uint32_t drk = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(q));
+        const float lse_q = q < N ? a.lse[bh_row(b, a.H, h, N, q)] * LOG2E : 0.f;
+        const float del_q = q < N ? a.delta[bh_row(b, a.H, h, N, q)] : 0.f;
+        const uint32_t drk = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), b, a.H, h, N, q);
         bf16x8 qfr[S][2], dof[S][2];
 #pragma unroll
         for (int sl = 0; sl < S; sl++)
@@ -282,8 +269,7 @@ __global__ __launch_bounds__(THREADS) void attn_wide_bwd_q_kernel(const sfcvit_a
                     }
                 float keep[4] = {1.f, 1.f, 1.f, 1.f};
                 if (drop) drop_keep4(drk, 16 * kfi + 4 * (lane >> 4), dth, dsc, keep);
-#pragma unroll
-                for (int r = 0; r < 4; r++) ds[t][r] = fast_exp2(s[r] * c2 - lse_q) * (dp[r] * keep[r] - del_q) * scale;
+                ds[t] = ds_from_scores<true>(s, dp, splat4(lse_q), splat4(del_q), keep, c2, scale);
                 if (16 * kfi + 16 > N) {
 #pragma unroll
                     for (int r = 0; r < 4; r++)

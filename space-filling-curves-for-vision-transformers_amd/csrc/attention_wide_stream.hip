@@ -1,8 +1,7 @@
 // Streaming attention for head dims 128 / 192 / 256 (= 64 S, S = 2..4), any N.
 //
 // attention.hip's tiled kernels with the head dimension cut into S slices of 64 columns, the way attention_wide.hip cut
-// attention_seq.hip's: every slice of a staged 64-row block has its own 128-byte-row LDS image (so the fragment addressing
-// and bank swizzles of the 64-wide kernels apply unchanged), scores sum over the slices, outputs are produced per slice.
+// attention_seq.hip's (one LDS image per slice: attention_wide.hip's header); scores sum over the slices, outputs are per slice.
 // LDS is two 64-row blocks of S slices whatever N is -- 32 / 48 / 64 KiB (+ 768 B of row data in the dK / dV kernel) --
 // so two workgroups fit on a CU at S = 4.
 //   forward         workgroup = 64 queries of one (batch, head), wave = 16; loop over 64-key blocks of K | V, online softmax
@@ -21,22 +20,21 @@ namespace {
 
 using namespace attn;
 
-constexpr float LOG2E = 1.4426950408889634f;
-
 template <int S>
 __global__ __launch_bounds__(THREADS) void attn_wide_stream_fwd_kernel(const sfcvit_attn_args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *kimg = smem, *vimg = smem + S * IMG_BYTES;            // slice sl of a block at + sl * IMG_BYTES
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.z, h = blockIdx.y, N = a.N, hd = 64 * S, D = a.H * hd, ld = 3 * D;
-    const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * hd;
-    const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
+    const HeadView hv = head_view(a, b, h, hd);
+    const uint16_t *qp = hv.qp, *kp = hv.kp, *vp = hv.vp;
     const int q0 = blockIdx.x * BLK + wave * 16;
     const float scale = a.scale;
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
     const float dsc = 1.f / (1.f - a.dropout_p);
-    const uint32_t drk = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(q0 + (lane & 15)));
+    const uint64_t row0 = bh_row(b, a.H, h, N, 0);
+    const uint32_t drk = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), row0 + uint64_t(q0 + (lane & 15)));
     const LaneOff lo = lane_offsets(lane);
 
     bf16x8 qf[S][2];
@@ -118,12 +116,12 @@ __global__ __launch_bounds__(THREADS) void attn_wide_stream_fwd_kernel(const sfc
     }
     const float l_tot = group_sum(l_run);
     const int q = q0 + (lane & 15);
-    uint16_t *out = static_cast<uint16_t *>(a.out) + size_t(b) * N * D + h * hd;
+    uint16_t *out = hv.rows(a.out);
     static_for<0, S>([&](auto ic) __attribute__((always_inline)) {
         constexpr int sl = decltype(ic)::value;
         store_rows(out + 64 * sl, D, q, q < N, o[sl], 1.f / l_tot, lane);
     });
-    if (q < N && lane < 16) a.lse[(size_t(b) * a.H + h) * N + q] = m_run + __logf(l_tot);
+    if (q < N && lane < 16) a.lse[row0 + q] = m_run + __logf(l_tot);
 }
 
 // dK, dV: one workgroup = 64 keys of one (b, h), wave = 16 keys; K / V fragments of all slices stay in registers.
@@ -135,17 +133,16 @@ __global__ __launch_bounds__(THREADS) void attn_wide_stream_bwd_kv_kernel(const 
     uint32_t *rkey_s = reinterpret_cast<uint32_t *>(del_s + BLK);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.z, h = blockIdx.y, N = a.N, hd = 64 * S, D = a.H * hd, ld = 3 * D;
-    const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * hd;
-    const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
-    const uint16_t *dop = static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * hd;
-    const float *lse = a.lse + (size_t(b) * a.H + h) * N, *del = a.delta + (size_t(b) * a.H + h) * N;
+    const HeadView hv = head_view(a, b, h, hd);
+    const uint16_t *qp = hv.qp, *kp = hv.kp, *vp = hv.vp;
+    const uint16_t *dop = hv.rows(a.dout);
+    const float *lse = a.lse + bh_row(b, a.H, h, N, 0), *del = a.delta + bh_row(b, a.H, h, N, 0);
     const int key0 = blockIdx.x * BLK + wave * 16, key = key0 + (lane & 15);
     const float scale = a.scale, c2 = a.scale * LOG2E;
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
     const float dsc = 1.f / (1.f - a.dropout_p);
     const uint32_t seed = eff_seed(a.dropout_seed, a.seed_off);
-    const uint64_t dbh = (uint64_t(b) * a.H + h) * uint64_t(N);
     const LaneOff lo = lane_offsets(lane);
 
     bf16x8 kf[S][2], vf[S][2];
@@ -170,9 +167,9 @@ __global__ __launch_bounds__(THREADS) void attn_wide_stream_bwd_kv_kernel(const 
         });
         if (tid < BLK) {                                         // queries >= N: lse = +inf gives P = 0
             const int q = q0 + tid;
-            lse_s[tid] = q < N ? lse[q] * LOG2E : INFINITY;
+            lse_s[tid] = lse_log2(lse, q, q < N, INFINITY);
             del_s[tid] = q < N ? del[q] : 0.f;
-            rkey_s[tid] = drop_row_key(seed, dbh + uint64_t(q));
+            rkey_s[tid] = mask_row_key(seed, b, a.H, h, N, q);
         }
         __syncthreads();
 #pragma unroll
@@ -224,7 +221,7 @@ __global__ __launch_bounds__(THREADS) void attn_wide_stream_bwd_kv_kernel(const 
         }
         mfma_fence();
     }
-    uint16_t *dbase = static_cast<uint16_t *>(a.dqkv) + size_t(b) * N * ld + h * hd;
+    uint16_t *dbase = hv.packed(a.dqkv);
     static_for<0, S>([&](auto ic) __attribute__((always_inline)) {
         constexpr int sl = decltype(ic)::value;
         store_rows(dbase + D + 64 * sl, ld, key, key < N, dk[sl], 1.f, lane);
@@ -239,17 +236,17 @@ __global__ __launch_bounds__(THREADS) void attn_wide_stream_bwd_q_kernel(const s
     char *kimg = smem, *vimg = smem + S * IMG_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.z, h = blockIdx.y, N = a.N, hd = 64 * S, D = a.H * hd, ld = 3 * D;
-    const uint16_t *base = static_cast<const uint16_t *>(a.qkv) + size_t(b) * N * ld + h * hd;
-    const uint16_t *qp = base, *kp = base + D, *vp = base + 2 * D;
-    const uint16_t *dop = static_cast<const uint16_t *>(a.dout) + size_t(b) * N * D + h * hd;
+    const HeadView hv = head_view(a, b, h, hd);
+    const uint16_t *qp = hv.qp, *kp = hv.kp, *vp = hv.vp;
+    const uint16_t *dop = hv.rows(a.dout);
     const int q0 = blockIdx.x * BLK + wave * 16, q = q0 + (lane & 15);
     const float scale = a.scale, c2 = a.scale * LOG2E;
-    const float lse_q = q < N ? a.lse[(size_t(b) * a.H + h) * N + q] * LOG2E : 0.f;
-    const float del_q = q < N ? a.delta[(size_t(b) * a.H + h) * N + q] : 0.f;
+    const float lse_q = q < N ? a.lse[bh_row(b, a.H, h, N, q)] * LOG2E : 0.f;
+    const float del_q = q < N ? a.delta[bh_row(b, a.H, h, N, q)] : 0.f;
     const bool drop = a.dropout_p > 0.f;
     const uint32_t dth = drop_thresh(a.dropout_p);
     const float dsc = 1.f / (1.f - a.dropout_p);
-    const uint32_t drk = drop_row_key(eff_seed(a.dropout_seed, a.seed_off), (uint64_t(b) * a.H + h) * uint64_t(N) + uint64_t(q));
+    const uint32_t drk = mask_row_key(eff_seed(a.dropout_seed, a.seed_off), b, a.H, h, N, q);
     const LaneOff lo = lane_offsets(lane);
 
     bf16x8 qf[S][2], dof[S][2];
@@ -312,7 +309,7 @@ __global__ __launch_bounds__(THREADS) void attn_wide_stream_bwd_q_kernel(const s
         }
         mfma_fence();
     }
-    uint16_t *dbase = static_cast<uint16_t *>(a.dqkv) + size_t(b) * N * ld + h * hd;
+    uint16_t *dbase = hv.packed(a.dqkv);
     static_for<0, S>([&](auto ic) __attribute__((always_inline)) {
         constexpr int sl = decltype(ic)::value;
         store_rows(dbase + 64 * sl, ld, q, q < N, dq[sl], 1.f, lane);
