@@ -499,6 +499,41 @@ int sfcvit_attention_probs(const sfcvit_attn_probe_args *a, void *stream);
 int sfcvit_attention_stats(const sfcvit_attn_probe_args *a, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Depth-wise convolution along the token sequence
+ *   replaces the first stage of TokenAggregator.forward (src/models/vit.py:37-42):
+ *   nn.Conv1d(dim, dim, k, s, padding=k//2, groups=dim) between two transposes.  Here the activation stays
+ *   [B, N, D] bf16 with D contiguous; the point-wise Conv1d, GELU and LayerNorm that follow are a GEMM,
+ *   the GELU pass and the LayerNorm of this library.
+ *
+ *   x [B, N, D] bf16;  w [D, k] bf16 (dw.weight [D, 1, k] viewed 2-D);  bias [D] bf16 or NULL;  u [B, Nout, D] bf16,
+ *   pad = k / 2, Nout = (N + 2 pad - k) / s + 1 (nn.Conv1d's rule: odd k with s = 1 keeps N, even k gives N + 1).
+ *   Supported: k in 1..9, s in 1..4, D % 8 == 0, B, N >= 1 (N < k included); everything else is SFCVIT_EINVAL, decided
+ *   before any HIP call.  x, u, du, dx and the workspace must be 16-byte aligned; w, bias, dw, db need no alignment.
+ *   No atomics: dw / db partial sums go through the workspace and are added in a fixed order (two runs, same bits);
+ *   their final reduction joins the deferred reductions above when deferral is on.
+ * ---------------------------------------------------------------------- */
+/* HOST: Nout, or a negative value for arguments the kernels refuse. */
+int sfcvit_dwconv1d_out_len(int N, int k, int s);
+/* u[b, n, d] = bf16( bias[d] + sum_t w[d, t] * x[b, n s + t - pad, d] ), rows outside 0 .. N - 1 counted as zero; the
+ * sum runs in fp32 in tap order t = 0 .. k - 1 starting from the bias, and is rounded once.  A tap never reaches into
+ * image b - 1 or b + 1. */
+int sfcvit_dwconv1d_fwd(const void *x, const void *w, const void *bias, void *u, int B, int N, int D, int k, int s, void *stream);
+/* HOST: workspace bytes of the backward call (0 for refused arguments). */
+int64_t sfcvit_dwconv1d_bwd_workspace(int B, int N, int D, int k, int s);
+/* du [B, Nout, D] bf16 in.  Each output may be NULL = skipped (not all three):
+ *   dx [B, N, D] bf16: dx[b, m, d] = sum_t w[d, t] * du[b, (m + pad - t) / s, d] over the taps where the division is
+ *      exact and in range (fp32 sum in tap order, one rounding); needs w
+ *   dw [D, k]:         dw[d, t] = sum_{b, n} du[b, n, d] * x[b, n s + t - pad, d]; needs x
+ *   db [D]:            db[d] = sum_{b, n} du[b, n, d]
+ * dw and db are summed in fp32 and written as fp32, or as bf16 when grads_bf16 != 0 (views of a flat gradient buffer).
+ * The workspace is needed for dw / db only. */
+int sfcvit_dwconv1d_bwd(const void *du, const void *x, const void *w, void *dx, void *dw, void *db, int grads_bf16, int B, int N,
+                        int D, int k, int s, void *workspace, int64_t workspace_bytes, void *stream);
+/* HOST: name of the main kernel the calling thread's last sfcvit_dwconv1d_fwd / _bwd launched, as rocprofv3 prints it
+ * (e.g. "dwconv3_bwd_kernel<true, true>"). */
+int sfcvit_last_dwconv_kernel(char *buf, int n);
+
+/* ------------------------------------------------------------------------
  * Elementwise / loss / optimizer
  * ---------------------------------------------------------------------- */
 /* y = gelu_erf(x) (nn.GELU in MultiLayerPredictor, vit.py:308); bf16, n elements. */

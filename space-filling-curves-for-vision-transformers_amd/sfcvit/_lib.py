@@ -138,6 +138,12 @@ SIGNATURES = {
     "sfcvit_attention_colsum_workspace": (c_int64, [c_int, c_int, c_int, c_int]),
     "sfcvit_attention_probs": (c_int, [ctypes.POINTER(AttnProbeArgs), c_void_p]),
     "sfcvit_attention_stats": (c_int, [ctypes.POINTER(AttnProbeArgs), c_void_p]),
+    "sfcvit_dwconv1d_out_len": (c_int, [c_int, c_int, c_int]),
+    "sfcvit_dwconv1d_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "sfcvit_dwconv1d_bwd_workspace": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "sfcvit_dwconv1d_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_void_p, c_int64, c_void_p]),
+    "sfcvit_last_dwconv_kernel": (c_int, [ctypes.c_char_p, c_int]),
     "sfcvit_gelu_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "sfcvit_gelu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sfcvit_soft_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

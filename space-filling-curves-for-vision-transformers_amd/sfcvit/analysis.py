@@ -80,6 +80,8 @@ def _head_eval(head, x):
 def _vit_layers(model, images):
     """VisionTransformer / VisionTransformer1D: yields (qkv, lse, n_heads, scale) per encoder layer, then the logits."""
     x = model.patch_embed(images)
+    if hasattr(model, "ta"):                 # token_aggregator=...: directly after the tokenizer, as the model's forward
+        x = model.ta(x)
     if isinstance(model, VisionTransformer1D):
         x = model.mlp_mixer(x)
     enc = model.encoder

@@ -4,6 +4,7 @@ Granularity follows the reference's modules so that every fusion the backward
 needs is local to one function:
   patch_embed    HilbertEmbedding1D / MortonEmbedding1D / RasterScan1DEmbedding / SFCEmbedding1D .forward
   mixer_block    MixerBlock.forward                     (src/models/vit.py:268-273)
+  token_aggregator TokenAggregator.forward              (src/models/vit.py:37-42)
   encoder_layer  nn.TransformerEncoderLayer, post-norm  (torch:nn/modules/transformer.py:951-982)
   predictor_head MultiLayerPredictor(n_layers=2)        (src/models/vit.py:295-319)
   linear, layer_norm, gelu                              generic pieces
@@ -479,6 +480,93 @@ def mixer_block(x, ln_w, ln_b, w1, b1, w2, b2, eps=1e-5):
 
 
 # ----------------------------------------------------------------------------
+def _dw_slots(w, b):
+    """out for ops.dwconv1d_bwd: (dw slot, db slot) when both parameters have one, else None."""
+    sw, sb = _slot(w), _slot(b)
+    return (sw, sb) if sw is not None and sb is not None else None
+
+
+def _dw_grads(dw, db, slots):
+    return (dw, db) if slots is not None else (dw.to(_BF16), db.to(_BF16) if db is not None else None)
+
+
+class _DwConv1d(Function):
+    """Depth-wise nn.Conv1d(D, D, k, stride, padding=k // 2, groups=D) on [B, N, D], D contiguous: no transposes."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, stride):
+        x = _c(x)
+        ctx.save_for_backward(x, w)
+        ctx.small, ctx.stride = (b,), stride
+        return ops.dwconv1d_fwd(x, w, b, stride)
+
+    @staticmethod
+    def backward(ctx, du):
+        x, w = ctx.saved_tensors
+        b = ctx.small[0]
+        slots = _dw_slots(w, b) if b is not None else None
+        dx, dw, db = ops.dwconv1d_bwd(_c(du), x, w, ctx.stride, want_dx=ctx.needs_input_grad[0], want_db=b is not None, out=slots)
+        return (dx, *_dw_grads(dw, db, slots), None)
+
+
+def dwconv1d(x, weight, bias=None, stride=1):
+    """x [B, N, D] -> [B, Nout, D] bf16; weight is the Conv1d parameter [D, 1, k] (or [D, k]), bias [D] or None."""
+    return _DwConv1d.apply(_bf(x), _c(_bf(weight)), _bf(bias), int(stride))
+
+
+class _TokenAggregator(Function):
+    """LN(gelu(pw(dw(x)))): TokenAggregator.forward (src/models/vit.py:37-42) without its two transposes -- the depth-wise
+    conv kernel on [B, N, D], the point-wise Conv1d as a GEMM, GELU with the pre-activation kept (the fast-shape split of
+    _Mixer), LayerNorm."""
+
+    @staticmethod
+    def forward(ctx, x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride, eps):
+        x = _c(x)
+        B, _, D = x.shape
+        u = ops.dwconv1d_fwd(x, dw_w, dw_b, stride)
+        u2 = u.view(-1, D)
+        pw2 = pw_w.view(D, D)
+        if _fast_gemm_shape(u2.shape[0], D, D):
+            v = ops.gemm(u2, pw2, bias=pw_b)
+            g = ops.gelu_fwd(v)
+        else:
+            g, v = ops.gemm(u2, pw2, bias=pw_b, act=ops.ACT_GELU, want_aux=True)
+        y, mean, rstd = ops.layernorm_fwd(g, ln_w, ln_b, eps)
+        ctx.save_for_backward(x, u2, v, g, mean, rstd, dw_w, pw_w, ln_w)
+        ctx.small, ctx.stride = (dw_b, pw_b, ln_b), stride
+        return y.view(B, -1, D)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, u2, v, g, mean, rstd, dw_w, pw_w, ln_w = ctx.saved_tensors
+        dw_b, pw_b, ln_b = ctx.small
+        B, _, D = x.shape
+        dy2 = _c(dy).view(-1, D)
+        go = _ln_slots(ln_w, ln_b)
+        dgl, dgam, dbeta = ops.layernorm_bwd(dy2, g, mean, rstd, ln_w, grad_out=go)
+        dv = ops.gelu_bwd(dgl, v)
+        spw = _slot(pw_w)                                     # the Conv1d weight [D, D, 1]: its slot is the [D, D] matrix
+        dpw = ops.gemm(dv, u2, a_kmajor=True, b_kmajor=True, out=None if spw is None else spw.view(D, D))
+        dpw = spw if spw is not None else dpw.view(pw_w.shape)
+        dpb = _bgrad(dv, pw_b)
+        du = ops.gemm_dx(dv, pw_w.view(D, D)).view(B, -1, D)
+        slots = _dw_slots(dw_w, dw_b)
+        want_dx = getattr(ctx, "needs_input_grad", (True,))[0]
+        dx, ddw, ddb = ops.dwconv1d_bwd(du, x, dw_w, ctx.stride, want_dx=want_dx, out=slots)
+        return (dx, *_dw_grads(ddw, ddb, slots), dpw, dpb, *_ln_grads(dgam, dbeta, go), None, None)
+
+
+def token_aggregator(x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride=1, eps=1e-5):
+    """TokenAggregator (src/models/vit.py:20-42) on x [B, N, D]: depth-wise Conv1d (dw_w [D, 1, k], padding k // 2, stride)
+    -> point-wise Conv1d (pw_w [D, D, 1]) -> erf-GELU -> LayerNorm.  -> [B, Nout, D] bf16."""
+    args = (_bf(x), _c(_bf(dw_w)), _bf(dw_b), _c(_bf(pw_w)), _bf(pw_b), _bf(ln_w), _bf(ln_b))
+    if _traced():
+        from . import library
+        return library.token_aggregator(*args, int(stride), float(eps))
+    return _TokenAggregator.apply(*args, int(stride), float(eps))
+
+
+# ----------------------------------------------------------------------------
 class _EncoderLayer(Function):
     """Post-norm transformer encoder layer (torch:nn/modules/transformer.py:951-982):
          a  = out_proj(attention(in_proj(x)));  x1 = LN1(x + drop1(a))
@@ -736,12 +824,12 @@ def mixed_target_cross_entropy(logits, y_a, y_b, mix):
 
 # ----------------------------------------------------------------------------
 # torch.compile (main.py:284 wraps the model in torch.compile(mode="reduce-overhead")).  The blocks a VisionTransformer{,1D}
-# is made of -- patch_embed, mixer_block, encoder_layer, predictor_head, soft_target_cross_entropy -- are registered as
+# is made of -- patch_embed, token_aggregator, mixer_block, encoder_layer, predictor_head, soft_target_cross_entropy -- are registered as
 # `sfcvit::` custom ops with fake kernels and autograd formulas (sfcvit/library.py) and take that path whenever Dynamo is
 # tracing: the model compiles into ONE graph and "reduce-overhead" replays it from a hipGraph.  The remaining pieces
 # (used by the hierarchical tokenizers, altvit and MultiLayerPredictor(n_layers > 2)) stay opaque: Dynamo breaks the graph
 # around each and runs it as written.
 # ----------------------------------------------------------------------------
-for _name in ("mixed_target_cross_entropy", "hier_tokenizer", "linear", "layer_norm", "gelu", "gelu_dropout", "attention"):
+for _name in ("mixed_target_cross_entropy", "hier_tokenizer", "linear", "layer_norm", "gelu", "gelu_dropout", "attention", "dwconv1d"):
     globals()[_name] = torch.compiler.disable(globals()[_name], recursive=True)
 del _name

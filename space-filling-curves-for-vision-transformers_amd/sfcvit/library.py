@@ -235,6 +235,61 @@ mixer_block_op.register_autograd(_mixer_backward, setup_context=_mixer_setup)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# token_aggregator (TokenAggregator: depth-wise conv along the sequence -> point-wise -> GELU -> LayerNorm)
+# ----------------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("sfcvit::token_aggregator", mutates_args=())
+def token_aggregator_op(x: Tensor, dw_w: Tensor, dw_b: Tensor, pw_w: Tensor, pw_b: Tensor, ln_w: Tensor, ln_b: Tensor, stride: int,
+                        eps: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    ctx = _Ctx()
+    y = F._TokenAggregator.forward(ctx, x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride, eps)
+    _, u2, v, g, mean, rstd = ctx.saved_tensors[:6]
+    return y, u2, v, g, mean, rstd
+
+
+@token_aggregator_op.register_fake
+def _(x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride, eps):
+    B, N, D = x.shape
+    k = dw_w.shape[-1]
+    n_out = (N + 2 * (k // 2) - k) // stride + 1
+    M = B * n_out
+    bf = lambda *s: x.new_empty(s, dtype=_BF16)              # noqa: E731
+    f32 = lambda *s: x.new_empty(s, dtype=torch.float32)      # noqa: E731
+    return bf(B, n_out, D), bf(M, D), bf(M, D), bf(M, D), f32(M), f32(M)
+
+
+@torch.library.custom_op("sfcvit::token_aggregator_bwd", mutates_args=())
+def token_aggregator_bwd_op(dy: Tensor, x: Tensor, u2: Tensor, v: Tensor, g: Tensor, mean: Tensor, rstd: Tensor, dw_w: Tensor,
+                            pw_w: Tensor, ln_w: Tensor, stride: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    ctx = _Ctx()
+    ctx.saved_tensors = (F._c(x), u2, v, g, mean, rstd, dw_w, pw_w, ln_w)
+    ctx.small, ctx.stride = (None, None, None), stride        # (no gradient slots inside a traced op: fresh tensors)
+    with _no_slots():
+        return tuple(F._TokenAggregator.backward(ctx, dy)[:7])
+
+
+@token_aggregator_bwd_op.register_fake
+def _(dy, x, u2, v, g, mean, rstd, dw_w, pw_w, ln_w, stride):
+    ne = lambda t: t.new_empty(t.shape)                       # noqa: E731
+    D = x.shape[-1]
+    return ne(x), ne(dw_w), dw_w.new_empty(D), ne(pw_w), pw_w.new_empty(D), ne(ln_w), ne(ln_w)
+
+
+def _ta_setup(ctx, inputs, output):
+    x, dw_w, _, pw_w, _, ln_w, _, stride, _ = inputs
+    ctx.save_for_backward(x, *output[1:], dw_w, pw_w, ln_w)
+    ctx.stride = stride
+    ctx.set_materialize_grads(False)
+
+
+def _ta_backward(ctx, dy, *_):
+    x, u2, v, g, mean, rstd, dw_w, pw_w, ln_w = ctx.saved_tensors
+    return (*torch.ops.sfcvit.token_aggregator_bwd(dy.contiguous(), x, u2, v, g, mean, rstd, dw_w, pw_w, ln_w, ctx.stride), None, None)
+
+
+token_aggregator_op.register_autograd(_ta_backward, setup_context=_ta_setup)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # encoder_layer (post-norm nn.TransformerEncoderLayer; seeds = [] -> drawn inside the op when p > 0)
 # ----------------------------------------------------------------------------------------------------------------------
 _ENC_SAVED = 12     # qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2 (+ hbits, seeds below)
@@ -424,6 +479,10 @@ def mix_images(x, mix):
 
 def mixer_block(x, ln_w, ln_b, w1, b1, w2, b2, eps):
     return torch.ops.sfcvit.mixer_block(x, ln_w, ln_b, w1, b1, w2, b2, eps)[0]
+
+
+def token_aggregator(x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride, eps):
+    return torch.ops.sfcvit.token_aggregator(x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride, eps)[0]
 
 
 def encoder_layer(args, n_heads, eps, p, scale):

@@ -17,6 +17,43 @@ from .. import functional as F
 from ..tokenizers.base_patch_embedding import BasePatchEmbedding
 
 
+class TokenAggregator(nn.Module):
+    """vit.py:20-42: depth-wise Conv1d(dim, dim, k, s, padding=k//2, groups=dim) along the token sequence, point-wise
+    Conv1d, erf-GELU, LayerNorm.  A k-tap window over neighbours in curve order: with a Hilbert tokenizer it covers a
+    2-D neighbourhood, with a raster one a row segment.  The reference transposes to [B, D, N] around the convolutions;
+    here the activation stays [B, N, D] (F.token_aggregator)."""
+
+    def __init__(self, dim: int, k: int = 3, s: int = 1):
+        super().__init__()
+        self.dw = nn.Conv1d(dim, dim, k, s, padding=k // 2, groups=dim)
+        self.pw = nn.Conv1d(dim, dim, 1, 1)
+        self.act = nn.GELU()
+        self.norm = nn.LayerNorm(dim)
+
+    def forward(self, x):
+        return F.token_aggregator(x, self.dw.weight, self.dw.bias, self.pw.weight, self.pw.bias, self.norm.weight,
+                                  self.norm.bias, stride=self.dw.stride[0], eps=self.norm.eps)
+
+
+def _make_aggregator(option, embed_dim):
+    """The models' `token_aggregator` keyword: False / None = none (the reference as shipped), True = the reference's
+    default kernel size 3, an int = that kernel size.  Inside a model the token count must not change: odd k only."""
+    if option is None or option is False:
+        return None
+    k = 3 if option is True else int(option)
+    if k < 1 or k % 2 == 0:
+        raise ValueError(f"token_aggregator={option!r}: the kernel size must be odd (an even one changes the token count)")
+    return TokenAggregator(embed_dim, k)
+
+
+def _attach_aggregator(model, option, embed_dim):
+    """`self.ta = TokenAggregator(embed_dim)` (vit.py:362, commented out there), on request only and constructed LAST: every
+    other parameter then draws the same initial values as without it, and the default module tree is today's."""
+    ta = _make_aggregator(option, embed_dim)
+    if ta is not None:
+        model.ta = ta
+
+
 class TransformerSeqEncoder(nn.Module):
     """vit.py:177-242: `depth` post-norm nn.TransformerEncoderLayer (relu, eps 1e-5)."""
 
@@ -133,7 +170,7 @@ class VisionTransformer(nn.Module):
     """vit.py:325-385 (`embed_dim` is ignored there too: taken from the tokenizer, :351)."""
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
-                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5):
+                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False):
         super().__init__()
         self.patch_embed = patch_embed
         embed_dim = patch_embed.embed_dim
@@ -142,10 +179,13 @@ class VisionTransformer(nn.Module):
                                              n_layers=depth, dropout_p=dropout_p)
         self.mlp_head = MultiLayerPredictor(embed_dim, self.patch_embed.n_patches, n_layers=2,
                                             num_classes=num_classes, dropout_p=head_dropout_p)
+        _attach_aggregator(self, token_aggregator, embed_dim)
 
     def forward(self, x, mix=None):
         """mix: a sfcvit.training.BatchMix applied to the image batch by the tokenizer, or None."""
         x = self.patch_embed(x) if mix is None else self.patch_embed(x, mix=mix)
+        if hasattr(self, "ta"):
+            x = self.ta(x)                                      # vit.py:381
         x = self.encoder(x)
         return self.mlp_head(x)
 
@@ -154,7 +194,7 @@ class VisionTransformer1D(nn.Module):
     """vit.py:392-458: tokenizer -> channel-mix block -> encoder stack -> factorised head."""
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
-                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5):
+                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False):
         super().__init__()
         self.patch_embed = patch_embed
         embed_dim = patch_embed.embed_dim
@@ -165,10 +205,13 @@ class VisionTransformer1D(nn.Module):
                                              method=self.patch_embed, dropout_p=dropout_p)
         self.mlp_head = MultiLayerPredictor(embed_dim, self.patch_embed.n_patches, n_layers=2,
                                             dropout_p=head_dropout_p, num_classes=num_classes)
+        _attach_aggregator(self, token_aggregator, embed_dim)
 
     def forward(self, x, mix=None):
         """mix: a sfcvit.training.BatchMix applied to the image batch by the tokenizer, or None."""
         x = self.patch_embed(x) if mix is None else self.patch_embed(x, mix=mix)
+        if hasattr(self, "ta"):
+            x = self.ta(x)
         x = self.mlp_mixer(x)
         x = self.encoder(x)
         return self.mlp_head(x)

@@ -796,6 +796,70 @@ def hier_tokenizer_fwd(x, pix_list, w_list, b_list, wf, bf):
 
 
 # ----------------------------------------------------------------------------
+# depth-wise conv1d along the token sequence (TokenAggregator.dw)
+# ----------------------------------------------------------------------------
+def last_dwconv_kernel():
+    buf = ctypes.create_string_buffer(96)
+    lib.sfcvit_last_dwconv_kernel(buf, 96)
+    return buf.value.decode()
+
+
+def dwconv1d_out_len(N, k, stride=1):
+    n = lib.sfcvit_dwconv1d_out_len(N, k, stride)
+    if n < 0:
+        check(1, "sfcvit_dwconv1d_out_len")
+    return n
+
+
+def _dw_weight(w, D):
+    """[D, k] or nn.Conv1d's [D, 1, k], contiguous bf16 -> k."""
+    if w.dim() not in (2, 3) or w.shape[0] != D or (w.dim() == 3 and w.shape[1] != 1):
+        raise ValueError(f"dwconv1d weight: [{D}, k] or [{D}, 1, k] expected, got {tuple(w.shape)}")
+    _need(w, _BF16, "dwconv1d weight")
+    return w.shape[-1]
+
+
+def dwconv1d_fwd(x, w, bias=None, stride=1):
+    """u[b, n, d] = bias[d] + sum_t w[d, t] x[b, n * stride + t - k // 2, d] on x [B, N, D] bf16 -> [B, Nout, D] bf16."""
+    _need(x, _BF16, "dwconv1d x", 3)
+    B, N, D = x.shape
+    k = _dw_weight(w, D)
+    if bias is not None and _need(bias, _BF16, "dwconv1d bias", 1).numel() != D:
+        raise ValueError(f"dwconv1d bias: [{D}] expected")
+    u = torch.empty((B, dwconv1d_out_len(N, k, stride), D), device=x.device, dtype=_BF16)
+    _launch("dwconv1d_fwd", 2.0 * x.numel() + 2.0 * u.numel(),
+            lambda: check(lib.sfcvit_dwconv1d_fwd(_p(x), _p(w), _p(bias), _p(u), B, N, D, k, stride, _stream()), "sfcvit_dwconv1d_fwd"))
+    return u
+
+
+def dwconv1d_bwd(du, x, w, stride=1, want_dx=True, want_dw=True, want_db=True, out=None):
+    """-> (dx [B, N, D] bf16, dw like w, db [D]); entries not wanted are None.  dw / db are fp32, or -- with
+    out = (dw, db) contiguous bf16 tensors, e.g. views of a flat gradient buffer (None entries are allocated) -- written
+    as bf16 in place."""
+    _need(du, _BF16, "dwconv1d du", 3)
+    _need(x, _BF16, "dwconv1d x", 3)
+    B, N, D = x.shape
+    k = _dw_weight(w, D)
+    if tuple(du.shape) != (B, dwconv1d_out_len(N, k, stride), D):
+        raise ValueError(f"dwconv1d du: shape {tuple(du.shape)} does not belong to x {tuple(x.shape)}, k={k}, stride={stride}")
+    gdt = torch.float32 if out is None else _BF16
+    given = (None, None) if out is None else out
+    for t, n in zip(given, (D * k, D)):
+        if t is not None and (t.dtype != _BF16 or t.numel() != n or not t.is_contiguous()):
+            raise ValueError("dwconv1d_bwd out: contiguous bf16 tensors of the weight's / bias's size expected")
+    dx = torch.empty_like(x) if want_dx else None
+    dw = (given[0] if given[0] is not None else torch.empty(w.shape, device=x.device, dtype=gdt)) if want_dw else None
+    db = (given[1] if given[1] is not None else torch.empty(D, device=x.device, dtype=gdt)) if want_db else None
+    nbytes = lib.sfcvit_dwconv1d_bwd_workspace(B, N, D, k, stride) if (want_dw or want_db) else 0
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if nbytes else None
+    with _Deferring([t for t in (dw, db) if t is not None], [ws]):
+        _launch("dwconv1d_bwd", 4.0 * x.numel() + 4.0 * du.numel() + 2.0 * nbytes,
+                lambda: check(lib.sfcvit_dwconv1d_bwd(_p(du), _p(x), _p(w), _p(dx), _p(dw), _p(db), int(gdt == _BF16), B, N, D, k, stride,
+                                                      _p(ws), nbytes, _stream()), "sfcvit_dwconv1d_bwd"))
+    return dx, dw, db
+
+
+# ----------------------------------------------------------------------------
 # elementwise / loss / optimizer
 # ----------------------------------------------------------------------------
 def gelu_fwd(x):
