@@ -534,6 +534,51 @@ int sfcvit_dwconv1d_bwd(const void *du, const void *x, const void *w, void *dx, 
 int sfcvit_last_dwconv_kernel(char *buf, int n);
 
 /* ------------------------------------------------------------------------
+ * Token mixing: GEMMs along the token axis of [B, N, D]
+ *   replaces the token-mix branch of MixerBlock.forward (src/models/vit.py:269-271, commented out there):
+ *       x = x + token_mix(token_mix_ln(x).transpose(1, 2)).transpose(1, 2)
+ *   with token_mix = Linear(N, hid) -> GELU -> Linear(hid, N) (src/models/vit.py:259-263).  The activation stays
+ *   [B, N, D] bf16 with D contiguous and the hidden tensor is [B, hid, D]: neither transposed copy exists.  Every
+ *   image's matrix is multiplied from the LEFT by a weight shared across the batch; a tile never crosses an image.
+ *
+ *   Supported: B >= 1, M >= 1, K >= 1, D % 8 == 0, and M % 8 == 0 or K % 8 == 0 (one of the two is the hidden width,
+ *   the other the token count, which may be anything: 196, 27, 1); everything else is SFCVIT_EINVAL, decided before
+ *   any HIP call.  x, c, bias-free activations (residual, aux_in, aux_out, g) and the workspace must be 16-byte
+ *   aligned; w, bias, dw, db need 2-byte alignment only (rows of a [hid, N] weight are 2 N bytes: the weight loader
+ *   uses the widest load the row pitch and the pointer allow).  Ragged M, K and D tails are zero-filled on load and
+ *   masked on store.  Nothing allocates, synchronises or copies to the host: graph-capturable.
+ * ---------------------------------------------------------------------- */
+typedef struct sfcvit_tokmix_args {
+    const void *w;        /* bf16, dense: [M, K] (k contiguous), or [K, M] when w_transposed != 0 */
+    const void *x;        /* bf16 [B, K, D] */
+    void *c;              /* bf16 [B, M, D] */
+    const void *bias;     /* bf16 [M] or NULL: a ROW bias */
+    const void *residual; /* bf16 [B, M, D] or NULL */
+    const void *aux_in;   /* bf16 [B, M, D] or NULL: the result is multiplied by gelu'(aux_in) */
+    void *aux_out;        /* bf16 [B, M, D] or NULL: the value before the activation */
+    int32_t B, M, K, D;
+    int32_t w_transposed;
+    int32_t act;          /* SFCVIT_ACT_NONE or SFCVIT_ACT_GELU (erf form) */
+} sfcvit_tokmix_args;
+/* C_b[M, D] = epi( op(W) X_b[K, D] ) for b = 0 .. B-1, fp32 accumulation, epilogue in fp32 in this order:
+ *   v += bias[m];  aux_out = bf16(v);  v = gelu(v);  v += residual[b, m, d];  v *= gelu'(aux_in[b, m, d]);  store bf16.
+ * The four jobs of the block: fc1 (W1, z -> U, H), fc2 (W2, H, residual x), dH = W2^T dy with the gelu'(U) factor
+ * (-> dU), dz = W1^T dU. */
+int sfcvit_tokmix_left(const sfcvit_tokmix_args *a, void *stream);
+/* HOST: workspace bytes of sfcvit_tokmix_wgrad (0 for refused arguments). */
+int64_t sfcvit_tokmix_wgrad_workspace(int B, int M, int K, int D);
+/* dW[M, K] = sum_b G_b[M, D] X_b[K, D]^T and db[m] = sum_{b, d} G_b[m, d]; g [B, M, D], x [B, K, D] bf16.  The
+ * contraction runs over (b, d): ranges of whole images write fp32 partials into the workspace, the library's ordered
+ * column reduction adds them (no atomics: two runs, same bits) and joins the deferred reductions when deferral is on.
+ * dw / db are fp32, or bf16 when grads_bf16 != 0 (views of a flat gradient buffer); either may be NULL = skipped
+ * (not both). */
+int sfcvit_tokmix_wgrad(const void *g, const void *x, void *dw, void *db, int grads_bf16, int B, int M, int K, int D,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+/* HOST: name of the main kernel the calling thread's last sfcvit_tokmix_left / _wgrad launched, as rocprofv3 prints it
+ * (e.g. "tokmix_left_kernel<false, true>"). */
+int sfcvit_last_tokmix_kernel(char *buf, int n);
+
+/* ------------------------------------------------------------------------
  * Elementwise / loss / optimizer
  * ---------------------------------------------------------------------- */
 /* y = gelu_erf(x) (nn.GELU in MultiLayerPredictor, vit.py:308); bf16, n elements. */

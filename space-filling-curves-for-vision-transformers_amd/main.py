@@ -111,6 +111,9 @@ def main():
                     help="apply the reference's TokenAggregator (src/models/vit.py:20-42: depth-wise conv of K taps along the "
                          "curve, point-wise conv, GELU, LayerNorm) directly after the tokenizer; K odd, default 3.  Checkpoints "
                          "then carry the ta.* keys")
+    ap.add_argument("--token-mix", action="store_true",
+                    help="switch the MixerBlock's token-mix branch on (src/models/vit.py:269-271, commented out in the "
+                         "reference): a learned mixing along the curve in front of the channel mix.  Checkpoints keep their keys")
     ap.add_argument("--mean", type=float, nargs=3, default=[0.4914, 0.4822, 0.4465])      # main.py:176-177 (CIFAR)
     ap.add_argument("--std", type=float, nargs=3, default=[0.2023, 0.1994, 0.2010])
     a = ap.parse_args()
@@ -162,7 +165,7 @@ def main():
     patch_embed = build_tokenizer(a)
     model = VisionTransformer1D(patch_embed=patch_embed, depth=a.depth, n_heads=a.heads, mlp_dim=a.mlp_dim,
                                 num_classes=a.classes,
-                                token_aggregator=a.token_aggregator or False).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
+                                token_aggregator=a.token_aggregator or False, token_mix=a.token_mix).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
     train_criterion, test_criterion = SoftTargetCrossEntropy(), nn.CrossEntropyLoss()
     optimizer = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=1.0)
     reducer = GradReducer(optimizer, overlap=not a.graph) if world > 1 else None    # --graph: collectives between two graphs

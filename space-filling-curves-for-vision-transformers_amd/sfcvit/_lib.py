@@ -58,6 +58,12 @@ class AttnProbeArgs(ctypes.Structure):
                 ("mass_rows", c_void_p)]
 
 
+class TokmixArgs(ctypes.Structure):
+    _fields_ = [("w", c_void_p), ("x", c_void_p), ("c", c_void_p), ("bias", c_void_p), ("residual", c_void_p),
+                ("aux_in", c_void_p), ("aux_out", c_void_p),
+                ("B", c_int32), ("M", c_int32), ("K", c_int32), ("D", c_int32), ("w_transposed", c_int32), ("act", c_int32)]
+
+
 class AdamWArgs(ctypes.Structure):
     _fields_ = [("param", c_void_p), ("master", c_void_p), ("grad", c_void_p), ("m", c_void_p),
                 ("v", c_void_p), ("sumsq", c_void_p), ("n", c_int64),
@@ -144,6 +150,11 @@ SIGNATURES = {
     "sfcvit_dwconv1d_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_void_p, c_int64, c_void_p]),
     "sfcvit_last_dwconv_kernel": (c_int, [ctypes.c_char_p, c_int]),
+    "sfcvit_tokmix_left": (c_int, [ctypes.POINTER(TokmixArgs), c_void_p]),
+    "sfcvit_tokmix_wgrad_workspace": (c_int64, [c_int, c_int, c_int, c_int]),
+    "sfcvit_tokmix_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64,
+                                    c_void_p]),
+    "sfcvit_last_tokmix_kernel": (c_int, [ctypes.c_char_p, c_int]),
     "sfcvit_gelu_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "sfcvit_gelu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sfcvit_soft_ce": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -4,6 +4,7 @@ Granularity follows the reference's modules so that every fusion the backward
 needs is local to one function:
   patch_embed    HilbertEmbedding1D / MortonEmbedding1D / RasterScan1DEmbedding / SFCEmbedding1D .forward
   mixer_block    MixerBlock.forward                     (src/models/vit.py:268-273)
+  token_mix      its token-mix branch                   (src/models/vit.py:269-271)
   token_aggregator TokenAggregator.forward              (src/models/vit.py:37-42)
   encoder_layer  nn.TransformerEncoderLayer, post-norm  (torch:nn/modules/transformer.py:951-982)
   predictor_head MultiLayerPredictor(n_layers=2)        (src/models/vit.py:295-319)
@@ -472,7 +473,76 @@ class _Mixer(Function):
         return (dx.view(dy.shape), *_ln_grads(dg, dbeta, go), dw1, db1, dw2, db2, None)
 
 
-def mixer_block(x, ln_w, ln_b, w1, b1, w2, b2, eps=1e-5):
+def _pair_slots(w, b):
+    """out for ops.tokmix_wgrad: (dw slot, db slot) when both parameters have one, else None."""
+    sw, sb = _slot(w), _slot(b)
+    return (sw, sb) if sw is not None and sb is not None else None
+
+
+class _TokenMix(Function):
+    """x + (W2 gelu(W1 LN(x) + b1) + b2) with the Linears applied along the TOKEN axis: the token-mix branch of MixerBlock
+    (src/models/vit.py:269-271) on [B, N, D] as it lies in memory.  W1 [hid, N] and W2 [N, hid] multiply every image's
+    [N, D] / [hid, D] matrix from the left (ops.tokmix_left); the biases are row biases; neither the activation nor the
+    hidden tensor [B, hid, D] is ever transposed.  Saved for backward: z = LN(x), the pre-activation U and H = gelu(U)."""
+
+    @staticmethod
+    def forward(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps):
+        x = _c(x)
+        B, N, D = x.shape
+        x2 = x.view(B * N, D)
+        z, mean, rstd = ops.layernorm_fwd(x2, ln_w, ln_b, eps)
+        h, u = ops.tokmix_left(w1, z.view(B, N, D), bias=b1, act=ops.ACT_GELU, want_aux=True)
+        y = ops.tokmix_left(w2, h, bias=b2, residual=x)
+        ctx.save_for_backward(x2, mean, rstd, z, u, h, ln_w, w1, w2)
+        ctx.small = (ln_b, b1, b2)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, mean, rstd, z, u, h, ln_w, w1, w2 = ctx.saved_tensors
+        ln_b, b1, b2 = ctx.small
+        dy = _c(dy)
+        B, N, D = dy.shape
+        s2 = _pair_slots(w2, b2)
+        dw2, db2 = ops.tokmix_wgrad(dy, h, out=s2)                           # dW2 = sum_b dy_b H_b^T, db2 = row sums of dy
+        du = ops.tokmix_left(w2, dy, transposed=True, aux_in=u)             # dU = (W2^T dy) * gelu'(U)
+        s1 = _pair_slots(w1, b1)
+        dw1, db1 = ops.tokmix_wgrad(du, z.view(B, N, D), out=s1)
+        dz = ops.tokmix_left(w1, du, transposed=True)                       # dz = W1^T dU
+        go = _ln_slots(ln_w, ln_b)
+        dx, dg, dbeta = ops.layernorm_bwd(dz.view(B * N, D), x2, mean, rstd, ln_w, dx_add=dy.view(B * N, D), grad_out=go)
+        if s1 is None:
+            dw1, db1 = dw1.to(_BF16), db1.to(_BF16)
+        if s2 is None:
+            dw2, db2 = dw2.to(_BF16), db2.to(_BF16)
+        return (dx.view(B, N, D), *_ln_grads(dg, dbeta, go), dw1, db1, dw2, db2, None)
+
+
+def token_mix(x, ln_w, ln_b, w1, b1, w2, b2, eps=1e-5):
+    """The token-mix branch of MixerBlock (src/models/vit.py:269-271) on x [B, N, D]:
+    x + fc2(gelu(fc1(LN(x)^T)))^T with fc1 = Linear(N, hid) (w1 [hid, N]), fc2 = Linear(hid, N) (w2 [N, hid]) -> [B, N, D]
+    bf16.  Any N; D and hid multiples of 8."""
+    N, hid = x.shape[1], w1.shape[0]
+    if x.dim() != 3 or tuple(w1.shape) != (hid, N) or tuple(w2.shape) != (N, hid):
+        raise ValueError(f"token_mix: x {tuple(x.shape)} needs w1 [hid, {N}] and w2 [{N}, hid], got {tuple(w1.shape)} and "
+                         f"{tuple(w2.shape)}: the token count is fixed by the weights")
+    if hid % 8 or x.shape[2] % 8:
+        raise ValueError(f"token_mix: hidden width {hid} and embedding width {x.shape[2]} must be multiples of 8")
+    args = (_bf(x), _bf(ln_w), _bf(ln_b), _c(_bf(w1)), _bf(b1), _c(_bf(w2)), _bf(b2))
+    if _traced():
+        from . import library
+        return library.token_mix(*args, float(eps))
+    return _TokenMix.apply(*args, float(eps))
+
+
+_token_mix = token_mix        # (mixer_block's keyword has the function's name)
+
+
+def mixer_block(x, ln_w, ln_b, w1, b1, w2, b2, eps=1e-5, token_mix=None):
+    """MixerBlock.forward (src/models/vit.py:268-273).  token_mix = None: the channel-mix branch alone (the reference as
+    shipped); (ln_w, ln_b, w1, b1, w2, b2) of the token-mix branch: that branch first (vit.py:269-271), same eps."""
+    if token_mix is not None:
+        x = _token_mix(x, *token_mix, eps=eps)
     if _traced():
         from . import library
         return library.mixer_block(_bf(x), _bf(ln_w), _bf(ln_b), _bf(w1), _bf(b1), _bf(w2), _bf(b2), eps)
@@ -824,7 +894,7 @@ def mixed_target_cross_entropy(logits, y_a, y_b, mix):
 
 # ----------------------------------------------------------------------------
 # torch.compile (main.py:284 wraps the model in torch.compile(mode="reduce-overhead")).  The blocks a VisionTransformer{,1D}
-# is made of -- patch_embed, token_aggregator, mixer_block, encoder_layer, predictor_head, soft_target_cross_entropy -- are registered as
+# is made of -- patch_embed, token_aggregator, token_mix, mixer_block, encoder_layer, predictor_head, soft_target_cross_entropy -- are registered as
 # `sfcvit::` custom ops with fake kernels and autograd formulas (sfcvit/library.py) and take that path whenever Dynamo is
 # tracing: the model compiles into ONE graph and "reduce-overhead" replays it from a hipGraph.  The remaining pieces
 # (used by the hierarchical tokenizers, altvit and MultiLayerPredictor(n_layers > 2)) stay opaque: Dynamo breaks the graph

@@ -235,6 +235,57 @@ mixer_block_op.register_autograd(_mixer_backward, setup_context=_mixer_setup)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# token_mix (the token-mix branch of MixerBlock: LayerNorm -> Linear along the token axis -> GELU -> Linear -> + x)
+# ----------------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("sfcvit::token_mix", mutates_args=())
+def token_mix_op(x: Tensor, ln_w: Tensor, ln_b: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor,
+                 eps: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    ctx = _Ctx()
+    y = F._TokenMix.forward(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps)
+    _, mean, rstd, z, u, h = ctx.saved_tensors[:6]
+    return y, mean, rstd, z, u, h
+
+
+@token_mix_op.register_fake
+def _(x, ln_w, ln_b, w1, b1, w2, b2, eps):
+    B, N, D = x.shape
+    f32 = lambda *s: x.new_empty(s, dtype=torch.float32)      # noqa: E731
+    hid = w1.shape[0]
+    return (x.new_empty((B, N, D)), f32(B * N), f32(B * N), x.new_empty((B * N, D)), x.new_empty((B, hid, D)),
+            x.new_empty((B, hid, D)))
+
+
+@torch.library.custom_op("sfcvit::token_mix_bwd", mutates_args=())
+def token_mix_bwd_op(dy: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, z: Tensor, u: Tensor, h: Tensor, ln_w: Tensor,
+                     w1: Tensor, w2: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    ctx = _Ctx()
+    ctx.saved_tensors = (F._c(x).view(-1, x.shape[-1]), mean, rstd, z, u, h, ln_w, w1, w2)
+    ctx.small = (None, None, None)                      # (no gradient slots inside a traced op: fresh tensors)
+    with _no_slots():
+        return tuple(F._TokenMix.backward(ctx, dy)[:7])
+
+
+@token_mix_bwd_op.register_fake
+def _(dy, x, mean, rstd, z, u, h, ln_w, w1, w2):
+    ne = lambda t: t.new_empty(t.shape)                       # noqa: E731
+    return ne(x), ne(ln_w), ne(ln_w), ne(w1), w1.new_empty(w1.shape[0]), ne(w2), w2.new_empty(w2.shape[0])
+
+
+def _tokmix_setup(ctx, inputs, output):
+    x, ln_w, _, w1, _, w2, _, _ = inputs
+    ctx.save_for_backward(x, *output[1:], ln_w, w1, w2)
+    ctx.set_materialize_grads(False)
+
+
+def _tokmix_backward(ctx, dy, *_):
+    x, mean, rstd, z, u, h, ln_w, w1, w2 = ctx.saved_tensors
+    return (*torch.ops.sfcvit.token_mix_bwd(dy.contiguous(), x, mean, rstd, z, u, h, ln_w, w1, w2), None)
+
+
+token_mix_op.register_autograd(_tokmix_backward, setup_context=_tokmix_setup)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # token_aggregator (TokenAggregator: depth-wise conv along the sequence -> point-wise -> GELU -> LayerNorm)
 # ----------------------------------------------------------------------------------------------------------------------
 @torch.library.custom_op("sfcvit::token_aggregator", mutates_args=())
@@ -479,6 +530,10 @@ def mix_images(x, mix):
 
 def mixer_block(x, ln_w, ln_b, w1, b1, w2, b2, eps):
     return torch.ops.sfcvit.mixer_block(x, ln_w, ln_b, w1, b1, w2, b2, eps)[0]
+
+
+def token_mix(x, ln_w, ln_b, w1, b1, w2, b2, eps):
+    return torch.ops.sfcvit.token_mix(x, ln_w, ln_b, w1, b1, w2, b2, eps)[0]
 
 
 def token_aggregator(x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride, eps):

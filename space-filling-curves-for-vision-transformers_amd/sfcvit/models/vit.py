@@ -1,7 +1,7 @@
 """VisionTransformer / VisionTransformer1D on HIP kernels, drop-in for
 src/models/vit.py:177-458 of the reference: same constructor signatures, module
-tree and state_dict keys, including the unused token-mix
-parameters and the tokenizer registered a second time under `encoder`.
+tree and state_dict keys, including the token-mix
+parameters (unused unless token_mix=True) and the tokenizer registered a second time under `encoder`.
 
 Parameters live in stock torch containers (nn.Linear, nn.LayerNorm,
 nn.TransformerEncoder as a *parameter holder*: identical keys and identical
@@ -82,11 +82,14 @@ class TransformerSeqEncoder(nn.Module):
 
 
 class MixerBlock(nn.Module):
-    """vit.py:250-273: only the channel-mix branch is live; the token-mix parameters
-    exist (state_dict compatibility) and never receive a gradient."""
+    """vit.py:250-273.  token_mix=False (the reference as shipped, :269-271 commented out): only the channel-mix branch
+    is live; the token-mix parameters exist (state_dict compatibility) and never receive a gradient.  token_mix=True: the
+    token-mix branch runs first, x + token_mix(token_mix_ln(x)^T)^T along the token axis (F.token_mix, no transposes), and
+    its six parameters train like every other.  The parameters are the same either way: same keys, same seeded values."""
 
-    def __init__(self, seq_len, embed_dim, hidden_dim, out_dim):
+    def __init__(self, seq_len, embed_dim, hidden_dim, out_dim, token_mix=False):
         super().__init__()
+        self.seq_len, self.use_token_mix = seq_len, bool(token_mix)
         self.token_mix_ln = nn.LayerNorm(embed_dim)
         self.channel_mix_ln = nn.LayerNorm(embed_dim)
         self.token_mix = nn.Sequential(nn.Linear(seq_len, hidden_dim), nn.GELU(), nn.Linear(hidden_dim, seq_len))
@@ -94,7 +97,15 @@ class MixerBlock(nn.Module):
 
     def forward(self, x):
         ln, fc1, fc2 = self.channel_mix_ln, self.channel_mix[0], self.channel_mix[2]
-        return F.mixer_block(x, ln.weight, ln.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, ln.eps)
+        tm = None
+        if self.use_token_mix:
+            if x.shape[1] != self.seq_len:
+                raise ValueError(f"MixerBlock(token_mix=True) was built for {self.seq_len} tokens and got {x.shape[1]}: the "
+                                 "token-mix weights fix the token count (a stride-changing TokenAggregator in front of it "
+                                 "is not supported)")
+            tln, t1, t2 = self.token_mix_ln, self.token_mix[0], self.token_mix[2]
+            tm = (tln.weight, tln.bias, t1.weight, t1.bias, t2.weight, t2.bias)
+        return F.mixer_block(x, ln.weight, ln.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, ln.eps, token_mix=tm)
 
 
 class FactorisedLinear(nn.Module):
@@ -191,15 +202,17 @@ class VisionTransformer(nn.Module):
 
 
 class VisionTransformer1D(nn.Module):
-    """vit.py:392-458: tokenizer -> channel-mix block -> encoder stack -> factorised head."""
+    """vit.py:392-458: tokenizer -> channel-mix block -> encoder stack -> factorised head.  token_mix=True switches the
+    MixerBlock's token-mix branch on (vit.py:269-271, commented out in the reference): a learned mixing along the curve,
+    the only pre-encoder component that sees absolute position in curve order."""
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
-                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False):
+                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False):
         super().__init__()
         self.patch_embed = patch_embed
         embed_dim = patch_embed.embed_dim
         self.mlp_mixer = MixerBlock(seq_len=self.patch_embed.n_patches, embed_dim=embed_dim,
-                                    hidden_dim=embed_dim * 2, out_dim=embed_dim)
+                                    hidden_dim=embed_dim * 2, out_dim=embed_dim, token_mix=token_mix)
         self.encoder = TransformerSeqEncoder(input_dim=embed_dim, max_len=self.patch_embed.n_patches,
                                              n_head=n_heads, hidden_dim=mlp_dim, n_layers=depth,
                                              method=self.patch_embed, dropout_p=dropout_p)

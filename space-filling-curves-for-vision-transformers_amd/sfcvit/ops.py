@@ -860,6 +860,71 @@ def dwconv1d_bwd(du, x, w, stride=1, want_dx=True, want_dw=True, want_db=True, o
 
 
 # ----------------------------------------------------------------------------
+# token mixing: GEMMs along the token axis of [B, N, D] (MixerBlock.token_mix)
+# ----------------------------------------------------------------------------
+def last_tokmix_kernel():
+    buf = ctypes.create_string_buffer(96)
+    lib.sfcvit_last_tokmix_kernel(buf, 96)
+    return buf.value.decode()
+
+
+def tokmix_left(w, x, *, transposed=False, bias=None, act=ACT_NONE, residual=None, aux_in=None, want_aux=False, out=None):
+    """C_b = epi(op(W) X_b) for every image b: x [B, K, D] bf16 -> [B, M, D] bf16 with w [M, K] (or [K, M] with
+    transposed=True) shared across the batch.  Epilogue (sfcvit_tokmix_left): + bias[m] (a row bias), pre-activation
+    kept (want_aux), erf-GELU (act), + residual, * gelu'(aux_in).  Returns C, or (C, pre-activation) with want_aux."""
+    _need(x, _BF16, "tokmix_left x", 3)
+    _need(w, _BF16, "tokmix_left w", 2)
+    B, K, D = x.shape
+    M, Kw = (w.shape[1], w.shape[0]) if transposed else (w.shape[0], w.shape[1])
+    if Kw != K:
+        raise ValueError(f"tokmix_left: contraction mismatch: w {tuple(w.shape)} (transposed={transposed}) against x {tuple(x.shape)}")
+    if bias is not None and _need(bias, _BF16, "tokmix_left bias", 1).numel() != M:
+        raise ValueError(f"tokmix_left bias: [{M}] expected")
+    for t, name in ((residual, "residual"), (aux_in, "aux_in"), (out, "out")):
+        if t is not None and tuple(_need(t, _BF16, f"tokmix_left {name}", 3).shape) != (B, M, D):
+            raise ValueError(f"tokmix_left {name}: shape {(B, M, D)} expected, got {tuple(t.shape)}")
+    c = out if out is not None else torch.empty((B, M, D), device=x.device, dtype=_BF16)
+    aux = torch.empty((B, M, D), device=x.device, dtype=_BF16) if want_aux else None
+    args = _lib.TokmixArgs()
+    args.w, args.x, args.c = w.data_ptr(), x.data_ptr(), c.data_ptr()
+    args.bias = bias.data_ptr() if bias is not None else None
+    args.residual = residual.data_ptr() if residual is not None else None
+    args.aux_in = aux_in.data_ptr() if aux_in is not None else None
+    args.aux_out = aux.data_ptr() if aux is not None else None
+    args.B, args.M, args.K, args.D = B, M, K, D
+    args.w_transposed, args.act = int(transposed), act
+    _launch("tokmix_left", 2.0 * B * M * K * D,
+            lambda: check(lib.sfcvit_tokmix_left(ctypes.byref(args), _stream()), "sfcvit_tokmix_left"))
+    return (c, aux) if want_aux else c
+
+
+def tokmix_wgrad(g, x, want_dw=True, want_db=True, out=None):
+    """-> (dW [M, K] = sum_b G_b X_b^T, db [M] = sum_{b, d} G_b[m, d]) for g [B, M, D], x [B, K, D] bf16; entries not
+    wanted are None.  fp32, or -- with out = (dw, db) contiguous bf16 tensors, e.g. views of a flat gradient buffer (None
+    entries are allocated) -- written as bf16 in place."""
+    _need(g, _BF16, "tokmix_wgrad g", 3)
+    _need(x, _BF16, "tokmix_wgrad x", 3)
+    B, M, D = g.shape
+    K = x.shape[1]
+    if x.shape[0] != B or x.shape[2] != D:
+        raise ValueError(f"tokmix_wgrad: g {tuple(g.shape)} and x {tuple(x.shape)} must share B and D")
+    gdt = torch.float32 if out is None else _BF16
+    given = (None, None) if out is None else out
+    for t, n in zip(given, (M * K, M)):
+        if t is not None and (t.dtype != _BF16 or t.numel() != n or not t.is_contiguous()):
+            raise ValueError("tokmix_wgrad out: contiguous bf16 tensors of the weight's / bias's size expected")
+    dw = (given[0] if given[0] is not None else torch.empty((M, K), device=g.device, dtype=gdt)) if want_dw else None
+    db = (given[1] if given[1] is not None else torch.empty(M, device=g.device, dtype=gdt)) if want_db else None
+    nbytes = lib.sfcvit_tokmix_wgrad_workspace(B, M, K, D)
+    ws = torch.empty(max(nbytes, 16), device=g.device, dtype=torch.uint8)
+    with _Deferring([t for t in (dw, db) if t is not None], [ws]):
+        _launch("tokmix_wgrad", 2.0 * B * M * K * D,
+                lambda: check(lib.sfcvit_tokmix_wgrad(_p(g), _p(x), _p(dw), _p(db), int(gdt == _BF16), B, M, K, D, _p(ws), nbytes,
+                                                      _stream()), "sfcvit_tokmix_wgrad"))
+    return dw, db
+
+
+# ----------------------------------------------------------------------------
 # elementwise / loss / optimizer
 # ----------------------------------------------------------------------------
 def gelu_fwd(x):

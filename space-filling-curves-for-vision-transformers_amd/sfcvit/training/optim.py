@@ -22,8 +22,8 @@ class FlatGradBuffer:
     dtype-agnostic torch plumbing; FusedAdamW adds the HIP step on top).
 
     The layout is decided after the first backward: parameters whose .grad is still None then
-    never get one in this model (MixerBlock.token_mix*, src/models/vit.py:269-272) and stay
-    outside the buffers, exactly as torch.optim skips them."""
+    never get one in this model (MixerBlock.token_mix* unless the model was built with token_mix=True,
+    src/models/vit.py:269-272) and stay outside the buffers, exactly as torch.optim skips them."""
 
     def __init__(self, params, grad_scale=1.0):
         self.params = [p for p in params if p.requires_grad]
@@ -39,7 +39,8 @@ class FlatGradBuffer:
 
     def _build(self, active=None):
         """`active` = the parameters that receive gradients; by default those that have one now (after the first
-        backward), which leaves out parameters the forward never touches (mlp_mixer.token_mix*, vit.py:269-272)."""
+        backward), which leaves out parameters the forward never touches (mlp_mixer.token_mix* of a model without token_mix=True,
+        vit.py:269-272)."""
         self.active = [p for p in self.params if p.grad is not None] if active is None else list(active)
         if not self.active:
             raise RuntimeError("step() before any backward")
