@@ -417,7 +417,7 @@ int64_t sfcvit_layernorm_bwd_ws(int M, int D);
 int sfcvit_last_rowwise_kernel(char *buf, int n);
 
 /* ------------------------------------------------------------------------
- * Multi-head self-attention core (no mask) on the packed projection
+ * Multi-head self-attention core (no mask; the masked form is the next section) on the packed projection
  *   replaces F.scaled_dot_product_attention as reached from nn.MultiheadAttention
  *   (torch:nn/functional.py:6623-6631); qkv is the in_proj output [B, N, 3*H*hd]
  *   with q | k | v in thirds, head h at columns h*hd .. h*hd+hd-1 of each third.
@@ -462,6 +462,55 @@ int sfcvit_attention_plan(const sfcvit_attn_args *a, int bwd, int any_length, ch
 /* HOST: name of the main kernel the calling thread's last sfcvit_attention_fwd / _bwd launched, as rocprofv3 prints it
  * (e.g. "attn_seq_bwd_fused_kernel<13, true>"): tests assert through it that a shape ran on the production kernel. */
 int sfcvit_last_attn_kernel(char *buf, int n);
+
+/* ------------------------------------------------------------------------
+ * Masked / windowed self-attention core (head dim 64)
+ *   replaces F.scaled_dot_product_attention(attn_mask=...) as reached from nn.TransformerEncoder.forward(src, mask)
+ *   and the reference's CustomTransformerEncoder (src/models/vit.py:152-174), which passes src_mask to every layer.
+ *
+ *   A mask is an additive fp32 matrix M [N, N] shared by all batches and heads; entries are finite or -inf:
+ *       s_ij = scale * q_i . k_j + M_ij,   P = softmax_j(s),   lse_i = log sum_j exp(s_ij)   (lse includes the mask)
+ *   Dropout acts on P with the mask function of sfcvit_attn_args: with an all-zero M the same elements are dropped as
+ *   in sfcvit_attention_fwd.  Preconditions (enforced by sfcvit_attention_mask_blocks, assumed by the kernels): no NaN,
+ *   no +inf, and every row has at least one finite entry.
+ *
+ *   The block map says, per (64-query block, 64-key block), whether the kernels visit it: a workgroup owns 64 queries
+ *   (forward, dQ) or 64 keys (dK / dV) and walks its row / column of the map, so a banded mask costs its band.  No
+ *   atomics: every output element is written once after sums in a fixed order (two runs, same bits); key blocks no
+ *   query sees get dK = dV = 0 written.
+ * ---------------------------------------------------------------------- */
+#define SFCVIT_MASK_BLOCK 64
+#define SFCVIT_MASK_MAX_N 4096
+/* HOST, no HIP call: validates mask_host [N, N] and writes map_host [nb][nb], nb = ceil(N / 64):
+ *   0 = no finite entry (skipped), 1 = mixed (the kernels read the mask), 2 = every entry 0.0f (no mask read).
+ * SFCVIT_EINVAL (reason in sfcvit_last_error()): null pointer, N < 1 or N > 4096, a NaN or +inf entry, a row without a
+ * finite entry (the message names the row). */
+int sfcvit_attention_mask_blocks(const float *mask_host, int N, uint8_t *map_host);
+typedef struct sfcvit_attn_mask_args {
+    /* the fields of sfcvit_attn_args, same meaning */
+    const void *qkv;
+    void *out;
+    float *lse;
+    const void *dout;
+    void *dqkv;
+    float *delta;
+    int32_t B, N, H, hd; /* hd = 64 only, 1 <= N <= 4096 */
+    float scale;
+    float dropout_p;
+    uint32_t dropout_seed;
+    const uint32_t *seed_off;
+    float *colsum_part;  /* workspace of sfcvit_attention_colsum_workspace(B, N, H, hd) bytes, with colsum_out */
+    int64_t colsum_part_bytes;
+    void *colsum_out;    /* bwd, optional: sfcvit_colsum over the dqkv written */
+    int32_t colsum_bf16;
+    /* the mask */
+    const float *mask;        /* device, [N, N] fp32 */
+    const uint8_t *block_map; /* device, [nb][nb] as written by sfcvit_attention_mask_blocks for this mask */
+} sfcvit_attn_mask_args;
+/* Argument checks (null, 16-byte alignment of the bf16 tensors, N, hd, dropout_p in [0, 1)) run before any HIP call.
+ * sfcvit_last_attn_kernel reports "attn_masked_fwd_kernel" / "attn_masked_bwd_kv_kernel". */
+int sfcvit_attention_masked_fwd(const sfcvit_attn_mask_args *a, void *stream);
+int sfcvit_attention_masked_bwd(const sfcvit_attn_mask_args *a, void *stream);
 
 /* ------------------------------------------------------------------------
  * Attention maps and attention-distance statistics

@@ -66,6 +66,7 @@ void note_rowwise_kernel(const char *fmt, ...) {
 
 void note_attn_kernel(const AttnPlan &p) { kernel_name(p, g_attn, sizeof(g_attn)); }
 void note_attn_kernel(const ProbePlan &p) { kernel_name(p, g_attn, sizeof(g_attn)); }
+void note_attn_kernel(const char *name) { snprintf(g_attn, sizeof(g_attn), "%s", name); }
 
 void note_gemm_kernel(const GemmPlan &p) {
     g_gemm = p;

@@ -31,6 +31,7 @@ int raise_lds_limit(const void *kernel, int bytes, const char *what);
 void note_gemm_kernel(const GemmPlan &p);
 void note_attn_kernel(const AttnPlan &p);
 void note_attn_kernel(const ProbePlan &p);      // sfcvit_attention_probs / _stats report through sfcvit_last_attn_kernel too
+void note_attn_kernel(const char *name);        // the masked kernels (attention_masked.hip) have no plan: one kernel per pass
 // Which row-wise kernel the calling thread's last sfcvit_layernorm_bwd* launched (sfcvit_last_rowwise_kernel).
 void note_rowwise_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 

@@ -1,13 +1,14 @@
 // Sanitizer driver for the HOST-ONLY code of libsfcvit_hip.so ("Race detection / sanitizers": GPU ASan is not
 // available on this pool, so the native host code gets a CPU-side -fsanitize=address,undefined build of its own):
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
-//   host part), the error path of common.cpp, and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid,
+//   host part), the error path of common.cpp, and the mask validation and block map of attention_masked.cpp (check_mask_blocks), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid,
 //   splits and post passes each GEMM / attention shape of the benchmarked models gets).  Every output buffer is a heap block of EXACTLY the documented size, so that
 // an off-by-one in a generator or in the descriptor writer is a heap-buffer-overflow report instead of silent corruption.
 // Built and run by `make asan` (tests/test_host_cpu.py::test_host_code_is_clean_under_address_sanitizer).  No GPU call.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <vector>
 
@@ -320,6 +321,44 @@ static void check_dispatch() {
     check_probe();
 }
 
+// sfcvit_attention_mask_blocks (attention_masked.cpp) with heap buffers of exactly N * N floats and nb * nb bytes.
+static void check_mask_blocks() {
+    const float ninf = -std::numeric_limits<float>::infinity();
+    struct W { int N, w, visited, total; };
+    const W windows[] = {{4, 1, 1, 1}, {70, 1, 4, 4}, {130, 40, 7, 9}, {196, 32, 10, 16}, {576, 64, 25, 81}, {4096, 0, 64, 4096}};
+    for (const W &q : windows) {
+        const int N = q.N, nb = (N + 63) / 64;
+        std::unique_ptr<float[]> m(new float[size_t(N) * N]);
+        std::unique_ptr<uint8_t[]> map(new uint8_t[size_t(nb) * nb]);
+        for (int i = 0; i < N; i++)
+            for (int j = 0; j < N; j++) m[size_t(i) * N + j] = (i - j <= q.w && j - i <= q.w) ? 0.f : ninf;
+        CHECK(sfcvit_attention_mask_blocks(m.get(), N, map.get()) == SFCVIT_OK, "mask blocks N %d w %d: %s", N, q.w, sfcvit_last_error());
+        int visited = 0;
+        for (int i = 0; i < nb * nb; i++) visited += map[i] != 0;
+        CHECK(visited == q.visited && nb * nb == q.total, "mask blocks N %d w %d: %d / %d visited, want %d / %d", N, q.w, visited, nb * nb,
+              q.visited, q.total);
+        // the diagonal block of a window >= 63 wide is all zero (2) when it is a whole block; a partial or narrower one is mixed
+        if (N == 576) CHECK(map[0] == 2 && map[1] == 1 && map[2] == 0, "mask blocks N 576: first row %d %d %d", map[0], map[1], map[2]);
+        const size_t last = size_t(N) * N - 1;
+        m[last] = std::numeric_limits<float>::quiet_NaN();
+        CHECK(sfcvit_attention_mask_blocks(m.get(), N, map.get()) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "NaN"), "mask blocks: NaN accepted");
+        m[last] = -ninf;
+        CHECK(sfcvit_attention_mask_blocks(m.get(), N, map.get()) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "+inf"), "mask blocks: +inf accepted");
+        for (int j = 0; j < N; j++) m[size_t(N - 1) * N + j] = ninf;
+        char want[32];
+        std::snprintf(want, sizeof(want), "row %d ", N - 1);
+        CHECK(sfcvit_attention_mask_blocks(m.get(), N, map.get()) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), want),
+              "mask blocks: hidden row %d accepted or not named: '%s'", N - 1, sfcvit_last_error());
+    }
+    float one = 0.f;
+    uint8_t b = 0;
+    CHECK(sfcvit_attention_mask_blocks(nullptr, 1, &b) == SFCVIT_EINVAL, "mask blocks: null mask accepted");
+    CHECK(sfcvit_attention_mask_blocks(&one, 1, nullptr) == SFCVIT_EINVAL, "mask blocks: null map accepted");
+    CHECK(sfcvit_attention_mask_blocks(&one, 0, &b) == SFCVIT_EINVAL, "mask blocks: N = 0 accepted");
+    CHECK(sfcvit_attention_mask_blocks(&one, 4097, &b) == SFCVIT_EINVAL, "mask blocks: N = 4097 accepted");
+    CHECK(sfcvit_attention_mask_blocks(&one, 1, &b) == SFCVIT_OK && b == 2, "mask blocks: N = 1, zero mask: %d", int(b));
+}
+
 int main() {
     const int curves[] = {SFCVIT_CURVE_HILBERT, SFCVIT_CURVE_Z, SFCVIT_CURVE_MOORE, SFCVIT_CURVE_PEANO, SFCVIT_CURVE_RASTER,
                           SFCVIT_CURVE_SPIRAL, SFCVIT_CURVE_HILBERT_T};
@@ -387,6 +426,7 @@ int main() {
     }
     CHECK(sfcvit_abi_version() == SFCVIT_ABI_VERSION, "abi version");
     check_dispatch();
+    check_mask_blocks();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     std::printf("host_check ok\n");
     return 0;

@@ -114,6 +114,13 @@ def main():
     ap.add_argument("--token-mix", action="store_true",
                     help="switch the MixerBlock's token-mix branch on (src/models/vit.py:269-271, commented out in the "
                          "reference): a learned mixing along the curve in front of the channel mix.  Checkpoints keep their keys")
+    win = ap.add_mutually_exclusive_group()
+    win.add_argument("--attn-window", type=int, default=None, metavar="W",
+                     help="local attention along the curve: every token attends to the tokens within W positions of it in "
+                          "sequence order (sfcvit.masks.curve_window); runs on the masked attention kernels, also with --graph")
+    win.add_argument("--attn-window-2d", type=float, default=None, metavar="R",
+                     help="local attention in the image: every token attends to the tokens whose centres lie within R pixels "
+                          "of its own in both axes (sfcvit.masks.image_window on the tokenizer's positions)")
     ap.add_argument("--mean", type=float, nargs=3, default=[0.4914, 0.4822, 0.4465])      # main.py:176-177 (CIFAR)
     ap.add_argument("--std", type=float, nargs=3, default=[0.2023, 0.1994, 0.2010])
     a = ap.parse_args()
@@ -163,9 +170,22 @@ def main():
         test_transform = DeviceAugment.test_transform(per_rank, a.img_size, a.img_size, mean=a.mean, std=a.std, device=device)
 
     patch_embed = build_tokenizer(a)
+    attn_mask = None
+    if a.attn_window is not None or a.attn_window_2d is not None:
+        from sfcvit import masks
+        from sfcvit.ops import AttentionMask
+        if a.attn_window is not None:
+            attn_mask = AttentionMask(masks.curve_window(patch_embed.n_patches, a.attn_window))
+        else:
+            from sfcvit.analysis import token_positions
+            attn_mask = AttentionMask(masks.image_window(token_positions(patch_embed), a.attn_window_2d))
+        if rank == 0:
+            print(f"attention mask: {attn_mask.visited_blocks}/{attn_mask.total_blocks} blocks of 64 x 64 visited "
+                  f"(N = {attn_mask.n_tokens})")
     model = VisionTransformer1D(patch_embed=patch_embed, depth=a.depth, n_heads=a.heads, mlp_dim=a.mlp_dim,
                                 num_classes=a.classes,
-                                token_aggregator=a.token_aggregator or False, token_mix=a.token_mix).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
+                                token_aggregator=a.token_aggregator or False, token_mix=a.token_mix,
+                                attn_mask=attn_mask).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
     train_criterion, test_criterion = SoftTargetCrossEntropy(), nn.CrossEntropyLoss()
     optimizer = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=1.0)
     reducer = GradReducer(optimizer, overlap=not a.graph) if world > 1 else None    # --graph: collectives between two graphs
@@ -188,6 +208,8 @@ def main():
             optimizer.lr = scheduler.lr_at(scheduler.n)
             if augment is not None and ck.get("augment_state_dict"):
                 augment.load_state_dict(ck["augment_state_dict"])       # the draw stream goes on where it stopped
+    if a.attention_report and attn_mask is not None:
+        raise SystemExit("--attention-report measures unmasked attention; it cannot be combined with --attn-window / --attn-window-2d")
     if a.attention_report and rank == 0:
         import json
         from sfcvit.analysis import attention_report, report_summary

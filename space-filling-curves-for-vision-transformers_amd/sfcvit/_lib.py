@@ -50,6 +50,10 @@ class AttnArgs(ctypes.Structure):
                 ("colsum_part", c_void_p), ("colsum_part_bytes", c_int64), ("colsum_out", c_void_p), ("colsum_bf16", c_int32)]
 
 
+class AttnMaskArgs(ctypes.Structure):
+    _fields_ = AttnArgs._fields_ + [("mask", c_void_p), ("block_map", c_void_p)]
+
+
 class AttnProbeArgs(ctypes.Structure):
     _fields_ = [("qkv", c_void_p), ("lse", c_void_p),
                 ("B", c_int32), ("N", c_int32), ("H", c_int32), ("hd", c_int32), ("scale", c_float),
@@ -142,6 +146,9 @@ SIGNATURES = {
     "sfcvit_attention_bwd_any": (c_int, [ctypes.POINTER(AttnArgs), c_void_p]),
     "sfcvit_attention_plan": (c_int, [ctypes.POINTER(AttnArgs), c_int, c_int, ctypes.c_char_p, c_int]),
     "sfcvit_attention_colsum_workspace": (c_int64, [c_int, c_int, c_int, c_int]),
+    "sfcvit_attention_mask_blocks": (c_int, [c_void_p, c_int, c_void_p]),
+    "sfcvit_attention_masked_fwd": (c_int, [ctypes.POINTER(AttnMaskArgs), c_void_p]),
+    "sfcvit_attention_masked_bwd": (c_int, [ctypes.POINTER(AttnMaskArgs), c_void_p]),
     "sfcvit_attention_probs": (c_int, [ctypes.POINTER(AttnProbeArgs), c_void_p]),
     "sfcvit_attention_stats": (c_int, [ctypes.POINTER(AttnProbeArgs), c_void_p]),
     "sfcvit_dwconv1d_out_len": (c_int, [c_int, c_int, c_int]),

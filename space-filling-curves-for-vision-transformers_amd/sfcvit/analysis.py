@@ -138,6 +138,9 @@ def attention_report(model, images, layers=None, maps=False, head_mean=True, row
                          "map": [B, N, N] mean over heads, or [B, H, N, N] with head_mean=False   with maps=True}, ...]}
     maps: True (fp32) or a dtype (torch.float32 / torch.bfloat16).  positions: [N, 2] token centres when the model's
     tokenizer cannot say (default: token_positions).  Supports VisionTransformer, VisionTransformer1D, SimpleViT, HilbertViT."""
+    if getattr(model, "attn_mask", None) is not None:
+        raise NotImplementedError("attention_report: the model was built with attn_mask=; the probe kernels rebuild the attention "
+                                  "map from q, k and lse WITHOUT a mask and would report wrong maps and distances")
     if isinstance(model, (VisionTransformer, VisionTransformer1D)):
         walk = _vit_layers
     elif isinstance(model, (altvit.SimpleViT, altvit.HilbertViT)):

@@ -387,6 +387,34 @@ def gelu_dropout(x, p):
     return _GeluDrop.apply(_bf(x), float(p), ops.next_seed())
 
 
+class _MaskedAttention(Function):
+    """_Attention with an additive mask (ops.AttentionMask): softmax(q k^T / sqrt(hd) + M) v on the masked kernels."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_heads, scale, mask):
+        qkv = _c(qkv)
+        m, bm = mask.on(qkv.device)
+        out, lse = ops.attention_masked_fwd(qkv, n_heads, m, bm, scale=scale)
+        ctx.save_for_backward(qkv, out, lse, m, bm)
+        ctx.n_heads, ctx.scale = n_heads, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, m, bm = ctx.saved_tensors
+        return ops.attention_masked_bwd(qkv, out, lse, _c(dout), ctx.n_heads, m, bm, scale=ctx.scale), None, None, None
+
+
+def _attention_mask(mask, n_tokens, what):
+    """ops.as_attention_mask for a layer call.  Under tracing a mask is refused: the torch.library ops have no masked form."""
+    if mask is None:
+        return None
+    if _traced():
+        raise NotImplementedError(f"{what}: an attention mask is not supported under torch.compile / tracing (the torch.library "
+                                  "ops have no masked form); run the masked model eagerly")
+    return ops.as_attention_mask(mask, n_tokens)
+
+
 class _Attention(Function):
     """softmax(q k^T / sqrt(hd)) v per head on a packed projection [B, N, 3 * H * hd] (q | k | v thirds, head h at
     columns h*hd.. of each third): the core of nn.MultiheadAttention and of altvit.Attention (altvit.py:131-142)."""
@@ -417,17 +445,22 @@ def _head_padding(D, n_heads):
     return hd, hp
 
 
-def attention(qkv, n_heads):
+def attention(qkv, n_heads, mask=None):
     """Head dims the kernels do not have (32, 48, 96, ...) run zero-padded to the next one that exists: the padded
-    q / k / v columns add nothing to q k^T or p v, the softmax scale stays 1 / sqrt(head dim)."""
+    q / k / v columns add nothing to q k^T or p v, the softmax scale stays 1 / sqrt(head dim).
+    mask: None, or an additive attention mask [N, N] shared by all batches and heads (ops.AttentionMask, a float tensor,
+    or a bool tensor with True = may not attend): scores q k^T / sqrt(hd) + mask on the masked kernels (kernel head dim
+    64: head dims up to 64).  Without a mask nothing changes."""
     qkv = _bf(qkv)
     D = qkv.shape[-1] // 3
     hd, hp = _head_padding(D, n_heads)
+    mask = _attention_mask(mask, qkv.shape[-2], "attention")
+    core = _Attention.apply if mask is None else (lambda t, H, sc: _MaskedAttention.apply(t, H, sc, mask))
     if hp == hd:
-        return _Attention.apply(qkv, n_heads, None)
+        return core(qkv, n_heads, None)
     lead = qkv.shape[:-1]
     padded = torch.nn.functional.pad(qkv.reshape(*lead, 3, n_heads, hd), (0, hp - hd)).reshape(*lead, 3 * n_heads * hp)
-    out = _Attention.apply(padded, n_heads, 1.0 / math.sqrt(hd))
+    out = core(padded, n_heads, 1.0 / math.sqrt(hd))
     return out.reshape(*lead, n_heads, hp)[..., :hd].reshape(*lead, D)
 
 
@@ -645,7 +678,8 @@ class _EncoderLayer(Function):
     identity.  Masks are functions of (seed, element index), regenerated in backward."""
 
     @staticmethod
-    def launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale):
+    def launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale,
+                 attn_mask=None):
         """The forward's kernel launches, every intermediate returned (forward saves them; encoder_layer_probe reads the
         attention inputs out of the same sequence, so what it carries on is what forward computes)."""
         B, N, D = x.shape
@@ -653,7 +687,10 @@ class _EncoderLayer(Function):
         sa, s1_, sf, s2_ = seeds
         x2 = _c(x).view(B * N, D)
         qkv = ops.gemm(x2, in_w, bias=in_b)
-        o, lse = ops.attention_fwd(qkv.view(B, N, 3 * Da), n_heads, p, sa, scale=scale, any_length=True)
+        if attn_mask is None:
+            o, lse = ops.attention_fwd(qkv.view(B, N, 3 * Da), n_heads, p, sa, scale=scale, any_length=True)
+        else:                                               # an ops.AttentionMask: the masked kernels, and only then
+            o, lse = ops.attention_masked_fwd(qkv.view(B, N, 3 * Da), n_heads, *attn_mask.on(x.device), p, sa, scale=scale)
         s1 = ops.gemm(o.view(B * N, Da), out_w, bias=out_b, residual=x2, dropout_p=p, dropout_seed=s1_)
         x1, mean1, rstd1 = ops.layernorm_fwd(s1, n1_w, n1_b, eps)
         # The dX GEMM through ReLU + dropout needs only the sign pattern of h: a bit matrix written by linear1's epilogue
@@ -666,11 +703,12 @@ class _EncoderLayer(Function):
         return x2, qkv, o, lse, s1, mean1, rstd1, x1, hbits, h, s2, y, mean2, rstd2
 
     @staticmethod
-    def forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale):
+    def forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale,
+                attn_mask=None):
         B, N, D = x.shape
         x2, qkv, o, lse, s1, mean1, rstd1, x1, hbits, h, s2, y, mean2, rstd2 = _EncoderLayer.launches(
-            x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale)
-        ctx.hbits = hbits
+            x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale, attn_mask)
+        ctx.hbits, ctx.attn_mask = hbits, attn_mask
         ctx.save_for_backward(x2, qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2,
                               in_w, out_w, n1_w, w1, w2, n2_w)
         ctx.n_heads, ctx.shape, ctx.p, ctx.seeds, ctx.scale = n_heads, (B, N, D), p, seeds, scale
@@ -723,8 +761,14 @@ class _EncoderLayer(Function):
         do = ops.gemm_dx(da, out_w)
         # the in_proj bias gradient (column sums of dqkv) comes out of the attention backward itself
         bi_slot = _slot(in_b)
-        dqkv, dbi = ops.attention_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), ctx.n_heads, p, sa,
-                                      colsum=bi_slot if bi_slot is not None else True, scale=ctx.scale, any_length=True)
+        attn_mask = getattr(ctx, "attn_mask", None)         # library.py's traced backward builds its own ctx: never masked
+        if attn_mask is None:
+            dqkv, dbi = ops.attention_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), ctx.n_heads, p, sa,
+                                          colsum=bi_slot if bi_slot is not None else True, scale=ctx.scale, any_length=True)
+        else:
+            dqkv, dbi = ops.attention_masked_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), ctx.n_heads,
+                                                 *attn_mask.on(dy2.device), p, sa,
+                                                 colsum=bi_slot if bi_slot is not None else True, scale=ctx.scale)
         dqkv = dqkv.view(B * N, 3 * Da)
         if bi_slot is None:
             dbi = dbi.to(_BF16)
@@ -732,7 +776,9 @@ class _EncoderLayer(Function):
         dx = ops.gemm_dx(dqkv, in_w, residual=ds1)
         if ss:
             ss.join(dw2, dw1, dwo, dwi)
-        return (dx.view(B, N, D), dwi, dbi, dwo, dbo, dg1, dbt1, dw1, db1, dw2, db2, dg2, dbt2, None, None, None, None, None)
+        # one gradient per argument of apply(): the mask is a 19th argument only when there is one
+        return ((dx.view(B, N, D), dwi, dbi, dwo, dbo, dg1, dbt1, dw1, db1, dw2, db2, dg2, dbt2, None, None, None, None, None)
+                + (() if attn_mask is None else (None,)))
 
 
 def _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads):
@@ -764,17 +810,23 @@ def encoder_layer_probe(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2,
 
 
 def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5,
-                  dropout_p=0.0):
+                  dropout_p=0.0, attn_mask=None):
     """dropout_p > 0 = training-mode nn.TransformerEncoderLayer (fresh masks every call).
+    attn_mask = nn.TransformerEncoderLayer's src_mask: None, or an additive [N, N] mask as in `attention` (build an
+    ops.AttentionMask once when the layer runs more than once).  With None the launches and the bits are those of a call
+    without the argument; with a mask the attention core alone changes, to the masked kernels (not under tracing).
     A head dim the attention kernels do not have (embed_dim / n_heads = 32, 48, 96, ...) runs on the next one that
     exists: in_proj's rows and out_proj's columns are zero-padded per head (differentiable torch plumbing on the
     weights, 3 D^2 elements -- not on the activations), so q, k, v come out of the projection GEMM already padded, the
     padded columns add nothing to q k^T or p v, and out_proj ignores them; the softmax scale stays 1 / sqrt(head dim)."""
     args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
+    attn_mask = _attention_mask(attn_mask, args[0].shape[1], "encoder_layer")
     if _traced():
         from . import library      # (dropout seeds are drawn inside the op: nothing data-dependent in the traced graph)
         return library.encoder_layer(args, n_heads, eps, float(dropout_p), scale)
     seeds = tuple(ops.next_seed() for _ in range(4)) if dropout_p > 0 else (0, 0, 0, 0)
+    if attn_mask is not None:
+        return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale, attn_mask)
     return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale)
 
 

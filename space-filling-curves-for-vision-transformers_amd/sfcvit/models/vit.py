@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import functional as F
+from .. import ops
 from ..tokenizers.base_patch_embedding import BasePatchEmbedding
 
 
@@ -55,7 +56,9 @@ def _attach_aggregator(model, option, embed_dim):
 
 
 class TransformerSeqEncoder(nn.Module):
-    """vit.py:177-242: `depth` post-norm nn.TransformerEncoderLayer (relu, eps 1e-5)."""
+    """vit.py:177-242: `depth` post-norm nn.TransformerEncoderLayer (relu, eps 1e-5).  forward(x, mask=None) mirrors
+    nn.TransformerEncoder.forward(src, mask): the mask goes to every layer (the reference's CustomTransformerEncoder,
+    vit.py:152-174).  A mask is not a parameter or a buffer: it never enters state_dict."""
 
     def __init__(self, input_dim, max_len, n_head, hidden_dim, method, dropout_p=0.1, n_layers=1):
         super().__init__()
@@ -70,14 +73,25 @@ class TransformerSeqEncoder(nn.Module):
                                                  enable_nested_tensor=False)
         self.to_patch_embedding = method
 
-    def forward(self, x):
+    def _mask(self, mask):
+        """The AttentionMask of `mask`; a tensor is validated and uploaded at its first use and remembered while the same
+        tensor object keeps coming."""
+        if mask is None or isinstance(mask, ops.AttentionMask):
+            return mask
+        cached = self.__dict__.get("_mask_cache")
+        if cached is None or cached[0] is not mask:
+            cached = self.__dict__["_mask_cache"] = (mask, ops.as_attention_mask(mask))
+        return cached[1]
+
+    def forward(self, x, mask=None):
         p = self.dropout_p if self.training else 0.0
+        mask = self._mask(mask)
         for layer in self.transformer.layers:
             a = layer.self_attn
             x = F.encoder_layer(x, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
                                 layer.norm1.weight, layer.norm1.bias, layer.linear1.weight, layer.linear1.bias,
                                 layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias,
-                                self.n_head, layer.norm1.eps, dropout_p=p)
+                                self.n_head, layer.norm1.eps, dropout_p=p, attn_mask=mask)
         return x
 
 
@@ -181,10 +195,13 @@ class VisionTransformer(nn.Module):
     """vit.py:325-385 (`embed_dim` is ignored there too: taken from the tokenizer, :351)."""
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
-                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False):
+                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, attn_mask=None):
+        """attn_mask: None, or a mask for every encoder layer (ops.as_attention_mask's forms; sfcvit.masks builds windows).
+        Held outside state_dict: checkpoint keys are the reference's with or without it."""
         super().__init__()
         self.patch_embed = patch_embed
         embed_dim = patch_embed.embed_dim
+        self.attn_mask = ops.as_attention_mask(attn_mask, patch_embed.n_patches)
         self.encoder = TransformerSeqEncoder(input_dim=embed_dim, max_len=self.patch_embed.n_patches,
                                              method=self.patch_embed, n_head=n_heads, hidden_dim=mlp_dim,
                                              n_layers=depth, dropout_p=dropout_p)
@@ -197,7 +214,7 @@ class VisionTransformer(nn.Module):
         x = self.patch_embed(x) if mix is None else self.patch_embed(x, mix=mix)
         if hasattr(self, "ta"):
             x = self.ta(x)                                      # vit.py:381
-        x = self.encoder(x)
+        x = self.encoder(x, mask=self.attn_mask)
         return self.mlp_head(x)
 
 
@@ -207,10 +224,12 @@ class VisionTransformer1D(nn.Module):
     the only pre-encoder component that sees absolute position in curve order."""
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
-                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False):
+                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False, attn_mask=None):
+        """attn_mask: as in VisionTransformer."""
         super().__init__()
         self.patch_embed = patch_embed
         embed_dim = patch_embed.embed_dim
+        self.attn_mask = ops.as_attention_mask(attn_mask, patch_embed.n_patches)
         self.mlp_mixer = MixerBlock(seq_len=self.patch_embed.n_patches, embed_dim=embed_dim,
                                     hidden_dim=embed_dim * 2, out_dim=embed_dim, token_mix=token_mix)
         self.encoder = TransformerSeqEncoder(input_dim=embed_dim, max_len=self.patch_embed.n_patches,
@@ -226,5 +245,5 @@ class VisionTransformer1D(nn.Module):
         if hasattr(self, "ta"):
             x = self.ta(x)
         x = self.mlp_mixer(x)
-        x = self.encoder(x)
+        x = self.encoder(x, mask=self.attn_mask)
         return self.mlp_head(x)

@@ -490,6 +490,111 @@ def attention_bwd(qkv, out, lse, dout, n_heads, dropout_p=0.0, dropout_seed=0, c
     return dqkv if cs is None else (dqkv, cs)
 
 
+class AttentionMask:
+    """An additive attention mask [N, N] (fp32, CPU; entries finite or -inf, shared by all batches and heads) validated by
+    sfcvit_attention_mask_blocks, with its block map (one byte per 64 x 64 block: 0 skip, 1 mixed, 2 all zero).  Built once
+    on the host; the device copies of mask and map are made once per device and stay put (graph capture replays them).
+    ValueError, with the library's message, for NaN, +inf, a row that hides every key, N < 1 or N > 4096."""
+
+    def __init__(self, mask):
+        if not isinstance(mask, torch.Tensor) or mask.is_cuda or mask.dtype != torch.float32 or mask.dim() != 2 or mask.shape[0] != mask.shape[1]:
+            raise ValueError("AttentionMask: a CPU fp32 [N, N] tensor is expected (sfcvit.masks builds them)")
+        self.mask = mask.contiguous()
+        self.n_tokens = N = int(mask.shape[0])
+        nb = (max(N, 1) + 63) // 64
+        self.block_map = torch.zeros((nb, nb), dtype=torch.uint8)
+        rc = lib.sfcvit_attention_mask_blocks(ctypes.c_void_p(self.mask.data_ptr()), N, ctypes.c_void_p(self.block_map.data_ptr()))
+        if rc != 0:
+            raise ValueError(lib.sfcvit_last_error().decode(errors="replace"))
+        self.total_blocks = nb * nb
+        self.visited_blocks = int((self.block_map != 0).sum())
+        self._dev = {}
+
+    def on(self, device):
+        """(mask, block map) on `device`, uploaded at the first request."""
+        key = torch.device(device)
+        if key.type == "cuda" and key.index is None:
+            key = torch.device("cuda", torch.cuda.current_device())
+        if key not in self._dev:
+            self._dev[key] = (self.mask.to(key), self.block_map.to(key))
+        return self._dev[key]
+
+    def __repr__(self):
+        return f"AttentionMask(N={self.n_tokens}, blocks {self.visited_blocks}/{self.total_blocks})"
+
+
+def as_attention_mask(mask, n_tokens=None):
+    """None, or the AttentionMask of an attention mask in any of nn.TransformerEncoder.forward's forms: an AttentionMask as
+    it is, a float additive [N, N] tensor (finite or -inf), or a bool tensor with True = may NOT attend (validated and
+    uploaded now: callers that run more than once convert once).  ValueError for a size other than n_tokens."""
+    if mask is None:
+        return None
+    if not isinstance(mask, AttentionMask):
+        from . import masks
+        mask = torch.as_tensor(mask)
+        mask = AttentionMask(masks.from_bool(mask) if mask.dtype == torch.bool else mask.detach().to("cpu", torch.float32))
+    if n_tokens is not None and mask.n_tokens != n_tokens:
+        raise ValueError(f"attention mask for {mask.n_tokens} tokens on a sequence of {n_tokens}")
+    return mask
+
+
+def _masked_args(qkv, n_heads, mask, block_map, dropout_p, dropout_seed, scale, what):
+    _need(qkv, _BF16, f"{what} qkv", 3)
+    B, N, D3 = qkv.shape
+    if D3 % 3 or (D3 // 3) % n_heads:
+        raise ValueError(f"{what}: packed width {D3} is not 3 * n_heads * head_dim for n_heads = {n_heads}")
+    hd = D3 // 3 // n_heads
+    nb = (N + 63) // 64
+    if tuple(_need(mask, torch.float32, f"{what} mask", 2).shape) != (N, N):
+        raise ValueError(f"{what}: mask must be [N, N] = {(N, N)}, got {tuple(mask.shape)}")
+    if tuple(_need(block_map, torch.uint8, f"{what} block_map", 2).shape) != (nb, nb):
+        raise ValueError(f"{what}: block_map must be {(nb, nb)}, got {tuple(block_map.shape)}")
+    a = _lib.AttnMaskArgs()
+    a.qkv, a.mask, a.block_map = qkv.data_ptr(), mask.data_ptr(), block_map.data_ptr()
+    a.B, a.N, a.H, a.hd, a.scale = B, N, n_heads, hd, (1.0 / math.sqrt(hd) if scale is None else float(scale))
+    a.dropout_p, a.dropout_seed = dropout_p, dropout_seed
+    if dropout_p > 0.0 and STEP_STATE is not None:
+        a.seed_off = STEP_STATE.data_ptr()
+    return a, B, N, D3 // 3, hd
+
+
+def attention_masked_fwd(qkv, n_heads, mask, block_map, dropout_p=0.0, dropout_seed=0, scale=None):
+    """attention_fwd with an additive mask: scores scale * q k^T + mask.  mask [N, N] fp32 and block_map [nb, nb] uint8 are
+    the device tensors of an AttentionMask (AttentionMask.on(device)).  Head dim 64 only, 1 <= N <= 4096.  The lse
+    includes the mask."""
+    a, B, N, D, hd = _masked_args(qkv, n_heads, mask, block_map, dropout_p, dropout_seed, scale, "attention_masked_fwd")
+    out = torch.empty((B, N, D), device=qkv.device, dtype=_BF16)
+    lse = torch.empty((B, n_heads, N), device=qkv.device, dtype=torch.float32)
+    a.out, a.lse = out.data_ptr(), lse.data_ptr()
+    check(_launch("attn_masked_fwd", 4.0 * B * n_heads * N * N * hd,
+                  lambda: lib.sfcvit_attention_masked_fwd(ctypes.byref(a), _stream())), "sfcvit_attention_masked_fwd")
+    return out, lse
+
+
+def attention_masked_bwd(qkv, out, lse, dout, n_heads, mask, block_map, dropout_p=0.0, dropout_seed=0, colsum=None, scale=None):
+    """-> dqkv [, column sums of dqkv as in attention_bwd]."""
+    a, B, N, D, hd = _masked_args(qkv, n_heads, mask, block_map, dropout_p, dropout_seed, scale, "attention_masked_bwd")
+    _need(dout, _BF16, "attention_masked_bwd dout", 3)
+    _need(out, _BF16, "attention_masked_bwd out", 3)
+    _need(lse, torch.float32, "attention_masked_bwd lse", 3)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty((B, n_heads, N), device=qkv.device, dtype=torch.float32)
+    a.out, a.lse, a.dout, a.dqkv, a.delta = out.data_ptr(), lse.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), delta.data_ptr()
+    cs = None
+    if colsum is not None and colsum is not False:
+        cs = torch.empty(3 * D, device=qkv.device, dtype=torch.float32) if colsum is True else colsum
+        if cs.numel() != 3 * D or not cs.is_contiguous() or cs.dtype not in (torch.float32, _BF16):
+            raise ValueError("attention_masked_bwd colsum: contiguous fp32 or bf16 [3D] expected")
+        nbytes = lib.sfcvit_attention_colsum_workspace(B, N, n_heads, hd)
+        ws = torch.empty(nbytes, device=qkv.device, dtype=torch.uint8)
+        a.colsum_part, a.colsum_part_bytes = ws.data_ptr(), nbytes
+        a.colsum_out, a.colsum_bf16 = cs.data_ptr(), int(cs.dtype == _BF16)
+    with _Deferring([colsum] if cs is not None and colsum is not True else [], [ws] if cs is not None else []):
+        check(_launch("attn_masked_bwd", 10.0 * B * n_heads * N * N * hd,
+                      lambda: lib.sfcvit_attention_masked_bwd(ctypes.byref(a), _stream())), "sfcvit_attention_masked_bwd")
+    return dqkv if cs is None else (dqkv, cs)
+
+
 def _probe_args(qkv, lse, n_heads, scale, what):
     _need(qkv, _BF16, f"{what} qkv", 3)
     _need(lse, torch.float32, f"{what} lse", 3)
