@@ -583,6 +583,31 @@ int sfcvit_dwconv1d_bwd(const void *du, const void *x, const void *w, void *dx, 
 int sfcvit_last_dwconv_kernel(char *buf, int n);
 
 /* ------------------------------------------------------------------------
+ * Positional embedding
+ *   the reference's commented-out `x = x + self.pos_embed` (src/models/vit.py:360-361, :382; :207-219, :240): one table
+ *   row per token index, added to every image directly after the tokenizer.
+ *
+ *   x, y, dy [B, N, D] bf16, D contiguous;  pos [N, D] bf16 (a [1, N, D] parameter viewed 2-D).
+ *   Supported: B, N >= 1, D >= 8 and D % 8 == 0 (16-byte vectors), byte counts within int64; everything else is
+ *   SFCVIT_EINVAL, decided before any HIP call.  x, pos, y, dy and the workspace must be 16-byte aligned; dpos needs the
+ *   alignment of its element only (a slot of a flat gradient buffer).  Nothing allocates, synchronises or copies to the
+ *   host: graph-capturable.  dx of the add is dy itself: there is no kernel for it.
+ * ---------------------------------------------------------------------- */
+/* y[b, n, :] = bf16( float(x[b, n, :]) + float(pos[n, :]) ): one rounding per element (the bits of torch's bf16 add).
+ * y may be x itself (in place). */
+int sfcvit_pos_embed_fwd(const void *x, const void *pos, void *y, int B, int N, int D, void *stream);
+/* HOST: workspace bytes of the backward call (0 for refused arguments, and 0 wherever the table alone fills the GPU). */
+int64_t sfcvit_pos_embed_bwd_workspace(int B, int N, int D);
+/* dpos[n, :] = sum_b dy[b, n, :], summed in fp32 in a fixed order (no atomics, one writer per element: two runs, same
+ * bits) and written as fp32, or as bf16 when grad_bf16 != 0 (a view of a flat gradient buffer).  Where the plan splits
+ * the batch (workspace > 0) the final reduction joins the deferred reductions above when deferral is on. */
+int sfcvit_pos_embed_bwd(const void *dy, void *dpos, int grad_bf16, int B, int N, int D, void *workspace, int64_t workspace_bytes,
+                         void *stream);
+/* HOST: name of the kernel the calling thread's last sfcvit_pos_embed_fwd / _bwd launched, as rocprofv3 prints it
+ * (e.g. "pos_embed_bwd_kernel<2>"). */
+int sfcvit_last_pos_embed_kernel(char *buf, int n);
+
+/* ------------------------------------------------------------------------
  * Token mixing: GEMMs along the token axis of [B, N, D]
  *   replaces the token-mix branch of MixerBlock.forward (src/models/vit.py:269-271, commented out there):
  *       x = x + token_mix(token_mix_ln(x).transpose(1, 2)).transpose(1, 2)

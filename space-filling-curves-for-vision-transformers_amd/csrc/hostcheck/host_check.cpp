@@ -1,12 +1,14 @@
 // Sanitizer driver for the HOST-ONLY code of libsfcvit_hip.so ("Race detection / sanitizers": GPU ASan is not
 // available on this pool, so the native host code gets a CPU-side -fsanitize=address,undefined build of its own):
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
-//   host part), the error path of common.cpp, and the mask validation and block map of attention_masked.cpp (check_mask_blocks), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid,
+//   host part), the error path of common.cpp, and the mask validation and block map of attention_masked.cpp (check_mask_blocks), the plan and refusals of pos_embed.cpp (check_pos_embed), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid,
 //   splits and post passes each GEMM / attention shape of the benchmarked models gets).  Every output buffer is a heap block of EXACTLY the documented size, so that
 // an off-by-one in a generator or in the descriptor writer is a heap-buffer-overflow report instead of silent corruption.
 // Built and run by `make asan` (tests/test_host_cpu.py::test_host_code_is_clean_under_address_sanitizer).  No GPU call.
+#include <climits>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <memory>
@@ -14,6 +16,7 @@
 
 #include "../../../include/sfcvit.h"
 #include "../dispatch.h"
+#include "../pos_embed.h"
 
 static int g_fail = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { std::fprintf(stderr, "host_check: " __VA_ARGS__); std::fprintf(stderr, " (%s:%d)\n", __FILE__, __LINE__); g_fail++; } } while (0)
@@ -359,6 +362,72 @@ static void check_mask_blocks() {
     CHECK(sfcvit_attention_mask_blocks(&one, 1, &b) == SFCVIT_OK && b == 2, "mask blocks: N = 1, zero mask: %d", int(b));
 }
 
+// pos_embed_plan / pos_embed_check_* (pos_embed.cpp): the geometry at the workload shapes and the edge shapes of the tests, and
+// every refusal, with heap buffers of exactly B N D bf16 (x, y, dy), N D bf16 (pos), N D fp32 (dpos) and the workspace the plan
+// names.  The checks read no byte of them; what is pinned is that every accepted geometry stays inside them.
+static void check_pos_embed() {
+    struct S { int B, N, D; };
+    const S shapes[] = {{1, 1, 8}, {2, 1, 8}, {3, 5, 72}, {2, 65, 200}, {67, 3, 8}, {5, 4, 192}, {2, 197, 768}, {2, 196, 1024},
+                        {256, 196, 768}, {64, 576, 1024}, {4096, 1, 8}, {100000, 2, 8}};
+    for (const S &q : shapes) {
+        const PosEmbedPlan p = pos_embed_plan("host_check", q.B, q.N, q.D);
+        CHECK(p.err == SFCVIT_OK, "pos_embed %d %d %d refused: %s", q.B, q.N, q.D, p.msg);
+        if (p.err) continue;
+        const int64_t nd = int64_t(q.N) * q.D, total = nd * q.B;
+        CHECK(p.vecs * 8 == nd, "pos_embed: vecs");
+        // forward: every table vector has a lane, every image a group, a lane's images end inside the batch or are clamped
+        CHECK(int64_t(p.fwd_blocks) * PE_THREADS >= p.vecs && int64_t(p.fwd_blocks - 1) * PE_THREADS < p.vecs, "pos_embed fwd blocks");
+        CHECK(p.imgs >= 1 && p.imgs <= PE_MAX_IMGS && int64_t(p.fwd_groups) * p.imgs >= q.B && int64_t(p.fwd_groups - 1) * p.imgs < q.B,
+              "pos_embed fwd groups %d x %d for B %d", p.fwd_groups, p.imgs, q.B);
+        CHECK(p.fwd_groups <= 65535, "pos_embed fwd grid.y");
+        // backward: slabs cover the table, ranges cover the batch, no range is empty, rows are whole rounds of the 8 image lanes
+        CHECK(int64_t(p.slabs) * PE_CV >= p.vecs && int64_t(p.slabs - 1) * PE_CV < p.vecs, "pos_embed bwd slabs");
+        CHECK(p.rows % PE_RL == 0 && int64_t(p.splits) * p.rows >= q.B && int64_t(p.splits - 1) * p.rows < q.B && p.splits <= 65535,
+              "pos_embed bwd ranges %d x %d for B %d", p.splits, p.rows, q.B);
+        CHECK(p.ws_bytes == (p.splits > 1 ? int64_t(p.splits) * nd * 4 : 0), "pos_embed workspace %lld", (long long)p.ws_bytes);
+        CHECK(p.splits == 1 || nd <= INT32_MAX, "pos_embed: a split table beyond the column reduction's int");
+        CHECK(sfcvit_pos_embed_bwd_workspace(q.B, q.N, q.D) == p.ws_bytes, "pos_embed workspace entry point");
+        if (total > (int64_t(1) << 24)) continue;              // the workload shapes: geometry only
+        void *x = std::aligned_alloc(16, size_t((total * 2 + 15) / 16 * 16)), *pos = std::aligned_alloc(16, size_t((nd * 2 + 15) / 16 * 16));
+        std::unique_ptr<float[]> dpos(new float[size_t(nd)]);
+        void *ws = p.ws_bytes ? std::aligned_alloc(16, size_t(p.ws_bytes)) : nullptr;
+        CHECK(pos_embed_check_fwd(p, x, pos, x) == SFCVIT_OK, "pos_embed fwd check: %s", sfcvit_last_error());
+        CHECK(pos_embed_check_bwd(p, x, dpos.get(), ws, p.ws_bytes) == SFCVIT_OK, "pos_embed bwd check: %s", sfcvit_last_error());
+        CHECK(pos_embed_check_bwd(p, x, reinterpret_cast<char *>(dpos.get()) + 2, ws, p.ws_bytes) == SFCVIT_OK, "pos_embed: dpos needs no alignment");
+        CHECK(pos_embed_check_fwd(p, nullptr, pos, x) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "null"), "pos_embed: null x accepted");
+        CHECK(pos_embed_check_fwd(p, x, nullptr, x) == SFCVIT_EINVAL, "pos_embed: null pos accepted");
+        CHECK(pos_embed_check_fwd(p, x, pos, nullptr) == SFCVIT_EINVAL, "pos_embed: null y accepted");
+        CHECK(pos_embed_check_fwd(p, static_cast<char *>(x) + 2, pos, x) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "aligned"),
+              "pos_embed: misaligned x accepted");
+        CHECK(pos_embed_check_bwd(p, nullptr, dpos.get(), ws, p.ws_bytes) == SFCVIT_EINVAL, "pos_embed: null dy accepted");
+        CHECK(pos_embed_check_bwd(p, x, nullptr, ws, p.ws_bytes) == SFCVIT_EINVAL, "pos_embed: null dpos accepted");
+        CHECK(pos_embed_check_bwd(p, static_cast<char *>(x) + 8, dpos.get(), ws, p.ws_bytes) == SFCVIT_EINVAL, "pos_embed: misaligned dy accepted");
+        if (p.ws_bytes) {
+            CHECK(pos_embed_check_bwd(p, x, dpos.get(), ws, p.ws_bytes - 1) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "workspace"),
+                  "pos_embed: short workspace accepted");
+            CHECK(pos_embed_check_bwd(p, x, dpos.get(), nullptr, p.ws_bytes) == SFCVIT_EINVAL, "pos_embed: null workspace accepted");
+            CHECK(pos_embed_check_bwd(p, x, dpos.get(), static_cast<char *>(ws) + 4, p.ws_bytes) == SFCVIT_EINVAL, "pos_embed: misaligned workspace accepted");
+        }
+        std::free(x);
+        std::free(pos);
+        std::free(ws);
+    }
+    const PosEmbedPlan b = pos_embed_plan("host_check", 256, 196, 768), l = pos_embed_plan("host_check", 64, 576, 1024);
+    CHECK(b.splits == 1 && b.slabs == 588 && b.imgs == 8 && b.fwd_blocks * b.fwd_groups == 74 * 32, "pos_embed ViT-B geometry");
+    CHECK(l.splits == 1 && l.slabs == 2304 && l.imgs == 8 && l.fwd_blocks * l.fwd_groups == 288 * 8, "pos_embed ViT-L geometry");
+    CHECK(pos_embed_plan("host_check", 67, 3, 8).splits == 2, "pos_embed: (67, 3, 8) must split the batch");
+    const S bad[] = {{0, 1, 8}, {1, 0, 8}, {-1, 1, 8}, {1, 1, 0}, {1, 1, 4}, {1, 1, 12}, {1, 1, -8}, {INT32_MAX, INT32_MAX, INT32_MAX - 7},
+                     {INT32_MAX, 1, 8}};
+    for (const S &q : bad) {
+        const PosEmbedPlan p = pos_embed_plan("host_check", q.B, q.N, q.D);
+        CHECK(p.err == SFCVIT_EINVAL && std::strlen(p.msg) > 0, "pos_embed %d %d %d accepted", q.B, q.N, q.D);
+        CHECK(sfcvit_pos_embed_bwd_workspace(q.B, q.N, q.D) == 0, "pos_embed: workspace of a refused shape");
+    }
+    char name[96];
+    CHECK(sfcvit_last_pos_embed_kernel(name, sizeof(name)) == SFCVIT_OK && !std::strcmp(name, "none"), "pos_embed: last kernel '%s'", name);
+    CHECK(sfcvit_last_pos_embed_kernel(nullptr, 4) == SFCVIT_EINVAL, "pos_embed: null name buffer accepted");
+}
+
 int main() {
     const int curves[] = {SFCVIT_CURVE_HILBERT, SFCVIT_CURVE_Z, SFCVIT_CURVE_MOORE, SFCVIT_CURVE_PEANO, SFCVIT_CURVE_RASTER,
                           SFCVIT_CURVE_SPIRAL, SFCVIT_CURVE_HILBERT_T};
@@ -427,6 +496,7 @@ int main() {
     CHECK(sfcvit_abi_version() == SFCVIT_ABI_VERSION, "abi version");
     check_dispatch();
     check_mask_blocks();
+    check_pos_embed();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     std::printf("host_check ok\n");
     return 0;

@@ -114,6 +114,13 @@ def main():
     ap.add_argument("--token-mix", action="store_true",
                     help="switch the MixerBlock's token-mix branch on (src/models/vit.py:269-271, commented out in the "
                          "reference): a learned mixing along the curve in front of the channel mix.  Checkpoints keep their keys")
+    ap.add_argument("--pos-embed", choices=["learned", "sincos1d", "sincos2d"], default=None,
+                    help="add a positional embedding directly after the tokenizer (src/models/vit.py:360-361, :382, commented "
+                         "out in the reference): a learned table (checkpoints then carry pos_embed [1, N, D]), a fixed sin-cos "
+                         "encoding of the token index along the curve, or a fixed sin-cos encoding of the token's centre in the "
+                         "image (the same whatever curve orders the tokens)")
+    ap.add_argument("--pos-embed-std", type=float, default=1.0,
+                    help="standard deviation of the learned table's initial values (the reference's randn: 1.0)")
     win = ap.add_mutually_exclusive_group()
     win.add_argument("--attn-window", type=int, default=None, metavar="W",
                      help="local attention along the curve: every token attends to the tokens within W positions of it in "
@@ -185,7 +192,8 @@ def main():
     model = VisionTransformer1D(patch_embed=patch_embed, depth=a.depth, n_heads=a.heads, mlp_dim=a.mlp_dim,
                                 num_classes=a.classes,
                                 token_aggregator=a.token_aggregator or False, token_mix=a.token_mix,
-                                attn_mask=attn_mask).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
+                                attn_mask=attn_mask, pos_embed=a.pos_embed,
+                                pos_embed_std=a.pos_embed_std).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
     train_criterion, test_criterion = SoftTargetCrossEntropy(), nn.CrossEntropyLoss()
     optimizer = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=1.0)
     reducer = GradReducer(optimizer, overlap=not a.graph) if world > 1 else None    # --graph: collectives between two graphs

@@ -82,6 +82,8 @@ def _vit_layers(model, images):
     x = model.patch_embed(images)
     if hasattr(model, "ta"):                 # token_aggregator=...: directly after the tokenizer, as the model's forward
         x = model.ta(x)
+    if hasattr(model, "pos_embed"):          # pos_embed=...: after the tokenizer and `ta`, as the model's forward
+        x = F.pos_embed(x, model.pos_embed)
     if isinstance(model, VisionTransformer1D):
         x = model.mlp_mixer(x)
     enc = model.encoder

@@ -6,6 +6,7 @@ needs is local to one function:
   mixer_block    MixerBlock.forward                     (src/models/vit.py:268-273)
   token_mix      its token-mix branch                   (src/models/vit.py:269-271)
   token_aggregator TokenAggregator.forward              (src/models/vit.py:37-42)
+  pos_embed      x + self.pos_embed                     (src/models/vit.py:382, commented out there)
   encoder_layer  nn.TransformerEncoderLayer, post-norm  (torch:nn/modules/transformer.py:951-982)
   predictor_head MultiLayerPredictor(n_layers=2)        (src/models/vit.py:295-319)
   linear, layer_norm, gelu                              generic pieces
@@ -670,6 +671,43 @@ def token_aggregator(x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride=1, eps=1e-5):
 
 
 # ----------------------------------------------------------------------------
+class _PosEmbed(Function):
+    """x + pos over the batch (src/models/vit.py:382, commented out there).  dx is dy itself; the table's gradient is the
+    batch sum of dy, computed only when the table asks for one (a fixed sin-cos buffer launches nothing in backward) and
+    written into the parameter's gradient slot when it has one."""
+
+    @staticmethod
+    def forward(ctx, x, pos):
+        ctx.small = (pos,)
+        return ops.pos_embed_fwd(_c(x), pos)
+
+    @staticmethod
+    def backward(ctx, dy):
+        pos = ctx.small[0]
+        if not getattr(ctx, "needs_input_grad", (True, True))[1]:
+            return dy, None
+        slot = _slot(pos)
+        dpos = ops.pos_embed_bwd(_c(dy), out=slot)
+        return dy, (dpos if slot is not None else dpos.to(_BF16).view(pos.shape))
+
+
+def _pos_table(x, pos):
+    if x.dim() != 3 or pos.dim() not in (2, 3) or (pos.dim() == 3 and pos.shape[0] != 1) or pos.shape[-1] != x.shape[-1]:
+        raise ValueError(f"pos_embed: x [B, N, D] and a table [N, D] or [1, N, D] expected, got {tuple(x.shape)} and {tuple(pos.shape)}")
+    if pos.shape[-2] != x.shape[1]:
+        raise ValueError(f"pos_embed: the activation has {x.shape[1]} tokens and the table {pos.shape[-2]}")
+
+
+def pos_embed(x, pos):
+    """x [B, N, D] + pos ([1, N, D] or [N, D]) -> [B, N, D] bf16: the positional table added to every image."""
+    _pos_table(x, pos)
+    if _traced():
+        from . import library
+        return library.pos_embed(_bf(x), _c(_bf(pos)))
+    return _PosEmbed.apply(_bf(x), _c(_bf(pos)))
+
+
+# ----------------------------------------------------------------------------
 class _EncoderLayer(Function):
     """Post-norm transformer encoder layer (torch:nn/modules/transformer.py:951-982):
          a  = out_proj(attention(in_proj(x)));  x1 = LN1(x + drop1(a))
@@ -946,7 +984,7 @@ def mixed_target_cross_entropy(logits, y_a, y_b, mix):
 
 # ----------------------------------------------------------------------------
 # torch.compile (main.py:284 wraps the model in torch.compile(mode="reduce-overhead")).  The blocks a VisionTransformer{,1D}
-# is made of -- patch_embed, token_aggregator, token_mix, mixer_block, encoder_layer, predictor_head, soft_target_cross_entropy -- are registered as
+# is made of -- patch_embed, token_aggregator, pos_embed, token_mix, mixer_block, encoder_layer, predictor_head, soft_target_cross_entropy -- are registered as
 # `sfcvit::` custom ops with fake kernels and autograd formulas (sfcvit/library.py) and take that path whenever Dynamo is
 # tracing: the model compiles into ONE graph and "reduce-overhead" replays it from a hipGraph.  The remaining pieces
 # (used by the hierarchical tokenizers, altvit and MultiLayerPredictor(n_layers > 2)) stay opaque: Dynamo breaks the graph

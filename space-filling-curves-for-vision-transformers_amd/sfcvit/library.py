@@ -341,6 +341,43 @@ token_aggregator_op.register_autograd(_ta_backward, setup_context=_ta_setup)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# pos_embed (x + table over the batch; backward: dx = dy, dpos = the batch sum of dy, only when the table trains)
+# ----------------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("sfcvit::pos_embed", mutates_args=())
+def pos_embed_op(x: Tensor, pos: Tensor) -> Tensor:
+    return F._PosEmbed.forward(_Ctx(), x, pos)
+
+
+@pos_embed_op.register_fake
+def _(x, pos):
+    return x.new_empty(x.shape, dtype=_BF16)
+
+
+@torch.library.custom_op("sfcvit::pos_embed_bwd", mutates_args=())
+def pos_embed_bwd_op(dy: Tensor, pos: Tensor) -> Tensor:
+    return ops.pos_embed_bwd(dy).to(_BF16).view(pos.shape)      # (no gradient slots inside a traced op: a fresh tensor)
+
+
+@pos_embed_bwd_op.register_fake
+def _(dy, pos):
+    return pos.new_empty(pos.shape)
+
+
+def _pos_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+    ctx.set_materialize_grads(False)
+
+
+def _pos_backward(ctx, dy):
+    (pos,) = ctx.saved_tensors
+    dpos = torch.ops.sfcvit.pos_embed_bwd(dy.contiguous(), pos) if ctx.needs_input_grad[1] else None
+    return dy, dpos
+
+
+pos_embed_op.register_autograd(_pos_backward, setup_context=_pos_setup)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # encoder_layer (post-norm nn.TransformerEncoderLayer; seeds = [] -> drawn inside the op when p > 0)
 # ----------------------------------------------------------------------------------------------------------------------
 _ENC_SAVED = 12     # qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2 (+ hbits, seeds below)
@@ -538,6 +575,10 @@ def token_mix(x, ln_w, ln_b, w1, b1, w2, b2, eps):
 
 def token_aggregator(x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride, eps):
     return torch.ops.sfcvit.token_aggregator(x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride, eps)[0]
+
+
+def pos_embed(x, pos):
+    return torch.ops.sfcvit.pos_embed(x, pos)
 
 
 def encoder_layer(args, n_heads, eps, p, scale):

@@ -55,6 +55,69 @@ def _attach_aggregator(model, option, embed_dim):
         model.ta = ta
 
 
+POS_EMBED_KINDS = ("learned", "sincos1d", "sincos2d")
+
+
+def posemb_sincos_2d(positions, dim, temperature: float = 10000.0, dtype=torch.float32):
+    """Sinusoidal table of token centres `positions` [N, 2] (row, col) in pixels: columns
+    [sin(col w) | cos(col w) | sin(row w) | cos(row w)], w_k = temperature^(-k / (dim / 4)), k = 0 .. dim / 4 - 1.  Angles
+    are formed in float64 and the table is rounded once.  A function of where a token IS, not of its index: two
+    tokenizers over the same centres give the same rows in their own orders."""
+    if dim % 4:
+        raise ValueError("posemb_sincos_2d: dim must be a multiple of 4")
+    q = dim // 4
+    freq = torch.pow(torch.tensor(float(temperature), dtype=torch.float64), -torch.arange(q, dtype=torch.float64) / q)
+    pos = positions.to(torch.float64)
+    col, row = torch.outer(pos[:, 1], freq), torch.outer(pos[:, 0], freq)
+    return torch.cat((col.sin(), col.cos(), row.sin(), row.cos()), dim=1).to(dtype)
+
+
+def _attach_pos_embed(model, kind, std):
+    """The models' `pos_embed` keyword (vit.py:360-361, commented out there), on request only and constructed LAST, after
+    `ta`: every other parameter then draws the same initial values as without it, and the default module tree is today's.
+    "learned" is the reference's line, a Parameter [1, N, D] = randn * std; "sincos1d" / "sincos2d" are persistent buffers
+    under the same key (no gradient, nothing launched in backward)."""
+    if kind is None or kind is False:
+        return
+    if kind not in POS_EMBED_KINDS:
+        raise ValueError(f"pos_embed={kind!r}: None, {', '.join(map(repr, POS_EMBED_KINDS))} expected")
+    n, d = model.patch_embed.n_patches, model.patch_embed.embed_dim
+    if d % 8:
+        raise ValueError(f"pos_embed={kind!r}: embed_dim={d} must be a multiple of 8 (the kernels move 16-byte vectors of 8 channels)")
+    if kind == "learned":
+        model.pos_embed = nn.Parameter(torch.randn(1, n, d) * std)
+        return
+    if kind == "sincos1d":
+        from .altvit import posemb_sincos_1d
+        table = posemb_sincos_1d(n, d)
+    else:
+        from ..analysis import token_positions                  # (analysis imports this module: resolved at call time)
+        table = posemb_sincos_2d(token_positions(model.patch_embed), d)
+    model.register_buffer("pos_embed", table.unsqueeze(0), persistent=True)
+
+
+def permute_pos_embed(table, from_tokenizer, to_tokenizer):
+    """A positional table ([1, N, D] or [N, D]) carried from one token order to another: row i of the result is the row
+    of `table` whose token has the centre of `to_tokenizer`'s token i.  Both tokenizers must cover the same set of token
+    centres (Hilbert -> Z -> raster at one geometry): anything else is a ValueError.  This is what lets a checkpoint
+    trained along one curve start a run along another; a change of resolution is not handled.  Host-only."""
+    from ..analysis import token_positions
+    src, dst = token_positions(from_tokenizer), token_positions(to_tokenizer)
+    if src.shape != dst.shape or table.shape[-2] != src.shape[0] or table.dim() not in (2, 3):
+        raise ValueError(f"permute_pos_embed: a table of {table.shape[-2] if table.dim() >= 2 else '?'} rows between tokenizers of "
+                         f"{src.shape[0]} and {dst.shape[0]} tokens")
+    where = {(float(r), float(c)): i for i, (r, c) in enumerate(src.tolist())}
+    if len(where) != src.shape[0]:
+        raise ValueError("permute_pos_embed: two tokens of the source tokenizer share a centre")
+    try:
+        index = torch.tensor([where[(float(r), float(c))] for r, c in dst.tolist()], dtype=torch.long)
+    except KeyError:
+        raise ValueError("permute_pos_embed: the tokenizers do not cover the same token centres (different geometry)") from None
+    if len(set(index.tolist())) != index.numel():
+        raise ValueError("permute_pos_embed: two tokens of the target tokenizer share a centre")
+    return table.index_select(table.dim() - 2, index.to(table.device))
+
+
 class TransformerSeqEncoder(nn.Module):
     """vit.py:177-242: `depth` post-norm nn.TransformerEncoderLayer (relu, eps 1e-5).  forward(x, mask=None) mirrors
     nn.TransformerEncoder.forward(src, mask): the mask goes to every layer (the reference's CustomTransformerEncoder,
@@ -195,9 +258,14 @@ class VisionTransformer(nn.Module):
     """vit.py:325-385 (`embed_dim` is ignored there too: taken from the tokenizer, :351)."""
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
-                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, attn_mask=None):
+                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, attn_mask=None,
+                 pos_embed=None, pos_embed_std=1.0):
         """attn_mask: None, or a mask for every encoder layer (ops.as_attention_mask's forms; sfcvit.masks builds windows).
-        Held outside state_dict: checkpoint keys are the reference's with or without it."""
+        Held outside state_dict: checkpoint keys are the reference's with or without it.
+        pos_embed: None / False (the reference as shipped), "learned" (vit.py:360-361: a Parameter [1, N, D] = randn *
+        pos_embed_std), "sincos1d" (fixed, of the token index along the curve) or "sincos2d" (fixed, of the token's centre in
+        the image: the same whatever curve orders the tokens).  Added directly after the tokenizer and, if present, `ta`
+        (vit.py:380-383): before the encoder here, before `mlp_mixer` in VisionTransformer1D -- one place for both models."""
         super().__init__()
         self.patch_embed = patch_embed
         embed_dim = patch_embed.embed_dim
@@ -208,12 +276,15 @@ class VisionTransformer(nn.Module):
         self.mlp_head = MultiLayerPredictor(embed_dim, self.patch_embed.n_patches, n_layers=2,
                                             num_classes=num_classes, dropout_p=head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
+        _attach_pos_embed(self, pos_embed, pos_embed_std)
 
     def forward(self, x, mix=None):
         """mix: a sfcvit.training.BatchMix applied to the image batch by the tokenizer, or None."""
         x = self.patch_embed(x) if mix is None else self.patch_embed(x, mix=mix)
         if hasattr(self, "ta"):
             x = self.ta(x)                                      # vit.py:381
+        if hasattr(self, "pos_embed"):
+            x = F.pos_embed(x, self.pos_embed)                  # vit.py:382
         x = self.encoder(x, mask=self.attn_mask)
         return self.mlp_head(x)
 
@@ -224,8 +295,10 @@ class VisionTransformer1D(nn.Module):
     the only pre-encoder component that sees absolute position in curve order."""
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
-                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False, attn_mask=None):
-        """attn_mask: as in VisionTransformer."""
+                 num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False, attn_mask=None,
+                 pos_embed=None, pos_embed_std=1.0):
+        """attn_mask, pos_embed, pos_embed_std: as in VisionTransformer (the table is added directly after the tokenizer and,
+        if present, `ta`: before `mlp_mixer`)."""
         super().__init__()
         self.patch_embed = patch_embed
         embed_dim = patch_embed.embed_dim
@@ -238,12 +311,15 @@ class VisionTransformer1D(nn.Module):
         self.mlp_head = MultiLayerPredictor(embed_dim, self.patch_embed.n_patches, n_layers=2,
                                             dropout_p=head_dropout_p, num_classes=num_classes)
         _attach_aggregator(self, token_aggregator, embed_dim)
+        _attach_pos_embed(self, pos_embed, pos_embed_std)
 
     def forward(self, x, mix=None):
         """mix: a sfcvit.training.BatchMix applied to the image batch by the tokenizer, or None."""
         x = self.patch_embed(x) if mix is None else self.patch_embed(x, mix=mix)
         if hasattr(self, "ta"):
             x = self.ta(x)
+        if hasattr(self, "pos_embed"):
+            x = F.pos_embed(x, self.pos_embed)
         x = self.mlp_mixer(x)
         x = self.encoder(x, mask=self.attn_mask)
         return self.mlp_head(x)

@@ -965,6 +965,50 @@ def dwconv1d_bwd(du, x, w, stride=1, want_dx=True, want_dw=True, want_db=True, o
 
 
 # ----------------------------------------------------------------------------
+# positional embedding: one table row per token index, added to every image (vit.py:360-361, :382)
+# ----------------------------------------------------------------------------
+def last_pos_embed_kernel():
+    buf = ctypes.create_string_buffer(96)
+    lib.sfcvit_last_pos_embed_kernel(buf, 96)
+    return buf.value.decode()
+
+
+def _pos_table(pos, N, D, name):
+    """[N, D] or [1, N, D], contiguous bf16."""
+    _need(pos, _BF16, name)
+    if tuple(pos.shape) not in ((N, D), (1, N, D)):
+        raise ValueError(f"{name}: a table of {N} tokens x {D} channels expected ([{N}, {D}] or [1, {N}, {D}]), got {tuple(pos.shape)}")
+
+
+def pos_embed_fwd(x, pos):
+    """y[b, n, :] = x[b, n, :] + pos[n, :] on x [B, N, D] bf16, pos [N, D] or [1, N, D] bf16 -> [B, N, D] bf16 (one rounding)."""
+    _need(x, _BF16, "pos_embed x", 3)
+    B, N, D = x.shape
+    _pos_table(pos, N, D, "pos_embed pos")
+    y = torch.empty_like(x)
+    _launch("pos_embed_fwd", 4.0 * x.numel() + 2.0 * pos.numel(),
+            lambda: check(lib.sfcvit_pos_embed_fwd(_p(x), _p(pos), _p(y), B, N, D, _stream()), "sfcvit_pos_embed_fwd"))
+    return y
+
+
+def pos_embed_bwd(dy, out=None):
+    """-> dpos [N, D] = sum_b dy[b] for dy [B, N, D] bf16: fp32, or -- with out = a contiguous bf16 tensor of N * D elements,
+    e.g. a view of a flat gradient buffer -- written as bf16 in place and returned."""
+    _need(dy, _BF16, "pos_embed dy", 3)
+    B, N, D = dy.shape
+    if out is not None and (out.dtype != _BF16 or out.numel() != N * D or not out.is_contiguous()):
+        raise ValueError("pos_embed_bwd out: a contiguous bf16 tensor of the table's size expected")
+    dpos = out if out is not None else torch.empty((N, D), device=dy.device, dtype=torch.float32)
+    nbytes = lib.sfcvit_pos_embed_bwd_workspace(B, N, D)
+    ws = torch.empty(nbytes, device=dy.device, dtype=torch.uint8) if nbytes else None
+    with _Deferring([dpos], [ws]):
+        _launch("pos_embed_bwd", 2.0 * dy.numel() + float(dpos.numel() * dpos.element_size()) + 2.0 * nbytes,
+                lambda: check(lib.sfcvit_pos_embed_bwd(_p(dy), _p(dpos), int(out is not None), B, N, D, _p(ws), nbytes, _stream()),
+                              "sfcvit_pos_embed_bwd"))
+    return dpos
+
+
+# ----------------------------------------------------------------------------
 # token mixing: GEMMs along the token axis of [B, N, D] (MixerBlock.token_mix)
 # ----------------------------------------------------------------------------
 def last_tokmix_kernel():
