@@ -608,6 +608,39 @@ int sfcvit_pos_embed_bwd(const void *dy, void *dpos, int grad_bf16, int B, int N
 int sfcvit_last_pos_embed_kernel(char *buf, int n);
 
 /* ------------------------------------------------------------------------
+ * CLS token and token pooling
+ *   the reference's commented-out learnable [CLS] token (src/models/vit.py:209-210, :237-238: `torch.cat([cls, x], dim=1)`
+ *   in front of the encoder), the read-out of token 0 its docstring promises, and the token mean of altvit.py.
+ *
+ *   Every tensor is bf16 with D contiguous.  Supported: B, N (T) >= 1, D >= 8 and D % 8 == 0 (16-byte vectors), byte counts
+ *   within int64; everything else is SFCVIT_EINVAL, decided before any HIP call.  Every tensor and the workspace must be
+ *   16-byte aligned, except dcls, which needs the alignment of its element only (a slot of a flat gradient buffer).
+ *   Nothing allocates, synchronises or copies to the host: graph-capturable.  No atomics, one writer per output element:
+ *   two runs give the same bits.
+ * ---------------------------------------------------------------------- */
+/* x [B, N, D], cls [D] -> y [B, N + 1, D]:  y[b, 0, :] = cls, y[b, 1 + n, :] = x[b, n, :].  A copy of bits.  y must not
+ * overlap x. */
+int sfcvit_cls_prepend_fwd(const void *x, const void *cls, void *y, int B, int N, int D, void *stream);
+/* HOST: workspace bytes of the backward call (0 for refused arguments, and 0 up to 2048 images). */
+int64_t sfcvit_cls_prepend_bwd_workspace(int B, int N, int D);
+/* dy [B, N + 1, D] -> dx [B, N, D] = dy[:, 1:, :] (a copy; dx may be NULL: dcls alone) and dcls[d] = sum_b dy[b, 0, d],
+ * summed in fp32 in a fixed order and written as fp32, or as bf16 when grad_bf16 != 0 (a view of a flat gradient buffer).
+ * Where the plan splits the batch (workspace > 0) the final reduction joins the deferred reductions above when deferral is
+ * on. */
+int sfcvit_cls_prepend_bwd(const void *dy, void *dx, void *dcls, int grad_bf16, int B, int N, int D, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+/* x [B, T, D] -> y [B, D]:  y[b, :] = bf16( (sum over t in [first, first + count) of float(x[b, t, :])) / count ): an fp32 sum
+ * in a fixed order, one fp32 division, one rounding.  Needs 0 <= first, count >= 1, first + count <= T.  count == 1 copies
+ * the row's bits (the CLS read-out: first = 0). */
+int sfcvit_token_pool_fwd(const void *x, void *y, int B, int T, int D, int first, int count, void *stream);
+/* dy [B, D] -> dx [B, T, D]:  dx[b, t, :] = bf16(float(dy[b, :]) / count) for t in [first, first + count) (the bits of dy
+ * when count == 1) and +0 elsewhere: every element of dx is written. */
+int sfcvit_token_pool_bwd(const void *dy, void *dx, int B, int T, int D, int first, int count, void *stream);
+/* HOST: name of the kernel the calling thread's last sfcvit_cls_prepend_* / sfcvit_token_pool_* launched, as rocprofv3
+ * prints it (e.g. "token_pool_fwd_kernel<16>": 16 lanes across columns, 256 / 16 = 16 lanes across the token range). */
+int sfcvit_last_token_pool_kernel(char *buf, int n);
+
+/* ------------------------------------------------------------------------
  * Token mixing: GEMMs along the token axis of [B, N, D]
  *   replaces the token-mix branch of MixerBlock.forward (src/models/vit.py:269-271, commented out there):
  *       x = x + token_mix(token_mix_ln(x).transpose(1, 2)).transpose(1, 2)

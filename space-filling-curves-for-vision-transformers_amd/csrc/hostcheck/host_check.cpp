@@ -1,7 +1,7 @@
 // Sanitizer driver for the HOST-ONLY code of libsfcvit_hip.so ("Race detection / sanitizers": GPU ASan is not
 // available on this pool, so the native host code gets a CPU-side -fsanitize=address,undefined build of its own):
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
-//   host part), the error path of common.cpp, and the mask validation and block map of attention_masked.cpp (check_mask_blocks), the plan and refusals of pos_embed.cpp (check_pos_embed), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid,
+//   host part), the error path of common.cpp, and the mask validation and block map of attention_masked.cpp (check_mask_blocks), the plan and refusals of pos_embed.cpp (check_pos_embed) and of token_pool.cpp (check_token_pool), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid,
 //   splits and post passes each GEMM / attention shape of the benchmarked models gets).  Every output buffer is a heap block of EXACTLY the documented size, so that
 // an off-by-one in a generator or in the descriptor writer is a heap-buffer-overflow report instead of silent corruption.
 // Built and run by `make asan` (tests/test_host_cpu.py::test_host_code_is_clean_under_address_sanitizer).  No GPU call.
@@ -17,6 +17,7 @@
 #include "../../../include/sfcvit.h"
 #include "../dispatch.h"
 #include "../pos_embed.h"
+#include "../token_pool.h"
 
 static int g_fail = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { std::fprintf(stderr, "host_check: " __VA_ARGS__); std::fprintf(stderr, " (%s:%d)\n", __FILE__, __LINE__); g_fail++; } } while (0)
@@ -428,6 +429,105 @@ static void check_pos_embed() {
     CHECK(sfcvit_last_pos_embed_kernel(nullptr, 4) == SFCVIT_EINVAL, "pos_embed: null name buffer accepted");
 }
 
+// cls_prepend_plan / token_pool_plan and their pointer checks (token_pool.cpp): the geometry at the workload shapes and the
+// edge shapes of the tests, and every refusal, with heap buffers of exactly the documented sizes.  The checks read no byte
+// of them; what is pinned is that every accepted geometry stays inside them.
+static void check_token_pool() {
+    struct S { int B, N, D; };
+    const S shapes[] = {{1, 1, 8}, {2, 1, 8}, {3, 5, 72}, {2, 65, 200}, {67, 3, 8}, {5, 4, 192}, {2, 196, 768}, {2, 576, 1024},
+                        {256, 196, 768}, {64, 576, 1024}, {4096, 1, 8}, {100000, 2, 8}};
+    for (const S &q : shapes) {
+        const ClsPrependPlan p = cls_prepend_plan("host_check", q.B, q.N, q.D);
+        CHECK(p.err == SFCVIT_OK, "cls_prepend %d %d %d refused: %s", q.B, q.N, q.D, p.msg);
+        if (p.err) continue;
+        const int64_t xn = int64_t(q.B) * q.N * q.D, yn = int64_t(q.B) * (q.N + 1) * q.D;
+        CHECK(p.dv * 8 == q.D && p.xv == int64_t(q.N) * p.dv, "cls_prepend: vectors");
+        CHECK(int64_t(p.fwd_blocks) * TP_THREADS >= p.xv + p.dv && int64_t(p.fwd_blocks - 1) * TP_THREADS < p.xv + p.dv, "cls_prepend fwd blocks");
+        CHECK(int64_t(p.bwd_blocks) * TP_THREADS >= p.xv && int64_t(p.bwd_blocks - 1) * TP_THREADS < p.xv, "cls_prepend bwd blocks");
+        CHECK((p.imgs == 1 || p.imgs == 2 || p.imgs == 4 || p.imgs == 8) && int64_t(p.groups) * p.imgs >= q.B &&
+              int64_t(p.groups - 1) * p.imgs < q.B && p.groups <= 65535, "cls_prepend groups %d x %d for B %d", p.groups, p.imgs, q.B);
+        CHECK(int64_t(p.slabs) * CP_CV >= p.dv && int64_t(p.slabs - 1) * CP_CV < p.dv, "cls_prepend dcls slabs");
+        CHECK(p.rows % CP_RL == 0 && p.rows <= CP_MAX_ROWS && int64_t(p.splits) * p.rows >= q.B && int64_t(p.splits - 1) * p.rows < q.B &&
+              p.splits <= 65535, "cls_prepend dcls ranges %d x %d for B %d", p.splits, p.rows, q.B);
+        CHECK(p.ws_bytes == (p.splits > 1 ? int64_t(p.splits) * q.D * 4 : 0), "cls_prepend workspace %lld", (long long)p.ws_bytes);
+        CHECK(sfcvit_cls_prepend_bwd_workspace(q.B, q.N, q.D) == p.ws_bytes, "cls_prepend workspace entry point");
+        // pool: every (first, count) of the tests
+        const int T = q.N + 1;
+        const int fc[][2] = {{0, 1}, {0, T}, {1, T - 1}, {T - 1, 1}};
+        for (const auto &r : fc) {
+            if (r[1] < 1) continue;
+            const TokenPoolPlan t = token_pool_plan("host_check", q.B, T, q.D, r[0], r[1]);
+            CHECK(t.err == SFCVIT_OK, "token_pool %d %d %d [%d, +%d) refused: %s", q.B, T, q.D, r[0], r[1], t.msg);
+            CHECK((t.cv == 8 || t.cv == 16 || t.cv == 32) && t.cv * t.tl == TP_THREADS && t.dv * 8 == q.D, "token_pool lanes %d x %d", t.cv, t.tl);
+            CHECK(int64_t(t.slabs) * t.cv >= t.dv && int64_t(t.slabs - 1) * t.cv < t.dv && t.slabs <= 65535, "token_pool slabs");
+            CHECK(int64_t(t.row_blocks) * TP_THREADS >= t.dv && int64_t(t.row_blocks - 1) * TP_THREADS < t.dv, "token_pool row blocks");
+            CHECK(t.row_copy == (r[1] == 1), "token_pool: count == 1 is the row copy");
+        }
+        if (yn > (int64_t(1) << 24)) continue;                 // the workload shapes: geometry only
+        void *x = std::aligned_alloc(16, size_t((xn * 2 + 15) / 16 * 16)), *y = std::aligned_alloc(16, size_t((yn * 2 + 15) / 16 * 16));
+        void *cls = std::aligned_alloc(16, size_t(q.D) * 2);
+        std::unique_ptr<float[]> dcls(new float[size_t(q.D)]);
+        void *ws = p.ws_bytes ? std::aligned_alloc(16, size_t(p.ws_bytes)) : nullptr;
+        CHECK(cls_prepend_check_fwd(p, x, cls, y, q.B, q.N, q.D) == SFCVIT_OK, "cls_prepend fwd check: %s", sfcvit_last_error());
+        CHECK(cls_prepend_check_bwd(p, y, x, dcls.get(), ws, p.ws_bytes) == SFCVIT_OK, "cls_prepend bwd check: %s", sfcvit_last_error());
+        CHECK(cls_prepend_check_bwd(p, y, nullptr, dcls.get(), ws, p.ws_bytes) == SFCVIT_OK, "cls_prepend: dx may be null");
+        CHECK(cls_prepend_check_bwd(p, y, x, reinterpret_cast<char *>(dcls.get()) + 2, ws, p.ws_bytes) == SFCVIT_OK, "cls_prepend: dcls needs no alignment");
+        CHECK(cls_prepend_check_fwd(p, nullptr, cls, y, q.B, q.N, q.D) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "null"), "cls_prepend: null x accepted");
+        CHECK(cls_prepend_check_fwd(p, x, nullptr, y, q.B, q.N, q.D) == SFCVIT_EINVAL, "cls_prepend: null cls accepted");
+        CHECK(cls_prepend_check_fwd(p, x, cls, nullptr, q.B, q.N, q.D) == SFCVIT_EINVAL, "cls_prepend: null y accepted");
+        CHECK(cls_prepend_check_fwd(p, static_cast<char *>(x) + 2, cls, y, q.B, q.N, q.D) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "aligned"),
+              "cls_prepend: misaligned x accepted");
+        CHECK(cls_prepend_check_fwd(p, y, cls, y, q.B, q.N, q.D) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "overlaps"), "cls_prepend: y == x accepted");
+        CHECK(cls_prepend_check_fwd(p, static_cast<char *>(y) + 16, cls, y, q.B, q.N, q.D) == SFCVIT_EINVAL, "cls_prepend: x inside y accepted");
+        CHECK(cls_prepend_check_bwd(p, nullptr, x, dcls.get(), ws, p.ws_bytes) == SFCVIT_EINVAL, "cls_prepend: null dy accepted");
+        CHECK(cls_prepend_check_bwd(p, y, x, nullptr, ws, p.ws_bytes) == SFCVIT_EINVAL, "cls_prepend: null dcls accepted");
+        CHECK(cls_prepend_check_bwd(p, static_cast<char *>(y) + 8, x, dcls.get(), ws, p.ws_bytes) == SFCVIT_EINVAL, "cls_prepend: misaligned dy accepted");
+        CHECK(cls_prepend_check_bwd(p, y, static_cast<char *>(x) + 8, dcls.get(), ws, p.ws_bytes) == SFCVIT_EINVAL, "cls_prepend: misaligned dx accepted");
+        if (p.ws_bytes) {
+            CHECK(cls_prepend_check_bwd(p, y, x, dcls.get(), ws, p.ws_bytes - 1) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "workspace"),
+                  "cls_prepend: short workspace accepted");
+            CHECK(cls_prepend_check_bwd(p, y, x, dcls.get(), nullptr, p.ws_bytes) == SFCVIT_EINVAL, "cls_prepend: null workspace accepted");
+            CHECK(cls_prepend_check_bwd(p, y, x, dcls.get(), static_cast<char *>(ws) + 4, p.ws_bytes) == SFCVIT_EINVAL, "cls_prepend: misaligned workspace accepted");
+        }
+        const TokenPoolPlan t = token_pool_plan("host_check", q.B, T, q.D, 0, T);
+        CHECK(token_pool_check(t, "token_pool_fwd", y, x) == SFCVIT_OK, "token_pool check: %s", sfcvit_last_error());
+        CHECK(token_pool_check(t, "token_pool_fwd", nullptr, x) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "null"), "token_pool: null x accepted");
+        CHECK(token_pool_check(t, "token_pool_bwd", y, nullptr) == SFCVIT_EINVAL, "token_pool: null dx accepted");
+        CHECK(token_pool_check(t, "token_pool_fwd", static_cast<char *>(y) + 2, x) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "aligned"),
+              "token_pool: misaligned x accepted");
+        std::free(x);
+        std::free(y);
+        std::free(cls);
+        std::free(ws);
+    }
+    const ClsPrependPlan b = cls_prepend_plan("host_check", 256, 196, 768), l = cls_prepend_plan("host_check", 64, 576, 1024);
+    CHECK(b.splits == 1 && b.slabs == 12 && b.imgs == 8 && b.fwd_blocks == 74 && b.groups == 32 && b.ws_bytes == 0, "cls_prepend ViT-B geometry");
+    CHECK(l.splits == 1 && l.slabs == 16 && l.imgs == 8 && l.fwd_blocks == 289 && l.groups == 8 && l.ws_bytes == 0, "cls_prepend ViT-L geometry");
+    CHECK(cls_prepend_plan("host_check", 4096, 1, 8).splits == 2 && cls_prepend_plan("host_check", 2049, 1, 8).splits == 2 &&
+          cls_prepend_plan("host_check", 2048, 1, 8).splits == 1, "cls_prepend: the batch splits above 2048 images");
+    const TokenPoolPlan tb = token_pool_plan("host_check", 256, 197, 768, 1, 196), tl = token_pool_plan("host_check", 64, 577, 1024, 1, 576);
+    CHECK(tb.cv == 16 && tb.tl == 16 && tb.slabs == 6, "token_pool ViT-B geometry %d x %d, %d slabs", tb.cv, tb.tl, tb.slabs);
+    CHECK(tl.cv == 8 && tl.tl == 32 && tl.slabs == 16, "token_pool ViT-L geometry %d x %d, %d slabs", tl.cv, tl.tl, tl.slabs);
+    const S bad[] = {{0, 1, 8}, {1, 0, 8}, {-1, 1, 8}, {1, 1, 0}, {1, 1, 4}, {1, 1, 12}, {1, 1, -8}, {INT32_MAX, INT32_MAX, INT32_MAX - 7},
+                     {INT32_MAX, 1, 8}};
+    for (const S &q : bad) {
+        const ClsPrependPlan p = cls_prepend_plan("host_check", q.B, q.N, q.D);
+        CHECK(p.err == SFCVIT_EINVAL && std::strlen(p.msg) > 0, "cls_prepend %d %d %d accepted", q.B, q.N, q.D);
+        CHECK(sfcvit_cls_prepend_bwd_workspace(q.B, q.N, q.D) == 0, "cls_prepend: workspace of a refused shape");
+        if (q.B == INT32_MAX && q.N == 1) continue;            // (the pool puts the batch on grid.x: accepted)
+        const TokenPoolPlan t = token_pool_plan("host_check", q.B, q.N, q.D, 0, 1);
+        CHECK(t.err == SFCVIT_EINVAL && std::strlen(t.msg) > 0, "token_pool %d %d %d accepted", q.B, q.N, q.D);
+    }
+    const int badr[][2] = {{-1, 1}, {0, 0}, {0, -1}, {0, 6}, {5, 1}, {3, 3}, {INT32_MAX, INT32_MAX}};
+    for (const auto &r : badr) {
+        const TokenPoolPlan t = token_pool_plan("host_check", 2, 5, 8, r[0], r[1]);
+        CHECK(t.err == SFCVIT_EINVAL && std::strstr(t.msg, "range"), "token_pool: tokens [%d, +%d) of 5 accepted", r[0], r[1]);
+    }
+    char name[96];
+    CHECK(sfcvit_last_token_pool_kernel(name, sizeof(name)) == SFCVIT_OK && !std::strcmp(name, "none"), "token_pool: last kernel '%s'", name);
+    CHECK(sfcvit_last_token_pool_kernel(nullptr, 4) == SFCVIT_EINVAL, "token_pool: null name buffer accepted");
+}
+
 int main() {
     const int curves[] = {SFCVIT_CURVE_HILBERT, SFCVIT_CURVE_Z, SFCVIT_CURVE_MOORE, SFCVIT_CURVE_PEANO, SFCVIT_CURVE_RASTER,
                           SFCVIT_CURVE_SPIRAL, SFCVIT_CURVE_HILBERT_T};
@@ -497,6 +597,7 @@ int main() {
     check_dispatch();
     check_mask_blocks();
     check_pos_embed();
+    check_token_pool();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     std::printf("host_check ok\n");
     return 0;

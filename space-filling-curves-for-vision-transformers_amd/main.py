@@ -121,6 +121,12 @@ def main():
                          "image (the same whatever curve orders the tokens)")
     ap.add_argument("--pos-embed-std", type=float, default=1.0,
                     help="standard deviation of the learned table's initial values (the reference's randn: 1.0)")
+    ap.add_argument("--pool", choices=["cls", "mean"], default=None,
+                    help="a pooled classifier head, LayerNorm + Linear on one vector per image, in place of the factorised head "
+                         "over all tokens: 'cls' puts a learnable [CLS] token in front of the encoder's sequence "
+                         "(src/models/vit.py:209-210, :237-238, commented out in the reference; checkpoints then carry "
+                         "encoder.cls_token) and reads it out, 'mean' reads the mean of the tokens.  The head then holds no weight "
+                         "per token index")
     win = ap.add_mutually_exclusive_group()
     win.add_argument("--attn-window", type=int, default=None, metavar="W",
                      help="local attention along the curve: every token attends to the tokens within W positions of it in "
@@ -182,10 +188,12 @@ def main():
         from sfcvit import masks
         from sfcvit.ops import AttentionMask
         if a.attn_window is not None:
-            attn_mask = AttentionMask(masks.curve_window(patch_embed.n_patches, a.attn_window))
+            window = masks.curve_window(patch_embed.n_patches, a.attn_window)
         else:
             from sfcvit.analysis import token_positions
-            attn_mask = AttentionMask(masks.image_window(token_positions(patch_embed), a.attn_window_2d))
+            window = masks.image_window(token_positions(patch_embed), a.attn_window_2d)
+        # --pool cls: the CLS token sees and is seen by every token; the window holds between the patch tokens
+        attn_mask = AttentionMask(masks.with_cls_token(window) if a.pool == "cls" else window)
         if rank == 0:
             print(f"attention mask: {attn_mask.visited_blocks}/{attn_mask.total_blocks} blocks of 64 x 64 visited "
                   f"(N = {attn_mask.n_tokens})")
@@ -193,7 +201,7 @@ def main():
                                 num_classes=a.classes,
                                 token_aggregator=a.token_aggregator or False, token_mix=a.token_mix,
                                 attn_mask=attn_mask, pos_embed=a.pos_embed,
-                                pos_embed_std=a.pos_embed_std).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
+                                pos_embed_std=a.pos_embed_std, pool=a.pool).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
     train_criterion, test_criterion = SoftTargetCrossEntropy(), nn.CrossEntropyLoss()
     optimizer = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=1.0)
     reducer = GradReducer(optimizer, overlap=not a.graph) if world > 1 else None    # --graph: collectives between two graphs
@@ -218,6 +226,8 @@ def main():
                 augment.load_state_dict(ck["augment_state_dict"])       # the draw stream goes on where it stopped
     if a.attention_report and attn_mask is not None:
         raise SystemExit("--attention-report measures unmasked attention; it cannot be combined with --attn-window / --attn-window-2d")
+    if a.attention_report and a.pool == "cls":
+        raise SystemExit("--attention-report has no place in the image for the CLS token; it cannot be combined with --pool cls")
     if a.attention_report and rank == 0:
         import json
         from sfcvit.analysis import attention_report, report_summary

@@ -161,6 +161,12 @@ SIGNATURES = {
     "sfcvit_pos_embed_bwd_workspace": (c_int64, [c_int, c_int, c_int]),
     "sfcvit_pos_embed_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "sfcvit_last_pos_embed_kernel": (c_int, [ctypes.c_char_p, c_int]),
+    "sfcvit_cls_prepend_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "sfcvit_cls_prepend_bwd_workspace": (c_int64, [c_int, c_int, c_int]),
+    "sfcvit_cls_prepend_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "sfcvit_token_pool_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "sfcvit_token_pool_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "sfcvit_last_token_pool_kernel": (c_int, [ctypes.c_char_p, c_int]),
     "sfcvit_tokmix_left": (c_int, [ctypes.POINTER(TokmixArgs), c_void_p]),
     "sfcvit_tokmix_wgrad_workspace": (c_int64, [c_int, c_int, c_int, c_int]),
     "sfcvit_tokmix_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64,

@@ -16,7 +16,7 @@ import torch
 from . import functional as F
 from . import ops
 from .models import altvit
-from .models.vit import VisionTransformer, VisionTransformer1D
+from .models.vit import PooledHead, VisionTransformer, VisionTransformer1D
 from .tokenizers import embeddings
 
 
@@ -68,7 +68,9 @@ def _model_positions(model):
 
 
 def _head_eval(head, x):
-    """MultiLayerPredictor at dropout 0 without reading or writing `head.training`."""
+    """MultiLayerPredictor at dropout 0 without reading or writing `head.training`; a PooledHead has no dropout."""
+    if isinstance(head, PooledHead):
+        return head(x)
     if head._n_layers == 2:
         ln, fact, fc = head[0], head[1], head[4]
         return F.predictor_head(x, ln.weight, ln.bias, fact.W_emb, fact.W_seq, fc.weight, fc.bias, ln.eps, dropout_p=0.0)
@@ -140,6 +142,9 @@ def attention_report(model, images, layers=None, maps=False, head_mean=True, row
                          "map": [B, N, N] mean over heads, or [B, H, N, N] with head_mean=False   with maps=True}, ...]}
     maps: True (fp32) or a dtype (torch.float32 / torch.bfloat16).  positions: [N, 2] token centres when the model's
     tokenizer cannot say (default: token_positions).  Supports VisionTransformer, VisionTransformer1D, SimpleViT, HilbertViT."""
+    if hasattr(getattr(model, "encoder", None), "cls_token"):
+        raise NotImplementedError("attention_report: the model was built with pool='cls'; the CLS token has no place in the "
+                                  "image, so distances over its N + 1 tokens would be wrong")
     if getattr(model, "attn_mask", None) is not None:
         raise NotImplementedError("attention_report: the model was built with attn_mask=; the probe kernels rebuild the attention "
                                   "map from q, k and lse WITHOUT a mask and would report wrong maps and distances")

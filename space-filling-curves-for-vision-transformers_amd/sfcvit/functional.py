@@ -7,6 +7,9 @@ needs is local to one function:
   token_mix      its token-mix branch                   (src/models/vit.py:269-271)
   token_aggregator TokenAggregator.forward              (src/models/vit.py:37-42)
   pos_embed      x + self.pos_embed                     (src/models/vit.py:382, commented out there)
+  cls_prepend    torch.cat([cls_token.expand(B, -1, -1), x], dim=1)  (src/models/vit.py:237-238, commented out there)
+  token_pool     x[:, 0] / x[:, a:b].mean(dim=1)        (the read-out of a pooled classifier head)
+  pooled_head    LayerNorm + Linear on the pooled token
   encoder_layer  nn.TransformerEncoderLayer, post-norm  (torch:nn/modules/transformer.py:951-982)
   predictor_head MultiLayerPredictor(n_layers=2)        (src/models/vit.py:295-319)
   linear, layer_norm, gelu                              generic pieces
@@ -708,6 +711,73 @@ def pos_embed(x, pos):
 
 
 # ----------------------------------------------------------------------------
+class _ClsPrepend(Function):
+    """cat([cls, x], dim=1) (src/models/vit.py:237-238, commented out there).  dx is dy without its first row; the token's
+    gradient is the batch sum of that row, written into the parameter's gradient slot when it has one."""
+
+    @staticmethod
+    def forward(ctx, x, cls):
+        ctx.small = (cls,)
+        return ops.cls_prepend_fwd(_c(x), cls)
+
+    @staticmethod
+    def backward(ctx, dy):
+        cls = ctx.small[0]
+        need = getattr(ctx, "needs_input_grad", (True, True))
+        if not need[1]:
+            return dy[:, 1:], None
+        slot = _slot(cls)
+        dx, dcls = ops.cls_prepend_bwd(_c(dy), want_dx=need[0], out=slot)
+        return dx, (dcls if slot is not None else dcls.to(_BF16).view(cls.shape))
+
+
+def cls_prepend(x, cls):
+    """x [B, N, D], cls ([1, 1, D] or [D]) -> [B, N + 1, D] bf16 with the token in front of every image's sequence."""
+    if x.dim() != 3 or cls.numel() != x.shape[-1] or tuple(cls.shape) not in ((x.shape[-1],), (1, 1, x.shape[-1])):
+        raise ValueError(f"cls_prepend: x [B, N, D] and a token [D] or [1, 1, D] expected, got {tuple(x.shape)} and {tuple(cls.shape)}")
+    if _traced():
+        from . import library
+        return library.cls_prepend(_bf(x), _c(_bf(cls)))
+    return _ClsPrepend.apply(_bf(x), _c(_bf(cls)))
+
+
+class _TokenPool(Function):
+    """Mean over a token range (count = 1: the row itself).  Backward writes every element of dx: the gradient over the
+    range, +0 outside it."""
+
+    @staticmethod
+    def forward(ctx, x, first, count):
+        ctx.geom = (x.shape[1], first, count)
+        return ops.token_pool_fwd(_c(x), first, count)
+
+    @staticmethod
+    def backward(ctx, dy):
+        T, first, count = ctx.geom
+        return ops.token_pool_bwd(_c(dy), T, first, count), None, None
+
+
+def token_pool(x, first=0, count=None):
+    """x [B, T, D] -> [B, D] bf16: the mean of tokens [first, first + count) (count = None: to the last token); count = 1
+    reads one token, bit for bit -- token_pool(x, 0, 1) is the CLS read-out."""
+    if x.dim() != 3:
+        raise ValueError(f"token_pool: x [B, T, D] expected, got {tuple(x.shape)}")
+    first, count = ops._pool_range(x.shape[1], first, count)
+    if _traced():
+        from . import library
+        return library.token_pool(_bf(x), first, count)
+    return _TokenPool.apply(_bf(x), first, count)
+
+
+def pooled_head(x, ln_w, ln_b, w, b, eps=1e-5):
+    """LayerNorm(D) + Linear(D, classes) on a pooled token x [B, D]: layer_norm and linear as they are; one traceable op
+    under torch.compile."""
+    if _traced():
+        from . import library
+        return library.pooled_head(_bf(x), _bf(ln_w), _bf(ln_b), _bf(w), _bf(b), eps)
+    return linear(layer_norm(x, ln_w, ln_b, eps), w, b)
+
+
+# ----------------------------------------------------------------------------
 class _EncoderLayer(Function):
     """Post-norm transformer encoder layer (torch:nn/modules/transformer.py:951-982):
          a  = out_proj(attention(in_proj(x)));  x1 = LN1(x + drop1(a))
@@ -984,7 +1054,7 @@ def mixed_target_cross_entropy(logits, y_a, y_b, mix):
 
 # ----------------------------------------------------------------------------
 # torch.compile (main.py:284 wraps the model in torch.compile(mode="reduce-overhead")).  The blocks a VisionTransformer{,1D}
-# is made of -- patch_embed, token_aggregator, pos_embed, token_mix, mixer_block, encoder_layer, predictor_head, soft_target_cross_entropy -- are registered as
+# is made of -- patch_embed, token_aggregator, pos_embed, cls_prepend, token_pool, pooled_head, token_mix, mixer_block, encoder_layer, predictor_head, soft_target_cross_entropy -- are registered as
 # `sfcvit::` custom ops with fake kernels and autograd formulas (sfcvit/library.py) and take that path whenever Dynamo is
 # tracing: the model compiles into ONE graph and "reduce-overhead" replays it from a hipGraph.  The remaining pieces
 # (used by the hierarchical tokenizers, altvit and MultiLayerPredictor(n_layers > 2)) stay opaque: Dynamo breaks the graph

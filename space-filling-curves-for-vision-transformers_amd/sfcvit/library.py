@@ -378,6 +378,137 @@ pos_embed_op.register_autograd(_pos_backward, setup_context=_pos_setup)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# cls_prepend (cat([cls, x], dim=1); backward: dx = dy[:, 1:], dcls = the batch sum of dy[:, 0]) and token_pool (mean over a
+# token range; backward writes every element of dx)
+# ----------------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("sfcvit::cls_prepend", mutates_args=())
+def cls_prepend_op(x: Tensor, cls: Tensor) -> Tensor:
+    return F._ClsPrepend.forward(_Ctx(), x, cls)
+
+
+@cls_prepend_op.register_fake
+def _(x, cls):
+    return x.new_empty((x.shape[0], x.shape[1] + 1, x.shape[2]), dtype=_BF16)
+
+
+@torch.library.custom_op("sfcvit::cls_prepend_bwd", mutates_args=())
+def cls_prepend_bwd_op(dy: Tensor, cls: Tensor) -> Tuple[Tensor, Tensor]:
+    dx, dcls = ops.cls_prepend_bwd(dy)                          # (no gradient slots inside a traced op: a fresh tensor)
+    return dx, dcls.to(_BF16).view(cls.shape)
+
+
+@cls_prepend_bwd_op.register_fake
+def _(dy, cls):
+    return dy.new_empty((dy.shape[0], dy.shape[1] - 1, dy.shape[2])), cls.new_empty(cls.shape)
+
+
+def _cls_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+    ctx.set_materialize_grads(False)
+
+
+def _cls_backward(ctx, dy):
+    (cls,) = ctx.saved_tensors
+    return torch.ops.sfcvit.cls_prepend_bwd(dy.contiguous(), cls)
+
+
+cls_prepend_op.register_autograd(_cls_backward, setup_context=_cls_setup)
+
+
+@torch.library.custom_op("sfcvit::token_pool", mutates_args=())
+def token_pool_op(x: Tensor, first: int, count: int) -> Tensor:
+    return ops.token_pool_fwd(x, first, count)
+
+
+@token_pool_op.register_fake
+def _(x, first, count):
+    return x.new_empty((x.shape[0], x.shape[2]), dtype=_BF16)
+
+
+@torch.library.custom_op("sfcvit::token_pool_bwd", mutates_args=())
+def token_pool_bwd_op(dy: Tensor, T: int, first: int, count: int) -> Tensor:
+    return ops.token_pool_bwd(dy, T, first, count)
+
+
+@token_pool_bwd_op.register_fake
+def _(dy, T, first, count):
+    return dy.new_empty((dy.shape[0], T, dy.shape[1]))
+
+
+def _pool_setup(ctx, inputs, output):
+    ctx.geom = (inputs[0].shape[1], inputs[1], inputs[2])
+    ctx.set_materialize_grads(False)
+
+
+def _pool_backward(ctx, dy):
+    return torch.ops.sfcvit.token_pool_bwd(dy.contiguous(), *ctx.geom), None, None
+
+
+token_pool_op.register_autograd(_pool_backward, setup_context=_pool_setup)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# pooled_head (LayerNorm + Linear on a pooled token [B, D]; the class count is padded to 8 inside, as F.linear pads it)
+# ----------------------------------------------------------------------------------------------------------------------
+def _pad_classes(wc, bc):
+    pad = (-wc.shape[0]) % 8
+    if pad:
+        wc, bc = torch.nn.functional.pad(wc, (0, 0, 0, pad)), torch.nn.functional.pad(bc, (0, pad))
+    return wc, bc
+
+
+@torch.library.custom_op("sfcvit::pooled_head", mutates_args=())
+def pooled_head_op(x: Tensor, ln_w: Tensor, ln_b: Tensor, wc: Tensor, bc: Tensor, eps: float) -> List[Tensor]:
+    ctx = _Ctx()
+    z = F._LayerNorm.forward(ctx, x, ln_w, ln_b, eps)
+    _, mean, rstd, _ = ctx.saved_tensors
+    wc_p, bc_p = _pad_classes(wc, bc)
+    logits = F._Linear.forward(_Ctx(), z, wc_p, bc_p, ops.ACT_NONE)[:, :wc.shape[0]]
+    return [logits.contiguous(), mean, rstd, z]
+
+
+@pooled_head_op.register_fake
+def _(x, ln_w, ln_b, wc, bc, eps):
+    B = x.shape[0]
+    return [x.new_empty((B, wc.shape[0]), dtype=_BF16), x.new_empty(B, dtype=torch.float32), x.new_empty(B, dtype=torch.float32),
+            x.new_empty(x.shape, dtype=_BF16)]
+
+
+@torch.library.custom_op("sfcvit::pooled_head_bwd", mutates_args=())
+def pooled_head_bwd_op(dlogits: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, z: Tensor, ln_w: Tensor, wc: Tensor) -> List[Tensor]:
+    C = wc.shape[0]
+    wc_p, _ = _pad_classes(wc, wc.new_zeros(C))
+    dl = torch.nn.functional.pad(dlogits, (0, wc_p.shape[0] - C)) if wc_p.shape[0] != C else dlogits
+    lin, ln = _Ctx(), _Ctx()
+    lin.saved_tensors, lin.act, lin.has_bias, lin.shape = (z, wc_p, None), ops.ACT_NONE, True, z.shape
+    ln.saved_tensors, ln.small = (x, mean, rstd, ln_w), (None,)
+    with _no_slots():
+        dz, dw, db, _ = F._Linear.backward(lin, dl.contiguous())
+        dx, dg, dbeta, _ = F._LayerNorm.backward(ln, dz)
+    return [dx.contiguous(), dg.contiguous(), dbeta.contiguous(), dw[:C].contiguous(), db[:C].contiguous()]
+
+
+@pooled_head_bwd_op.register_fake
+def _(dlogits, x, mean, rstd, z, ln_w, wc):
+    ne = lambda t: t.new_empty(t.shape)                       # noqa: E731
+    return [ne(x), ne(ln_w), ne(ln_w), ne(wc), wc.new_empty(wc.shape[0])]
+
+
+def _phead_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], *output[1:], inputs[1], inputs[3])
+    ctx.set_materialize_grads(False)
+
+
+def _phead_backward(ctx, grads):
+    x, mean, rstd, z, ln_w, wc = ctx.saved_tensors
+    g = torch.ops.sfcvit.pooled_head_bwd(grads[0].contiguous(), x, mean, rstd, z, ln_w, wc)
+    return (*g, None)
+
+
+pooled_head_op.register_autograd(_phead_backward, setup_context=_phead_setup)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # encoder_layer (post-norm nn.TransformerEncoderLayer; seeds = [] -> drawn inside the op when p > 0)
 # ----------------------------------------------------------------------------------------------------------------------
 _ENC_SAVED = 12     # qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2 (+ hbits, seeds below)
@@ -579,6 +710,18 @@ def token_aggregator(x, dw_w, dw_b, pw_w, pw_b, ln_w, ln_b, stride, eps):
 
 def pos_embed(x, pos):
     return torch.ops.sfcvit.pos_embed(x, pos)
+
+
+def cls_prepend(x, cls):
+    return torch.ops.sfcvit.cls_prepend(x, cls)
+
+
+def token_pool(x, first, count):
+    return torch.ops.sfcvit.token_pool(x.contiguous(), first, count)
+
+
+def pooled_head(x, ln_w, ln_b, wc, bc, eps):
+    return torch.ops.sfcvit.pooled_head(x, ln_w, ln_b, wc, bc, eps)[0]
 
 
 def encoder_layer(args, n_heads, eps, p, scale):

@@ -43,3 +43,20 @@ def from_bool(blocked):
     if blocked.dtype != torch.bool or blocked.dim() != 2 or blocked.shape[0] != blocked.shape[1]:
         raise ValueError(f"from_bool: a square bool matrix is expected, got {blocked.dtype} {tuple(blocked.shape)}")
     return _additive(~blocked.cpu())
+
+
+def with_cls_token(mask):
+    """An [N, N] mask (additive float, or bool with True = blocked) carried to the N + 1 tokens of a model built with
+    pool="cls": the CLS token (row 0 and column 0) sees every token and is seen by every token, and the patch tokens keep
+    their mask, shifted by one.  -> additive fp32 [N + 1, N + 1]."""
+    mask = torch.as_tensor(mask)
+    if mask.dim() != 2 or mask.shape[0] != mask.shape[1]:
+        raise ValueError(f"with_cls_token: a square [N, N] mask is expected, got {tuple(mask.shape)}")
+    if mask.dtype == torch.bool:
+        mask = from_bool(mask)
+    elif not mask.is_floating_point():
+        raise ValueError(f"with_cls_token: a float additive or a bool mask is expected, got {mask.dtype}")
+    n = mask.shape[0]
+    out = torch.zeros((n + 1, n + 1), dtype=torch.float32)
+    out[1:, 1:] = mask.detach().to("cpu", torch.float32)
+    return out

@@ -123,7 +123,10 @@ class TransformerSeqEncoder(nn.Module):
     nn.TransformerEncoder.forward(src, mask): the mask goes to every layer (the reference's CustomTransformerEncoder,
     vit.py:152-174).  A mask is not a parameter or a buffer: it never enters state_dict."""
 
-    def __init__(self, input_dim, max_len, n_head, hidden_dim, method, dropout_p=0.1, n_layers=1):
+    def __init__(self, input_dim, max_len, n_head, hidden_dim, method, dropout_p=0.1, n_layers=1, cls_token=False):
+        """cls_token=True: a learnable [CLS] token `cls_token` [1, 1, input_dim] of zeros (vit.py:209-210, commented out
+        there) that forward puts in front of the sequence before the first layer (vit.py:237-238): [B, N, D] in,
+        [B, N + 1, D] out.  Constructed last: every other parameter draws what it draws without it."""
         super().__init__()
         self.max_len = max_len
         self.grid_size = int(math.sqrt(max_len))
@@ -135,6 +138,11 @@ class TransformerSeqEncoder(nn.Module):
         self.transformer = nn.TransformerEncoder(encoder_layer, num_layers=n_layers,
                                                  enable_nested_tensor=False)
         self.to_patch_embedding = method
+        if cls_token:
+            if input_dim % 8:
+                raise ValueError(f"cls_token=True: input_dim={input_dim} must be a multiple of 8 (the kernels move 16-byte "
+                                 "vectors of 8 channels)")
+            self.cls_token = nn.Parameter(torch.zeros(1, 1, input_dim))
 
     def _mask(self, mask):
         """The AttentionMask of `mask`; a tensor is validated and uploaded at its first use and remembered while the same
@@ -149,6 +157,8 @@ class TransformerSeqEncoder(nn.Module):
     def forward(self, x, mask=None):
         p = self.dropout_p if self.training else 0.0
         mask = self._mask(mask)
+        if hasattr(self, "cls_token"):
+            x = F.cls_prepend(x, self.cls_token)                # vit.py:237-238
         for layer in self.transformer.layers:
             a = layer.self_attn
             x = F.encoder_layer(x, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
@@ -254,27 +264,77 @@ class MultiLayerPredictor(nn.Sequential):
         return x
 
 
+POOL_KINDS = ("cls", "mean")
+
+
+class PooledHead(nn.Sequential):
+    """The head of a pooled classifier: LayerNorm(D), Linear(D, num_classes) on ONE vector per image -- token 0 of a model
+    with a CLS token (pool="cls") or the mean of the tokens (pool="mean").  Unlike MultiLayerPredictor it holds no weight
+    per token index: its size and its checkpoint do not depend on N, and it has no view of a token's place on the curve."""
+
+    def __init__(self, embed_dim, num_classes=10, pool="mean"):
+        super().__init__(nn.LayerNorm(embed_dim), nn.Linear(embed_dim, num_classes))
+        self.pool = pool
+
+    def forward(self, x):
+        x = F.token_pool(x, 0, 1) if self.pool == "cls" else F.token_pool(x)
+        ln, fc = self[0], self[1]
+        return F.pooled_head(x, ln.weight, ln.bias, fc.weight, fc.bias, ln.eps)
+
+
+def _check_pool(pool, embed_dim):
+    if pool is None:
+        return
+    if pool not in POOL_KINDS:
+        raise ValueError(f"pool={pool!r}: None, {', '.join(map(repr, POOL_KINDS))} expected")
+    if embed_dim % 8:
+        raise ValueError(f"pool={pool!r}: embed_dim={embed_dim} must be a multiple of 8 (the kernels move 16-byte vectors of 8 channels)")
+
+
+def _model_mask(attn_mask, n_patches, pool):
+    """The models' attn_mask: N x N, or (N + 1) x (N + 1) with pool="cls" (masks.with_cls_token carries a window over)."""
+    n = n_patches + 1 if pool == "cls" else n_patches
+    if attn_mask is None:
+        return None
+    rows = attn_mask.n_tokens if isinstance(attn_mask, ops.AttentionMask) else torch.as_tensor(attn_mask).shape[0]
+    if pool == "cls" and rows == n_patches:
+        raise ValueError(f"attn_mask has {n_patches} rows and pool='cls' gives the encoder {n} tokens: pass "
+                         "sfcvit.masks.with_cls_token(mask)")
+    return ops.as_attention_mask(attn_mask, n)
+
+
+def _make_head(pool, embed_dim, n_patches, num_classes, head_dropout_p):
+    if pool is None:
+        return MultiLayerPredictor(embed_dim, n_patches, n_layers=2, num_classes=num_classes, dropout_p=head_dropout_p)
+    return PooledHead(embed_dim, num_classes, pool)
+
+
 class VisionTransformer(nn.Module):
     """vit.py:325-385 (`embed_dim` is ignored there too: taken from the tokenizer, :351)."""
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, attn_mask=None,
-                 pos_embed=None, pos_embed_std=1.0):
+                 pos_embed=None, pos_embed_std=1.0, pool=None):
         """attn_mask: None, or a mask for every encoder layer (ops.as_attention_mask's forms; sfcvit.masks builds windows).
         Held outside state_dict: checkpoint keys are the reference's with or without it.
         pos_embed: None / False (the reference as shipped), "learned" (vit.py:360-361: a Parameter [1, N, D] = randn *
         pos_embed_std), "sincos1d" (fixed, of the token index along the curve) or "sincos2d" (fixed, of the token's centre in
         the image: the same whatever curve orders the tokens).  Added directly after the tokenizer and, if present, `ta`
-        (vit.py:380-383): before the encoder here, before `mlp_mixer` in VisionTransformer1D -- one place for both models."""
+        (vit.py:380-383): before the encoder here, before `mlp_mixer` in VisionTransformer1D -- one place for both models.
+        pool: None (the reference as shipped: the factorised head over all tokens), "cls" (the encoder owns a learnable
+        `encoder.cls_token`, vit.py:209-210, :237-238, put in front of the N patch tokens; `ta` and `pos_embed` act on the patch
+        tokens only, the CLS row gets no positional row; the head reads token 0; attn_mask must then be (N + 1) x (N + 1):
+        sfcvit.masks.with_cls_token) or "mean" (no extra token; the head reads the mean of the N tokens).  Both pooled kinds
+        use `mlp_head = PooledHead`: LayerNorm(D), Linear(D, num_classes); head_dropout_p is unused with a pooled head."""
         super().__init__()
         self.patch_embed = patch_embed
         embed_dim = patch_embed.embed_dim
-        self.attn_mask = ops.as_attention_mask(attn_mask, patch_embed.n_patches)
+        _check_pool(pool, embed_dim)
+        self.attn_mask = _model_mask(attn_mask, patch_embed.n_patches, pool)
         self.encoder = TransformerSeqEncoder(input_dim=embed_dim, max_len=self.patch_embed.n_patches,
                                              method=self.patch_embed, n_head=n_heads, hidden_dim=mlp_dim,
-                                             n_layers=depth, dropout_p=dropout_p)
-        self.mlp_head = MultiLayerPredictor(embed_dim, self.patch_embed.n_patches, n_layers=2,
-                                            num_classes=num_classes, dropout_p=head_dropout_p)
+                                             n_layers=depth, dropout_p=dropout_p, cls_token=pool == "cls")
+        self.mlp_head = _make_head(pool, embed_dim, self.patch_embed.n_patches, num_classes, head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)
 
@@ -296,20 +356,21 @@ class VisionTransformer1D(nn.Module):
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False, attn_mask=None,
-                 pos_embed=None, pos_embed_std=1.0):
-        """attn_mask, pos_embed, pos_embed_std: as in VisionTransformer (the table is added directly after the tokenizer and,
-        if present, `ta`: before `mlp_mixer`)."""
+                 pos_embed=None, pos_embed_std=1.0, pool=None):
+        """attn_mask, pos_embed, pos_embed_std, pool: as in VisionTransformer (the table is added directly after the tokenizer
+        and, if present, `ta`: before `mlp_mixer`; with pool="cls" the token joins after `mlp_mixer`, whose weights stay sized
+        for the N patch tokens)."""
         super().__init__()
         self.patch_embed = patch_embed
         embed_dim = patch_embed.embed_dim
-        self.attn_mask = ops.as_attention_mask(attn_mask, patch_embed.n_patches)
+        _check_pool(pool, embed_dim)
+        self.attn_mask = _model_mask(attn_mask, patch_embed.n_patches, pool)
         self.mlp_mixer = MixerBlock(seq_len=self.patch_embed.n_patches, embed_dim=embed_dim,
                                     hidden_dim=embed_dim * 2, out_dim=embed_dim, token_mix=token_mix)
         self.encoder = TransformerSeqEncoder(input_dim=embed_dim, max_len=self.patch_embed.n_patches,
                                              n_head=n_heads, hidden_dim=mlp_dim, n_layers=depth,
-                                             method=self.patch_embed, dropout_p=dropout_p)
-        self.mlp_head = MultiLayerPredictor(embed_dim, self.patch_embed.n_patches, n_layers=2,
-                                            dropout_p=head_dropout_p, num_classes=num_classes)
+                                             method=self.patch_embed, dropout_p=dropout_p, cls_token=pool == "cls")
+        self.mlp_head = _make_head(pool, embed_dim, self.patch_embed.n_patches, num_classes, head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)
 

@@ -1009,6 +1009,79 @@ def pos_embed_bwd(dy, out=None):
 
 
 # ----------------------------------------------------------------------------
+# CLS token and token pooling (vit.py:209-210, :237-238, commented out there; altvit's x.mean(dim=1))
+# ----------------------------------------------------------------------------
+def last_token_pool_kernel():
+    buf = ctypes.create_string_buffer(96)
+    lib.sfcvit_last_token_pool_kernel(buf, 96)
+    return buf.value.decode()
+
+
+def cls_prepend_fwd(x, cls):
+    """y [B, N + 1, D] = cat([cls, x], dim=1) for x [B, N, D] bf16 and a contiguous bf16 cls of D elements: the bits move."""
+    _need(x, _BF16, "cls_prepend x", 3)
+    _need(cls, _BF16, "cls_prepend cls")
+    B, N, D = x.shape
+    if cls.numel() != D:
+        raise ValueError(f"cls_prepend cls: {D} channels expected ([{D}] or [1, 1, {D}]), got {tuple(cls.shape)}")
+    y = torch.empty((B, N + 1, D), device=x.device, dtype=_BF16)
+    _launch("cls_prepend_fwd", 2.0 * x.numel() + 2.0 * y.numel(),
+            lambda: check(lib.sfcvit_cls_prepend_fwd(_p(x), _p(cls), _p(y), B, N, D, _stream()), "sfcvit_cls_prepend_fwd"))
+    return y
+
+
+def cls_prepend_bwd(dy, want_dx=True, out=None):
+    """dy [B, N + 1, D] bf16 -> (dx [B, N, D] = dy[:, 1:] or None, dcls [D] = sum_b dy[b, 0]): dcls is fp32, or -- with out = a
+    contiguous bf16 tensor of D elements, e.g. a view of a flat gradient buffer -- written as bf16 in place and returned."""
+    _need(dy, _BF16, "cls_prepend dy", 3)
+    B, N1, D = dy.shape
+    if N1 < 2:
+        raise ValueError("cls_prepend_bwd: dy must hold the CLS row and at least one token")
+    if out is not None and (out.dtype != _BF16 or out.numel() != D or not out.is_contiguous()):
+        raise ValueError("cls_prepend_bwd out: a contiguous bf16 tensor of D elements expected")
+    dx = torch.empty((B, N1 - 1, D), device=dy.device, dtype=_BF16) if want_dx else None
+    dcls = out if out is not None else torch.empty(D, device=dy.device, dtype=torch.float32)
+    nbytes = lib.sfcvit_cls_prepend_bwd_workspace(B, N1 - 1, D)
+    ws = torch.empty(nbytes, device=dy.device, dtype=torch.uint8) if nbytes else None
+    with _Deferring([dcls], [ws]):
+        _launch("cls_prepend_bwd", (4.0 if want_dx else 0.0) * B * (N1 - 1) * D + 2.0 * B * D,
+                lambda: check(lib.sfcvit_cls_prepend_bwd(_p(dy), _p(dx), _p(dcls), int(out is not None), B, N1 - 1, D, _p(ws), nbytes,
+                                                         _stream()), "sfcvit_cls_prepend_bwd"))
+    return dx, dcls
+
+
+def _pool_range(T, first, count):
+    first = int(first)
+    count = T - first if count is None else int(count)
+    if first < 0 or count < 1 or first + count > T:
+        raise ValueError(f"token_pool: tokens [{first}, {first} + {count}) are not a non-empty range of the {T} tokens")
+    return first, count
+
+
+def token_pool_fwd(x, first=0, count=None):
+    """y [B, D] = mean over tokens [first, first + count) of x [B, T, D] bf16 (fp32 sum, one division, one rounding); count = 1
+    copies the row's bits; count = None: to the last token."""
+    _need(x, _BF16, "token_pool x", 3)
+    B, T, D = x.shape
+    first, count = _pool_range(T, first, count)
+    y = torch.empty((B, D), device=x.device, dtype=_BF16)
+    _launch("token_pool_fwd", 2.0 * B * count * D + 2.0 * B * D,
+            lambda: check(lib.sfcvit_token_pool_fwd(_p(x), _p(y), B, T, D, first, count, _stream()), "sfcvit_token_pool_fwd"))
+    return y
+
+
+def token_pool_bwd(dy, T, first=0, count=None):
+    """dx [B, T, D] = dy [B, D] / count on tokens [first, first + count), +0 elsewhere: every element written."""
+    _need(dy, _BF16, "token_pool dy", 2)
+    B, D = dy.shape
+    first, count = _pool_range(int(T), first, count)
+    dx = torch.empty((B, int(T), D), device=dy.device, dtype=_BF16)
+    _launch("token_pool_bwd", 2.0 * dx.numel() + 2.0 * B * D,
+            lambda: check(lib.sfcvit_token_pool_bwd(_p(dy), _p(dx), B, int(T), D, first, count, _stream()), "sfcvit_token_pool_bwd"))
+    return dx
+
+
+# ----------------------------------------------------------------------------
 # token mixing: GEMMs along the token axis of [B, N, D] (MixerBlock.token_mix)
 # ----------------------------------------------------------------------------
 def last_tokmix_kernel():

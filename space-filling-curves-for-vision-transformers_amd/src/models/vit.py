@@ -1,2 +1,2 @@
-from sfcvit.models.vit import (FactorisedLinear, MixerBlock, MultiLayerPredictor, TokenAggregator, TransformerSeqEncoder,  # noqa: F401
+from sfcvit.models.vit import (FactorisedLinear, MixerBlock, MultiLayerPredictor, PooledHead, TokenAggregator, TransformerSeqEncoder,  # noqa: F401
                                VisionTransformer, VisionTransformer1D)
