@@ -12,6 +12,7 @@ thread_local GemmPlan g_gemm;
 thread_local bool g_gemm_noted = false;
 thread_local char g_attn[96] = "none";
 thread_local char g_rowwise[96] = "none";
+thread_local char g_tokenizer[96] = "none";
 }
 
 int env_int(const char *name, int def) {
@@ -61,6 +62,13 @@ void note_rowwise_kernel(const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_rowwise, sizeof(g_rowwise), fmt, ap);
+    va_end(ap);
+}
+
+void note_tokenizer_kernel(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_tokenizer, sizeof(g_tokenizer), fmt, ap);
     va_end(ap);
 }
 
@@ -146,6 +154,12 @@ extern "C" int sfcvit_last_attn_kernel(char *buf, int n) {
 extern "C" int sfcvit_last_rowwise_kernel(char *buf, int n) {
     if (!buf || n <= 0) return SFCVIT_EINVAL;
     snprintf(buf, size_t(n), "%s", sfcvit::g_rowwise);
+    return SFCVIT_OK;
+}
+
+extern "C" int sfcvit_last_tokenizer_kernel(char *buf, int n) {
+    if (!buf || n <= 0) return SFCVIT_EINVAL;
+    snprintf(buf, size_t(n), "%s", sfcvit::g_tokenizer);
     return SFCVIT_OK;
 }
 

@@ -34,6 +34,9 @@ void note_attn_kernel(const ProbePlan &p);      // sfcvit_attention_probs / _sta
 void note_attn_kernel(const char *name);        // the masked kernels (attention_masked.hip) have no plan: one kernel per pass
 // Which row-wise kernel the calling thread's last sfcvit_layernorm_bwd* launched (sfcvit_last_rowwise_kernel).
 void note_rowwise_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+// Which tokenizer kernel (patch_embed.hip, patch_embed_tiled.hip, hier_tokenizer.hip) the calling thread launched last
+// (sfcvit_last_tokenizer_kernel): noted on the host just before the launch.
+void note_tokenizer_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 
 // rowwise.hip: out[n] = sum over `nparts` rows of part[nparts][N] in a fixed order; out fp32 or bf16.
 int launch_colsum_reduce(const float *part, int nparts, int N, void *out, int out_bf16, void *stream);

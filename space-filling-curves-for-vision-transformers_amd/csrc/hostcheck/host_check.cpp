@@ -526,6 +526,8 @@ static void check_token_pool() {
     char name[96];
     CHECK(sfcvit_last_token_pool_kernel(name, sizeof(name)) == SFCVIT_OK && !std::strcmp(name, "none"), "token_pool: last kernel '%s'", name);
     CHECK(sfcvit_last_token_pool_kernel(nullptr, 4) == SFCVIT_EINVAL, "token_pool: null name buffer accepted");
+    CHECK(sfcvit_last_tokenizer_kernel(name, sizeof(name)) == SFCVIT_OK && !std::strcmp(name, "none") &&
+          sfcvit_last_tokenizer_kernel(nullptr, 4) == SFCVIT_EINVAL && sfcvit_last_tokenizer_kernel(name, 0) == SFCVIT_EINVAL, "tokenizer: last kernel '%s'", name);
 }
 
 int main() {

@@ -167,6 +167,7 @@ SIGNATURES = {
     "sfcvit_token_pool_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "sfcvit_token_pool_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "sfcvit_last_token_pool_kernel": (c_int, [ctypes.c_char_p, c_int]),
+    "sfcvit_last_tokenizer_kernel": (c_int, [ctypes.c_char_p, c_int]),
     "sfcvit_tokmix_left": (c_int, [ctypes.POINTER(TokmixArgs), c_void_p]),
     "sfcvit_tokmix_wgrad_workspace": (c_int64, [c_int, c_int, c_int, c_int]),
     "sfcvit_tokmix_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64,

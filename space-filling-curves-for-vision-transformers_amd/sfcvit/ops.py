@@ -661,6 +661,13 @@ def attention_stats(qkv, lse, n_heads, pos=None, scale=None, out=None):
 # ----------------------------------------------------------------------------
 # tokenizer
 # ----------------------------------------------------------------------------
+def last_tokenizer_kernel():
+    """Name of the tokenizer kernel this thread launched last (sfcvit_last_tokenizer_kernel), "none" before any."""
+    buf = ctypes.create_string_buffer(96)
+    lib.sfcvit_last_tokenizer_kernel(buf, 96)
+    return buf.value.decode()
+
+
 class TileDesc:
     """Device copy + host facts of a tile descriptor (sfcvit_tile_descriptors): the tokenizer's pixel table turned out
     to be 16 x 16 pixel tiles (or 256-pixel strips), so the coalesced kernels of csrc/patch_embed_tiled.hip apply."""

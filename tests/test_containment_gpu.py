@@ -1,20 +1,28 @@
-"""Containment of the GEMM, attention and row-wise kernels: nothing is read or written outside the buffers of a call, every
-output element is written, and no result depends on what a workspace held before the call.
+"""Containment of the GEMM, attention, row-wise and tokenizer kernels: nothing is read or written outside the buffers of a
+call, every output element is written, and no result depends on what a workspace held before the call.
 
 Every case runs the C ABI (sfcvit._lib) twice or three times: once on ordinary dense tensors (the plain run), then with every
 input, output and workspace inside guarded allocations (tests/guarded.py; workspaces pre-filled with 0xFF in one run and 0x00
 in another, sized by the library's own queries and not a byte more).  After synchronizing: all guards intact, every output
 finite and torch.equal to the plain run, the inputs unchanged, and the same kernel ran as in the plain run (and it is the one
 the case is about).  No tolerance appears anywhere: byte patterns and torch.equal only.  Numeric accuracy is the business of
-tests/test_kernels_gpu.py and the attention test files.
+tests/test_kernels_gpu.py, the attention test files and tests/test_tokenizer_kernels_gpu.py.
+
+The tokenizer kernels (pe_fwd_kernel / pe_bwd_kernel / pe_bwd_reduce, pe2_*, the three token gathers and their mixing
+instances, hier_fwd_kernel in both forms, hier_resample_concat_kernel / _bwd_kernel) address memory through tables: pixel
+tables, tile descriptors, orders, origins, perm and the mix record are guarded INPUTS.  Their 0xFF guards read as -1, an
+offset that lands in a guard of the same allocation, so a stray table read shows up as a NaN or a broken guard, never as a
+fault.  Every table used is valid for its image.
 """
 import ctypes
 import math
+import struct
 
 import numpy as np
 import pytest
 import torch
 
+import tokenizer_ref as TR
 from guarded import assert_guards_intact, assert_written, guarded_inout, guarded_input, guarded_output, guarded_workspace
 
 pytestmark = pytest.mark.gpu
@@ -610,3 +618,205 @@ def test_transpose_batched(L):
     out = contain("transpose_batched", launch, inputs, {"dst": ((total,), BF16)})
     for m, o in zip(mats, offs):
         assert torch.equal(out["dst"][o:o + m.numel()].cpu().view(m.shape[1], m.shape[0]), m.t().contiguous())
+
+
+# ---- tokenizers ------------------------------------------------------------------------------------------------------------------
+def _last_tok(L):
+    return lambda: _name(L.lib.sfcvit_last_tokenizer_kernel)
+
+
+def _desc_host(L, pix_h, img):
+    N = pix_h.shape[0]
+    desc = np.zeros(16 + 2 * N + 2 * 8 * 256, dtype=np.int32)
+    n = L.lib.sfcvit_tile_descriptors(ctypes.c_void_p(pix_h.ctypes.data), N, 256, img, ctypes.c_void_p(desc.ctypes.data), desc.size)
+    assert n > 0
+    return desc[:n].copy()
+
+
+def _pe_contain(L, what, dims, pix_h, desc_h, xdt, want_dbias, fwd_expect, bwd_expect):
+    (HW, N, P, C), D, B = dims
+    lib = L.lib
+    g = torch.Generator().manual_seed(2000 + HW + D + B)
+    H, W = TR.image_hw(HW)
+    inputs = {"x": torch.randn(B, C, H, W, generator=g).to(xdt), "pix": torch.from_numpy(pix_h), "w": _rand(g, D, P * C, scale=(P * C) ** -0.5),
+              "bias": _rand(g, D)}
+    if desc_h is not None:
+        inputs["desc"] = torch.from_numpy(desc_h)
+
+    def args(t, bwd):
+        a = L.PatchEmbedArgs()
+        a.x, a.pix, a.y = t["x"].data_ptr(), t["pix"].data_ptr(), t["y"].data_ptr()
+        a.B, a.C, a.HW, a.N, a.P, a.D, a.x_is_bf16 = B, C, HW, N, P, D, int(xdt == BF16)
+        a.workspace, a.workspace_bytes = t["ws"].data_ptr(), t["ws"].numel()
+        if desc_h is not None:
+            a.desc, a.desc_ncls = t["desc"].data_ptr(), int(desc_h[1])
+            for c in range(int(desc_h[1])):
+                a.desc_cnt[c] = int(desc_h[7 + c] - desc_h[6 + c])
+        if bwd:
+            a.dw, a.dbias = t["dw"].data_ptr(), (t["dbias"].data_ptr() if want_dbias else None)
+        else:
+            a.w, a.bias = t["w"].data_ptr(), t["bias"].data_ptr()
+        return a
+
+    contain(what + " fwd", lambda t: L.check(lib.sfcvit_patch_embed_fwd(ctypes.byref(args(t, False)), _stream()), what), inputs,
+            {"y": ((B * N, D), BF16)}, {"ws": lib.sfcvit_patch_embed_workspace(B, C, N, P, D, 0)}, last_kernel=_last_tok(L), expect=fwd_expect)
+    binputs = {k: v for k, v in inputs.items() if k in ("x", "pix", "desc")}
+    binputs["y"] = _rand(g, B * N, D)
+    outputs = {"dw": ((D, P * C), F32)}
+    if want_dbias:
+        outputs["dbias"] = ((D,), F32)
+    contain(what + " bwd", lambda t: L.check(lib.sfcvit_patch_embed_bwd(ctypes.byref(args(t, True)), _stream()), what), binputs,
+            outputs, {"ws": lib.sfcvit_patch_embed_workspace(B, C, N, P, D, 1)}, last_kernel=_last_tok(L), expect=bwd_expect)
+
+
+@pytest.mark.parametrize("want_dbias", [True, False], ids=["dbias", "no-dbias"])
+@pytest.mark.parametrize("dims", TR.CONTAIN_PE, ids=lambda d: "HW%d-N%d-P%d-C%d-D%d-B%d" % (*d[0], d[1], d[2]))
+def test_patch_embed_generic(L, dims, want_dbias):
+    """Scalar gather with K padded to 32; M and D past a 128 tile; 66 split slabs in a workspace of exactly the queried size."""
+    (HW, N, P, C), D, B = dims
+    xdt = F32 if want_dbias else BF16
+    _pe_contain(L, f"patch_embed generic {dims}", dims, TR.hostile_table(HW, N, P, seed=HW + B), None, xdt, want_dbias,
+                f"pe_fwd_kernel<{'fp32' if xdt == F32 else 'bf16'}>", f"pe_bwd_kernel<{'fp32' if xdt == F32 else 'bf16'}>")
+
+
+@pytest.mark.parametrize("case", TR.CONTAIN_PE2, ids=lambda c: "%s%d-C%d-B%d" % c)
+def test_patch_embed_tiled(L, case):
+    """Hilbert at B = 33 (ragged classes, padded row tiles) and the 8-class table (classes of 3-6 rows inside 128-row tiles)."""
+    name, img, C, B = case
+    pix_h = TR.pe2_table(name, img)
+    _pe_contain(L, f"patch_embed tiled {case}", ((img * img, pix_h.shape[0], 256, C), TR.PE2_D, B), pix_h, _desc_host(L, pix_h, img), F32, True,
+                "pe2_fwd_kernel<fp32>", "pe2_bwd_kernel<fp32>")
+
+
+@pytest.mark.parametrize("table,B,extra", TR.CONTAIN_GATHER, ids=["p256-P16", "general-P512", "general-P512-ld+24"])
+def test_tokens_gather(L, table, B, extra):
+    HW, N, P, C = table
+    g = torch.Generator().manual_seed(2100 + P + extra)
+    ld = (P * C + 7) // 8 * 8 + extra
+    inputs = {"x": torch.randn(B, C, *TR.image_hw(HW), generator=g), "pix": torch.from_numpy(TR.hostile_table(HW, N, P, seed=P))}
+
+    def launch(t):
+        L.check(L.lib.sfcvit_tokens_gather(_p(t["x"]), 0, _p(t["pix"]), None, B, C, HW, N, P, _p(t["tokens"]), ld, _stream()), "tokens_gather")
+
+    out = contain(f"tokens_gather {table} ld {ld}", launch, inputs, {"tokens": ((B * N, ld), BF16)}, last_kernel=_last_tok(L),
+                  expect="tokens_gather_p256_kernel<fp32>" if P <= 256 else "tokens_gather_kernel<fp32>")
+    assert not bool(out["tokens"][:, P * C:].any())
+
+
+def _tile_tables(L, img):
+    from sfcvit import ops
+    pix_h = TR.curve_pixel_table("hilbert", img, 256)
+    desc = _desc_host(L, pix_h, img)
+    N = pix_h.shape[0]
+    return pix_h, torch.from_numpy(desc[16 + N:16 + 2 * N].copy()), torch.from_numpy(ops.gather_order(pix_h))
+
+
+@pytest.mark.parametrize("ordered", [True, False], ids=["order", "no-order"])
+def test_tokens_gather_tiles(L, ordered):
+    """48 px: nine tiles, so the last workgroup holds one token; B = 5: a second group of four images holding one."""
+    img, C, B = 48, 3, 5
+    pix_h, origin, order = _tile_tables(L, img)
+    N = pix_h.shape[0]
+    inputs = {"x": torch.randn(B, C, img, img, generator=torch.Generator().manual_seed(2200)), "pix": torch.from_numpy(pix_h), "origin": origin}
+    if ordered:
+        inputs["order"] = order
+
+    def launch(t):
+        L.check(L.lib.sfcvit_tokens_gather_tiles(_p(t["x"]), _p(t["pix"]), _p(t["order"]) if ordered else None, _p(t["origin"]), B, C, img, img, N,
+                                                 _p(t["tokens"]), 256 * C, _stream()), "tokens_gather_tiles")
+
+    contain(f"tokens_gather_tiles 48 px ordered={ordered}", launch, inputs, {"tokens": ((B * N, 256 * C), BF16)}, last_kernel=_last_tok(L),
+            expect="tokens_gather_tiles_kernel<3, fp32>")
+
+
+def _cutmix_rec(r0, r1, c0, c1, lam):
+    bits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]              # noqa: E731
+    return torch.tensor([2, r0, r1, c0, c1, bits(lam), bits(float(np.float32(1.0 - lam))), 0], dtype=torch.int32)
+
+
+@pytest.mark.parametrize("path", ["tiles", "pixel"])
+def test_tokens_gather_mix(L, path):
+    """One CutMix box that cuts through tokens; perm and the record are guarded inputs like the tables."""
+    C = 3
+    img, P, B = (48, 256, 5) if path == "tiles" else (32, 16, 9)
+    g = torch.Generator().manual_seed(2300 + P)
+    if path == "tiles":
+        pix_h, origin, order = _tile_tables(L, img)
+    else:
+        pix_h, origin, order = TR.curve_pixel_table("hilbert", img, P), None, None
+    N = pix_h.shape[0]
+    inputs = {"x": torch.randn(B, C, img, img, generator=g), "pix": torch.from_numpy(pix_h),
+              "perm": torch.randperm(B, generator=g).to(torch.int32), "rec": _cutmix_rec(5, 30, 10, 27, 0.7)}
+    if origin is not None:
+        inputs.update(origin=origin, order=order)
+
+    def launch(t):
+        L.check(L.lib.sfcvit_tokens_gather_mix(_p(t["x"]), _p(t["pix"]), _p(t["order"]) if "order" in t else None,
+                                               _p(t["origin"]) if "origin" in t else None, _p(t["perm"]), _p(t["rec"]), B, C, img, img, N, P,
+                                               _p(t["tokens"]), P * C, _stream()), "tokens_gather_mix")
+
+    out = contain(f"tokens_gather_mix {path}", launch, inputs, {"tokens": ((B * N, P * C), BF16)}, last_kernel=_last_tok(L),
+                  expect="tokens_gather_tiles_kernel<3, mix>" if path == "tiles" else "tokens_gather_p256_kernel<mix>")
+    plain = torch.zeros_like(out["tokens"])
+    L.check(L.lib.sfcvit_tokens_gather(_p(inputs["x"].cuda()), 0, _p(inputs["pix"].cuda()), None, B, C, img * img, N, P, _p(plain), P * C, _stream()),
+            "tokens_gather")
+    assert not torch.equal(out["tokens"], plain)                                  # the box did mix something
+
+
+@pytest.mark.parametrize("biased", [True, False], ids=["biases", "all-biases-null"])
+@pytest.mark.parametrize("fuse", [True, False], ids=["fuse", "levels"])
+@pytest.mark.parametrize("case", TR.CONTAIN_HIER, ids=["M65", "M20"])
+def test_hier_tokenizer(L, case, fuse, biased):
+    """M = 65: one row in the second workgroup; M = 20: wave 3 idle in the level phase (D = 192), four levels of K = 96.  In the wf = NULL form y is not
+    passed; every bias null once per case and form."""
+    Lv, D, C, P, N, B = case
+    E = Lv * D
+    g = torch.Generator().manual_seed(2400 + D)
+    tabs = TR.hier_tables(case, True)
+    inputs = {"x": torch.randn(B, C, *TR.image_hw(N * P), generator=g)}
+    for l in range(Lv):
+        inputs[f"pix{l}"], inputs[f"w{l}"] = torch.from_numpy(tabs[l]), _rand(g, D, P * C, scale=(P * C) ** -0.5)
+        if biased:
+            inputs[f"b{l}"] = _rand(g, D)
+    outputs = {"h": ((B * N, E), BF16)}
+    if fuse:
+        inputs["wf"] = _rand(g, E, E, scale=E ** -0.5)
+        outputs["y"] = ((B * N, E), BF16)
+        if biased:
+            inputs["bf"] = _rand(g, E)
+
+    def launch(t):
+        a = L.HierArgs()
+        a.x, a.h = t["x"].data_ptr(), t["h"].data_ptr()
+        for l in range(Lv):
+            a.pix[l], a.w[l], a.P[l] = t[f"pix{l}"].data_ptr(), t[f"w{l}"].data_ptr(), P
+            a.b[l] = t[f"b{l}"].data_ptr() if biased else None
+        if fuse:
+            a.wf, a.y = t["wf"].data_ptr(), t["y"].data_ptr()
+            a.bf = t["bf"].data_ptr() if biased else None
+        a.B, a.C, a.HW, a.N, a.L, a.D = B, C, N * P, N, Lv, D
+        L.check(L.lib.sfcvit_hier_tokenizer_fwd(ctypes.byref(a), _stream()), "hier_tokenizer_fwd")
+
+    contain(f"hier_tokenizer {case} fuse={fuse} biased={biased}", launch, inputs, outputs, last_kernel=_last_tok(L),
+            expect=f"hier_fwd_kernel<fp32, {'fuse' if fuse else 'levels'}>")
+
+
+@pytest.mark.parametrize("counts", TR.CONTAIN_RESAMPLE, ids=str)
+def test_hier_resample_concat_pair(L, counts):
+    D, B, n0, nl = TR.RESAMPLE_D[0], TR.RESAMPLE_B, counts[0], len(counts)
+    g = torch.Generator().manual_seed(2500 + n0)
+    levels = {f"lev{l}": _rand(g, B, n, D) for l, n in enumerate(counts)}
+    n_tok = (ctypes.c_int32 * nl)(*counts)
+
+    def fwd(t):
+        ptrs = (ctypes.c_void_p * nl)(*[t[f"lev{l}"].data_ptr() for l in range(nl)])
+        L.check(L.lib.sfcvit_hier_resample_concat(ptrs, n_tok, nl, B, n0, D, _p(t["out"]), _stream()), "hier_resample_concat")
+
+    def bwd(t):
+        ptrs = (ctypes.c_void_p * nl)(*[t[f"dlev{l}"].data_ptr() for l in range(nl)])
+        L.check(L.lib.sfcvit_hier_resample_concat_bwd(_p(t["dout"]), n_tok, nl, B, n0, D, ptrs, _stream()), "hier_resample_concat_bwd")
+
+    contain(f"hier_resample_concat {counts}", fwd, levels, {"out": ((B, n0, nl * D), BF16)}, last_kernel=_last_tok(L),
+            expect="hier_resample_concat_kernel")
+    contain(f"hier_resample_concat_bwd {counts}", bwd, {"dout": _rand(g, B, n0, nl * D)}, {f"dlev{l}": ((B, n, D), BF16) for l, n in enumerate(counts)},
+            last_kernel=_last_tok(L), expect="hier_resample_concat_bwd_kernel")
