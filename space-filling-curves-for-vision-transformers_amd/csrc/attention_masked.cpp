@@ -1,6 +1,5 @@
 // Host side of masked attention (attention_masked.h): mask validation with the block map, and the argument checks of the
-// two entry points.  Plain host code in the style of token_agg.cpp: no HIP call, no allocation, so every refusal is
-// testable on a machine without a GPU.
+// two entry points.  Plain host code: no HIP call, no allocation, so every refusal is testable on a machine without a GPU.
 #include "attention_masked.h"
 
 #include <cmath>

@@ -377,7 +377,7 @@ using namespace sfcvit;
 
 extern "C" int sfcvit_attention_masked_fwd(const sfcvit_attn_mask_args *a, void *stream) {
     if (const int rc = attn_masked_check(a, false, "attention_masked_fwd")) return rc;
-    note_attn_kernel("attn_masked_fwd_kernel");
+    g_attn.set("attn_masked_fwd_kernel");
     hipLaunchKernelGGL(attn_masked_fwd_kernel, dim3(mask_blocks(a->N), a->H, a->B), dim3(attn::THREADS), 0,
                        static_cast<hipStream_t>(stream), *a);
     return check_launch("attention_masked_fwd");
@@ -387,7 +387,7 @@ extern "C" int sfcvit_attention_masked_bwd(const sfcvit_attn_mask_args *a, void 
     if (const int rc = attn_masked_check(a, true, "attention_masked_bwd")) return rc;
     if (a->colsum_out && (!a->colsum_part || a->colsum_part_bytes < sfcvit_attention_colsum_workspace(a->B, a->N, a->H, a->hd)))
         return fail(SFCVIT_EINVAL, "attention_masked_bwd: colsum_out needs colsum_part of sfcvit_attention_colsum_workspace bytes");
-    note_attn_kernel("attn_masked_bwd_kv_kernel");
+    g_attn.set("attn_masked_bwd_kv_kernel");
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = SFCVIT_OK;
     const int64_t groups = int64_t(a->B) * a->N * a->H;

@@ -2,6 +2,7 @@
 
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <cstdarg>
 #include <cstdlib>
 #include <mutex>
 
@@ -10,10 +11,8 @@ namespace {
 thread_local char g_err[512] = "";
 thread_local GemmPlan g_gemm;
 thread_local bool g_gemm_noted = false;
-thread_local char g_attn[96] = "none";
-thread_local char g_rowwise[96] = "none";
-thread_local char g_tokenizer[96] = "none";
 }
+thread_local KernelNote g_attn, g_rowwise, g_tokenizer;
 
 int env_int(const char *name, int def) {
     const char *e = getenv(name);
@@ -58,24 +57,32 @@ Knobs read_knobs(KnobScope scope) {
     return k;
 }
 
-void note_rowwise_kernel(const char *fmt, ...) {
+// ---- the scaffold of plan.h ----
+void refuse(PlanStatus &p, int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(g_rowwise, sizeof(g_rowwise), fmt, ap);
+    vsnprintf(p.msg, sizeof(p.msg), fmt, ap);
+    va_end(ap);
+    p.err = code;
+}
+
+void KernelNote::set(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(name, sizeof(name), fmt, ap);
     va_end(ap);
 }
 
-void note_tokenizer_kernel(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_tokenizer, sizeof(g_tokenizer), fmt, ap);
-    va_end(ap);
+int KernelNote::read(char *buf, int n) const {
+    if (!buf || n <= 0) return SFCVIT_EINVAL;
+    snprintf(buf, size_t(n), "%s", name);
+    return SFCVIT_OK;
 }
 
-void note_attn_kernel(const AttnPlan &p) { kernel_name(p, g_attn, sizeof(g_attn)); }
-void note_attn_kernel(const ProbePlan &p) { kernel_name(p, g_attn, sizeof(g_attn)); }
-void note_attn_kernel(const char *name) { snprintf(g_attn, sizeof(g_attn), "%s", name); }
+void note_attn_kernel(const AttnPlan &p) { kernel_name(p, g_attn.name, sizeof(g_attn.name)); }
+void note_attn_kernel(const ProbePlan &p) { kernel_name(p, g_attn.name, sizeof(g_attn.name)); }
 
+// The GEMM note stays a copy of the plan (about 100 launches per training step): the name is formatted when it is asked for.
 void note_gemm_kernel(const GemmPlan &p) {
     g_gemm = p;
     g_gemm_noted = true;
@@ -139,29 +146,16 @@ extern "C" int sfcvit_abi_version(void) { return SFCVIT_ABI_VERSION; }
 extern "C" const char *sfcvit_last_error(void) { return sfcvit::g_err; }
 
 extern "C" int sfcvit_last_gemm_kernel(char *buf, int n) {
-    if (!buf || n <= 0) return SFCVIT_EINVAL;
-    if (sfcvit::g_gemm_noted) sfcvit::kernel_name(sfcvit::g_gemm, buf, size_t(n));
-    else snprintf(buf, size_t(n), "none");
-    return SFCVIT_OK;
+    sfcvit::KernelNote note;                                     // "none" until a GEMM has run
+    if (sfcvit::g_gemm_noted) sfcvit::kernel_name(sfcvit::g_gemm, note.name, sizeof(note.name));
+    return note.read(buf, n);
 }
 
-extern "C" int sfcvit_last_attn_kernel(char *buf, int n) {
-    if (!buf || n <= 0) return SFCVIT_EINVAL;
-    snprintf(buf, size_t(n), "%s", sfcvit::g_attn);
-    return SFCVIT_OK;
-}
+extern "C" int sfcvit_last_attn_kernel(char *buf, int n) { return sfcvit::g_attn.read(buf, n); }
 
-extern "C" int sfcvit_last_rowwise_kernel(char *buf, int n) {
-    if (!buf || n <= 0) return SFCVIT_EINVAL;
-    snprintf(buf, size_t(n), "%s", sfcvit::g_rowwise);
-    return SFCVIT_OK;
-}
+extern "C" int sfcvit_last_rowwise_kernel(char *buf, int n) { return sfcvit::g_rowwise.read(buf, n); }
 
-extern "C" int sfcvit_last_tokenizer_kernel(char *buf, int n) {
-    if (!buf || n <= 0) return SFCVIT_EINVAL;
-    snprintf(buf, size_t(n), "%s", sfcvit::g_tokenizer);
-    return SFCVIT_OK;
-}
+extern "C" int sfcvit_last_tokenizer_kernel(char *buf, int n) { return sfcvit::g_tokenizer.read(buf, n); }
 
 extern "C" int sfcvit_device_count(void) {
     int n = 0;

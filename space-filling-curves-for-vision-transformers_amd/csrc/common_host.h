@@ -1,6 +1,6 @@
-// Host-side helpers shared by every translation unit of libsfcvit_hip.so.
+// Host-side helpers shared by every translation unit of libsfcvit_hip.so (plan.h, through dispatch.h: PlanStatus, refuse,
+// ceil_div, aligned / aligned16, KernelNote).
 #pragma once
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
@@ -31,12 +31,11 @@ int raise_lds_limit(const void *kernel, int bytes, const char *what);
 void note_gemm_kernel(const GemmPlan &p);
 void note_attn_kernel(const AttnPlan &p);
 void note_attn_kernel(const ProbePlan &p);      // sfcvit_attention_probs / _stats report through sfcvit_last_attn_kernel too
-void note_attn_kernel(const char *name);        // the masked kernels (attention_masked.hip) have no plan: one kernel per pass
-// Which row-wise kernel the calling thread's last sfcvit_layernorm_bwd* launched (sfcvit_last_rowwise_kernel).
-void note_rowwise_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-// Which tokenizer kernel (patch_embed.hip, patch_embed_tiled.hip, hier_tokenizer.hip) the calling thread launched last
-// (sfcvit_last_tokenizer_kernel): noted on the host just before the launch.
-void note_tokenizer_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+// g_attn: what note_attn_kernel formats into; the masked kernels (attention_masked.hip) have no plan and set it by name.
+// g_rowwise: which row-wise kernel the calling thread's last sfcvit_layernorm_bwd* launched (sfcvit_last_rowwise_kernel).
+// g_tokenizer: which tokenizer kernel (patch_embed.hip, patch_embed_tiled.hip, hier_tokenizer.hip) the calling thread launched
+// last (sfcvit_last_tokenizer_kernel): noted on the host just before the launch.
+extern thread_local KernelNote g_attn, g_rowwise, g_tokenizer;
 
 // rowwise.hip: out[n] = sum over `nparts` rows of part[nparts][N] in a fixed order; out fp32 or bf16.
 int launch_colsum_reduce(const float *part, int nparts, int N, void *out, int out_bf16, void *stream);
@@ -45,7 +44,5 @@ int launch_colsum_reduce(const float *part, int nparts, int N, void *out, int ou
 // produces a parameter gradient nothing reads before the pass ends: 60 launches of 5 us per ViT-B step become one).
 int reduce_cols(const float *part, int nparts, int ld, int ncols, void *out, int out_bf16, void *stream);
 bool reduce_deferring();
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace sfcvit

@@ -2,23 +2,11 @@
 // instance, grid and post passes.  Plain host code: no HIP call, no allocation, no lock.
 #include "dispatch.h"
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 
 namespace sfcvit {
 namespace {
-
-__attribute__((format(printf, 3, 4))) void refuse(PlanStatus &p, int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(p.msg, sizeof(p.msg), fmt, ap);
-    va_end(ap);
-    p.err = code;
-}
-#define REFUSE(...) do { refuse(p, __VA_ARGS__); return p; } while (0)
-
-bool aligned(const void *ptr, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(ptr) & (bytes - 1)) == 0; }
 
 // The persistent 8-phase kernel (gemm8p.hip): false when the shape / options are not eligible.
 bool plan_p8(GemmPlan &p, const sfcvit_gemm_args &a, int splits, int cus, const Knobs &k) {

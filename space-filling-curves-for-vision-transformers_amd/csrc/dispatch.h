@@ -30,6 +30,7 @@
 #include <cstddef>
 
 #include "../../include/sfcvit.h"
+#include "plan.h"
 
 namespace sfcvit {
 
@@ -82,11 +83,6 @@ int env_int(const char *name, int def);
 char env_first(const char *name);
 inline bool env_off(const char *name) { return env_first(name) == '0'; }
 int env_pair(const char *name, int *a, int *b);
-
-struct PlanStatus {
-    int err = SFCVIT_OK;                                     // else an error code; msg says why
-    char msg[160] = "";
-};
 
 // ---- GEMM ----
 enum class GemmFamily : unsigned char { P8, P8_KM, RING, GENERIC };

@@ -279,7 +279,7 @@ extern "C" int sfcvit_hier_tokenizer_fwd(const sfcvit_hier_args *a, void *stream
     const void *k = a->x_is_bf16 ? (fuse ? reinterpret_cast<const void *>(&hier_fwd_kernel<true, true>) : reinterpret_cast<const void *>(&hier_fwd_kernel<true, false>))
                                  : (fuse ? reinterpret_cast<const void *>(&hier_fwd_kernel<false, true>) : reinterpret_cast<const void *>(&hier_fwd_kernel<false, false>));
     if (int rc = raise_lds_limit(k, 160 * 1024, "hier_tokenizer_fwd attribute")) return rc;
-    note_tokenizer_kernel("hier_fwd_kernel<%s, %s>", a->x_is_bf16 ? "bf16" : "fp32", fuse ? "fuse" : "levels");
+    g_tokenizer.set("hier_fwd_kernel<%s, %s>", a->x_is_bf16 ? "bf16" : "fp32", fuse ? "fuse" : "levels");
     if (a->x_is_bf16 && fuse) hipLaunchKernelGGL((hier_fwd_kernel<true, true>), dim3(grid), dim3(HT_THREADS), lds, s, g);
     else if (a->x_is_bf16) hipLaunchKernelGGL((hier_fwd_kernel<true, false>), dim3(grid), dim3(HT_THREADS), lds, s, g);
     else if (fuse) hipLaunchKernelGGL((hier_fwd_kernel<false, true>), dim3(grid), dim3(HT_THREADS), lds, s, g);
@@ -404,7 +404,7 @@ extern "C" int sfcvit_hier_resample_concat(const void *const *levels, const int3
     a.L = L; a.B = B; a.N0 = N0; a.D = D;
     const int64_t total = int64_t(B) * N0 * L * (D / 8);
     const unsigned blocks = unsigned(std::min<int64_t>((total + 255) / 256, 1 << 16));
-    note_tokenizer_kernel("hier_resample_concat_kernel");
+    g_tokenizer.set("hier_resample_concat_kernel");
     hipLaunchKernelGGL(hier_resample_concat_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a, static_cast<uint16_t *>(out));
     return check_launch("hier_resample_concat");
 }
@@ -418,7 +418,7 @@ extern "C" int sfcvit_hier_resample_concat_bwd(const void *dout, const int32_t *
     for (int l = 0; l < L; l++) {
         const int64_t total = int64_t(B) * n_tokens[l] * (D / 8);
         const unsigned blocks = unsigned(std::min<int64_t>((total + 255) / 256, 1 << 16));
-        note_tokenizer_kernel("hier_resample_concat_bwd_kernel");
+        g_tokenizer.set("hier_resample_concat_bwd_kernel");
         hipLaunchKernelGGL(hier_resample_concat_bwd_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a,
                            static_cast<const uint16_t *>(dout), l);
         if (int rc = check_launch("hier_resample_concat_bwd")) return rc;

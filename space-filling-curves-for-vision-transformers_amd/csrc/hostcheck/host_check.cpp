@@ -1,9 +1,12 @@
 // Sanitizer driver for the HOST-ONLY code of libsfcvit_hip.so ("Race detection / sanitizers": GPU ASan is not
 // available on this pool, so the native host code gets a CPU-side -fsanitize=address,undefined build of its own):
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
-//   host part), the error path of common.cpp, and the mask validation and block map of attention_masked.cpp (check_mask_blocks), the plan and refusals of pos_embed.cpp (check_pos_embed) and of token_pool.cpp (check_token_pool), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid,
-//   splits and post passes each GEMM / attention shape of the benchmarked models gets).  Every output buffer is a heap block of EXACTLY the documented size, so that
-// an off-by-one in a generator or in the descriptor writer is a heap-buffer-overflow report instead of silent corruption.
+//   host part), the error path of common.cpp, the mask validation and block map of attention_masked.cpp (check_mask_blocks),
+//   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv)
+//   and token_mix.cpp (check_tokmix), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
+//   and post passes each GEMM / attention shape of the benchmarked models gets).
+// Every buffer is a heap block of EXACTLY the documented size, so that an off-by-one in a generator or in the descriptor
+// writer is a heap-buffer-overflow report instead of silent corruption.
 // Built and run by `make asan` (tests/test_host_cpu.py::test_host_code_is_clean_under_address_sanitizer).  No GPU call.
 #include <climits>
 #include <cstdint>
@@ -17,6 +20,8 @@
 #include "../../../include/sfcvit.h"
 #include "../dispatch.h"
 #include "../pos_embed.h"
+#include "../token_agg.h"
+#include "../token_mix.h"
 #include "../token_pool.h"
 
 static int g_fail = 0;
@@ -530,6 +535,236 @@ static void check_token_pool() {
           sfcvit_last_tokenizer_kernel(nullptr, 4) == SFCVIT_EINVAL && sfcvit_last_tokenizer_kernel(name, 0) == SFCVIT_EINVAL, "tokenizer: last kernel '%s'", name);
 }
 
+// dwconv_plan and its pointer checks (token_agg.cpp): every bound of the envelope one step inside and one step outside, the
+// geometry against a brute-force count of the window positions, and the pointer rules with heap buffers of exactly the
+// documented sizes (the checks read no byte of them).
+static void check_dwconv() {
+    const auto plan = [](int B, int N, int D, int k, int s) { return dwconv_plan("host_check", B, N, D, k, s); };
+    const auto refused = [&](int B, int N, int D, int k, int s, const char *why) {
+        const DwconvPlan p = plan(B, N, D, k, s);
+        CHECK(p.err == SFCVIT_EINVAL && std::strstr(p.msg, why), "dwconv B=%d N=%d D=%d k=%d s=%d: '%s' lacks '%s'", B, N, D, k, s, p.msg, why);
+        CHECK(sfcvit_dwconv1d_bwd_workspace(B, N, D, k, s) == 0, "dwconv: workspace of a refused shape");
+    };
+    const auto accepted = [&](int B, int N, int D, int k, int s) {
+        const DwconvPlan p = plan(B, N, D, k, s);
+        CHECK(p.err == SFCVIT_OK, "dwconv B=%d N=%d D=%d k=%d s=%d refused: %s", B, N, D, k, s, p.msg);
+        return p;
+    };
+    for (int k : {1, 3, DWC_MAX_K}) accepted(2, 5, 16, k, 1);
+    for (int k : {0, DWC_MAX_K + 1, -1, INT32_MAX}) refused(2, 5, 16, k, 1, "kernel size");
+    for (int s : {1, DWC_MAX_S}) accepted(2, 5, 16, 3, s);
+    for (int s : {0, DWC_MAX_S + 1, -1, INT32_MAX}) refused(2, 5, 16, 3, s, "stride");
+    accepted(2, 5, 8, 3, 1);
+    for (int D : {0, 12, -8, INT32_MAX}) refused(2, 5, D, 3, 1, "multiple of 8");
+    for (int k : {1, 3, DWC_MAX_K}) {                              // ld = D (k + 1) is an int
+        const int dmax = INT32_MAX / (k + 1) / 8 * 8;
+        const DwconvPlan p = accepted(1, 1, dmax, k, 1);
+        CHECK(p.ld == int64_t(dmax) * (k + 1) && p.ws_bytes == int64_t(p.ld) * 4 && int64_t(p.slabs) * DWC_CV * 8 >= dmax, "dwconv: widest D, k=%d", k);
+        refused(1, 1, dmax + 8, k, 1, "too wide");
+        refused(1, 1, INT32_MAX / 8 * 8, k, 1, "too wide");        // D + 255 leaves int: the slab count must not
+    }
+    accepted(1, 5, 16, 3, 1);
+    accepted(65535, 5, 16, 3, 1);
+    for (int B : {0, 65536, -1, INT32_MAX}) refused(B, 5, 16, 3, 1, "B=");
+    for (int N : {0, -1}) refused(2, N, 16, 3, 1, "B=");
+    for (int k : {2, 3}) {                                          // the longest sequence: 65535 workgroups of 8 x 32 rows
+        const int nmax = 65535 * DWC_RL * DWC_MAX_RUN - (k % 2 ? 0 : 1);   // an even k makes Nout = N + 1 rows
+        for (int N : {1, 2, nmax}) {
+            const DwconvPlan p = accepted(1, N, 8, k, 1);
+            CHECK(p.groups == (N == nmax ? 65535 : 1) && p.run_out <= DWC_MAX_RUN && p.run_in <= DWC_MAX_RUN, "dwconv N=%d k=%d: groups %d", N, k, p.groups);
+        }
+        refused(1, nmax + 1, 8, k, 1, "launch grid");
+    }
+    refused(1, INT32_MAX / 2 - 2 * DWC_MAX_K, 8, 3, 1, "launch grid");
+    refused(1, INT32_MAX / 2 - 2 * DWC_MAX_K + 1, 8, 3, 1, "too long");
+    refused(1, INT32_MAX, 8, 3, 1, "too long");
+    // B x groups is grid.z x grid.y and one int in the reduction: 65535 x 32768 fits, 65535 x 32769 does not
+    CHECK(accepted(65535, 32768 * DWC_RL * DWC_MAX_RUN, 8, 3, 1).ws_bytes == int64_t(65535) * 32768 * 32 * 4, "dwconv: largest B x groups");
+    refused(65535, 32768 * DWC_RL * DWC_MAX_RUN + 1, 8, 3, 1, "launch grid");
+    refused(65535, 65535 * DWC_RL * DWC_MAX_RUN, 8, 3, 1, "launch grid");
+    refused(65535, 32768 * DWC_RL * DWC_MAX_RUN, INT32_MAX / 4 / 8 * 8, 3, 1, "int64");   // every extent at its bound: 2^64 bytes
+
+    for (int N = 1; N <= 40; N++)
+        for (int k = 1; k <= DWC_MAX_K; k++)
+            for (int s = 1; s <= DWC_MAX_S; s++) {
+                const int B = 3, D = 24;
+                const DwconvPlan p = accepted(B, N, D, k, s);
+                int count = 0;                                     // windows [n s - pad, n s - pad + k) inside the padded sequence
+                while (count * s + k <= N + 2 * (k / 2)) count++;
+                CHECK(p.pad == k / 2 && p.Nout == count, "dwconv N=%d k=%d s=%d: Nout %d, counted %d", N, k, s, p.Nout, count);
+                CHECK(p.groups >= 1 && p.groups * DWC_RL * p.run_out >= p.Nout && p.groups * DWC_RL * p.run_in >= N, "dwconv N=%d k=%d s=%d: runs", N, k, s);
+                CHECK(p.run_out <= DWC_MAX_RUN && p.run_in <= DWC_MAX_RUN && p.slabs == 1 && p.spec == (k == 3 && s == 1), "dwconv N=%d k=%d s=%d: geometry", N, k, s);
+                CHECK(p.ld == D * (k + 1) && p.ws_bytes == int64_t(B) * p.groups * p.ld * 4, "dwconv N=%d k=%d s=%d: workspace", N, k, s);
+                CHECK(sfcvit_dwconv1d_out_len(N, k, s) == p.Nout && sfcvit_dwconv1d_bwd_workspace(B, N, D, k, s) == p.ws_bytes, "dwconv N=%d k=%d s=%d: entry points", N, k, s);
+            }
+    CHECK(sfcvit_dwconv1d_out_len(5, 0, 1) == -1 && std::strstr(sfcvit_last_error(), "kernel size"), "dwconv: out_len of a refused k");
+
+    const int B = 2, N = 5, D = 16, k = 3;
+    const DwconvPlan p = accepted(B, N, D, k, 2);
+    const size_t xb = size_t(B) * N * D * 2, ub = size_t(B) * p.Nout * D * 2;
+    void *x = std::aligned_alloc(16, xb), *dx = std::aligned_alloc(16, xb), *u = std::aligned_alloc(16, ub), *ws = std::aligned_alloc(16, size_t(p.ws_bytes));
+    std::unique_ptr<uint16_t[]> w(new uint16_t[D * k]);
+    std::unique_ptr<float[]> dw(new float[D * k]), db(new float[D]);
+    char *const u2 = static_cast<char *>(u) + 2;
+    CHECK(dwconv_check_fwd(p, x, w.get(), u) == SFCVIT_OK, "dwconv fwd check: %s", sfcvit_last_error());
+    CHECK(dwconv_check_fwd(p, nullptr, w.get(), u) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "null"), "dwconv: null x accepted");
+    CHECK(dwconv_check_fwd(p, x, nullptr, u) == SFCVIT_EINVAL && dwconv_check_fwd(p, x, w.get(), nullptr) == SFCVIT_EINVAL, "dwconv: null w / u accepted");
+    CHECK(dwconv_check_fwd(p, x, w.get(), u2) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "aligned"), "dwconv: misaligned u accepted");
+    CHECK(dwconv_check_fwd(plan(B, N, 12, k, 2), x, w.get(), u) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "D=12"), "dwconv: the plan's refusal is the call's");
+    CHECK(dwconv_check_bwd(p, u, x, w.get(), dx, dw.get(), db.get(), ws, p.ws_bytes) == SFCVIT_OK, "dwconv bwd check: %s", sfcvit_last_error());
+    CHECK(dwconv_check_bwd(p, u, nullptr, w.get(), dx, nullptr, nullptr, nullptr, 0) == SFCVIT_OK, "dwconv: dx alone needs neither x nor a workspace");
+    CHECK(dwconv_check_bwd(p, u, nullptr, nullptr, nullptr, nullptr, db.get(), ws, p.ws_bytes) == SFCVIT_OK, "dwconv: db alone needs neither x nor w");
+    CHECK(dwconv_check_bwd(p, nullptr, x, w.get(), dx, dw.get(), db.get(), ws, p.ws_bytes) == SFCVIT_EINVAL, "dwconv: null du accepted");
+    CHECK(dwconv_check_bwd(p, u, x, w.get(), nullptr, nullptr, nullptr, ws, p.ws_bytes) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "nothing to compute"),
+          "dwconv: no output accepted");
+    CHECK(dwconv_check_bwd(p, u, x, nullptr, dx, nullptr, nullptr, ws, p.ws_bytes) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "needed for dx"),
+          "dwconv: dx without w accepted");
+    CHECK(dwconv_check_bwd(p, u, nullptr, w.get(), nullptr, dw.get(), nullptr, ws, p.ws_bytes) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "needed for dw"),
+          "dwconv: dw without x accepted");
+    CHECK(dwconv_check_bwd(p, u, x, w.get(), dx, dw.get(), db.get(), ws, p.ws_bytes - 1) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "workspace of"),
+          "dwconv: short workspace accepted");
+    CHECK(dwconv_check_bwd(p, u, x, w.get(), dx, dw.get(), db.get(), nullptr, p.ws_bytes) == SFCVIT_EINVAL, "dwconv: null workspace accepted");
+    CHECK(dwconv_check_bwd(p, u2, x, w.get(), dx, dw.get(), db.get(), ws, p.ws_bytes) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "aligned"),
+          "dwconv: misaligned du accepted");
+    CHECK(dwconv_check_bwd(p, u, x, w.get(), dx, dw.get(), db.get(), static_cast<char *>(ws) + 4, p.ws_bytes) == SFCVIT_EINVAL, "dwconv: misaligned workspace accepted");
+    std::free(x);
+    std::free(dx);
+    std::free(u);
+    std::free(ws);
+    char name[96];
+    CHECK(sfcvit_last_dwconv_kernel(name, sizeof(name)) == SFCVIT_OK && !std::strcmp(name, "none"), "dwconv: last kernel '%s'", name);
+    CHECK(sfcvit_last_dwconv_kernel(nullptr, 4) == SFCVIT_EINVAL && sfcvit_last_dwconv_kernel(name, 0) == SFCVIT_EINVAL, "dwconv: null / empty name buffer accepted");
+}
+
+// tokmix_left_plan, tokmix_wgrad_plan and tokmix_check_wgrad (token_mix.cpp): the shared envelope with its three int guards
+// one step inside and outside, the weight loader's vector width, the image ranges of wgrad, and the pointer rules.
+static void check_tokmix() {
+    const auto args = [](int B, int M, int K, int D) {
+        sfcvit_tokmix_args a{};
+        a.w = ptr(0); a.x = ptr(1); a.c = ptr(2);
+        a.B = B; a.M = M; a.K = K; a.D = D;
+        return a;
+    };
+    // both plans share the envelope: a shape is accepted or refused by both, with the same reason
+    const auto refused = [&](int B, int M, int K, int D, const char *why) {
+        const sfcvit_tokmix_args a = args(B, M, K, D);
+        const TokmixPlan l = tokmix_left_plan(&a), g = tokmix_wgrad_plan("host_check", B, M, K, D);
+        CHECK(l.err == SFCVIT_EINVAL && std::strstr(l.msg, why), "tokmix_left B=%d M=%d K=%d D=%d: '%s' lacks '%s'", B, M, K, D, l.msg, why);
+        CHECK(g.err == SFCVIT_EINVAL && std::strstr(g.msg, why), "tokmix_wgrad B=%d M=%d K=%d D=%d: '%s' lacks '%s'", B, M, K, D, g.msg, why);
+        CHECK(sfcvit_tokmix_wgrad_workspace(B, M, K, D) == 0, "tokmix: workspace of a refused shape");
+    };
+    const auto accepted = [&](int B, int M, int K, int D) {
+        const sfcvit_tokmix_args a = args(B, M, K, D);
+        const TokmixPlan l = tokmix_left_plan(&a), g = tokmix_wgrad_plan("host_check", B, M, K, D);
+        CHECK(l.err == SFCVIT_OK, "tokmix_left B=%d M=%d K=%d D=%d refused: %s", B, M, K, D, l.msg);
+        CHECK(g.err == SFCVIT_OK, "tokmix_wgrad B=%d M=%d K=%d D=%d refused: %s", B, M, K, D, g.msg);
+        if (l.err || g.err) return g;
+        CHECK(int64_t(l.tiles_m) * TMX_TILE >= M && int64_t(l.tiles_n) * TMX_TILE >= D && l.grid == int64_t(l.tiles_m) * l.tiles_n * B, "tokmix_left: tiles");
+        CHECK(int64_t(g.tiles_m) * TMX_TILE >= M && int64_t(g.tiles_n) * TMX_TILE >= K && g.grid == int64_t(g.tiles_m) * g.tiles_n * g.ranges, "tokmix_wgrad: tiles");
+        CHECK(g.ranges >= 1 && g.ranges <= TMX_MAX_RANGES && int64_t(g.ranges) * g.per_range >= B && int64_t(g.ranges - 1) * g.per_range < B,
+              "tokmix_wgrad B=%d: %d ranges of %d images", B, g.ranges, g.per_range);
+        CHECK(g.ld == int64_t(M) * K + M && g.ws_bytes == int64_t(g.ranges) * g.ld * 4, "tokmix_wgrad: workspace");
+        CHECK(sfcvit_tokmix_wgrad_workspace(B, M, K, D) == g.ws_bytes, "tokmix_wgrad: workspace entry point");
+        return g;
+    };
+    const TokmixPlan null_plan = tokmix_left_plan(nullptr);
+    CHECK(null_plan.err == SFCVIT_EINVAL && std::strstr(null_plan.msg, "null argument block"), "tokmix_left: null argument block accepted");
+    accepted(1, 8, 1, 8);
+    accepted(1, 1, 8, 8);
+    accepted(2, 32, 5, 16);
+    refused(0, 8, 8, 8, "every extent");
+    refused(1, 0, 8, 8, "every extent");
+    refused(1, 8, 0, 8, "every extent");
+    refused(-1, 8, 8, 8, "every extent");
+    refused(1, 1, 1, 8, "hidden width");
+    refused(2, 12, 5, 16, "hidden width");
+    refused(2, 36, 5, 16, "hidden width");
+    for (int D : {0, 12, -8, INT32_MAX}) refused(2, 32, 5, D, "multiple of 8");
+    // M K + M, M D and K D are ints (2^31 - 1 is prime: no product lands on it)
+    CHECK(accepted(1, 32768, 65534, 8).ld == 32768 * 65535, "tokmix: largest M K + M");
+    refused(1, 32768, 65535, 8, "too large");
+    accepted(1, 16, 8, INT32_MAX / 16 / 8 * 8);                  // M D
+    refused(1, 16, 8, INT32_MAX / 16 / 8 * 8 + 8, "too large");
+    accepted(1, 8, 16, INT32_MAX / 16 / 8 * 8);                  // K D
+    refused(1, 8, 16, INT32_MAX / 16 / 8 * 8 + 8, "too large");
+    refused(1, INT32_MAX / 8 * 8, INT32_MAX / 8 * 8, 8, "too large");
+    // the batch has no bound of its own: wgrad splits it into at most 64 ranges, left puts it on the grid
+    for (int B = 1; B <= 200; B++) accepted(B, 32, 5, 16);
+    CHECK(accepted(2, 32, 5, 16).ws_bytes == 2 * (32 * 5 + 32) * 4 && accepted(4096, 32, 5, 16).ws_bytes == 64 * (32 * 5 + 32) * 4, "tokmix_wgrad: the pinned workspaces");
+    CHECK(accepted(INT32_MAX, 8, 8, 8).ranges == TMX_MAX_RANGES, "tokmix: the largest batch");
+    {
+        const sfcvit_tokmix_args a = args(INT32_MAX, 136, 8, 8);   // two row tiles: 2 (2^31 - 1) workgroups
+        const TokmixPlan l = tokmix_left_plan(&a);
+        CHECK(l.err == SFCVIT_EINVAL && std::strstr(l.msg, "launch grid"), "tokmix_left: a grid beyond int accepted: %s", l.msg);
+        CHECK(tokmix_wgrad_plan("host_check", INT32_MAX, 136, 8, 8).err == SFCVIT_OK, "tokmix_wgrad: the same shape keeps 64 ranges");
+    }
+    for (int act : {int(SFCVIT_ACT_NONE), int(SFCVIT_ACT_RELU), int(SFCVIT_ACT_GELU), -1, 3}) {
+        sfcvit_tokmix_args a = args(2, 32, 5, 16);
+        a.act = act;
+        const TokmixPlan l = tokmix_left_plan(&a);
+        if (act == SFCVIT_ACT_NONE || act == SFCVIT_ACT_GELU) CHECK(l.err == SFCVIT_OK, "tokmix_left: act=%d refused: %s", act, l.msg);
+        else CHECK(l.err == SFCVIT_EINVAL && std::strstr(l.msg, "act="), "tokmix_left: act=%d accepted", act);
+    }
+    // weight loader: the widest of 8 / 4 / 2 / 1 elements that divides the row pitch and whose bytes the pointer is aligned to
+    const int M = 8, KMAX = 12;
+    void *wblk = std::aligned_alloc(16, size_t(M) * KMAX * 2 + 16), *blk = std::aligned_alloc(16, 32);
+    for (int pitch : {8, 12, 6, 5})
+        for (int off : {0, 8, 4, 2})
+            for (int tr = 0; tr < 2; tr++) {
+                sfcvit_tokmix_args a = tr ? args(2, pitch, M, 16) : args(2, M, pitch, 16);
+                a.w = static_cast<char *>(wblk) + off;
+                a.w_transposed = tr;
+                int want = 1;
+                for (int u : {2, 4, 8})
+                    if (pitch % u == 0 && off % (2 * u) == 0) want = u;
+                const TokmixPlan l = tokmix_left_plan(&a);
+                CHECK(l.err == SFCVIT_OK && l.wunit == want, "tokmix_left pitch %d, w at +%d, transposed %d: wunit %d, expected %d (%s)", pitch, off, tr, l.wunit, want, l.msg);
+            }
+    {
+        sfcvit_tokmix_args a = args(2, 32, 5, 16);
+        a.w = static_cast<char *>(wblk) + 1;
+        CHECK(tokmix_left_plan(&a).err == SFCVIT_EINVAL, "tokmix_left: odd w accepted");
+        a.w = wblk;
+        a.bias = static_cast<char *>(blk) + 1;
+        CHECK(tokmix_left_plan(&a).err == SFCVIT_EINVAL, "tokmix_left: odd bias accepted");
+        a.bias = static_cast<char *>(blk) + 2;
+        CHECK(tokmix_left_plan(&a).err == SFCVIT_OK, "tokmix_left: a 2-byte aligned bias refused");
+        a.residual = static_cast<char *>(blk) + 8;
+        CHECK(tokmix_left_plan(&a).err == SFCVIT_EINVAL && std::strstr(tokmix_left_plan(&a).msg, "16-byte"), "tokmix_left: misaligned residual accepted");
+        a.residual = nullptr;
+        a.x = nullptr;
+        CHECK(tokmix_left_plan(&a).err == SFCVIT_EINVAL && std::strstr(tokmix_left_plan(&a).msg, "null pointer"), "tokmix_left: null x accepted");
+    }
+    std::free(wblk);
+    std::free(blk);
+
+    const int B = 2, Mw = 32, K = 5, D = 16;
+    const TokmixPlan p = accepted(B, Mw, K, D);
+    void *g = std::aligned_alloc(16, size_t(B) * Mw * D * 2), *x = std::aligned_alloc(16, size_t(B) * K * D * 2), *ws = std::aligned_alloc(16, size_t(p.ws_bytes));
+    std::unique_ptr<float[]> dw(new float[Mw * K]), db(new float[Mw]);
+    CHECK(tokmix_check_wgrad(p, g, x, dw.get(), db.get(), ws, p.ws_bytes) == SFCVIT_OK, "tokmix_wgrad check: %s", sfcvit_last_error());
+    CHECK(tokmix_check_wgrad(p, g, nullptr, nullptr, db.get(), ws, p.ws_bytes) == SFCVIT_OK, "tokmix_wgrad: db alone needs no x");
+    CHECK(tokmix_check_wgrad(p, nullptr, x, dw.get(), db.get(), ws, p.ws_bytes) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "(g)"), "tokmix_wgrad: null g accepted");
+    CHECK(tokmix_check_wgrad(p, g, x, nullptr, nullptr, ws, p.ws_bytes) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "nothing to compute"),
+          "tokmix_wgrad: no output accepted");
+    CHECK(tokmix_check_wgrad(p, g, nullptr, dw.get(), nullptr, ws, p.ws_bytes) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "needed for dw"),
+          "tokmix_wgrad: dw without x accepted");
+    CHECK(tokmix_check_wgrad(p, static_cast<char *>(g) + 8, x, dw.get(), db.get(), ws, p.ws_bytes) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "aligned"),
+          "tokmix_wgrad: misaligned g accepted");
+    CHECK(tokmix_check_wgrad(p, g, x, dw.get(), db.get(), static_cast<char *>(ws) + 4, p.ws_bytes) == SFCVIT_EINVAL, "tokmix_wgrad: misaligned workspace accepted");
+    CHECK(tokmix_check_wgrad(p, g, x, dw.get(), db.get(), ws, p.ws_bytes - 1) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "workspace of"),
+          "tokmix_wgrad: short workspace accepted");
+    CHECK(tokmix_check_wgrad(p, g, x, dw.get(), db.get(), nullptr, p.ws_bytes) == SFCVIT_EINVAL, "tokmix_wgrad: null workspace accepted");
+    CHECK(tokmix_check_wgrad(tokmix_wgrad_plan("tokmix_wgrad", B, Mw, K, 12), g, x, dw.get(), db.get(), ws, p.ws_bytes) == SFCVIT_EINVAL &&
+          std::strstr(sfcvit_last_error(), "D=12"), "tokmix_wgrad: the plan's refusal is the call's");
+    std::free(g);
+    std::free(x);
+    std::free(ws);
+    char name[96];
+    CHECK(sfcvit_last_tokmix_kernel(name, sizeof(name)) == SFCVIT_OK && !std::strcmp(name, "none"), "tokmix: last kernel '%s'", name);
+    CHECK(sfcvit_last_tokmix_kernel(nullptr, 4) == SFCVIT_EINVAL && sfcvit_last_tokmix_kernel(name, 0) == SFCVIT_EINVAL, "tokmix: null / empty name buffer accepted");
+}
+
 int main() {
     const int curves[] = {SFCVIT_CURVE_HILBERT, SFCVIT_CURVE_Z, SFCVIT_CURVE_MOORE, SFCVIT_CURVE_PEANO, SFCVIT_CURVE_RASTER,
                           SFCVIT_CURVE_SPIRAL, SFCVIT_CURVE_HILBERT_T};
@@ -600,6 +835,8 @@ int main() {
     check_mask_blocks();
     check_pos_embed();
     check_token_pool();
+    check_dwconv();
+    check_tokmix();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     std::printf("host_check ok\n");
     return 0;

@@ -565,7 +565,7 @@ int gather_tiles_impl(const char *what, const void *x, const int32_t *pix, const
     // the same: 69 vs 37 us).  Streaming loads do not allocate: 46.0 us; with streaming stores 43.2 us alone, 44.0 us in
     // the step (profiles/r4/gather_ab.txt).  SFCVIT_GATHER_NT=0..3 for the A/B.
     static const int nt = env_int("SFCVIT_GATHER_NT", 3);
-    note_tokenizer_kernel("tokens_gather_tiles_kernel<%d, %s>", C, perm ? "mix" : "fp32");
+    g_tokenizer.set("tokens_gather_tiles_kernel<%d, %s>", C, perm ? "mix" : "fp32");
 #define TILES_K(CC, NTV, UU, MX) hipLaunchKernelGGL((tokens_gather_tiles_kernel<CC, NTV, UU, MX>), grid, dim3(TG_THREADS), lds, s, xp, pix, order, origin, tp, B, HW, W, wmagic, N, perm, rec)
 #define TILES(CC, NTV) do { if (perm) TILES_K(CC, NTV, 1, true); else if (upw == 2) TILES_K(CC, NTV, 2, false); else TILES_K(CC, NTV, 1, false); } while (0)
 #define TILES_C(CC) do { if (nt == 1) TILES(CC, 1); else if (nt == 2) TILES(CC, 2); else if (nt == 3) TILES(CC, 3); else TILES(CC, 0); } while (0)
@@ -596,7 +596,7 @@ int gather_impl(const char *what, const void *x, int x_is_bf16, const int32_t *p
     if (P <= GT && C <= 4 && size_t(2) * GIMG * ld * 2 <= 64 * 1024) {
         const dim3 grid2((N + 1) / 2, grid.y);
         const size_t lds = size_t(2) * GIMG * ld * 2;
-        note_tokenizer_kernel("tokens_gather_p256_kernel<%s>", perm ? "mix" : x_is_bf16 ? "bf16" : "fp32");
+        g_tokenizer.set("tokens_gather_p256_kernel<%s>", perm ? "mix" : x_is_bf16 ? "bf16" : "fp32");
         if (perm)
             hipLaunchKernelGGL((tokens_gather_p256_kernel<false, 4, true>), grid2, dim3(2 * GT), lds, s, x, pix, order, tp, B, C, HW, N, P, ld, W, perm, rec);
         else if (x_is_bf16)
@@ -605,7 +605,7 @@ int gather_impl(const char *what, const void *x, int x_is_bf16, const int32_t *p
             hipLaunchKernelGGL((tokens_gather_p256_kernel<false, 4, false>), grid2, dim3(2 * GT), lds, s, x, pix, order, tp, B, C, HW, N, P, ld, W, perm, rec);
         return check_launch(what);
     }
-    note_tokenizer_kernel("tokens_gather_kernel<%s>", perm ? "mix" : x_is_bf16 ? "bf16" : "fp32");
+    g_tokenizer.set("tokens_gather_kernel<%s>", perm ? "mix" : x_is_bf16 ? "bf16" : "fp32");
     if (perm)
         hipLaunchKernelGGL((tokens_gather_kernel<false, true>), grid, dim3(GT), size_t(ld) * 2, s, x, pix, tp, B, C, HW, N, P, ld, W, perm, rec);
     else if (x_is_bf16)
@@ -669,7 +669,7 @@ extern "C" int sfcvit_patch_embed_fwd(const sfcvit_patch_embed_args *a, void *st
     if (int rc = check_launch("patch_embed_fwd permute")) return rc;
     dim3 grid(((a->D + BN - 1) / BN) * ((g.M + BM - 1) / BM)), block(THREADS);
     const size_t lds = 4 * TILE_BYTES;
-    note_tokenizer_kernel("pe_fwd_kernel<%s>", a->x_is_bf16 ? "bf16" : "fp32");
+    g_tokenizer.set("pe_fwd_kernel<%s>", a->x_is_bf16 ? "bf16" : "fp32");
     if (a->x_is_bf16)
         hipLaunchKernelGGL(pe_fwd_kernel<true>, grid, block, lds, s, g, wp, static_cast<const uint16_t *>(a->bias),
                            static_cast<uint16_t *>(a->y), a->D);
@@ -698,7 +698,7 @@ extern "C" int sfcvit_patch_embed_bwd(const sfcvit_patch_embed_args *a, void *st
     float *slabs = static_cast<float *>(a->workspace);
     dim3 grid(((g.Kp + BN - 1) / BN) * ((a->D + BM - 1) / BM) * zs), block(THREADS);
     const size_t lds = 4 * TILE_BYTES;
-    note_tokenizer_kernel("pe_bwd_kernel<%s>", a->x_is_bf16 ? "bf16" : "fp32");
+    g_tokenizer.set("pe_bwd_kernel<%s>", a->x_is_bf16 ? "bf16" : "fp32");
     if (a->x_is_bf16)
         hipLaunchKernelGGL(pe_bwd_kernel<true>, grid, block, lds, s, g, static_cast<const uint16_t *>(a->y), slabs, a->D, m_per_split);
     else

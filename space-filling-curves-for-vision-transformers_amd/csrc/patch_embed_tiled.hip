@@ -376,7 +376,7 @@ int pe2_fwd(const sfcvit_patch_embed_args &a, hipStream_t s) {
     const int NCT = a.D / TN;
     const int groups = (n_row_tiles + 7) / 8;                       // row tiles are dealt to the 8 XCD slots in groups of 8
     dim3 grid(unsigned(groups) * 8u * unsigned(NCT)), block(PT);
-    note_tokenizer_kernel("pe2_fwd_kernel<%s>", a.x_is_bf16 ? "bf16" : "fp32");
+    g_tokenizer.set("pe2_fwd_kernel<%s>", a.x_is_bf16 ? "bf16" : "fp32");
     if (a.x_is_bf16)
         hipLaunchKernelGGL(pe2_fwd_kernel<true>, grid, block, PE2_LDS, s, a.x, a.desc, wp, static_cast<const uint16_t *>(a.bias),
                            static_cast<uint16_t *>(a.y), a.B, a.C, a.HW, a.D, n_row_tiles);
@@ -403,7 +403,7 @@ int pe2_bwd(const sfcvit_patch_embed_args &a, hipStream_t s) {
         if (int rc = raise_lds_limit(k, PE2_BWD_LDS, "patch_embed_bwd (tiled) attribute")) return rc;
     float *slabs = static_cast<float *>(a.workspace);
     dim3 grid(unsigned((nz + 7) / 8) * 8u * unsigned((a.D / 256) * a.C)), block(PT);      // row ranges dealt to the 8 XCD slots
-    note_tokenizer_kernel("pe2_bwd_kernel<%s>", a.x_is_bf16 ? "bf16" : "fp32");
+    g_tokenizer.set("pe2_bwd_kernel<%s>", a.x_is_bf16 ? "bf16" : "fp32");
     if (a.x_is_bf16)
         hipLaunchKernelGGL(pe2_bwd_kernel<true>, grid, block, PE2_BWD_LDS, s, a.x, a.desc, static_cast<const uint16_t *>(a.y), slabs, a.B, a.C, a.HW, a.D, KR);
     else

@@ -1,53 +1,29 @@
-// Argument checks and launch geometry of sfcvit_pos_embed_fwd / _bwd (pos_embed.h).  Plain host code in the style of
-// token_agg.cpp: no HIP call, no allocation, so every refusal is testable on a machine without a GPU.
+// Argument checks and launch geometry of sfcvit_pos_embed_fwd / _bwd (pos_embed.h), on the scaffold of plan.h.  Plain host
+// code: no HIP call, no allocation, so every refusal is testable on a machine without a GPU.
 #include "pos_embed.h"
-
-#include <cstdarg>
-#include <cstdio>
 
 #include "common_host.h"
 
 namespace sfcvit {
-namespace {
 
-thread_local char g_pos_embed[96] = "none";
-
-__attribute__((format(printf, 2, 3))) void refuse(PosEmbedPlan &p, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(p.msg, sizeof(p.msg), fmt, ap);
-    va_end(ap);
-    p.err = SFCVIT_EINVAL;
-}
-#define REFUSE(...) do { refuse(p, __VA_ARGS__); return p; } while (0)
-
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-}  // namespace
-
-void note_pos_embed_kernel(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_pos_embed, sizeof(g_pos_embed), fmt, ap);
-    va_end(ap);
-}
+thread_local KernelNote g_pos_embed;
 
 PosEmbedPlan pos_embed_plan(const char *what, int B, int N, int D) {
     PosEmbedPlan p;
-    if (B <= 0 || N <= 0) REFUSE("%s: B=%d N=%d (B, N >= 1)", what, B, N);
-    if (D < 8 || D % 8) REFUSE("%s: D=%d must be a positive multiple of 8 (16-byte vectors)", what, D);
+    if (B <= 0 || N <= 0) REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d (B, N >= 1)", what, B, N);
+    if (D < 8 || D % 8) REFUSE(SFCVIT_EINVAL, "%s: D=%d must be a positive multiple of 8 (16-byte vectors)", what, D);
     const int64_t nd = int64_t(N) * D;                          // < 2^62
-    if (nd > (INT64_MAX / 4) / B) REFUSE("%s: B=%d N=%d D=%d: the byte counts leave int64", what, B, N, D);
+    if (nd > (INT64_MAX / 4) / B) REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d D=%d: the byte counts leave int64", what, B, N, D);
     p.vecs = nd / 8;
     const int64_t fwd_blocks = ceil_div(p.vecs, PE_THREADS), slabs = ceil_div(p.vecs, PE_CV);
-    if (slabs > INT32_MAX) REFUSE("%s: N=%d D=%d beyond the launch grid", what, N, D);
+    if (slabs > INT32_MAX) REFUSE(SFCVIT_EINVAL, "%s: N=%d D=%d beyond the launch grid", what, N, D);
     p.fwd_blocks = int(fwd_blocks);
     p.slabs = int(slabs);
     // forward: as many images per lane as still leave ~1024 workgroups, at most PE_MAX_IMGS
     int64_t imgs = fwd_blocks * B / 1024;
     p.imgs = imgs < 1 ? 1 : imgs > PE_MAX_IMGS ? PE_MAX_IMGS : int(imgs);
     const int64_t groups = ceil_div(B, p.imgs);
-    if (groups > 65535) REFUSE("%s: B=%d beyond the launch grid", what, B);
+    if (groups > 65535) REFUSE(SFCVIT_EINVAL, "%s: B=%d beyond the launch grid", what, B);
     p.fwd_groups = int(groups);
     // backward: the batch is split only where the table alone gives too few workgroups and a lane keeps >= 4 images
     const int64_t want = ceil_div(PE_MIN_WGS, slabs), most = B / (PE_RL * 4) > 1 ? B / (PE_RL * 4) : 1;
@@ -81,8 +57,4 @@ extern "C" int64_t sfcvit_pos_embed_bwd_workspace(int B, int N, int D) {
     return p.err ? 0 : p.ws_bytes;
 }
 
-extern "C" int sfcvit_last_pos_embed_kernel(char *buf, int n) {
-    if (!buf || n <= 0) return SFCVIT_EINVAL;
-    snprintf(buf, size_t(n), "%s", sfcvit::g_pos_embed);
-    return SFCVIT_OK;
-}
+extern "C" int sfcvit_last_pos_embed_kernel(char *buf, int n) { return sfcvit::g_pos_embed.read(buf, n); }

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "../../include/sfcvit.h"
+#include "plan.h"
 
 namespace sfcvit {
 
@@ -14,9 +15,7 @@ constexpr int PE_CV = 32;           // backward: lanes across columns, a workgro
 constexpr int PE_RL = 8;            // backward: lanes across images; lane rl sums images rl, rl + 8, ... of its workgroup's range
 constexpr int PE_MIN_WGS = 512;     // two workgroups per CU of the MI355X before the batch is left whole
 
-struct PosEmbedPlan {
-    int err = SFCVIT_OK;
-    char msg[160] = "";
+struct PosEmbedPlan : PlanStatus {
     int64_t vecs = 0;               // N * D / 8: 16-byte vectors of the table
     // forward: grid (fwd_blocks, fwd_groups); a lane owns one table vector and `imgs` consecutive images
     int fwd_blocks = 0, fwd_groups = 0, imgs = 0;
@@ -30,6 +29,7 @@ PosEmbedPlan pos_embed_plan(const char *what, int B, int N, int D);
 // The pointer / workspace checks of the two entry points, after the plan: SFCVIT_OK or the refusal (message recorded).
 int pos_embed_check_fwd(const PosEmbedPlan &p, const void *x, const void *pos, const void *y);
 int pos_embed_check_bwd(const PosEmbedPlan &p, const void *dy, const void *dpos, const void *workspace, int64_t workspace_bytes);
-void note_pos_embed_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+// Which kernel of this family the calling thread launched last (sfcvit_last_pos_embed_kernel).
+extern thread_local KernelNote g_pos_embed;
 
 }  // namespace sfcvit

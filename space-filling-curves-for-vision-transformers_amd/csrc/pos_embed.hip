@@ -119,7 +119,7 @@ extern "C" int sfcvit_pos_embed_fwd(const void *x, const void *pos, void *y, int
     case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: CALL(8); break;
     }
 #undef CALL
-    note_pos_embed_kernel("pos_embed_fwd_kernel<%d>", p.imgs);
+    g_pos_embed.set("pos_embed_fwd_kernel<%d>", p.imgs);
     return check_launch("pos_embed_fwd");
 }
 
@@ -134,7 +134,7 @@ extern "C" int sfcvit_pos_embed_bwd(const void *dy, void *dpos, int grad_bf16, i
     if (out == 0) hipLaunchKernelGGL(pos_embed_bwd_kernel<0>, grid, dim3(PE_THREADS), 0, st, ds, workspace, B, p.rows, p.vecs);
     else if (out == 1) hipLaunchKernelGGL(pos_embed_bwd_kernel<1>, grid, dim3(PE_THREADS), 0, st, ds, dpos, B, p.rows, p.vecs);
     else hipLaunchKernelGGL(pos_embed_bwd_kernel<2>, grid, dim3(PE_THREADS), 0, st, ds, dpos, B, p.rows, p.vecs);
-    note_pos_embed_kernel("pos_embed_bwd_kernel<%d>", out);
+    g_pos_embed.set("pos_embed_bwd_kernel<%d>", out);
     if (int rc = check_launch("pos_embed_bwd")) return rc;
     if (out == 0) {
         const int64_t nd = p.vecs * 8;                         // splits > 1 only where N D < PE_MIN_WGS x 256: fits int

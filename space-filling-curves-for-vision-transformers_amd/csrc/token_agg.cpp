@@ -1,56 +1,34 @@
-// Argument checks and launch geometry of sfcvit_dwconv1d_fwd / _bwd (token_agg.h).  Plain host code in the style of
-// attention_probe.cpp: no HIP call, no allocation, so every refusal is testable on a machine without a GPU.
+// Argument checks and launch geometry of sfcvit_dwconv1d_fwd / _bwd (token_agg.h), on the scaffold of plan.h.  Plain host
+// code: no HIP call, no allocation, so every refusal is testable on a machine without a GPU.
 #include "token_agg.h"
-
-#include <cstdarg>
-#include <cstdio>
 
 #include "common_host.h"
 
 namespace sfcvit {
-namespace {
 
-thread_local char g_dwconv[96] = "none";
-
-__attribute__((format(printf, 2, 3))) void refuse(DwconvPlan &p, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(p.msg, sizeof(p.msg), fmt, ap);
-    va_end(ap);
-    p.err = SFCVIT_EINVAL;
-}
-#define REFUSE(...) do { refuse(p, __VA_ARGS__); return p; } while (0)
-
-int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-}  // namespace
-
-void note_dwconv_kernel(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_dwconv, sizeof(g_dwconv), fmt, ap);
-    va_end(ap);
-}
+thread_local KernelNote g_dwconv;
 
 DwconvPlan dwconv_plan(const char *what, int B, int N, int D, int k, int s) {
     DwconvPlan p;
-    if (k < 1 || k > DWC_MAX_K) REFUSE("%s: kernel size k=%d not supported (1..%d)", what, k, DWC_MAX_K);
-    if (s < 1 || s > DWC_MAX_S) REFUSE("%s: stride s=%d not supported (1..%d)", what, s, DWC_MAX_S);
-    if (D <= 0 || D % 8) REFUSE("%s: D=%d must be a positive multiple of 8", what, D);
-    if (B <= 0 || N <= 0 || B > 65535) REFUSE("%s: B=%d N=%d (1 <= B <= 65535, N >= 1)", what, B, N);
-    if (int64_t(N) + 2 * DWC_MAX_K > INT32_MAX / 2) REFUSE("%s: N=%d too long", what, N);
+    if (k < 1 || k > DWC_MAX_K) REFUSE(SFCVIT_EINVAL, "%s: kernel size k=%d not supported (1..%d)", what, k, DWC_MAX_K);
+    if (s < 1 || s > DWC_MAX_S) REFUSE(SFCVIT_EINVAL, "%s: stride s=%d not supported (1..%d)", what, s, DWC_MAX_S);
+    if (D <= 0 || D % 8) REFUSE(SFCVIT_EINVAL, "%s: D=%d must be a positive multiple of 8", what, D);
+    if (B <= 0 || N <= 0 || B > 65535) REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d (1 <= B <= 65535, N >= 1)", what, B, N);
+    if (int64_t(N) + 2 * DWC_MAX_K > INT32_MAX / 2) REFUSE(SFCVIT_EINVAL, "%s: N=%d too long", what, N);
     p.pad = k / 2;
     p.Nout = (N + 2 * p.pad - k) / s + 1;       // >= 1: N + 2 (k / 2) >= k for every N >= 1
     p.spec = k == 3 && s == 1;
-    p.slabs = ceil_div(D, DWC_CV * 8);
+    p.slabs = int(ceil_div(D, DWC_CV * 8));
     const int rows = p.Nout > N ? p.Nout : N;
-    p.groups = ceil_div(rows, DWC_RL * DWC_MAX_RUN);
-    if (p.groups > 65535 || int64_t(B) * p.groups > INT32_MAX) REFUSE("%s: B=%d N=%d beyond the launch grid", what, B, N);
-    p.run_out = ceil_div(p.Nout, p.groups * DWC_RL);
-    p.run_in = ceil_div(N, p.groups * DWC_RL);
-    if (int64_t(D) * (k + 1) > INT32_MAX) REFUSE("%s: D=%d too wide", what, D);
+    p.groups = int(ceil_div(rows, DWC_RL * DWC_MAX_RUN));
+    if (p.groups > 65535 || int64_t(B) * p.groups > INT32_MAX) REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d beyond the launch grid", what, B, N);
+    p.run_out = int(ceil_div(p.Nout, p.groups * DWC_RL));
+    p.run_in = int(ceil_div(N, p.groups * DWC_RL));
+    if (int64_t(D) * (k + 1) > INT32_MAX) REFUSE(SFCVIT_EINVAL, "%s: D=%d too wide", what, D);
     p.ld = D * (k + 1);
-    p.ws_bytes = int64_t(B) * p.groups * p.ld * int64_t(sizeof(float));
+    const int64_t parts = int64_t(B) * p.groups;                // < 2^31 partial rows of < 2^31 floats
+    if (parts > (INT64_MAX / 4) / p.ld) REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d D=%d: the byte counts leave int64", what, B, N, D);
+    p.ws_bytes = parts * p.ld * int64_t(sizeof(float));
     return p;
 }
 
@@ -91,8 +69,4 @@ extern "C" int64_t sfcvit_dwconv1d_bwd_workspace(int B, int N, int D, int k, int
     return p.err ? 0 : p.ws_bytes;
 }
 
-extern "C" int sfcvit_last_dwconv_kernel(char *buf, int n) {
-    if (!buf || n <= 0) return SFCVIT_EINVAL;
-    snprintf(buf, size_t(n), "%s", sfcvit::g_dwconv);
-    return SFCVIT_OK;
-}
+extern "C" int sfcvit_last_dwconv_kernel(char *buf, int n) { return sfcvit::g_dwconv.read(buf, n); }

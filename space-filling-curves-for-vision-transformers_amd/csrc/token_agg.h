@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "../../include/sfcvit.h"
+#include "plan.h"
 
 namespace sfcvit {
 
@@ -14,9 +15,7 @@ constexpr int DWC_THREADS = DWC_CV * DWC_RL;
 constexpr int DWC_MAX_K = 9, DWC_MAX_S = 4;
 constexpr int DWC_MAX_RUN = 32;   // rows a lane walks at most; longer sequences take more workgroups per image
 
-struct DwconvPlan {
-    int err = SFCVIT_OK;
-    char msg[160] = "";
+struct DwconvPlan : PlanStatus {
     bool spec = false;            // k = 3, s = 1: the register-window kernels
     int pad = 0, Nout = 0;
     int slabs = 0;                // grid.x: ceil(D / 256)
@@ -32,6 +31,7 @@ DwconvPlan dwconv_plan(const char *what, int B, int N, int D, int k, int s);
 int dwconv_check_fwd(const DwconvPlan &p, const void *x, const void *w, const void *u);
 int dwconv_check_bwd(const DwconvPlan &p, const void *du, const void *x, const void *w, const void *dx, const void *dw, const void *db,
                      const void *workspace, int64_t workspace_bytes);
-void note_dwconv_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+// Which kernel of this family the calling thread launched last (sfcvit_last_dwconv_kernel).
+extern thread_local KernelNote g_dwconv;
 
 }  // namespace sfcvit

@@ -301,12 +301,12 @@ extern "C" int sfcvit_dwconv1d_fwd(const void *x, const void *w, const void *bia
     u16 *us = static_cast<u16 *>(u);
     if (p.spec) {
         hipLaunchKernelGGL(dwconv3_fwd_kernel, grid, dim3(DWC_THREADS), 0, st, xs, ws, bs, us, N, D, p.run_out);
-        note_dwconv_kernel("dwconv3_fwd_kernel");
+        g_dwconv.set("dwconv3_fwd_kernel");
     } else {
 #define CALL(KK) launch_fwd<KK>(p, grid, st, xs, ws, bs, us, N, D, s)
         DWC_FOR_K(k, CALL)
 #undef CALL
-        note_dwconv_kernel("dwconv_fwd_kernel<%d>", k);
+        g_dwconv.set("dwconv_fwd_kernel<%d>", k);
     }
     return check_launch("dwconv1d_fwd");
 }
@@ -325,12 +325,12 @@ extern "C" int sfcvit_dwconv1d_bwd(const void *du, const void *x, const void *w,
         if (dx && sums) hipLaunchKernelGGL((dwconv3_bwd_kernel<true, true>), grid, dim3(DWC_THREADS), 0, st, ds, xs, ws, dxs, part, N, D, p.run_out, p.ld);
         else if (dx) hipLaunchKernelGGL((dwconv3_bwd_kernel<true, false>), grid, dim3(DWC_THREADS), 0, st, ds, xs, ws, dxs, part, N, D, p.run_out, p.ld);
         else hipLaunchKernelGGL((dwconv3_bwd_kernel<false, true>), grid, dim3(DWC_THREADS), 0, st, ds, xs, ws, dxs, part, N, D, p.run_out, p.ld);
-        note_dwconv_kernel("dwconv3_bwd_kernel<%s, %s>", dx ? "true" : "false", sums ? "true" : "false");
+        g_dwconv.set("dwconv3_bwd_kernel<%s, %s>", dx ? "true" : "false", sums ? "true" : "false");
     } else {          // (also k = 3, s = 1 asked for db alone, without x)
 #define CALL(KK) launch_bwd<KK>(p, grid, st, ds, xs, ws, dxs, part, N, D, s)
         DWC_FOR_K(k, CALL)
 #undef CALL
-        note_dwconv_kernel("dwconv_bwd_kernel<%d>", k);
+        g_dwconv.set("dwconv_bwd_kernel<%d>", k);
     }
     if (int rc = check_launch("dwconv1d_bwd")) return rc;
     const int nparts = B * p.groups;

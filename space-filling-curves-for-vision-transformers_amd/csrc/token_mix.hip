@@ -245,7 +245,7 @@ extern "C" int sfcvit_tokmix_left(const sfcvit_tokmix_args *a, void *stream) {
     const bool heavy = a->act == SFCVIT_ACT_GELU || a->aux_in != nullptr;
     if (a->w_transposed) launch_left<true>(*a, p, heavy, s);
     else launch_left<false>(*a, p, heavy, s);
-    note_tokmix_kernel("tokmix_left_kernel<%s, %s>", a->w_transposed ? "true" : "false", heavy ? "true" : "false");
+    g_tokmix.set("tokmix_left_kernel<%s, %s>", a->w_transposed ? "true" : "false", heavy ? "true" : "false");
     return check_launch("tokmix_left");
 }
 
@@ -261,7 +261,7 @@ extern "C" int sfcvit_tokmix_wgrad(const void *g, const void *x, void *dw, void 
     hipLaunchKernelGGL(tokmix_wgrad_kernel, dim3(tiles * p.ranges), dim3(gemm_core::THREADS), 4 * gemm_core::TILE_BYTES, s,
                        static_cast<const uint16_t *>(g), static_cast<const uint16_t *>(x), part, B, M, K, D, tiles_n, tiles,
                        p.per_range, p.ld, dw ? 1 : 0, db ? 1 : 0);
-    note_tokmix_kernel("tokmix_wgrad_kernel");
+    g_tokmix.set("tokmix_wgrad_kernel");
     if (int rc = check_launch("tokmix_wgrad")) return rc;
     if (dw)
         if (int rc = reduce_cols(part, p.ranges, p.ld, M * K, dw, grads_bf16, stream)) return rc;

@@ -1,50 +1,25 @@
-// Argument checks and launch geometry of sfcvit_cls_prepend_fwd / _bwd and sfcvit_token_pool_fwd / _bwd (token_pool.h).
-// Plain host code in the style of pos_embed.cpp: no HIP call, no allocation, so every refusal is testable on a machine
-// without a GPU.
+// Argument checks and launch geometry of sfcvit_cls_prepend_fwd / _bwd and sfcvit_token_pool_fwd / _bwd (token_pool.h), on
+// the scaffold of plan.h.  Plain host code: no HIP call, no allocation, so every refusal is testable on a machine without
+// a GPU.
 #include "token_pool.h"
-
-#include <cstdarg>
-#include <cstdio>
 
 #include "common_host.h"
 
 namespace sfcvit {
-namespace {
 
-thread_local char g_token_pool[96] = "none";
-
-template <class P>
-__attribute__((format(printf, 2, 3))) void refuse(P &p, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(p.msg, sizeof(p.msg), fmt, ap);
-    va_end(ap);
-    p.err = SFCVIT_EINVAL;
-}
-#define REFUSE(...) do { refuse(p, __VA_ARGS__); return p; } while (0)
-
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-}  // namespace
-
-void note_token_pool_kernel(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_token_pool, sizeof(g_token_pool), fmt, ap);
-    va_end(ap);
-}
+thread_local KernelNote g_token_pool;
 
 ClsPrependPlan cls_prepend_plan(const char *what, int B, int N, int D) {
     ClsPrependPlan p;
-    if (B <= 0 || N <= 0) REFUSE("%s: B=%d N=%d (B, N >= 1)", what, B, N);
-    if (D < 8 || D % 8) REFUSE("%s: D=%d must be a positive multiple of 8 (16-byte vectors)", what, D);
+    if (B <= 0 || N <= 0) REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d (B, N >= 1)", what, B, N);
+    if (D < 8 || D % 8) REFUSE(SFCVIT_EINVAL, "%s: D=%d must be a positive multiple of 8 (16-byte vectors)", what, D);
     const int64_t nd1 = (int64_t(N) + 1) * D;                   // < 2^62
-    if (nd1 > (INT64_MAX / 4) / B) REFUSE("%s: B=%d N=%d D=%d: the byte counts leave int64", what, B, N, D);
+    if (nd1 > (INT64_MAX / 4) / B) REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d D=%d: the byte counts leave int64", what, B, N, D);
     p.dv = D / 8;
     p.xv = int64_t(N) * p.dv;
     const int64_t fwd_blocks = ceil_div(p.xv + p.dv, TP_THREADS), bwd_blocks = ceil_div(p.xv, TP_THREADS);
     p.slabs = int(ceil_div(p.dv, CP_CV));
-    if (fwd_blocks + p.slabs > INT32_MAX) REFUSE("%s: N=%d D=%d beyond the launch grid", what, N, D);
+    if (fwd_blocks + p.slabs > INT32_MAX) REFUSE(SFCVIT_EINVAL, "%s: N=%d D=%d beyond the launch grid", what, N, D);
     p.fwd_blocks = int(fwd_blocks);
     p.bwd_blocks = int(bwd_blocks);
     // copies: as many images per lane (1, 2, 4, 8) as still leave ~1024 workgroups
@@ -52,7 +27,7 @@ ClsPrependPlan cls_prepend_plan(const char *what, int B, int N, int D) {
     p.imgs = 1;
     while (p.imgs < CP_MAX_IMGS && p.imgs * 2 <= want) p.imgs *= 2;
     const int64_t groups = ceil_div(B, p.imgs);
-    if (groups > 65535) REFUSE("%s: B=%d beyond the launch grid", what, B);
+    if (groups > 65535) REFUSE(SFCVIT_EINVAL, "%s: B=%d beyond the launch grid", what, B);
     p.groups = int(groups);
     // dcls: one range of the batch up to 2048 images (64 per image lane), whole rounds of the 32 image lanes
     const int64_t splits = ceil_div(B, CP_MAX_ROWS);
@@ -64,11 +39,11 @@ ClsPrependPlan cls_prepend_plan(const char *what, int B, int N, int D) {
 
 TokenPoolPlan token_pool_plan(const char *what, int B, int T, int D, int first, int count) {
     TokenPoolPlan p;
-    if (B <= 0 || T <= 0) REFUSE("%s: B=%d T=%d (B, T >= 1)", what, B, T);
-    if (D < 8 || D % 8) REFUSE("%s: D=%d must be a positive multiple of 8 (16-byte vectors)", what, D);
+    if (B <= 0 || T <= 0) REFUSE(SFCVIT_EINVAL, "%s: B=%d T=%d (B, T >= 1)", what, B, T);
+    if (D < 8 || D % 8) REFUSE(SFCVIT_EINVAL, "%s: D=%d must be a positive multiple of 8 (16-byte vectors)", what, D);
     if (first < 0 || count < 1 || int64_t(first) + count > T)
-        REFUSE("%s: tokens [%d, %d + %d) are not a non-empty range of the %d tokens", what, first, first, count, T);
-    if (int64_t(T) * D > (INT64_MAX / 4) / B) REFUSE("%s: B=%d T=%d D=%d: the byte counts leave int64", what, B, T, D);
+        REFUSE(SFCVIT_EINVAL, "%s: tokens [%d, %d + %d) are not a non-empty range of the %d tokens", what, first, first, count, T);
+    if (int64_t(T) * D > (INT64_MAX / 4) / B) REFUSE(SFCVIT_EINVAL, "%s: B=%d T=%d D=%d: the byte counts leave int64", what, B, T, D);
     p.dv = D / 8;
     // the column slab narrows (32 -> 16 -> 8 vectors) while B x slabs leaves the GPU short of workgroups: the lanes it
     // frees split the token range further
@@ -77,7 +52,7 @@ TokenPoolPlan token_pool_plan(const char *what, int B, int T, int D, int first, 
     p.tl = TP_THREADS / p.cv;
     p.slabs = int(ceil_div(p.dv, p.cv));
     p.row_blocks = int(ceil_div(p.dv, TP_THREADS));
-    if (p.slabs > 65535) REFUSE("%s: D=%d beyond the launch grid", what, D);
+    if (p.slabs > 65535) REFUSE(SFCVIT_EINVAL, "%s: D=%d beyond the launch grid", what, D);
     p.row_copy = count == 1;
     return p;
 }
@@ -117,8 +92,4 @@ extern "C" int64_t sfcvit_cls_prepend_bwd_workspace(int B, int N, int D) {
     return p.err ? 0 : p.ws_bytes;
 }
 
-extern "C" int sfcvit_last_token_pool_kernel(char *buf, int n) {
-    if (!buf || n <= 0) return SFCVIT_EINVAL;
-    snprintf(buf, size_t(n), "%s", sfcvit::g_token_pool);
-    return SFCVIT_OK;
-}
+extern "C" int sfcvit_last_token_pool_kernel(char *buf, int n) { return sfcvit::g_token_pool.read(buf, n); }

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "../../include/sfcvit.h"
+#include "plan.h"
 
 namespace sfcvit {
 
@@ -17,9 +18,7 @@ constexpr int TP_MAX_CV = 32;       // pool: lanes across columns, 32, 16 or 8; 
 constexpr int TP_MIN_CV = 8;
 constexpr int TP_MIN_WGS = 1024;    // pool: four workgroups per CU of the MI355X before the column slab stops narrowing
 
-struct ClsPrependPlan {
-    int err = SFCVIT_OK;
-    char msg[160] = "";
+struct ClsPrependPlan : PlanStatus {
     int dv = 0;                     // D / 8: 16-byte vectors of a token row
     int64_t xv = 0;                 // N * D / 8: vectors of an image of x (y has xv + dv)
     // copies: grid.x blocks of 256 lanes over the vectors of one image, grid.y groups of `imgs` consecutive images
@@ -29,9 +28,7 @@ struct ClsPrependPlan {
     int64_t ws_bytes = 0;           // splits > 1 (B > 2048): [splits][D] fp32 partial sums; one range writes dcls itself
 };
 
-struct TokenPoolPlan {
-    int err = SFCVIT_OK;
-    char msg[160] = "";
+struct TokenPoolPlan : PlanStatus {
     int dv = 0;                     // D / 8
     int cv = 0, tl = 0;             // a workgroup is cv column lanes x tl token lanes, cv * tl = 256
     int slabs = 0;                  // grid (B, slabs); the count == 1 forward copy: grid (B, row_blocks), a lane per vector
@@ -47,6 +44,7 @@ int cls_prepend_check_fwd(const ClsPrependPlan &p, const void *x, const void *cl
 int cls_prepend_check_bwd(const ClsPrependPlan &p, const void *dy, const void *dx, const void *dcls, const void *workspace,
                           int64_t workspace_bytes);
 int token_pool_check(const TokenPoolPlan &p, const char *what, const void *a, const void *b);
-void note_token_pool_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+// Which kernel of this family the calling thread launched last (sfcvit_last_token_pool_kernel).
+extern thread_local KernelNote g_token_pool;
 
 }  // namespace sfcvit

@@ -197,7 +197,7 @@ extern "C" int sfcvit_cls_prepend_fwd(const void *x, const void *cls, void *y, i
 #define CALL(I) hipLaunchKernelGGL(cls_prepend_fwd_kernel<I>, grid, dim3(TP_THREADS), 0, st, xs, cs, ys, B, p.xv, p.dv)
     BY_IMGS(CALL)
 #undef CALL
-    note_token_pool_kernel("cls_prepend_fwd_kernel<%d>", p.imgs);
+    g_token_pool.set("cls_prepend_fwd_kernel<%d>", p.imgs);
     return check_launch("cls_prepend_fwd");
 }
 
@@ -216,7 +216,7 @@ extern "C" int sfcvit_cls_prepend_bwd(const void *dy, void *dx, void *dcls, int 
                                    p.dv, p.slabs, groups)
     BY_IMGS(CALL)
 #undef CALL
-    note_token_pool_kernel("cls_prepend_bwd_kernel<%d>", p.imgs);
+    g_token_pool.set("cls_prepend_bwd_kernel<%d>", p.imgs);
     if (int rc = check_launch("cls_prepend_bwd")) return rc;
     if (kind == 0) return reduce_cols(static_cast<const float *>(workspace), p.splits, D, D, dcls, grad_bf16, stream);
     return SFCVIT_OK;
@@ -230,14 +230,14 @@ extern "C" int sfcvit_token_pool_fwd(const void *x, void *y, int B, int T, int D
     u16 *ys = static_cast<u16 *>(y);
     if (p.row_copy) {
         hipLaunchKernelGGL(token_pool_row_kernel, dim3(B, p.row_blocks), dim3(TP_THREADS), 0, st, xs, ys, T, p.dv, first);
-        note_token_pool_kernel("token_pool_row_kernel");
+        g_token_pool.set("token_pool_row_kernel");
         return check_launch("token_pool_fwd");
     }
     const dim3 grid(B, p.slabs);
 #define CALL(C) hipLaunchKernelGGL(token_pool_fwd_kernel<C>, grid, dim3(TP_THREADS), 0, st, xs, ys, T, p.dv, first, count)
     BY_CV(CALL)
 #undef CALL
-    note_token_pool_kernel("token_pool_fwd_kernel<%d>", p.cv);
+    g_token_pool.set("token_pool_fwd_kernel<%d>", p.cv);
     return check_launch("token_pool_fwd");
 }
 
@@ -251,6 +251,6 @@ extern "C" int sfcvit_token_pool_bwd(const void *dy, void *dx, int B, int T, int
 #define CALL(C) hipLaunchKernelGGL(token_pool_bwd_kernel<C>, grid, dim3(TP_THREADS), 0, st, ds, xs, T, p.dv, first, count)
     BY_CV(CALL)
 #undef CALL
-    note_token_pool_kernel("token_pool_bwd_kernel<%d>", p.cv);
+    g_token_pool.set("token_pool_bwd_kernel<%d>", p.cv);
     return check_launch("token_pool_bwd");
 }

@@ -52,22 +52,23 @@ TIMER = None
 KERNEL_LOG = None     # tests: set to a list and every GEMM / attention launch appends the kernel symbol the library chose
 
 
-def last_gemm_kernel():
+def _last_kernel(fn):
+    """What one of the library's sfcvit_last_*_kernel readers says: the kernel symbol as rocprofv3 names it, "none" before any."""
     buf = ctypes.create_string_buffer(96)
-    lib.sfcvit_last_gemm_kernel(buf, 96)
+    fn(buf, 96)
     return buf.value.decode()
+
+
+def last_gemm_kernel():
+    return _last_kernel(lib.sfcvit_last_gemm_kernel)
 
 
 def last_attn_kernel():
-    buf = ctypes.create_string_buffer(96)
-    lib.sfcvit_last_attn_kernel(buf, 96)
-    return buf.value.decode()
+    return _last_kernel(lib.sfcvit_last_attn_kernel)
 
 
 def last_rowwise_kernel():
-    buf = ctypes.create_string_buffer(96)
-    lib.sfcvit_last_rowwise_kernel(buf, 96)
-    return buf.value.decode()
+    return _last_kernel(lib.sfcvit_last_rowwise_kernel)
 
 
 def _launch(key, work, fn):
@@ -119,6 +120,20 @@ def _rows2d(t, dtype, name):
     if t.dtype != dtype or t.dim() != 2 or t.stride(1) != 1:
         raise ValueError(f"{name}: expected 2-D {dtype} with unit inner stride, got {t.dtype} {tuple(t.shape)} {t.stride()}")
     return t
+
+
+def _grad_outs(what, out, shapes, wanted, device, expected):
+    """The parameter gradients of a backward wrapper, one per entry of `shapes`: fp32, or -- with `out`, one tensor or a
+    tuple with an entry per shape, e.g. views of a flat gradient buffer (None entries are allocated) -- bf16 written in
+    place.  -> (the tensors, None where not wanted; whether they are bf16: the C calls' grad_bf16 flag)."""
+    given = (None,) * len(shapes) if out is None else (out,) if torch.is_tensor(out) else out
+    for t, shape in zip(given, shapes):
+        if t is not None and (t.dtype != _BF16 or t.numel() != math.prod(shape) or not t.is_contiguous()):
+            raise ValueError(f"{what} out: {expected} expected")
+    gdt = torch.float32 if out is None else _BF16
+    grads = [None if not want else t if t is not None else torch.empty(tuple(shape), device=device, dtype=gdt)
+             for t, shape, want in zip(given, shapes, wanted)]
+    return grads, out is not None
 
 
 # ----------------------------------------------------------------------------
@@ -663,9 +678,7 @@ def attention_stats(qkv, lse, n_heads, pos=None, scale=None, out=None):
 # ----------------------------------------------------------------------------
 def last_tokenizer_kernel():
     """Name of the tokenizer kernel this thread launched last (sfcvit_last_tokenizer_kernel), "none" before any."""
-    buf = ctypes.create_string_buffer(96)
-    lib.sfcvit_last_tokenizer_kernel(buf, 96)
-    return buf.value.decode()
+    return _last_kernel(lib.sfcvit_last_tokenizer_kernel)
 
 
 class TileDesc:
@@ -911,9 +924,7 @@ def hier_tokenizer_fwd(x, pix_list, w_list, b_list, wf, bf):
 # depth-wise conv1d along the token sequence (TokenAggregator.dw)
 # ----------------------------------------------------------------------------
 def last_dwconv_kernel():
-    buf = ctypes.create_string_buffer(96)
-    lib.sfcvit_last_dwconv_kernel(buf, 96)
-    return buf.value.decode()
+    return _last_kernel(lib.sfcvit_last_dwconv_kernel)
 
 
 def dwconv1d_out_len(N, k, stride=1):
@@ -954,19 +965,14 @@ def dwconv1d_bwd(du, x, w, stride=1, want_dx=True, want_dw=True, want_db=True, o
     k = _dw_weight(w, D)
     if tuple(du.shape) != (B, dwconv1d_out_len(N, k, stride), D):
         raise ValueError(f"dwconv1d du: shape {tuple(du.shape)} does not belong to x {tuple(x.shape)}, k={k}, stride={stride}")
-    gdt = torch.float32 if out is None else _BF16
-    given = (None, None) if out is None else out
-    for t, n in zip(given, (D * k, D)):
-        if t is not None and (t.dtype != _BF16 or t.numel() != n or not t.is_contiguous()):
-            raise ValueError("dwconv1d_bwd out: contiguous bf16 tensors of the weight's / bias's size expected")
+    (dw, db), grad_bf16 = _grad_outs("dwconv1d_bwd", out, (w.shape, (D,)), (want_dw, want_db), x.device,
+                                     "contiguous bf16 tensors of the weight's / bias's size")
     dx = torch.empty_like(x) if want_dx else None
-    dw = (given[0] if given[0] is not None else torch.empty(w.shape, device=x.device, dtype=gdt)) if want_dw else None
-    db = (given[1] if given[1] is not None else torch.empty(D, device=x.device, dtype=gdt)) if want_db else None
     nbytes = lib.sfcvit_dwconv1d_bwd_workspace(B, N, D, k, stride) if (want_dw or want_db) else 0
     ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if nbytes else None
     with _Deferring([t for t in (dw, db) if t is not None], [ws]):
         _launch("dwconv1d_bwd", 4.0 * x.numel() + 4.0 * du.numel() + 2.0 * nbytes,
-                lambda: check(lib.sfcvit_dwconv1d_bwd(_p(du), _p(x), _p(w), _p(dx), _p(dw), _p(db), int(gdt == _BF16), B, N, D, k, stride,
+                lambda: check(lib.sfcvit_dwconv1d_bwd(_p(du), _p(x), _p(w), _p(dx), _p(dw), _p(db), int(grad_bf16), B, N, D, k, stride,
                                                       _p(ws), nbytes, _stream()), "sfcvit_dwconv1d_bwd"))
     return dx, dw, db
 
@@ -975,9 +981,7 @@ def dwconv1d_bwd(du, x, w, stride=1, want_dx=True, want_dw=True, want_db=True, o
 # positional embedding: one table row per token index, added to every image (vit.py:360-361, :382)
 # ----------------------------------------------------------------------------
 def last_pos_embed_kernel():
-    buf = ctypes.create_string_buffer(96)
-    lib.sfcvit_last_pos_embed_kernel(buf, 96)
-    return buf.value.decode()
+    return _last_kernel(lib.sfcvit_last_pos_embed_kernel)
 
 
 def _pos_table(pos, N, D, name):
@@ -1003,14 +1007,12 @@ def pos_embed_bwd(dy, out=None):
     e.g. a view of a flat gradient buffer -- written as bf16 in place and returned."""
     _need(dy, _BF16, "pos_embed dy", 3)
     B, N, D = dy.shape
-    if out is not None and (out.dtype != _BF16 or out.numel() != N * D or not out.is_contiguous()):
-        raise ValueError("pos_embed_bwd out: a contiguous bf16 tensor of the table's size expected")
-    dpos = out if out is not None else torch.empty((N, D), device=dy.device, dtype=torch.float32)
+    (dpos,), grad_bf16 = _grad_outs("pos_embed_bwd", out, ((N, D),), (True,), dy.device, "a contiguous bf16 tensor of the table's size")
     nbytes = lib.sfcvit_pos_embed_bwd_workspace(B, N, D)
     ws = torch.empty(nbytes, device=dy.device, dtype=torch.uint8) if nbytes else None
     with _Deferring([dpos], [ws]):
         _launch("pos_embed_bwd", 2.0 * dy.numel() + float(dpos.numel() * dpos.element_size()) + 2.0 * nbytes,
-                lambda: check(lib.sfcvit_pos_embed_bwd(_p(dy), _p(dpos), int(out is not None), B, N, D, _p(ws), nbytes, _stream()),
+                lambda: check(lib.sfcvit_pos_embed_bwd(_p(dy), _p(dpos), int(grad_bf16), B, N, D, _p(ws), nbytes, _stream()),
                               "sfcvit_pos_embed_bwd"))
     return dpos
 
@@ -1019,9 +1021,7 @@ def pos_embed_bwd(dy, out=None):
 # CLS token and token pooling (vit.py:209-210, :237-238, commented out there; altvit's x.mean(dim=1))
 # ----------------------------------------------------------------------------
 def last_token_pool_kernel():
-    buf = ctypes.create_string_buffer(96)
-    lib.sfcvit_last_token_pool_kernel(buf, 96)
-    return buf.value.decode()
+    return _last_kernel(lib.sfcvit_last_token_pool_kernel)
 
 
 def cls_prepend_fwd(x, cls):
@@ -1044,15 +1044,13 @@ def cls_prepend_bwd(dy, want_dx=True, out=None):
     B, N1, D = dy.shape
     if N1 < 2:
         raise ValueError("cls_prepend_bwd: dy must hold the CLS row and at least one token")
-    if out is not None and (out.dtype != _BF16 or out.numel() != D or not out.is_contiguous()):
-        raise ValueError("cls_prepend_bwd out: a contiguous bf16 tensor of D elements expected")
+    (dcls,), grad_bf16 = _grad_outs("cls_prepend_bwd", out, ((D,),), (True,), dy.device, "a contiguous bf16 tensor of D elements")
     dx = torch.empty((B, N1 - 1, D), device=dy.device, dtype=_BF16) if want_dx else None
-    dcls = out if out is not None else torch.empty(D, device=dy.device, dtype=torch.float32)
     nbytes = lib.sfcvit_cls_prepend_bwd_workspace(B, N1 - 1, D)
     ws = torch.empty(nbytes, device=dy.device, dtype=torch.uint8) if nbytes else None
     with _Deferring([dcls], [ws]):
         _launch("cls_prepend_bwd", (4.0 if want_dx else 0.0) * B * (N1 - 1) * D + 2.0 * B * D,
-                lambda: check(lib.sfcvit_cls_prepend_bwd(_p(dy), _p(dx), _p(dcls), int(out is not None), B, N1 - 1, D, _p(ws), nbytes,
+                lambda: check(lib.sfcvit_cls_prepend_bwd(_p(dy), _p(dx), _p(dcls), int(grad_bf16), B, N1 - 1, D, _p(ws), nbytes,
                                                          _stream()), "sfcvit_cls_prepend_bwd"))
     return dx, dcls
 
@@ -1092,9 +1090,7 @@ def token_pool_bwd(dy, T, first=0, count=None):
 # token mixing: GEMMs along the token axis of [B, N, D] (MixerBlock.token_mix)
 # ----------------------------------------------------------------------------
 def last_tokmix_kernel():
-    buf = ctypes.create_string_buffer(96)
-    lib.sfcvit_last_tokmix_kernel(buf, 96)
-    return buf.value.decode()
+    return _last_kernel(lib.sfcvit_last_tokmix_kernel)
 
 
 def tokmix_left(w, x, *, transposed=False, bias=None, act=ACT_NONE, residual=None, aux_in=None, want_aux=False, out=None):
@@ -1137,18 +1133,13 @@ def tokmix_wgrad(g, x, want_dw=True, want_db=True, out=None):
     K = x.shape[1]
     if x.shape[0] != B or x.shape[2] != D:
         raise ValueError(f"tokmix_wgrad: g {tuple(g.shape)} and x {tuple(x.shape)} must share B and D")
-    gdt = torch.float32 if out is None else _BF16
-    given = (None, None) if out is None else out
-    for t, n in zip(given, (M * K, M)):
-        if t is not None and (t.dtype != _BF16 or t.numel() != n or not t.is_contiguous()):
-            raise ValueError("tokmix_wgrad out: contiguous bf16 tensors of the weight's / bias's size expected")
-    dw = (given[0] if given[0] is not None else torch.empty((M, K), device=g.device, dtype=gdt)) if want_dw else None
-    db = (given[1] if given[1] is not None else torch.empty(M, device=g.device, dtype=gdt)) if want_db else None
+    (dw, db), grad_bf16 = _grad_outs("tokmix_wgrad", out, ((M, K), (M,)), (want_dw, want_db), g.device,
+                                     "contiguous bf16 tensors of the weight's / bias's size")
     nbytes = lib.sfcvit_tokmix_wgrad_workspace(B, M, K, D)
     ws = torch.empty(max(nbytes, 16), device=g.device, dtype=torch.uint8)
     with _Deferring([t for t in (dw, db) if t is not None], [ws]):
         _launch("tokmix_wgrad", 2.0 * B * M * K * D,
-                lambda: check(lib.sfcvit_tokmix_wgrad(_p(g), _p(x), _p(dw), _p(db), int(gdt == _BF16), B, M, K, D, _p(ws), nbytes,
+                lambda: check(lib.sfcvit_tokmix_wgrad(_p(g), _p(x), _p(dw), _p(db), int(grad_bf16), B, M, K, D, _p(ws), nbytes,
                                                       _stream()), "sfcvit_tokmix_wgrad"))
     return dw, db
 
