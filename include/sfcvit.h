@@ -420,9 +420,29 @@ int sfcvit_layernorm_bwd_drop(const void *dy, const void *x, const float *mean, 
 /* grads_bf16 != 0: dgamma / dbeta / dcol are bf16 [D] instead of fp32 -- the caller passes views of its flat
  * gradient buffer and no cast / accumulate pass follows. */
 int64_t sfcvit_layernorm_bwd_ws(int M, int D);
-/* HOST: name of the main kernel the calling thread's last sfcvit_layernorm_bwd / _bwd_drop launched, as rocprofv3 prints
+/* HOST: name of the main kernel the calling thread's last sfcvit_layernorm_bwd / _bwd_drop / _bwd_path or
+ * sfcvit_add_layernorm_path_fwd launched, as rocprofv3 prints
  * it (e.g. "ln_bwd_cols_kernel<4, true>"): tests assert through it that a width ran on the column-sum kernel. */
 int sfcvit_last_rowwise_kernel(char *buf, int n);
+
+/* Stochastic depth (DropPath, timm's drop_path with scale_by_keep) on a residual site of the post-norm encoder layer:
+ *   s = bf16(x + c[b] * branch),  y = LayerNorm(s),  c[b] = keep(b) / (1 - rate),  b = row / N, one flag per image.
+ * keep(b) is element (b, 0) of the mask sfcvit_dropout_mask writes for `seed` at p = rate (seed_off: the device word the
+ * dropout sites add, NULL = 0); nothing is stored, backward regenerates it.  branch, x, s, y: bf16 [B * N, D]; branch is the
+ * sub-layer's output after its own dropout, WITHOUT the residual; a dropped image's rows of branch are not read and its rows
+ * of s are the bits of x.  mean, rstd fp32 [B * N] are those of the rounded s.  D % 8 == 0, D <= 4096; s and y overlap
+ * neither an input nor each other.  Notes its kernel ("add_ln_path_kernel<2>") for sfcvit_last_rowwise_kernel. */
+int sfcvit_add_layernorm_path_fwd(const void *branch, const void *x, const void *gamma, const void *beta, void *s, void *y,
+                                  float *mean, float *rstd, int B, int N, int D, float eps, float rate,
+                                  uint32_t seed, const uint32_t *seed_off, void *stream);
+/* sfcvit_layernorm_bwd_drop over M = B * rows_per_image rows with the branch scale of the site above in the outgoing gradient:
+ *   dx_drop[m, d] = keep_path(m / rows_per_image) && keep(m, d) ? dx / ((1 - p) (1 - path_rate)) : 0
+ * dx_drop is required and written at p = 0 too; dcol sums it as stored, i.e. rounded to bf16 (nothing from dropped images); dx, dgamma and dbeta are those of
+ * sfcvit_layernorm_bwd_drop.  Same workspace (sfcvit_layernorm_bwd_ws(B * rows_per_image, D)), deferral and grads_bf16 forms. */
+int sfcvit_layernorm_bwd_path(const void *dy, const void *x, const float *mean, const float *rstd, const void *gamma,
+                              const void *dx_add, void *dx, void *dx_drop, float p, uint32_t seed,
+                              const uint32_t *seed_off, void *dgamma, void *dbeta, void *dcol, int grads_bf16, int B,
+                              int rows_per_image, int D, void *ws, float path_rate, uint32_t path_seed, void *stream);
 
 /* ------------------------------------------------------------------------
  * Multi-head self-attention core (no mask; the masked form is the next section) on the packed projection

@@ -2,8 +2,8 @@
 // available on this pool, so the native host code gets a CPU-side -fsanitize=address,undefined build of its own):
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
 //   host part), the error path of common.cpp, the mask validation and block map of attention_masked.cpp (check_mask_blocks),
-//   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv)
-//   and token_mix.cpp (check_tokmix), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
+//   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv),
+//   token_mix.cpp (check_tokmix) and drop_path.cpp (check_drop_path), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
 //   and post passes each GEMM / attention shape of the benchmarked models gets).
 // Every buffer is a heap block of EXACTLY the documented size, so that an off-by-one in a generator or in the descriptor
 // writer is a heap-buffer-overflow report instead of silent corruption.
@@ -19,6 +19,7 @@
 
 #include "../../../include/sfcvit.h"
 #include "../dispatch.h"
+#include "../drop_path.h"
 #include "../pos_embed.h"
 #include "../token_agg.h"
 #include "../token_mix.h"
@@ -765,6 +766,92 @@ static void check_tokmix() {
     CHECK(sfcvit_last_tokmix_kernel(nullptr, 4) == SFCVIT_EINVAL && sfcvit_last_tokmix_kernel(name, 0) == SFCVIT_EINVAL, "tokmix: null / empty name buffer accepted");
 }
 
+// add_ln_path_plan / ln_bwd_path_plan (drop_path.cpp): the geometry at the workload shapes and the edge shapes of the tests, and
+// every refusal, with heap buffers of exactly B N D bf16 (branch, x, s, y and the gradients), D bf16 (gamma, beta) and B N fp32
+// (mean, rstd).  The plans read no byte of them; what is pinned is that every accepted geometry stays inside them.
+static void check_drop_path() {
+    using namespace sfcvit;
+    const struct { int B, N, D, vpl; } ok[] = {{1, 1, 8, 1}, {2, 1, 8, 1}, {5, 3, 72, 1}, {2, 65, 200, 1}, {3, 7, 520, 2}, {2, 9, 1536, 4},
+                                               {2, 3, 2048, 4}, {22, 197, 768, 2}, {8, 577, 1024, 2}, {1, 2, 4096, 8},
+                                               {256, 196, 768, 2}, {64, 576, 1024, 2}};
+    for (const auto &q : ok) {
+        const size_t rows = size_t(q.B) * q.N, bytes = rows * q.D * 2;
+        std::unique_ptr<char[]> a(new char[bytes + 16]), x(new char[bytes + 16]), s(new char[bytes + 16]), y(new char[bytes + 16]);
+        std::unique_ptr<char[]> g(new char[q.D * 2 + 16]), b(new char[q.D * 2 + 16]);
+        std::unique_ptr<float[]> mean(new float[rows]), rstd(new float[rows]);
+        auto al = [](char *p) { return reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(p) + 15) & ~uintptr_t(15)); };
+        void *ap = al(a.get()), *xp = al(x.get()), *sp = al(s.get()), *yp = al(y.get()), *gp = al(g.get()), *bp = al(b.get());
+        const AddLnPathPlan p = add_ln_path_plan(ap, xp, gp, bp, sp, yp, mean.get(), rstd.get(), q.B, q.N, q.D, 0.1f);
+        CHECK(p.err == SFCVIT_OK, "drop_path fwd %d %d %d refused: %s", q.B, q.N, q.D, p.msg);
+        CHECK(p.M == int(rows) && p.vpl == q.vpl && p.vpl * 512 >= q.D, "drop_path fwd %d %d %d: M %d vpl %d", q.B, q.N, q.D, p.M, p.vpl);
+        CHECK(int64_t(p.blocks) * DP_WAVES >= p.M && int64_t(p.blocks - 1) * DP_WAVES < p.M, "drop_path fwd blocks %d for %d rows", p.blocks, p.M);
+        auto fwd = [&](const void *a_, const void *x_, const void *g_, const void *b_, const void *s_, const void *y_, const float *m_,
+                       const float *r_, int B, int N, int D, float rate, const char *frag, const char *what) {
+            const AddLnPathPlan r = add_ln_path_plan(a_, x_, g_, b_, s_, y_, m_, r_, B, N, D, rate);
+            CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag), "drop_path fwd %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
+        };
+        float *mp = mean.get(), *rp = rstd.get();
+        fwd(nullptr, xp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null branch");
+        fwd(ap, nullptr, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null x");
+        fwd(ap, xp, nullptr, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null gamma");
+        fwd(ap, xp, gp, nullptr, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null beta");
+        fwd(ap, xp, gp, bp, nullptr, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null s");
+        fwd(ap, xp, gp, bp, sp, nullptr, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null y");
+        fwd(ap, xp, gp, bp, sp, yp, nullptr, rp, q.B, q.N, q.D, 0.1f, "null", "null mean");
+        fwd(ap, xp, gp, bp, sp, yp, mp, nullptr, q.B, q.N, q.D, 0.1f, "null", "null rstd");
+        fwd(ap, xp, gp, bp, sp, yp, mp, rp, 0, q.N, q.D, 0.1f, "B=0", "B = 0");
+        fwd(ap, xp, gp, bp, sp, yp, mp, rp, q.B, -1, q.D, 0.1f, "N=-1", "N = -1");
+        fwd(ap, xp, gp, bp, sp, yp, mp, rp, 65536, 32768, q.D, 0.1f, "leave int", "B * N = 2^31");
+        fwd(ap, xp, gp, bp, sp, yp, mp, rp, q.B, q.N, 0, 0.1f, "D=0", "D = 0");
+        fwd(ap, xp, gp, bp, sp, yp, mp, rp, q.B, q.N, 12, 0.1f, "D=12", "D = 12");
+        fwd(ap, xp, gp, bp, sp, yp, mp, rp, q.B, q.N, 4104, 0.1f, "D=4104", "D = 4104");
+        fwd(static_cast<char *>(ap) + 2, xp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "aligned", "misaligned branch");
+        fwd(ap, xp, gp, bp, static_cast<char *>(sp) + 8, yp, mp, rp, q.B, q.N, q.D, 0.1f, "aligned", "misaligned s");
+        fwd(ap, xp, static_cast<char *>(gp) + 4, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "aligned", "misaligned gamma");
+        fwd(ap, xp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 1.f, "rate=1", "rate 1");
+        fwd(ap, xp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, -0.25f, "rate=-0.25", "rate < 0");
+        fwd(ap, xp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, std::numeric_limits<float>::quiet_NaN(), "rate=", "rate NaN");
+        fwd(ap, xp, gp, bp, xp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "overlaps", "s = x");
+        fwd(ap, xp, gp, bp, sp, ap, mp, rp, q.B, q.N, q.D, 0.1f, "overlaps", "y = branch");
+        fwd(ap, xp, gp, bp, sp, sp, mp, rp, q.B, q.N, q.D, 0.1f, "overlaps", "y = s");
+        if (bytes > 16) fwd(ap, xp, gp, bp, static_cast<char *>(xp) + bytes - 16, yp, mp, rp, q.B, q.N, q.D, 0.1f, "overlaps", "s starts in x's last vector");
+
+        if (q.D > DP_BWD_MAX_D) continue;
+        std::unique_ptr<float[]> ws(new float[3 * q.D]);
+        const LnBwdPathPlan pb = ln_bwd_path_plan(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, ws.get(), 0.5f);
+        CHECK(pb.err == SFCVIT_OK && pb.M == int(rows), "drop_path bwd %d %d %d refused: %s", q.B, q.N, q.D, pb.msg);
+        CHECK(ln_bwd_path_plan(ap, xp, mp, rp, gp, ap, sp, yp, 0.f, mp, rp, q.B, q.N, q.D, ws.get(), 0.f).err == SFCVIT_OK, "drop_path bwd: dx_add, p = 0, rate = 0 refused");
+        auto bwd = [&](const void *dy_, const void *x_, const float *m_, const float *r_, const void *g_, const void *add_, const void *dx_,
+                       const void *dd_, float dp, const void *dg_, const void *db_, int B, int N, int D, const void *ws_, float rate,
+                       const char *frag, const char *what) {
+            const LnBwdPathPlan r = ln_bwd_path_plan(dy_, x_, m_, r_, g_, add_, dx_, dd_, dp, dg_, db_, B, N, D, ws_, rate);
+            CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag), "drop_path bwd %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
+        };
+        const void *w = ws.get();
+        bwd(nullptr, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, w, 0.5f, "null", "null dy");
+        bwd(ap, nullptr, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, w, 0.5f, "null", "null x");
+        bwd(ap, xp, nullptr, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, w, 0.5f, "null", "null mean");
+        bwd(ap, xp, mp, nullptr, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, w, 0.5f, "null", "null rstd");
+        bwd(ap, xp, mp, rp, nullptr, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, w, 0.5f, "null", "null gamma");
+        bwd(ap, xp, mp, rp, gp, nullptr, nullptr, yp, 0.1f, mp, rp, q.B, q.N, q.D, w, 0.5f, "null", "null dx");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, nullptr, 0.1f, mp, rp, q.B, q.N, q.D, w, 0.5f, "dx_drop", "missing dx_drop");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, nullptr, rp, q.B, q.N, q.D, w, 0.5f, "null", "null dgamma");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, nullptr, q.B, q.N, q.D, w, 0.5f, "null", "null dbeta");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, nullptr, 0.5f, "null", "null workspace");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, 0, q.N, q.D, w, 0.5f, "B=0", "B = 0");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, 0, q.D, w, 0.5f, "N=0", "rows_per_image = 0");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, 46341, 46341, q.D, w, 0.5f, "leave int", "B * N > int");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, 2056, w, 0.5f, "D=2056", "D = 2056");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, 4, w, 0.5f, "D=4", "D = 4");
+        bwd(ap, xp, mp, rp, gp, static_cast<char *>(ap) + 8, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, w, 0.5f, "aligned", "misaligned dx_add");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, static_cast<char *>(yp) + 2, 0.1f, mp, rp, q.B, q.N, q.D, w, 0.5f, "aligned", "misaligned dx_drop");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 1.f, mp, rp, q.B, q.N, q.D, w, 0.5f, "dropout p=1", "dropout p = 1");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, -0.5f, mp, rp, q.B, q.N, q.D, w, 0.5f, "dropout p=-0.5", "dropout p < 0");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, w, 1.f, "rate=1", "rate 1");
+        bwd(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, w, -1.f, "rate=-1", "rate < 0");
+    }
+}
+
 int main() {
     const int curves[] = {SFCVIT_CURVE_HILBERT, SFCVIT_CURVE_Z, SFCVIT_CURVE_MOORE, SFCVIT_CURVE_PEANO, SFCVIT_CURVE_RASTER,
                           SFCVIT_CURVE_SPIRAL, SFCVIT_CURVE_HILBERT_T};
@@ -837,6 +924,7 @@ int main() {
     check_token_pool();
     check_dwconv();
     check_tokmix();
+    check_drop_path();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     std::printf("host_check ok\n");
     return 0;

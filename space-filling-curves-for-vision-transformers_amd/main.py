@@ -67,7 +67,7 @@ def build_tokenizer(a):
     return hier[a.tokenizer](a.img_size, 3, a.levels, a.embed_dim)          # main.py:269-274: ([16, 4, 1], 256)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokenizer", default="hier_morton")       # the reference's active menu entry (main.py:232-240)
     ap.add_argument("--img-size", type=int, default=32)
@@ -127,6 +127,10 @@ def main():
                          "(src/models/vit.py:209-210, :237-238, commented out in the reference; checkpoints then carry "
                          "encoder.cls_token) and reads it out, 'mean' reads the mean of the tokens.  The head then holds no weight "
                          "per token index")
+    ap.add_argument("--drop-path", type=float, default=0.0, metavar="R",
+                    help="stochastic depth (DropPath, the DeiT recipe's drop_path_rate): in training every encoder layer drops "
+                         "each of its two residual branches per image, with a probability that grows linearly with depth from 0 "
+                         "to R, and scales the kept ones up; 0 <= R < 1, default 0 (off).  Works with --graph; no checkpoint key")
     win = ap.add_mutually_exclusive_group()
     win.add_argument("--attn-window", type=int, default=None, metavar="W",
                      help="local attention along the curve: every token attends to the tokens within W positions of it in "
@@ -136,7 +140,20 @@ def main():
                           "of its own in both axes (sfcvit.masks.image_window on the tokenizer's positions)")
     ap.add_argument("--mean", type=float, nargs=3, default=[0.4914, 0.4822, 0.4465])      # main.py:176-177 (CIFAR)
     ap.add_argument("--std", type=float, nargs=3, default=[0.2023, 0.1994, 0.2010])
-    a = ap.parse_args()
+    return ap
+
+
+def build_model(a, patch_embed, attn_mask=None):
+    """The model of the parsed arguments `a` (fp32, on the CPU: main() moves and casts it)."""
+    return VisionTransformer1D(patch_embed=patch_embed, depth=a.depth, n_heads=a.heads, mlp_dim=a.mlp_dim,
+                               num_classes=a.classes,
+                               token_aggregator=a.token_aggregator or False, token_mix=a.token_mix,
+                               attn_mask=attn_mask, pos_embed=a.pos_embed,
+                               pos_embed_std=a.pos_embed_std, pool=a.pool, drop_path_rate=a.drop_path)
+
+
+def main():
+    a = build_parser().parse_args()
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     torch.cuda.set_device(local)
@@ -197,11 +214,7 @@ def main():
         if rank == 0:
             print(f"attention mask: {attn_mask.visited_blocks}/{attn_mask.total_blocks} blocks of 64 x 64 visited "
                   f"(N = {attn_mask.n_tokens})")
-    model = VisionTransformer1D(patch_embed=patch_embed, depth=a.depth, n_heads=a.heads, mlp_dim=a.mlp_dim,
-                                num_classes=a.classes,
-                                token_aggregator=a.token_aggregator or False, token_mix=a.token_mix,
-                                attn_mask=attn_mask, pos_embed=a.pos_embed,
-                                pos_embed_std=a.pos_embed_std, pool=a.pool).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
+    model = build_model(a, patch_embed, attn_mask).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
     train_criterion, test_criterion = SoftTargetCrossEntropy(), nn.CrossEntropyLoss()
     optimizer = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=1.0)
     reducer = GradReducer(optimizer, overlap=not a.graph) if world > 1 else None    # --graph: collectives between two graphs

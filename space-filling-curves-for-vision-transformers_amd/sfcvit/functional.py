@@ -783,11 +783,15 @@ class _EncoderLayer(Function):
          a  = out_proj(attention(in_proj(x)));  x1 = LN1(x + drop1(a))
          f  = W2 drop(relu(W1 x1 + b1)) + b2;   y  = LN2(x1 + drop2(f))
     with dropout p on the attention probabilities as well.  p = 0 (eval) makes every mask the
-    identity.  Masks are functions of (seed, element index), regenerated in backward."""
+    identity.  Masks are functions of (seed, element index), regenerated in backward.
+    drop_path = (rate, (seed1, seed2)), rate > 0: stochastic depth on the two residual sites,
+         x1 = LN1(x + c1[b] drop1(a));  y = LN2(x1 + c2[b] drop2(f)),  c[b] = keep[b] / (1 - rate), one flag per image and site
+    (functions of (seed, image index), regenerated in backward): the branch GEMMs store drop(a) / drop(f) without the residual and
+    ops.add_layernorm_path_fwd adds, rounds once to s1 / s2 and normalises."""
 
     @staticmethod
     def launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale,
-                 attn_mask=None):
+                 attn_mask=None, drop_path=None):
         """The forward's kernel launches, every intermediate returned (forward saves them; encoder_layer_probe reads the
         attention inputs out of the same sequence, so what it carries on is what forward computes)."""
         B, N, D = x.shape
@@ -799,24 +803,32 @@ class _EncoderLayer(Function):
             o, lse = ops.attention_fwd(qkv.view(B, N, 3 * Da), n_heads, p, sa, scale=scale, any_length=True)
         else:                                               # an ops.AttentionMask: the masked kernels, and only then
             o, lse = ops.attention_masked_fwd(qkv.view(B, N, 3 * Da), n_heads, *attn_mask.on(x.device), p, sa, scale=scale)
-        s1 = ops.gemm(o.view(B * N, Da), out_w, bias=out_b, residual=x2, dropout_p=p, dropout_seed=s1_)
-        x1, mean1, rstd1 = ops.layernorm_fwd(s1, n1_w, n1_b, eps)
+        if drop_path is None:
+            s1 = ops.gemm(o.view(B * N, Da), out_w, bias=out_b, residual=x2, dropout_p=p, dropout_seed=s1_)
+            x1, mean1, rstd1 = ops.layernorm_fwd(s1, n1_w, n1_b, eps)
+        else:
+            a = ops.gemm(o.view(B * N, Da), out_w, bias=out_b, dropout_p=p, dropout_seed=s1_)
+            s1, x1, mean1, rstd1 = ops.add_layernorm_path_fwd(a, x2, n1_w, n1_b, B, drop_path[0], drop_path[1][0], eps)
         # The dX GEMM through ReLU + dropout needs only the sign pattern of h: a bit matrix written by linear1's epilogue
         # (19 MB instead of 308 MB per ViT-B layer read back in backward; sfcvit_gemm_args.actmask)
         hbits = (torch.empty((B * N, w1.shape[0] // 8), device=x.device, dtype=torch.uint8)
                  if USE_ACTMASK and w1.shape[0] % 16 == 0 else None)
         h = ops.gemm(x1, w1, bias=b1, act=ops.ACT_RELU, dropout_p=p, dropout_seed=sf, actmask=hbits)
-        s2 = ops.gemm(h, w2, bias=b2, residual=x1, dropout_p=p, dropout_seed=s2_)
-        y, mean2, rstd2 = ops.layernorm_fwd(s2, n2_w, n2_b, eps)
+        if drop_path is None:
+            s2 = ops.gemm(h, w2, bias=b2, residual=x1, dropout_p=p, dropout_seed=s2_)
+            y, mean2, rstd2 = ops.layernorm_fwd(s2, n2_w, n2_b, eps)
+        else:
+            f = ops.gemm(h, w2, bias=b2, dropout_p=p, dropout_seed=s2_)
+            s2, y, mean2, rstd2 = ops.add_layernorm_path_fwd(f, x1, n2_w, n2_b, B, drop_path[0], drop_path[1][1], eps)
         return x2, qkv, o, lse, s1, mean1, rstd1, x1, hbits, h, s2, y, mean2, rstd2
 
     @staticmethod
     def forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale,
-                attn_mask=None):
+                attn_mask=None, drop_path=None):
         B, N, D = x.shape
         x2, qkv, o, lse, s1, mean1, rstd1, x1, hbits, h, s2, y, mean2, rstd2 = _EncoderLayer.launches(
-            x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale, attn_mask)
-        ctx.hbits, ctx.attn_mask = hbits, attn_mask
+            x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale, attn_mask, drop_path)
+        ctx.hbits, ctx.attn_mask, ctx.drop_path = hbits, attn_mask, drop_path
         ctx.save_for_backward(x2, qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2,
                               in_w, out_w, n1_w, w1, w2, n2_w)
         ctx.n_heads, ctx.shape, ctx.p, ctx.seeds, ctx.scale = n_heads, (B, N, D), p, seeds, scale
@@ -835,13 +847,18 @@ class _EncoderLayer(Function):
         ss = _SideStream(dy2.device) if SIDE_STREAM_WGRAD else None
         wg = (lambda a_, b_, w_: ss.run(lambda: _wgrad(a_, b_, w_), a_, b_)) if ss else _wgrad
 
-        def ln_bwd(dyv, s, mean, rstd, g_w, g_b, prev_bias, seed):
+        drop_path = getattr(ctx, "drop_path", None)         # (library.py's traced backward builds its own ctx: never set)
+
+        def ln_bwd(dyv, s, mean, rstd, g_w, g_b, prev_bias, seed, site):
             """LayerNorm backward; also returns the column sums of the gradient it hands to the sub-layer = the bias
             gradient of linear2 / out_proj, for free in the same pass.  Gradients go straight into their slots when
             all three parameters have one."""
             slots = (_slot(g_w), _slot(g_b), _slot(prev_bias))
             go = slots if all(t is not None for t in slots) else None
-            if p > 0:
+            if drop_path is not None:                       # the per-image branch scale rides on the dropout multiplier
+                dsv, dg, dbt, dsub, dcol = ops.layernorm_bwd_path(dyv, s, mean, rstd, g_w, N, drop_path[0], drop_path[1][site],
+                                                                  drop_p=p, drop_seed=seed, want_colsum=True, grad_out=go)
+            elif p > 0:
                 dsv, dg, dbt, dsub, dcol = ops.layernorm_bwd(dyv, s, mean, rstd, g_w, drop_p=p, drop_seed=seed,
                                                              want_colsum=True, grad_out=go)
             else:
@@ -851,7 +868,7 @@ class _EncoderLayer(Function):
                 dg, dbt, dcol = dg.to(_BF16), dbt.to(_BF16), dcol.to(_BF16)
             return dsv, dg, dbt, dsub, dcol
 
-        ds2, dg2, dbt2, df, db2 = ln_bwd(dy2, s2, mean2, rstd2, n2_w, n2_b, b2, s2_)
+        ds2, dg2, dbt2, df, db2 = ln_bwd(dy2, s2, mean2, rstd2, n2_w, n2_b, b2, s2_, 1)
         dw2 = wg(df, h, w2)
         # h is stored after relu + dropout: (h > 0) is the joint mask, 1/(1-p) the dropout scale
         # ... and the bias gradient of linear1 is the column sum of dh: fused into that GEMM's epilogue
@@ -862,7 +879,7 @@ class _EncoderLayer(Function):
             db1 = db1.to(_BF16)
         dw1 = wg(dh, x1, w1)
         dx1 = ops.gemm_dx(dh, w1, residual=ds2)
-        ds1, dg1, dbt1, da, dbo = ln_bwd(dx1, s1, mean1, rstd1, n1_w, n1_b, out_b, s1_)
+        ds1, dg1, dbt1, da, dbo = ln_bwd(dx1, s1, mean1, rstd1, n1_w, n1_b, out_b, s1_, 0)
         Da = in_w.shape[0] // 3
         o2 = o.view(B * N, Da)
         dwo = wg(da, o2, out_w)
@@ -884,9 +901,9 @@ class _EncoderLayer(Function):
         dx = ops.gemm_dx(dqkv, in_w, residual=ds1)
         if ss:
             ss.join(dw2, dw1, dwo, dwi)
-        # one gradient per argument of apply(): the mask is a 19th argument only when there is one
+        # one gradient per argument of apply(): the mask is a 19th argument only when there is one, stochastic depth a 20th
         return ((dx.view(B, N, D), dwi, dbi, dwo, dbo, dg1, dbt1, dw1, db1, dw2, db2, dg2, dbt2, None, None, None, None, None)
-                + (() if attn_mask is None else (None,)))
+                + ((None, None) if drop_path is not None else () if attn_mask is None else (None,)))
 
 
 def _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads):
@@ -918,7 +935,7 @@ def encoder_layer_probe(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2,
 
 
 def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5,
-                  dropout_p=0.0, attn_mask=None):
+                  dropout_p=0.0, attn_mask=None, drop_path=0.0):
     """dropout_p > 0 = training-mode nn.TransformerEncoderLayer (fresh masks every call).
     attn_mask = nn.TransformerEncoderLayer's src_mask: None, or an additive [N, N] mask as in `attention` (build an
     ops.AttentionMask once when the layer runs more than once).  With None the launches and the bits are those of a call
@@ -926,13 +943,25 @@ def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w,
     A head dim the attention kernels do not have (embed_dim / n_heads = 32, 48, 96, ...) runs on the next one that
     exists: in_proj's rows and out_proj's columns are zero-padded per head (differentiable torch plumbing on the
     weights, 3 D^2 elements -- not on the activations), so q, k, v come out of the projection GEMM already padded, the
-    padded columns add nothing to q k^T or p v, and out_proj ignores them; the softmax scale stays 1 / sqrt(head dim)."""
+    padded columns add nothing to q k^T or p v, and out_proj ignores them; the softmax scale stays 1 / sqrt(head dim).
+    drop_path = r in (0, 1): stochastic depth for a layer in TRAINING mode (the caller passes 0 in eval, as it passes
+    dropout_p = 0): each of the two residual branches is dropped per image with probability r and scaled by 1 / (1 - r)
+    otherwise, the two sites drawing independently (timm's drop_path1 / drop_path2, scale_by_keep=True).  0 runs the launches
+    and gives the bits of a call without the argument.  Not under tracing."""
+    drop_path = float(drop_path)
+    if not 0.0 <= drop_path < 1.0:
+        raise ValueError(f"encoder_layer: drop_path={drop_path} outside [0, 1)")
     args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
     attn_mask = _attention_mask(attn_mask, args[0].shape[1], "encoder_layer")
+    if drop_path > 0 and _traced():
+        raise NotImplementedError("encoder_layer: drop_path > 0 has no traced form (torch.compile); run the layer eagerly")
     if _traced():
         from . import library      # (dropout seeds are drawn inside the op: nothing data-dependent in the traced graph)
         return library.encoder_layer(args, n_heads, eps, float(dropout_p), scale)
     seeds = tuple(ops.next_seed() for _ in range(4)) if dropout_p > 0 else (0, 0, 0, 0)
+    if drop_path > 0:
+        path = (drop_path, (ops.next_seed(), ops.next_seed()))
+        return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale, attn_mask, path)
     if attn_mask is not None:
         return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale, attn_mask)
     return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale)

@@ -118,13 +118,27 @@ def permute_pos_embed(table, from_tokenizer, to_tokenizer):
     return table.index_select(table.dim() - 2, index.to(table.device))
 
 
+def drop_path_rates(drop_path_rate, n_layers):
+    """The stochastic-depth rate of each encoder layer: linear in depth from 0 to drop_path_rate (timm's rule); one layer gets
+    drop_path_rate itself."""
+    r = float(drop_path_rate)
+    if not 0.0 <= r < 1.0:
+        raise ValueError(f"drop_path_rate={drop_path_rate} must be in [0, 1)")
+    return [r * l / (n_layers - 1) if n_layers > 1 else r for l in range(n_layers)]
+
+
 class TransformerSeqEncoder(nn.Module):
     """vit.py:177-242: `depth` post-norm nn.TransformerEncoderLayer (relu, eps 1e-5).  forward(x, mask=None) mirrors
     nn.TransformerEncoder.forward(src, mask): the mask goes to every layer (the reference's CustomTransformerEncoder,
     vit.py:152-174).  A mask is not a parameter or a buffer: it never enters state_dict."""
 
-    def __init__(self, input_dim, max_len, n_head, hidden_dim, method, dropout_p=0.1, n_layers=1, cls_token=False):
-        """cls_token=True: a learnable [CLS] token `cls_token` [1, 1, input_dim] of zeros (vit.py:209-210, commented out
+    def __init__(self, input_dim, max_len, n_head, hidden_dim, method, dropout_p=0.1, n_layers=1, cls_token=False,
+                 drop_path_rate=0.0):
+        """drop_path_rate: stochastic depth (DropPath) in training mode.  Layer l of L drops each of its two residual branches
+        per image with probability drop_path_rates[l] = drop_path_rate * l / (L - 1) (0 for the first layer; a single layer
+        gets drop_path_rate) and scales the kept ones by 1 / (1 - rate).  No parameter, buffer or state_dict key; eval mode and
+        rate 0 run the launches they run without it.
+        cls_token=True: a learnable [CLS] token `cls_token` [1, 1, input_dim] of zeros (vit.py:209-210, commented out
         there) that forward puts in front of the sequence before the first layer (vit.py:237-238): [B, N, D] in,
         [B, N + 1, D] out.  Constructed last: every other parameter draws what it draws without it."""
         super().__init__()
@@ -132,6 +146,7 @@ class TransformerSeqEncoder(nn.Module):
         self.grid_size = int(math.sqrt(max_len))
         self.n_head = n_head
         self.dropout_p = dropout_p
+        self.drop_path_rates = drop_path_rates(drop_path_rate, n_layers)
         encoder_layer = nn.TransformerEncoderLayer(d_model=input_dim, nhead=n_head,
                                                    dim_feedforward=hidden_dim, dropout=dropout_p,
                                                    batch_first=True)
@@ -159,12 +174,13 @@ class TransformerSeqEncoder(nn.Module):
         mask = self._mask(mask)
         if hasattr(self, "cls_token"):
             x = F.cls_prepend(x, self.cls_token)                # vit.py:237-238
-        for layer in self.transformer.layers:
+        for layer, rate in zip(self.transformer.layers, self.drop_path_rates):
             a = layer.self_attn
+            path = {"drop_path": rate} if self.training and rate > 0 else {}      # else: the call as it is without the feature
             x = F.encoder_layer(x, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
                                 layer.norm1.weight, layer.norm1.bias, layer.linear1.weight, layer.linear1.bias,
                                 layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias,
-                                self.n_head, layer.norm1.eps, dropout_p=p, attn_mask=mask)
+                                self.n_head, layer.norm1.eps, dropout_p=p, attn_mask=mask, **path)
         return x
 
 
@@ -314,8 +330,9 @@ class VisionTransformer(nn.Module):
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, attn_mask=None,
-                 pos_embed=None, pos_embed_std=1.0, pool=None):
-        """attn_mask: None, or a mask for every encoder layer (ops.as_attention_mask's forms; sfcvit.masks builds windows).
+                 pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0):
+        """drop_path_rate: stochastic depth over the encoder layers (TransformerSeqEncoder; `encoder.drop_path_rates`).
+        attn_mask: None, or a mask for every encoder layer (ops.as_attention_mask's forms; sfcvit.masks builds windows).
         Held outside state_dict: checkpoint keys are the reference's with or without it.
         pos_embed: None / False (the reference as shipped), "learned" (vit.py:360-361: a Parameter [1, N, D] = randn *
         pos_embed_std), "sincos1d" (fixed, of the token index along the curve) or "sincos2d" (fixed, of the token's centre in
@@ -333,7 +350,8 @@ class VisionTransformer(nn.Module):
         self.attn_mask = _model_mask(attn_mask, patch_embed.n_patches, pool)
         self.encoder = TransformerSeqEncoder(input_dim=embed_dim, max_len=self.patch_embed.n_patches,
                                              method=self.patch_embed, n_head=n_heads, hidden_dim=mlp_dim,
-                                             n_layers=depth, dropout_p=dropout_p, cls_token=pool == "cls")
+                                             n_layers=depth, dropout_p=dropout_p, cls_token=pool == "cls",
+                                             drop_path_rate=drop_path_rate)
         self.mlp_head = _make_head(pool, embed_dim, self.patch_embed.n_patches, num_classes, head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)
@@ -356,8 +374,8 @@ class VisionTransformer1D(nn.Module):
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False, attn_mask=None,
-                 pos_embed=None, pos_embed_std=1.0, pool=None):
-        """attn_mask, pos_embed, pos_embed_std, pool: as in VisionTransformer (the table is added directly after the tokenizer
+                 pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0):
+        """attn_mask, pos_embed, pos_embed_std, pool, drop_path_rate: as in VisionTransformer (the table is added directly after the tokenizer
         and, if present, `ta`: before `mlp_mixer`; with pool="cls" the token joins after `mlp_mixer`, whose weights stay sized
         for the N patch tokens)."""
         super().__init__()
@@ -369,7 +387,8 @@ class VisionTransformer1D(nn.Module):
                                     hidden_dim=embed_dim * 2, out_dim=embed_dim, token_mix=token_mix)
         self.encoder = TransformerSeqEncoder(input_dim=embed_dim, max_len=self.patch_embed.n_patches,
                                              n_head=n_heads, hidden_dim=mlp_dim, n_layers=depth,
-                                             method=self.patch_embed, dropout_p=dropout_p, cls_token=pool == "cls")
+                                             method=self.patch_embed, dropout_p=dropout_p, cls_token=pool == "cls",
+                                             drop_path_rate=drop_path_rate)
         self.mlp_head = _make_head(pool, embed_dim, self.patch_embed.n_patches, num_classes, head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)

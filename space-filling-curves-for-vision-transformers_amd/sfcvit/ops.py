@@ -426,6 +426,62 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dx_add=None, drop_p=0.0, drop_seed=0
 
 
 # ----------------------------------------------------------------------------
+# Stochastic depth (DropPath) on a residual site: one keep flag per image, a function of (seed, image index)
+# ----------------------------------------------------------------------------
+def drop_path_keep(B, rate, seed, device="cuda"):
+    """bool [B]: which images a site with `seed` keeps at `rate` -- column 0 of the dropout mask of that seed, which is what
+    the kernels regenerate (without STEP_STATE's device offset: tests and debugging)."""
+    return dropout_mask(B, 8, rate, seed, device)[:, 0] > 0
+
+
+def add_layernorm_path_fwd(branch, x, gamma, beta, B, rate, seed, eps=1e-5):
+    """s = bf16(x + c[b] * branch), LayerNorm(s) -> (s, y, mean, rstd); c[b] = keep(b) / (1 - rate) per image b = row // (M / B).
+    branch, x: bf16 [M, D], M = B * tokens.  A dropped image's rows of s are the bits of x."""
+    _need(branch, _BF16, "add_layernorm_path branch", 2)
+    _need(x, _BF16, "add_layernorm_path x", 2)
+    M, D = x.shape
+    if branch.shape != x.shape or B <= 0 or M % B:
+        raise ValueError(f"add_layernorm_path: branch {tuple(branch.shape)} and x {tuple(x.shape)} must be equal [B * N, D] with B = {B}")
+    s, y = torch.empty_like(x), torch.empty_like(x)
+    mean = torch.empty(M, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(M, device=x.device, dtype=torch.float32)
+    check(lib.sfcvit_add_layernorm_path_fwd(_p(branch), _p(x), _p(_need(gamma, _BF16, "gamma", 1)), _p(_need(beta, _BF16, "beta", 1)),
+                                            _p(s), _p(y), _p(mean), _p(rstd), B, M // B, D, eps, rate, seed, _seed_off(), _stream()),
+          "sfcvit_add_layernorm_path_fwd")
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append(last_rowwise_kernel())
+    return s, y, mean, rstd
+
+
+def layernorm_bwd_path(dy, x, mean, rstd, gamma, rows_per_image, path_rate, path_seed, dx_add=None, drop_p=0.0, drop_seed=0,
+                       want_colsum=False, grad_out=None):
+    """layernorm_bwd for a residual site with stochastic depth -> dx, dgamma, dbeta, dx_drop [, colsum of dx_drop].  dx_drop, the
+    gradient entering the sub-layer, is always returned (also at drop_p = 0): image b = row // rows_per_image gets
+    dx * dropout mask / ((1 - drop_p)(1 - path_rate)) when the site of `path_seed` kept it, zeros otherwise.  dx (the residual
+    path), dgamma and dbeta are those of layernorm_bwd; grad_out as there."""
+    _need(dy, _BF16, "layernorm dy", 2)
+    _need(x, _BF16, "layernorm x", 2)
+    M, D = x.shape
+    if rows_per_image <= 0 or M % rows_per_image:
+        raise ValueError(f"layernorm_bwd_path: {M} rows are not whole images of {rows_per_image}")
+    dx, dx_drop = torch.empty_like(x), torch.empty_like(x)
+    shapes = ((D,), (D,), (D,))
+    (dg, db, dcol), bf16 = _grad_outs("layernorm_bwd_path", grad_out, shapes, (True, True, want_colsum), x.device,
+                                      "contiguous bf16 [D] tensors")
+    ws = torch.empty(lib.sfcvit_layernorm_bwd_ws(M, D), device=x.device, dtype=torch.uint8)
+    if dx_add is not None:
+        _need(dx_add, _BF16, "layernorm dx_add", 2)
+    with _Deferring([dg, db] + ([dcol] if dcol is not None else []), [ws]):
+        check(lib.sfcvit_layernorm_bwd_path(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_add), _p(dx), _p(dx_drop),
+                                            drop_p, drop_seed, _seed_off(), _p(dg), _p(db), _p(dcol), int(bf16),
+                                            M // rows_per_image, rows_per_image, D, _p(ws), path_rate, path_seed, _stream()),
+              "sfcvit_layernorm_bwd_path")
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append(last_rowwise_kernel())
+    return (dx, dg, db, dx_drop) + ((dcol,) if want_colsum else ())
+
+
+# ----------------------------------------------------------------------------
 # attention
 # ----------------------------------------------------------------------------
 SUPPORTED_HEAD_DIMS = (64, 128, 192, 256)

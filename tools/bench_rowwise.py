@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the row-wise kernels at the ViT-B step's shapes (M = 50176, D = 768; or `M D` on the command line):
-LayerNorm fwd / bwd, column sums.  Prints us per launch and the achieved HBM rate on the algorithmic bytes.
+LayerNorm fwd / bwd, the stochastic-depth forms of both (rate 0.1, images of M / B rows with B = 256, 64 or 1), column sums.
+The cases run in turn, ROUNDS times over (default 5, third argument); prints the median us per launch with the spread over the
+rounds and the achieved HBM rate on the algorithmic bytes.
 SFCVIT_LN_BLOCKS=<n> changes the LayerNorm-backward grid (one process per setting)."""
 import os
 import sys
@@ -18,6 +20,8 @@ w = torch.randn(D, device="cuda", generator=g).bfloat16()
 b = torch.randn(D, device="cuda", generator=g).bfloat16()
 big = torch.randn(M, 3072, device="cuda", generator=g).bfloat16()
 y, mean, rstd = ops.layernorm_fwd(x, w, b, 1e-5)
+ROUNDS = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+B = next(n for n in (256, 64, 1) if M % n == 0)
 
 
 def timeit(fn, n=20):
@@ -35,9 +39,19 @@ def timeit(fn, n=20):
 cases = [("ln_fwd", lambda: ops.layernorm_fwd(x, w, b, 1e-5), 2 * M * D * 2),
          ("ln_bwd", lambda: ops.layernorm_bwd(dy, x, mean, rstd, w), 3 * M * D * 2),
          ("ln_bwd + dropout out + colsum", lambda: ops.layernorm_bwd(dy, x, mean, rstd, w, drop_p=0.1, drop_seed=5, want_colsum=True), 4 * M * D * 2),
+         # s = x + c[b] branch, LayerNorm(s): reads x and the branch, writes s and y
+         ("add + ln_fwd, drop path 0.1", lambda: ops.add_layernorm_path_fwd(dy, x, w, b, B, 0.1, 1234, 1e-5), 4 * M * D * 2),
+         ("ln_bwd path + dropout out + colsum", lambda: ops.layernorm_bwd_path(dy, x, mean, rstd, w, M // B, 0.1, 1234, drop_p=0.1, drop_seed=5,
+                                                                              want_colsum=True), 4 * M * D * 2),
          ("colsum [M,768]", lambda: ops.colsum(x), M * D * 2),
          ("colsum [M,3072]", lambda: ops.colsum(big), M * 3072 * 2)]
 print("SFCVIT_LN_BLOCKS =", os.environ.get("SFCVIT_LN_BLOCKS", "(default)"))
-for name, fn, nbytes in cases:
-    us = timeit(fn)
-    print(f"{name:34s} {us:8.1f} us  {nbytes / us / 1e6:6.2f} TB/s")
+print(f"M = {M}, D = {D}, B = {B}; median of {ROUNDS} rounds of 20 launches [min .. max]")
+times = {name: [] for name, _, _ in cases}
+for _ in range(ROUNDS):
+    for name, fn, _ in cases:
+        times[name].append(timeit(fn))
+for name, _, nbytes in cases:
+    t = sorted(times[name])
+    us = t[len(t) // 2]
+    print(f"{name:34s} {us:8.1f} us [{t[0]:7.1f} .. {t[-1]:7.1f}]  {nbytes / us / 1e6:6.2f} TB/s")
