@@ -760,6 +760,22 @@ typedef struct sfcvit_adamw_args {
 } sfcvit_adamw_args;
 int sfcvit_adamw_step(const sfcvit_adamw_args *a, void *stream);
 
+/* Model EMA: sfcvit_adamw_step with an exponential moving average of the fp32 master weights updated in the same kernel
+ * (timm's --model-ema): per parameter, once the step has produced the new master value w,
+ *     e <- e + (1 - d_t) * (w - e)                                   e fp32 [n], every operation in fp32
+ * d_t = decay, or with warmup != 0  d_t = min(decay, float(1 + t) / float(10 + t))  (a correctly rounded fp32 division),
+ * t = the 1-based step of this update: a->step, or word [1] of a->dev_state when that is set, read when the kernel RUNS --
+ * a captured step replays with the right decay.  param, master, m and v get the bits sfcvit_adamw_step gives them; the
+ * average costs one more fp32 stream in and out (36 bytes per parameter instead of 28) and no launch.
+ * Refused (SFCVIT_EINVAL, before any HIP call): what sfcvit_adamw_step refuses, a null e or ema, an ema that is not 16-byte
+ * aligned, a decay outside [0, 1) or NaN, an ema that shares a byte with param, master, grad, m or v. */
+typedef struct sfcvit_ema_args {
+    float *ema;        /* fp32 [n]: the average (updated) */
+    float decay;       /* 0 <= decay < 1 */
+    int32_t warmup;    /* != 0: d_t = min(decay, (1 + t) / (10 + t)) */
+} sfcvit_ema_args;
+int sfcvit_adamw_ema_step(const sfcvit_adamw_args *a, const sfcvit_ema_args *e, void *stream);
+
 /* Device-resident step state, 8 words (16-byte aligned): [0] dropout seed offset (uint32), [1] step (int32), [2] learning
  * rate (float, host-written), [3] 1 - beta1^step, [4] 1 / sqrt(1 - beta2^step).  sfcvit_step_advance increments the step
  * and refreshes [0], [3], [4]; run it once per training step before the forward (first node of a captured step).  The

@@ -3,7 +3,7 @@
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
 //   host part), the error path of common.cpp, the mask validation and block map of attention_masked.cpp (check_mask_blocks),
 //   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv),
-//   token_mix.cpp (check_tokmix) and drop_path.cpp (check_drop_path), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
+//   token_mix.cpp (check_tokmix), drop_path.cpp (check_drop_path) and model_ema.cpp (check_model_ema), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
 //   and post passes each GEMM / attention shape of the benchmarked models gets).
 // Every buffer is a heap block of EXACTLY the documented size, so that an off-by-one in a generator or in the descriptor
 // writer is a heap-buffer-overflow report instead of silent corruption.
@@ -20,6 +20,7 @@
 #include "../../../include/sfcvit.h"
 #include "../dispatch.h"
 #include "../drop_path.h"
+#include "../model_ema.h"
 #include "../pos_embed.h"
 #include "../token_agg.h"
 #include "../token_mix.h"
@@ -852,6 +853,68 @@ static void check_drop_path() {
     }
 }
 
+// adamw_ema_plan (model_ema.cpp): the grid at the sizes of the tests and the workloads, and every refusal, with heap buffers of
+// exactly n bf16 (param, grad) and n fp32 (master, m, v, ema).  The plan reads the two structs and no byte of the buffers.
+static void check_model_ema() {
+    using namespace sfcvit;
+    const struct { int64_t n; int grid; } ok[] = {{1, 1}, {3, 1}, {4, 1}, {7, 1}, {2048, 1}, {2049, 2}, {2451, 2}, {5525002, 2048}, {4194304, 2048},
+                                                  {4194296, 2048}, {4194305, 2048}, {12582917, 2048}, {86567656, 2048}};
+    for (const auto &q : ok) {
+        const size_t n = size_t(q.n);
+        std::unique_ptr<char[]> pb(new char[n * 2 + 16]), gb(new char[n * 2 + 16]), wb(new char[n * 4 + 16]), mb(new char[n * 4 + 16]),
+            vb(new char[n * 4 + 16]), eb(new char[n * 4 + 16]);
+        auto al = [](char *p) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(p) + 15) & ~uintptr_t(15)); };
+        sfcvit_adamw_args a{};
+        a.param = al(pb.get()); a.grad = al(gb.get());
+        a.master = reinterpret_cast<float *>(al(wb.get())); a.m = reinterpret_cast<float *>(al(mb.get())); a.v = reinterpret_cast<float *>(al(vb.get()));
+        a.n = q.n; a.lr = 3e-4f; a.beta1 = 0.9f; a.beta2 = 0.999f; a.eps = 1e-8f; a.grad_scale = 1.f; a.step = 1;
+        sfcvit_ema_args e{reinterpret_cast<float *>(al(eb.get())), 0.9999f, 1};
+        const AdamwEmaPlan p = adamw_ema_plan(&a, &e);
+        CHECK(p.err == SFCVIT_OK, "model_ema n %lld refused: %s", (long long)q.n, p.msg);
+        CHECK(p.grid == q.grid && p.grid >= 1 && p.grid <= ADAMW_MAX_BLOCKS, "model_ema n %lld: grid %d, want %d", (long long)q.n, p.grid, q.grid);
+        // one lane per 8 parameters covers everything below the cap
+        CHECK(p.grid == ADAMW_MAX_BLOCKS || int64_t(p.grid) * ADAMW_THREADS * 8 >= q.n, "model_ema n %lld: grid %d is short", (long long)q.n, p.grid);
+        e.decay = 0.f;
+        CHECK(adamw_ema_plan(&a, &e).err == SFCVIT_OK, "model_ema: decay 0 refused");
+        e.decay = 0.9999f;
+        { sfcvit_adamw_args b = a; b.step = 0; float st[8] = {}; b.dev_state = st;
+          CHECK(adamw_ema_plan(&b, &e).err == SFCVIT_OK, "model_ema: step 0 with dev_state refused"); }
+        auto bad = [&](const sfcvit_adamw_args *a_, const sfcvit_ema_args *e_, const char *frag, const char *what) {
+            const AdamwEmaPlan r = adamw_ema_plan(a_, e_);
+            CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag) && r.grid == 0, "model_ema %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
+        };
+        bad(nullptr, &e, "null pointer (a)", "null a");
+        bad(&a, nullptr, "null pointer (e)", "null e");
+        { sfcvit_adamw_args b = a; b.param = nullptr; bad(&b, &e, "null", "null param"); }
+        { sfcvit_adamw_args b = a; b.master = nullptr; bad(&b, &e, "null", "null master"); }
+        { sfcvit_adamw_args b = a; b.grad = nullptr; bad(&b, &e, "null", "null grad"); }
+        { sfcvit_adamw_args b = a; b.m = nullptr; bad(&b, &e, "null", "null m"); }
+        { sfcvit_adamw_args b = a; b.v = nullptr; bad(&b, &e, "null", "null v"); }
+        { sfcvit_ema_args f = e; f.ema = nullptr; bad(&a, &f, "(ema)", "null ema"); }
+        { sfcvit_adamw_args b = a; b.n = 0; bad(&b, &e, "n=0", "n = 0"); }
+        { sfcvit_adamw_args b = a; b.n = -5; bad(&b, &e, "n=-5", "n < 0"); }
+        { sfcvit_adamw_args b = a; b.n = INT64_MAX; bad(&b, &e, "address space", "n = 2^63 - 1"); }
+        { sfcvit_adamw_args b = a; b.step = 0; bad(&b, &e, "step=0", "step 0 without dev_state"); }
+        { sfcvit_adamw_args b = a; b.param = static_cast<char *>(a.param) + 2; bad(&b, &e, "aligned", "misaligned param"); }
+        { sfcvit_adamw_args b = a; b.master = a.master + 1; bad(&b, &e, "aligned", "misaligned master"); }
+        { sfcvit_adamw_args b = a; b.v = a.v + 2; bad(&b, &e, "aligned", "misaligned v"); }
+        { sfcvit_ema_args f = e; f.ema = e.ema + 1; bad(&a, &f, "ema must be 16-byte aligned", "misaligned ema"); }
+        for (float d : {1.f, -0.1f, 1.5f, std::numeric_limits<float>::quiet_NaN(), std::numeric_limits<float>::infinity()}) {
+            sfcvit_ema_args f = e; f.decay = d; bad(&a, &f, "decay=", "decay outside [0, 1)");
+        }
+        { sfcvit_ema_args f = e; f.ema = a.master; bad(&a, &f, "ema overlaps master", "ema = master"); }
+        { sfcvit_ema_args f = e; f.ema = a.m; bad(&a, &f, "ema overlaps m", "ema = m"); }
+        { sfcvit_ema_args f = e; f.ema = a.v; bad(&a, &f, "ema overlaps v", "ema = v"); }
+        { sfcvit_ema_args f = e; f.ema = static_cast<float *>(a.param); bad(&a, &f, "ema overlaps param", "ema = param"); }
+        { sfcvit_ema_args f = e; f.ema = reinterpret_cast<float *>(const_cast<void *>(a.grad)); bad(&a, &f, "ema overlaps", "ema = grad"); }       // n fp32 from grad may reach a neighbouring block first
+        if (q.n >= 8) {       // starts in master's last vector / ends in master's first
+            sfcvit_ema_args f = e;
+            f.ema = a.master + (q.n - 1) / 4 * 4; bad(&a, &f, "ema overlaps", "ema starts in master's last vector");
+            sfcvit_adamw_args b = a; b.master = e.ema + (q.n - 1) / 4 * 4; bad(&b, &e, "ema overlaps", "master starts in ema's last vector");
+        }
+    }
+}
+
 int main() {
     const int curves[] = {SFCVIT_CURVE_HILBERT, SFCVIT_CURVE_Z, SFCVIT_CURVE_MOORE, SFCVIT_CURVE_PEANO, SFCVIT_CURVE_RASTER,
                           SFCVIT_CURVE_SPIRAL, SFCVIT_CURVE_HILBERT_T};
@@ -925,6 +988,7 @@ int main() {
     check_dwconv();
     check_tokmix();
     check_drop_path();
+    check_model_ema();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     std::printf("host_check ok\n");
     return 0;

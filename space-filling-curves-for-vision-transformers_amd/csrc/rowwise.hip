@@ -10,6 +10,7 @@
 #include "common_host.h"
 #include "device_common.h"
 #include "drop_path.h"
+#include "model_ema.h"
 
 namespace sfcvit {
 namespace {
@@ -1162,6 +1163,99 @@ __global__ __launch_bounds__(THREADS) void adamw_kernel(sfcvit_adamw_args a, flo
     }
 }
 
+// adamw_kernel plus an exponential moving average of the fp32 master weights (model_ema.h): after adamw_one has produced the
+// new w, e <- e + (1 - d_t) * (w - e) with e fp32, one more 16-byte stream in and out per lane (36 bytes per parameter instead
+// of 28, no second pass over master).  d_t = decay, or with `warmup` min(decay, (1 + t) / (10 + t)), t the 1-based step of
+// this update: a.step, or the device counter when dev_state is set, read when the kernel runs -- so a captured step replays
+// with the right decay.  A kernel of its own: param, master, m and v get adamw_kernel's bits, and adamw_kernel keeps its
+// text (a shared templated body changes the existing instantiations, profiles/drop_path/isa_identity.txt).
+template <int NT>      // as adamw_kernel
+__global__ __launch_bounds__(THREADS) void adamw_ema_kernel(sfcvit_adamw_args a, float bc1, float rbc2, float *__restrict__ ema,
+                                                            float decay, int warmup, int t) {
+    if (a.dev_state) {            // t arrives as a.step in an argument of its own: a value, not a second address to load from
+        a.lr = a.dev_state[2];
+        bc1 = a.dev_state[3];
+        rbc2 = a.dev_state[4];
+        t = reinterpret_cast<const int32_t *>(a.dev_state)[1];
+    }
+    const float d = warmup ? fminf(decay, float(1 + t) / float(10 + t)) : decay;      // a true (correctly rounded) division
+    const float omd = 1.f - d;                                                         // exact for d >= 0.5 (Sterbenz)
+    float gmul = a.grad_scale;
+    if (a.sumsq) {
+        const float norm = sqrtf(*a.sumsq) * a.grad_scale;
+        gmul *= fminf(1.f, a.max_norm / (norm + 1e-6f));
+    }
+    uint16_t *p = static_cast<uint16_t *>(a.param);
+    const uint16_t *g = static_cast<const uint16_t *>(a.grad);
+    // adamw_kernel's layout: four parameters per lane and group, two groups in flight (2 x 72 bytes per lane here)
+    const int64_t nq = a.n >> 2, step = int64_t(gridDim.x) * THREADS;
+    auto load = [&](int64_t i, u32x2 &gq, f32x4 &wv, f32x4 &mv, f32x4 &vv, f32x4 &ev) __attribute__((always_inline)) {
+        if (NT & 1) {
+            gq = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(g) + i);
+            wv = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(a.master) + i);
+            mv = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(a.m) + i);
+            vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(a.v) + i);
+            ev = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(ema) + i);
+        } else {
+            gq = reinterpret_cast<const u32x2 *>(g)[i];
+            wv = reinterpret_cast<const f32x4 *>(a.master)[i];
+            mv = reinterpret_cast<const f32x4 *>(a.m)[i];
+            vv = reinterpret_cast<const f32x4 *>(a.v)[i];
+            ev = reinterpret_cast<const f32x4 *>(ema)[i];
+        }
+    };
+    auto update = [&](int64_t i, const u32x2 &gq, f32x4 wv, f32x4 mv, f32x4 vv, f32x4 ev) __attribute__((always_inline)) {
+        const float gr[4] = {bf2f(uint16_t(gq[0])), bf2f(uint16_t(gq[0] >> 16)), bf2f(uint16_t(gq[1])), bf2f(uint16_t(gq[1] >> 16))};
+        float w[4], m[4], v[4], e[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            w[j] = wv[j];
+            m[j] = mv[j];
+            v[j] = vv[j];
+            adamw_one(w[j], m[j], v[j], gr[j] * gmul, a, bc1, rbc2);
+            e[j] = ev[j] + omd * (w[j] - ev[j]);
+        }
+        if (NT & 2) {
+            __builtin_nontemporal_store(f32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<f32x4 *>(a.master) + i);
+            __builtin_nontemporal_store(f32x4{m[0], m[1], m[2], m[3]}, reinterpret_cast<f32x4 *>(a.m) + i);
+            __builtin_nontemporal_store(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4 *>(a.v) + i);
+            __builtin_nontemporal_store(f32x4{e[0], e[1], e[2], e[3]}, reinterpret_cast<f32x4 *>(ema) + i);
+        } else {
+            reinterpret_cast<f32x4 *>(a.master)[i] = f32x4{w[0], w[1], w[2], w[3]};
+            reinterpret_cast<f32x4 *>(a.m)[i] = f32x4{m[0], m[1], m[2], m[3]};
+            reinterpret_cast<f32x4 *>(a.v)[i] = f32x4{v[0], v[1], v[2], v[3]};
+            reinterpret_cast<f32x4 *>(ema)[i] = f32x4{e[0], e[1], e[2], e[3]};
+        }
+        reinterpret_cast<u32x2 *>(p)[i] = u32x2{pack2bf(w[0], w[1]), pack2bf(w[2], w[3])};
+    };
+    int64_t i = blockIdx.x * int64_t(THREADS) + threadIdx.x;
+    for (; i + step < nq; i += 2 * step) {
+        u32x2 g0, g1;
+        f32x4 w0, m0, v0, e0, w1, m1, v1, e1;
+        load(i, g0, w0, m0, v0, e0);
+        load(i + step, g1, w1, m1, v1, e1);
+        update(i, g0, w0, m0, v0, e0);
+        update(i + step, g1, w1, m1, v1, e1);
+    }
+    if (i < nq) {
+        u32x2 g0;
+        f32x4 w0, m0, v0, e0;
+        load(i, g0, w0, m0, v0, e0);
+        update(i, g0, w0, m0, v0, e0);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < int(a.n & 3)) {
+        const int64_t k = (nq << 2) + threadIdx.x;
+        float w = a.master[k], m = a.m[k], v = a.v[k];
+        const float e = ema[k];
+        adamw_one(w, m, v, bf2f(g[k]) * gmul, a, bc1, rbc2);
+        a.master[k] = w;
+        a.m[k] = m;
+        a.v[k] = v;
+        ema[k] = e + omd * (w - e);
+        p[k] = f2bf(w);
+    }
+}
+
 int grid_for(int64_t work_items) {
     int64_t b = (work_items + THREADS - 1) / THREADS;
     if (b < 1) b = 1;
@@ -1525,6 +1619,21 @@ extern "C" int sfcvit_adamw_step(const sfcvit_adamw_args *a, void *stream) {
     if (nt == 3) ADAMW(3); else if (nt == 2) ADAMW(2); else if (nt == 1) ADAMW(1); else ADAMW(0);
 #undef ADAMW
     return check_launch("adamw");
+}
+
+// The same step with the weight average in it (model_ema.h).  Every refusal and the grid are the plan's, before any HIP call.
+static_assert(ADAMW_THREADS == THREADS, "model_ema.h plans the grid for this file's workgroup size");
+extern "C" int sfcvit_adamw_ema_step(const sfcvit_adamw_args *a, const sfcvit_ema_args *e, void *stream) {
+    const AdamwEmaPlan p = adamw_ema_plan(a, e);
+    if (p.err) return fail(p.err, "%s", p.msg);
+    const float bc1 = 1.f - powf(a->beta1, float(a->step));
+    const float bc2 = 1.f - powf(a->beta2, float(a->step));
+    static const int nt = env_int("SFCVIT_ADAMW_NT", 3) & 3;
+    g_rowwise.set("adamw_ema_kernel<%d>", nt);
+#define ADAMW_EMA(NT) hipLaunchKernelGGL(adamw_ema_kernel<NT>, dim3(p.grid), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *a, bc1, 1.f / sqrtf(bc2), e->ema, e->decay, int(e->warmup), int(a->step))
+    if (nt == 3) ADAMW_EMA(3); else if (nt == 2) ADAMW_EMA(2); else if (nt == 1) ADAMW_EMA(1); else ADAMW_EMA(0);
+#undef ADAMW_EMA
+    return check_launch("adamw_ema");
 }
 
 // ---------------------------------------------------------------------------

@@ -131,6 +131,14 @@ def build_parser():
                     help="stochastic depth (DropPath, the DeiT recipe's drop_path_rate): in training every encoder layer drops "
                          "each of its two residual branches per image, with a probability that grows linearly with depth from 0 "
                          "to R, and scales the kept ones up; 0 <= R < 1, default 0 (off).  Works with --graph; no checkpoint key")
+    ap.add_argument("--model-ema", type=float, nargs="?", const=0.9999, default=None, metavar="DECAY",
+                    help="keep an exponential moving average of the weights (timm's --model-ema; DECAY defaults to 0.9999): "
+                         "averaged in fp32 inside the AdamW kernel, evaluated after every epoch next to the raw weights (one "
+                         "extra 'EMA Test Loss / EMA Test Acc' line) and checkpointed as model_ema_state_dict / ema_test_acc; "
+                         "--resume continues the average.  Works with --graph, --device-mix and --device-augment")
+    ap.add_argument("--model-ema-warmup", action="store_true",
+                    help="with --model-ema: the decay of step t is min(DECAY, (1 + t) / (10 + t)), so that the average follows "
+                         "the weights closely in the first steps")
     win = ap.add_mutually_exclusive_group()
     win.add_argument("--attn-window", type=int, default=None, metavar="W",
                      help="local attention along the curve: every token attends to the tokens within W positions of it in "
@@ -216,7 +224,10 @@ def main():
                   f"(N = {attn_mask.n_tokens})")
     model = build_model(a, patch_embed, attn_mask).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
     train_criterion, test_criterion = SoftTargetCrossEntropy(), nn.CrossEntropyLoss()
-    optimizer = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=1.0)
+    if a.model_ema_warmup and a.model_ema is None:
+        raise SystemExit("--model-ema-warmup needs --model-ema")
+    optimizer = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=1.0,
+                           ema_decay=a.model_ema, ema_warmup=a.model_ema_warmup)
     reducer = GradReducer(optimizer, overlap=not a.graph) if world > 1 else None    # --graph: collectives between two graphs
     scheduler = WarmupCosine(optimizer, a.warmup_epochs * len(train_loader), a.epochs * len(train_loader))
     start_epoch, best = 0, 0.0
@@ -273,20 +284,29 @@ def main():
                                                      device, reducer=reducer, graphed=graphed, device_mix=a.device_mix,
                                                      augment=augment)
         te_loss, te_acc = evaluate(model, test_loader, test_criterion, device, transform=test_transform)
+        ema_loss = ema_acc = 0.0
+        if a.model_ema is not None:
+            with optimizer.ema_weights():              # the same model, its parameters pointing at the averaged weights
+                ema_loss, ema_acc = evaluate(model, test_loader, test_criterion, device, transform=test_transform)
         if world > 1:                                  # equal shards per rank: the global figures are the rank means
-            t = torch.tensor([tr_loss, tr_acc, te_loss, te_acc], device=device, dtype=torch.float64)
+            t = torch.tensor([tr_loss, tr_acc, te_loss, te_acc, ema_loss, ema_acc], device=device, dtype=torch.float64)
             dist.all_reduce(t)
-            tr_loss, tr_acc, te_loss, te_acc = (t / world).tolist()
+            tr_loss, tr_acc, te_loss, te_acc, ema_loss, ema_acc = (t / world).tolist()
         if rank == 0:
             print(f"Epoch {epoch + 1}/{a.epochs} | Train Loss: {tr_loss:.4f}, Train Acc: {tr_acc:.4f} | "
                   f"Test Loss: {te_loss:.4f}, Test Acc: {te_acc:.4f}")            # main.py:331-335
+            if a.model_ema is not None:
+                print(f"Epoch {epoch + 1}/{a.epochs} | EMA Test Loss: {ema_loss:.4f}, EMA Test Acc: {ema_acc:.4f}")
             if te_acc > best or epoch == start_epoch:
                 best = te_acc
-                torch.save({"epoch": epoch, "model_state_dict": model.state_dict(),
-                            "optimizer_state_dict": optimizer.state_dict() if optimizer.master is not None else {},
-                            "scheduler_state_dict": {"n": scheduler.n},
-                            "augment_state_dict": augment.state_dict() if augment is not None else {}, "train_loss": tr_loss, "train_acc": tr_acc,
-                            "test_loss": te_loss, "test_acc": te_acc}, ckpt)      # main.py:345-354 keys
+                ck = {"epoch": epoch, "model_state_dict": model.state_dict(),
+                      "optimizer_state_dict": optimizer.state_dict() if optimizer.master is not None else {},
+                      "scheduler_state_dict": {"n": scheduler.n},
+                      "augment_state_dict": augment.state_dict() if augment is not None else {}, "train_loss": tr_loss, "train_acc": tr_acc,
+                      "test_loss": te_loss, "test_acc": te_acc}                  # main.py:345-354 keys
+                if a.model_ema is not None:            # the averaged weights under the reference's keys: model.load_state_dict takes them
+                    ck.update(model_ema_state_dict=optimizer.ema_state_dict(model), ema_test_acc=ema_acc)
+                torch.save(ck, ckpt)
     if world > 1:
         dist.destroy_process_group()
 

@@ -76,6 +76,10 @@ class AdamWArgs(ctypes.Structure):
                 ("step", c_int32), ("dev_state", c_void_p)]
 
 
+class EmaArgs(ctypes.Structure):
+    _fields_ = [("ema", c_void_p), ("decay", c_float), ("warmup", c_int32)]
+
+
 class AugmentCfg(ctypes.Structure):
     _fields_ = [("S", c_int32), ("crop", c_int32), ("flip", c_int32), ("out_is_bf16", c_int32),
                 ("scale", ctypes.c_double * 2), ("ratio", ctypes.c_double * 2),
@@ -184,6 +188,7 @@ SIGNATURES = {
                                c_float, c_void_p]),
     "sfcvit_sumsq_accum": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "sfcvit_adamw_step": (c_int, [ctypes.POINTER(AdamWArgs), c_void_p]),
+    "sfcvit_adamw_ema_step": (c_int, [ctypes.POINTER(AdamWArgs), ctypes.POINTER(EmaArgs), c_void_p]),
 }
 
 

@@ -1318,8 +1318,7 @@ def sumsq_accum(g, out):
     check(lib.sfcvit_sumsq_accum(_p(g), g.numel(), int(is_f32), _p(out), _p(ws), _stream()), "sfcvit_sumsq_accum")
 
 
-def adamw_step(param, master, grad, m, v, sumsq, *, lr, beta1, beta2, eps, weight_decay, max_norm, step,
-               grad_scale=1.0, dev_state=None):
+def _adamw_args(param, master, grad, m, v, sumsq, lr, beta1, beta2, eps, weight_decay, max_norm, step, grad_scale, dev_state):
     a = _lib.AdamWArgs()
     a.param, a.master, a.grad, a.m, a.v = (param.data_ptr(), master.data_ptr(), grad.data_ptr(),
                                            m.data_ptr(), v.data_ptr())
@@ -1329,4 +1328,24 @@ def adamw_step(param, master, grad, m, v, sumsq, *, lr, beta1, beta2, eps, weigh
     a.grad_scale = grad_scale
     if dev_state is not None:
         a.dev_state = dev_state.data_ptr()
+    return a
+
+
+def adamw_step(param, master, grad, m, v, sumsq, *, lr, beta1, beta2, eps, weight_decay, max_norm, step,
+               grad_scale=1.0, dev_state=None):
+    a = _adamw_args(param, master, grad, m, v, sumsq, lr, beta1, beta2, eps, weight_decay, max_norm, step, grad_scale, dev_state)
     check(lib.sfcvit_adamw_step(ctypes.byref(a), _stream()), "sfcvit_adamw_step")
+
+
+def adamw_ema_step(param, master, grad, m, v, sumsq, ema, ema_decay, ema_warmup=False, *, lr, beta1, beta2, eps, weight_decay,
+                   max_norm, step, grad_scale=1.0, dev_state=None):
+    """adamw_step plus, in the same kernel, ema <- ema + (1 - d_t) * (master - ema) on the new fp32 master (ema fp32 [n]);
+    d_t = ema_decay, or with ema_warmup min(ema_decay, (1 + t) / (10 + t)) with t = `step` (the device counter under
+    dev_state): sfcvit_adamw_ema_step.  param, master, m and v get adamw_step's bits."""
+    _need(ema, torch.float32, "adamw_ema_step ema", 1)
+    if ema.numel() != param.numel():
+        raise ValueError(f"adamw_ema_step: ema has {ema.numel()} elements, param {param.numel()}")
+    a = _adamw_args(param, master, grad, m, v, sumsq, lr, beta1, beta2, eps, weight_decay, max_norm, step, grad_scale, dev_state)
+    e = _lib.EmaArgs()
+    e.ema, e.decay, e.warmup = ema.data_ptr(), ema_decay, int(bool(ema_warmup))
+    check(lib.sfcvit_adamw_ema_step(ctypes.byref(a), ctypes.byref(e), _stream()), "sfcvit_adamw_ema_step")

@@ -8,6 +8,9 @@ a second flat buffer (`p.grad` are views of it), and a step is two kernels: one 
 of squares, one fused clip + AdamW with fp32 master weights and moments.  Nothing
 synchronises with the host.
 """
+import collections
+import contextlib
+
 import torch
 
 from .. import ops
@@ -152,11 +155,26 @@ class FlatGradBuffer:
 class FusedAdamW(FlatGradBuffer):
     """Not a torch.optim.Optimizer subclass on purpose: state is three flat fp32
     buffers, not per-tensor dicts.  API: zero_grad(), step(), lr attribute,
-    state_dict() / load_state_dict()."""
+    state_dict() / load_state_dict().
+
+    ema_decay (None = off: today's launches, bits and state-dict keys): an exponential moving average of the fp32 master
+    weights (timm's --model-ema), `ema` fp32 [flat size], updated inside the AdamW kernel (ops.adamw_ema_step: no second pass,
+    no extra launch, replayable from a captured step).  It starts at the weights, e <- e + (1 - d_t) * (w - e) per step with
+    d_t = ema_decay, or with ema_warmup min(ema_decay, (1 + t) / (10 + t)) for the t-th step.  ema_state_dict(model) and
+    ema_weights() hand the average to evaluation and checkpoints.  Parameters outside the flat buffers never receive a
+    gradient, so their average is their value.  Data parallel: every rank applies the same update to the same weights
+    (GradReducer reduces the gradients and synchronises the replicas), so every rank holds the same average and the EMA
+    needs no collective of its own."""
 
     def __init__(self, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-5, max_grad_norm=1.0,
-                 grad_scale=1.0):
+                 grad_scale=1.0, ema_decay=None, ema_warmup=False):
         super().__init__(params, grad_scale)
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:          # (NaN fails both comparisons)
+            raise ValueError(f"ema_decay={ema_decay} outside [0, 1)")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = None                  # fp32 average of `master`, allocated with it when ema_decay is set
+        self._ema_swapped = False        # inside ema_weights()
         # one group, shaped like torch.optim's so that schedulers written against `param_groups[0]['lr']` work
         self.param_groups = [{"lr": lr, "betas": betas, "eps": eps, "weight_decay": weight_decay}]
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
@@ -222,9 +240,13 @@ class FusedAdamW(FlatGradBuffer):
         self.m = torch.zeros_like(self.master)
         self.v = torch.zeros_like(self.master)
         self._sumsq = torch.zeros(1, device=self.master.device, dtype=torch.float32)
+        if self.ema_decay is not None:
+            self.ema = self.master.clone()       # the average starts at the weights (timm: a deep copy of the model)
 
     @torch.no_grad()
     def step(self):
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.step() inside ema_weights(): the parameters are views of the average")
         if self.flat_grad is None:
             self._build()
         else:
@@ -237,6 +259,13 @@ class FusedAdamW(FlatGradBuffer):
             self._sumsq.zero_()
             ops.sumsq_accum(self.flat_grad, self._sumsq)
             sumsq = self._sumsq
+        if self.ema is not None:
+            ops.adamw_ema_step(self.flat_param, self.master, self.flat_grad, self.m, self.v, sumsq,
+                               self.ema, self.ema_decay, self.ema_warmup,
+                               lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                               weight_decay=self.weight_decay, max_norm=self.max_grad_norm or 0.0,
+                               step=max(1, self.step_count), grad_scale=self.grad_scale, dev_state=self.dev_state)
+            return
         ops.adamw_step(self.flat_param, self.master, self.flat_grad, self.m, self.v, sumsq,
                        lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
                        weight_decay=self.weight_decay, max_norm=self.max_grad_norm or 0.0,
@@ -248,8 +277,59 @@ class FusedAdamW(FlatGradBuffer):
 
     def state_dict(self):
         index = {id(p): i for i, p in enumerate(self.params)}
-        return {"step": self.step_count, "lr": self.lr, "master": self.master, "m": self.m, "v": self.v,
-                "active": [index[id(p)] for p in self.active]}
+        sd = {"step": self.step_count, "lr": self.lr, "master": self.master, "m": self.m, "v": self.v,
+              "active": [index[id(p)] for p in self.active]}
+        if self.ema is not None:
+            sd.update(ema=self.ema, ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
+        return sd
+
+    def _need_ema(self, what):
+        if self.ema_decay is None:
+            raise RuntimeError(f"{what}: this FusedAdamW keeps no average (ema_decay=None)")
+        if self.ema is None:
+            raise RuntimeError(f"{what}: the flat buffers do not exist yet (no step() and no load_state_dict())")
+
+    def ema_state_dict(self, model):
+        """model.state_dict() with the averaged weights: the same keys in the same order; every parameter of the flat buffer
+        comes from `ema` (cast to the parameter's dtype), everything else -- parameters outside the flat buffer, buffers such
+        as the tokenizers' index tables -- is the model's own tensor.  model.load_state_dict() takes it."""
+        self._need_ema("ema_state_dict")
+        flat = self.ema.to(self.flat_param.dtype)
+        mine = {}
+        for name, p in model.named_parameters(remove_duplicate=False):
+            slot = getattr(p, "_sfcvit_slot", None)
+            if slot is not None and slot[0] is self:
+                mine[name] = flat[slot[1]:slot[1] + p.numel()].view(p.shape)
+        out = collections.OrderedDict()
+        for k, v in model.state_dict().items():
+            out[k] = mine.get(k, v)
+        return out
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """While active, the model computes with the averaged weights: every parameter of the flat buffer has as `.data` a
+        view of ONE bf16 flat copy of `ema`, cast once on entry.  A pointer swap only: nothing is written into flat_param (a
+        captured step holds its address), and on exit `.data` is the view it was before, so the parameter bits and the next
+        training step are untouched.  Does not nest, and cannot be entered while a stream is capturing (the swap is host
+        state a replay would not redo).  Nothing in the package caches a value derived from a parameter across forward
+        passes -- the tokenizers' device tables are keyed on index buffers, the attention-mask cache on the mask, and
+        `transposed` serves backward passes only -- so an eval forward inside the context reads nothing stale."""
+        self._need_ema("ema_weights")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() does not nest")
+        if self.ema.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ema_weights() cannot be entered during a stream capture")
+        flat = self.ema.to(self.flat_param.dtype)
+        saved = [p.data for p in self.active]
+        self._ema_swapped = True
+        try:
+            for p, o in zip(self.active, self.offsets):
+                p.data = flat[o:o + p.numel()].view(p.shape)
+            yield flat
+        finally:
+            for p, d in zip(self.active, saved):
+                p.data = d
+            self._ema_swapped = False
 
     def load_torch_state_dict(self, sd):
         """The state_dict of a torch.optim.AdamW over the same model.parameters() (what the reference's main.py:345-354
@@ -283,6 +363,8 @@ class FusedAdamW(FlatGradBuffer):
             self.dev_state[1] = self.step_count
         self.lr = float(groups[0]["lr"])
         self.master.copy_(self.flat_param.float())
+        if self.ema is not None:
+            self.ema.copy_(self.master)          # torch.optim keeps no average: it starts at the loaded weights
 
     def load_state_dict(self, sd):
         if "param_groups" in sd and "state" in sd:           # a torch.optim optimizer's state (reference checkpoint)
@@ -298,6 +380,8 @@ class FusedAdamW(FlatGradBuffer):
         self.m.copy_(sd["m"])
         self.v.copy_(sd["v"])
         self.flat_param.copy_(self.master)
+        if self.ema is not None:                 # a state without "ema" (an older checkpoint): the average starts at the loaded weights
+            self.ema.copy_(sd["ema"] if sd.get("ema") is not None else self.master)
 
 
 class WarmupCosine:

@@ -112,7 +112,8 @@ class GraphedTrainStep:
         o = self.opt
         sched = None if self.sched is None else {k: v for k, v in vars(self.sched).items() if isinstance(v, (int, float))}
         return {"params": [p.detach().clone() for p in o.params], "step": o.step_count, "lr": o.lr, "sched": sched,
-                "moments": None if o.master is None else (o.master.clone(), o.m.clone(), o.v.clone())}
+                "moments": None if o.master is None else (o.master.clone(), o.m.clone(), o.v.clone()),
+                "ema": None if getattr(o, "ema", None) is None else o.ema.clone()}
 
     @torch.no_grad()
     def _restore(self, s):
@@ -126,6 +127,8 @@ class GraphedTrainStep:
             o.master.copy_(o.flat_param.float())
             o.m.zero_()
             o.v.zero_()
+        if getattr(o, "ema", None) is not None:       # the weight average takes no part in the warm-up either
+            o.ema.copy_(o.master if s["ema"] is None else s["ema"])
         o.step_count = s["step"]
         o.dev_state[1] = s["step"]
         if self.sched is not None:
