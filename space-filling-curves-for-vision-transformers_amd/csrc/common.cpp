@@ -1,4 +1,5 @@
 #include "common_host.h"
+#include "rowwise.h"
 
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -55,6 +56,18 @@ Knobs read_knobs(KnobScope scope) {
         if (env_pair("SFCVIT_ATTN_STAGGER_BWD", &slots, &k.attn_stagger_ticks)) k.attn_stagger_slots = slots < 1 ? 1 : slots;
     }
     return k;
+}
+
+const RowwiseKnobs &read_rowwise_knobs() {
+    static const RowwiseKnobs once = [] {
+        RowwiseKnobs k;
+        k.ln_cols = !env_off("SFCVIT_LN_COLS");
+        k.ln_blocks = env_int("SFCVIT_LN_BLOCKS", k.ln_blocks);
+        k.ln_fwd_two_rows = env_int("SFCVIT_LN_FWD_TWO_ROWS", k.ln_fwd_two_rows);
+        k.adamw_nt = env_int("SFCVIT_ADAMW_NT", k.adamw_nt);
+        return k;
+    }();
+    return once;
 }
 
 // ---- the scaffold of plan.h ----

@@ -38,7 +38,8 @@ void note_attn_kernel(const ProbePlan &p);      // sfcvit_attention_probs / _sta
 // last (sfcvit_last_tokenizer_kernel): noted on the host just before the launch.
 extern thread_local KernelNote g_attn, g_rowwise, g_tokenizer;
 
-// rowwise.hip: out[n] = sum over `nparts` rows of part[nparts][N] in a fixed order; out fp32 or bf16.
+// rowwise.hip (layernorm.hip and the GEMM launchers call these too): out[n] = sum over `nparts` rows of part[nparts][N] in a
+// fixed order; out fp32 or bf16.
 int launch_colsum_reduce(const float *part, int nparts, int N, void *out, int out_bf16, void *stream);
 // The general form: out[c] = sum_p part[p * ld + c], c < ncols.  Launched now -- or, between sfcvit_reduce_defer(1) and
 // sfcvit_reduce_defer(0), queued for ONE batched launch at sfcvit_reduce_flush (every such reduction of a backward pass

@@ -4,7 +4,8 @@
 // checked on the CPU by hostcheck/host_check.cpp.  kernel_name(plan) is the symbol rocprofv3 shows for the plan's main
 // kernel (sfcvit_last_gemm_kernel / sfcvit_last_attn_kernel).
 //
-// Environment switches, for A/B measurements and tests (never needed in production).  Read by read_knobs (common.cpp):
+// Environment switches, for A/B measurements and tests (never needed in production).  Read by read_knobs and, the four of
+// the row-wise family (rowwise.h: RowwiseKnobs), read_rowwise_knobs (common.cpp):
 //   read per call (tests flip them between calls)
 //     SFCVIT_GEMM_2PHASE       1        "0": four-phase k-tile schedule of the persistent GEMMs
 //     SFCVIT_GEMM_STAGGER      4,200    "slots,ticks" (10 ns) start-up stagger of the persistent GEMM; "1,0" = off
@@ -20,10 +21,10 @@
 //     SFCVIT_GEMM_WALK         6 if N >= 1792, else 0  tile-walk window width of the persistent GEMM; 0 = row-major
 //     SFCVIT_ATTN_BWD_QUEUE    1        "0": fixed item stride in the persistent attention backward
 //     SFCVIT_ATTN_NT           0        bit 0: nontemporal LDS-DMA in the attention backward
-//     SFCVIT_LN_COLS           1        "0": 16-byte-vector LayerNorm backward also at D = 768 (rowwise.hip)
-//     SFCVIT_LN_BLOCKS         0 (auto) workgroups of the LayerNorm backward (rowwise.hip)
-//     SFCVIT_LN_FWD_TWO_ROWS   1        "0": one row per wave in the LayerNorm forward (rowwise.hip)
-//     SFCVIT_ADAMW_NT          3        nontemporal loads (1) / stores (2) of the optimizer state (rowwise.hip)
+//     SFCVIT_LN_COLS           1        "0": 16-byte-vector LayerNorm backward also at D = 768 (ln_bwd_plan)
+//     SFCVIT_LN_BLOCKS         0 (auto) workgroups of the LayerNorm backward (ln_bwd_plan)
+//     SFCVIT_LN_FWD_TWO_ROWS   1        "0": one row per wave in the LayerNorm forward (ln_fwd_plan)
+//     SFCVIT_ADAMW_NT          3        nontemporal loads (1) / stores (2) of the optimizer state (adamw_plan)
 //     SFCVIT_GATHER_U          1        images per wave of the tile gather, 1 or 2 (patch_embed.hip)
 //     SFCVIT_GATHER_NT         3        nontemporal loads (1) / stores (2) of the tile gather (patch_embed.hip)
 #pragma once

@@ -6,14 +6,6 @@
 
 namespace sfcvit {
 
-namespace {
-// [a, a + bytes) and [b, b + bytes) share a byte
-bool overlap(const void *a, const void *b, uint64_t bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + bytes && b0 < a0 + bytes;
-}
-}  // namespace
-
 AddLnPathPlan add_ln_path_plan(const void *branch, const void *x, const void *gamma, const void *beta, const void *s, const void *y,
                                const float *mean, const float *rstd, int B, int N, int D, float rate) {
     AddLnPathPlan p;
@@ -22,23 +14,24 @@ AddLnPathPlan add_ln_path_plan(const void *branch, const void *x, const void *ga
         REFUSE(SFCVIT_EINVAL, "%s: null pointer (branch / x / gamma / beta / s / y / mean / rstd)", what);
     if (B <= 0 || N <= 0) REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d (B, N >= 1)", what, B, N);
     if (int64_t(B) * N > INT_MAX) REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d: B * N rows leave int", what, B, N);
-    if (D < 8 || D % 8 || D > DP_FWD_MAX_D) REFUSE(SFCVIT_EINVAL, "%s: D=%d (D %% 8 == 0, 8 <= D <= %d)", what, D, DP_FWD_MAX_D);
+    if (D < 8 || D % 8 || D > LN_FWD_MAX_D) REFUSE(SFCVIT_EINVAL, "%s: D=%d (D %% 8 == 0, 8 <= D <= %d)", what, D, LN_FWD_MAX_D);
     if (!aligned16(branch) || !aligned16(x) || !aligned16(gamma) || !aligned16(beta) || !aligned16(s) || !aligned16(y))
         REFUSE(SFCVIT_EINVAL, "%s: branch, x, gamma, beta, s and y must be 16-byte aligned", what);
     if (!(rate >= 0.f && rate < 1.f)) REFUSE(SFCVIT_EINVAL, "%s: rate=%g outside [0, 1)", what, rate);
     p.M = B * N;
     const uint64_t bytes = uint64_t(p.M) * D * 2;
     // a wave stores a row of s before it has read the row's gamma / beta, and y while other waves still read their inputs
-    if (overlap(s, x, bytes) || overlap(s, branch, bytes) || overlap(y, x, bytes) || overlap(y, branch, bytes) || overlap(s, y, bytes))
+    const auto shares = [bytes](const void *a, const void *b) { return overlap(a, bytes, b, bytes); };
+    if (shares(s, x) || shares(s, branch) || shares(y, x) || shares(y, branch) || shares(s, y))
         REFUSE(SFCVIT_EINVAL, "%s: s or y overlaps an input or the other output (no in-place form)", what);
-    p.vpl = D <= 512 ? 1 : D <= 1024 ? 2 : D <= 2048 ? 4 : 8;
-    p.blocks = int(ceil_div(p.M, DP_WAVES));
+    ln_fwd_rows(p.M, D, p.vpl, p.blocks);
     return p;
 }
 
 LnBwdPathPlan ln_bwd_path_plan(const void *dy, const void *x, const float *mean, const float *rstd, const void *gamma,
                                const void *dx_add, const void *dx, const void *dx_drop, float drop_p, const void *dgamma,
-                               const void *dbeta, int B, int rows_per_image, int D, const void *ws, float path_rate) {
+                               const void *dbeta, int B, int rows_per_image, int D, const void *ws, float path_rate,
+                               const RowwiseKnobs &k) {
     LnBwdPathPlan p;
     const char *what = "layernorm_bwd_path";
     if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || !ws) REFUSE(SFCVIT_EINVAL, "%s: null pointer", what);
@@ -46,13 +39,12 @@ LnBwdPathPlan ln_bwd_path_plan(const void *dy, const void *x, const float *mean,
     if (B <= 0 || rows_per_image <= 0) REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d (B, rows_per_image >= 1)", what, B, rows_per_image);
     if (int64_t(B) * rows_per_image > INT_MAX)
         REFUSE(SFCVIT_EINVAL, "%s: B=%d N=%d: B * rows_per_image rows leave int", what, B, rows_per_image);
-    if (D < 8 || D % 8 || D > DP_BWD_MAX_D) REFUSE(SFCVIT_EINVAL, "%s: D=%d (D %% 8 == 0, 8 <= D <= %d)", what, D, DP_BWD_MAX_D);
+    if (D < 8 || D % 8 || D > LN_BWD_MAX_D) REFUSE(SFCVIT_EINVAL, "%s: D=%d (D %% 8 == 0, 8 <= D <= %d)", what, D, LN_BWD_MAX_D);
     if (!aligned16(dy) || !aligned16(x) || !aligned16(gamma) || !aligned16(dx_add) || !aligned16(dx) || !aligned16(dx_drop))
         REFUSE(SFCVIT_EINVAL, "%s: dy, x, gamma, dx_add, dx and dx_drop must be 16-byte aligned", what);
     if (!(drop_p >= 0.f && drop_p < 1.f)) REFUSE(SFCVIT_EINVAL, "%s: dropout p=%g outside [0, 1)", what, drop_p);
     if (!(path_rate >= 0.f && path_rate < 1.f)) REFUSE(SFCVIT_EINVAL, "%s: rate=%g outside [0, 1)", what, path_rate);
-    p.M = B * rows_per_image;
-    return p;
+    return ln_bwd_geometry(B * rows_per_image, D, dx_add != nullptr, k);
 }
 
 }  // namespace sfcvit

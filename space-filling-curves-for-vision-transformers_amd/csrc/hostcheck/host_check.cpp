@@ -3,7 +3,7 @@
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
 //   host part), the error path of common.cpp, the mask validation and block map of attention_masked.cpp (check_mask_blocks),
 //   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv),
-//   token_mix.cpp (check_tokmix), drop_path.cpp (check_drop_path) and model_ema.cpp (check_model_ema), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
+//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), drop_path.cpp (check_drop_path) and model_ema.cpp (check_model_ema), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
 //   and post passes each GEMM / attention shape of the benchmarked models gets).
 // Every buffer is a heap block of EXACTLY the documented size, so that an off-by-one in a generator or in the descriptor
 // writer is a heap-buffer-overflow report instead of silent corruption.
@@ -22,6 +22,7 @@
 #include "../drop_path.h"
 #include "../model_ema.h"
 #include "../pos_embed.h"
+#include "../rowwise.h"
 #include "../token_agg.h"
 #include "../token_mix.h"
 #include "../token_pool.h"
@@ -772,6 +773,7 @@ static void check_tokmix() {
 // (mean, rstd).  The plans read no byte of them; what is pinned is that every accepted geometry stays inside them.
 static void check_drop_path() {
     using namespace sfcvit;
+    const RowwiseKnobs k0;
     const struct { int B, N, D, vpl; } ok[] = {{1, 1, 8, 1}, {2, 1, 8, 1}, {5, 3, 72, 1}, {2, 65, 200, 1}, {3, 7, 520, 2}, {2, 9, 1536, 4},
                                                {2, 3, 2048, 4}, {22, 197, 768, 2}, {8, 577, 1024, 2}, {1, 2, 4096, 8},
                                                {256, 196, 768, 2}, {64, 576, 1024, 2}};
@@ -785,7 +787,7 @@ static void check_drop_path() {
         const AddLnPathPlan p = add_ln_path_plan(ap, xp, gp, bp, sp, yp, mean.get(), rstd.get(), q.B, q.N, q.D, 0.1f);
         CHECK(p.err == SFCVIT_OK, "drop_path fwd %d %d %d refused: %s", q.B, q.N, q.D, p.msg);
         CHECK(p.M == int(rows) && p.vpl == q.vpl && p.vpl * 512 >= q.D, "drop_path fwd %d %d %d: M %d vpl %d", q.B, q.N, q.D, p.M, p.vpl);
-        CHECK(int64_t(p.blocks) * DP_WAVES >= p.M && int64_t(p.blocks - 1) * DP_WAVES < p.M, "drop_path fwd blocks %d for %d rows", p.blocks, p.M);
+        CHECK(int64_t(p.blocks) * ROW_WAVES >= p.M && int64_t(p.blocks - 1) * ROW_WAVES < p.M, "drop_path fwd blocks %d for %d rows", p.blocks, p.M);
         auto fwd = [&](const void *a_, const void *x_, const void *g_, const void *b_, const void *s_, const void *y_, const float *m_,
                        const float *r_, int B, int N, int D, float rate, const char *frag, const char *what) {
             const AddLnPathPlan r = add_ln_path_plan(a_, x_, g_, b_, s_, y_, m_, r_, B, N, D, rate);
@@ -817,15 +819,15 @@ static void check_drop_path() {
         fwd(ap, xp, gp, bp, sp, sp, mp, rp, q.B, q.N, q.D, 0.1f, "overlaps", "y = s");
         if (bytes > 16) fwd(ap, xp, gp, bp, static_cast<char *>(xp) + bytes - 16, yp, mp, rp, q.B, q.N, q.D, 0.1f, "overlaps", "s starts in x's last vector");
 
-        if (q.D > DP_BWD_MAX_D) continue;
+        if (q.D > LN_BWD_MAX_D) continue;
         std::unique_ptr<float[]> ws(new float[3 * q.D]);
-        const LnBwdPathPlan pb = ln_bwd_path_plan(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, ws.get(), 0.5f);
+        const LnBwdPathPlan pb = ln_bwd_path_plan(ap, xp, mp, rp, gp, nullptr, sp, yp, 0.1f, mp, rp, q.B, q.N, q.D, ws.get(), 0.5f, k0);
         CHECK(pb.err == SFCVIT_OK && pb.M == int(rows), "drop_path bwd %d %d %d refused: %s", q.B, q.N, q.D, pb.msg);
-        CHECK(ln_bwd_path_plan(ap, xp, mp, rp, gp, ap, sp, yp, 0.f, mp, rp, q.B, q.N, q.D, ws.get(), 0.f).err == SFCVIT_OK, "drop_path bwd: dx_add, p = 0, rate = 0 refused");
+        CHECK(ln_bwd_path_plan(ap, xp, mp, rp, gp, ap, sp, yp, 0.f, mp, rp, q.B, q.N, q.D, ws.get(), 0.f, k0).err == SFCVIT_OK, "drop_path bwd: dx_add, p = 0, rate = 0 refused");
         auto bwd = [&](const void *dy_, const void *x_, const float *m_, const float *r_, const void *g_, const void *add_, const void *dx_,
                        const void *dd_, float dp, const void *dg_, const void *db_, int B, int N, int D, const void *ws_, float rate,
                        const char *frag, const char *what) {
-            const LnBwdPathPlan r = ln_bwd_path_plan(dy_, x_, m_, r_, g_, add_, dx_, dd_, dp, dg_, db_, B, N, D, ws_, rate);
+            const LnBwdPathPlan r = ln_bwd_path_plan(dy_, x_, m_, r_, g_, add_, dx_, dd_, dp, dg_, db_, B, N, D, ws_, rate, k0);
             CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag), "drop_path bwd %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
         };
         const void *w = ws.get();
@@ -857,6 +859,7 @@ static void check_drop_path() {
 // exactly n bf16 (param, grad) and n fp32 (master, m, v, ema).  The plan reads the two structs and no byte of the buffers.
 static void check_model_ema() {
     using namespace sfcvit;
+    const RowwiseKnobs k0;
     const struct { int64_t n; int grid; } ok[] = {{1, 1}, {3, 1}, {4, 1}, {7, 1}, {2048, 1}, {2049, 2}, {2451, 2}, {5525002, 2048}, {4194304, 2048},
                                                   {4194296, 2048}, {4194305, 2048}, {12582917, 2048}, {86567656, 2048}};
     for (const auto &q : ok) {
@@ -869,18 +872,18 @@ static void check_model_ema() {
         a.master = reinterpret_cast<float *>(al(wb.get())); a.m = reinterpret_cast<float *>(al(mb.get())); a.v = reinterpret_cast<float *>(al(vb.get()));
         a.n = q.n; a.lr = 3e-4f; a.beta1 = 0.9f; a.beta2 = 0.999f; a.eps = 1e-8f; a.grad_scale = 1.f; a.step = 1;
         sfcvit_ema_args e{reinterpret_cast<float *>(al(eb.get())), 0.9999f, 1};
-        const AdamwEmaPlan p = adamw_ema_plan(&a, &e);
+        const AdamwEmaPlan p = adamw_ema_plan(&a, &e, k0);
         CHECK(p.err == SFCVIT_OK, "model_ema n %lld refused: %s", (long long)q.n, p.msg);
         CHECK(p.grid == q.grid && p.grid >= 1 && p.grid <= ADAMW_MAX_BLOCKS, "model_ema n %lld: grid %d, want %d", (long long)q.n, p.grid, q.grid);
         // one lane per 8 parameters covers everything below the cap
         CHECK(p.grid == ADAMW_MAX_BLOCKS || int64_t(p.grid) * ADAMW_THREADS * 8 >= q.n, "model_ema n %lld: grid %d is short", (long long)q.n, p.grid);
         e.decay = 0.f;
-        CHECK(adamw_ema_plan(&a, &e).err == SFCVIT_OK, "model_ema: decay 0 refused");
+        CHECK(adamw_ema_plan(&a, &e, k0).err == SFCVIT_OK, "model_ema: decay 0 refused");
         e.decay = 0.9999f;
         { sfcvit_adamw_args b = a; b.step = 0; float st[8] = {}; b.dev_state = st;
-          CHECK(adamw_ema_plan(&b, &e).err == SFCVIT_OK, "model_ema: step 0 with dev_state refused"); }
+          CHECK(adamw_ema_plan(&b, &e, k0).err == SFCVIT_OK, "model_ema: step 0 with dev_state refused"); }
         auto bad = [&](const sfcvit_adamw_args *a_, const sfcvit_ema_args *e_, const char *frag, const char *what) {
-            const AdamwEmaPlan r = adamw_ema_plan(a_, e_);
+            const AdamwEmaPlan r = adamw_ema_plan(a_, e_, k0);
             CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag) && r.grid == 0, "model_ema %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
         };
         bad(nullptr, &e, "null pointer (a)", "null a");
@@ -913,6 +916,175 @@ static void check_model_ema() {
             sfcvit_adamw_args b = a; b.master = e.ema + (q.n - 1) / 4 * 4; bad(&b, &e, "ema overlaps", "master starts in ema's last vector");
         }
     }
+}
+
+// The plans of rowwise.cpp: which kernel, grid, LDS and workspace the LayerNorm, AdamW and column-sum shapes of the workloads
+// and the edge shapes get, what the four switches change, and one refusal of each kind per entry point.  The plans read no
+// pointer, so fake aligned ones serve.
+static void check_rowwise() {
+    using namespace sfcvit;
+    const RowwiseKnobs k0;
+    CHECK(k0.ln_cols == 1 && k0.ln_blocks == 0 && k0.ln_fwd_two_rows == 1 && k0.adamw_nt == 3, "rowwise: knob defaults");
+    void *a = ptr(0), *b = ptr(1), *c = ptr(2), *d = ptr(3), *odd = static_cast<char *>(ptr(4)) + 8;
+    float *f = static_cast<float *>(ptr(5)), *g = static_cast<float *>(ptr(6));
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    auto refused = [](const PlanStatus &p, const char *frag, const char *what) {
+        CHECK(p.err == SFCVIT_EINVAL && std::strstr(p.msg, frag), "rowwise %s: want '%s', got %d '%s'", what, frag, p.err, p.msg);
+    };
+
+    // LayerNorm backward, and its stochastic-depth twin: the same geometry, the ..._path_kernel names
+    struct LB { int M, D; bool add; int ln_cols, ln_blocks; const char *name, *path_name; int blocks; };
+    const LB lbs[] = {
+        {50176, 768, true, 1, 0, "ln_bwd_cols_kernel<3, true>", "ln_bwd_cols_path_kernel<3, true>", 768},
+        {36864, 1024, false, 1, 0, "ln_bwd_cols_kernel<4, false>", "ln_bwd_cols_path_kernel<4, false>", 512},
+        {50176, 768, false, 0, 0, "ln_bwd_kernel<2, false>", "ln_bwd_path_kernel<2, false>", 512},
+        {50176, 512, true, 1, 0, "ln_bwd_kernel<1, true>", "ln_bwd_path_kernel<1, true>", 512},
+        {50176, 2048, false, 1, 0, "ln_bwd_kernel<4, false>", "ln_bwd_path_kernel<4, false>", 512},
+        {10, 16, false, 1, 0, "ln_bwd_kernel<1, false>", "ln_bwd_path_kernel<1, false>", 3},
+        {50176, 768, false, 1, 100, "ln_bwd_cols_kernel<3, false>", "ln_bwd_cols_path_kernel<3, false>", 100},
+        {50176, 1032, false, 1, 0, "ln_bwd_kernel<4, false>", "ln_bwd_path_kernel<4, false>", 512},
+    };
+    for (const LB &q : lbs) {
+        RowwiseKnobs k;
+        k.ln_cols = q.ln_cols;
+        k.ln_blocks = q.ln_blocks;
+        const LnBwdPlan p = ln_bwd_plan(a, b, f, g, c, q.add ? d : nullptr, ptr(7), ptr(8), 0.1f, ptr(9), ptr(10), q.M, q.D, ptr(11), k);
+        const LnBwdPlan pp = ln_bwd_path_plan(a, b, f, g, c, q.add ? d : nullptr, ptr(7), ptr(8), 0.1f, ptr(9), ptr(10), q.M / 2, 2, q.D,
+                                              ptr(11), 0.5f, k);
+        char name[96], path_name[96];
+        kernel_name(p, false, name, sizeof(name));
+        kernel_name(pp, true, path_name, sizeof(path_name));
+        CHECK(p.err == SFCVIT_OK && pp.err == SFCVIT_OK, "ln_bwd %d %d refused: %s %s", q.M, q.D, p.msg, pp.msg);
+        CHECK(!std::strcmp(name, q.name) && !std::strcmp(path_name, q.path_name), "ln_bwd %d %d: %s / %s", q.M, q.D, name, path_name);
+        CHECK(p.blocks == q.blocks && p.M == q.M && p.D == q.D, "ln_bwd %d %d: %d workgroups, want %d", q.M, q.D, p.blocks, q.blocks);
+        CHECK(p.lds == size_t(4) * 3 * q.D * 4 && p.ws_bytes == int64_t(q.blocks) * 3 * q.D * 4, "ln_bwd %d %d: lds %zu ws %lld", q.M, q.D,
+              p.lds, (long long)p.ws_bytes);
+        CHECK(pp.blocks == p.blocks && pp.lds == p.lds && pp.ws_bytes == p.ws_bytes && pp.M == p.M && pp.cols == p.cols && pp.inst == p.inst,
+              "ln_bwd_path %d %d: geometry differs from ln_bwd's", q.M, q.D);
+        CHECK(ln_bwd_geometry(q.M, q.D, false, k).ws_bytes == p.ws_bytes, "ln_bwd %d %d: the workspace query disagrees", q.M, q.D);
+    }
+    CHECK(ln_bwd_plan(a, b, f, g, c, d, ptr(7), ptr(8), 0.1f, ptr(9), ptr(10), 50176, 768, ptr(11), k0).lds == 36864, "ln_bwd: LDS at D 768");
+    CHECK(ln_bwd_plan(a, b, f, g, c, nullptr, ptr(7), nullptr, nan, ptr(9), ptr(10), 8, 8, ptr(11), k0).err == SFCVIT_OK, "ln_bwd: p unused without dx_drop");
+    refused(ln_bwd_plan(nullptr, b, f, g, c, d, ptr(7), ptr(8), 0.1f, ptr(9), ptr(10), 8, 8, ptr(11), k0), "null", "ln_bwd null dy");
+    refused(ln_bwd_plan(a, b, f, g, c, d, ptr(7), ptr(8), 0.1f, ptr(9), ptr(10), 8, 8, nullptr, k0), "null", "ln_bwd null ws");
+    refused(ln_bwd_plan(a, b, f, g, c, d, ptr(7), ptr(8), 0.1f, ptr(9), ptr(10), 8, 2056, ptr(11), k0), "D=2056", "ln_bwd D 2056");
+    refused(ln_bwd_plan(a, b, f, g, c, d, ptr(7), ptr(8), 0.1f, ptr(9), ptr(10), 0, 8, ptr(11), k0), "M=0", "ln_bwd M 0");
+    refused(ln_bwd_plan(a, b, f, g, c, d, ptr(7), ptr(8), 0.1f, ptr(9), ptr(10), 8, 12, ptr(11), k0), "D=12", "ln_bwd D 12");
+    refused(ln_bwd_plan(a, b, f, g, c, odd, ptr(7), ptr(8), 0.1f, ptr(9), ptr(10), 8, 8, ptr(11), k0), "alignment", "ln_bwd dx_add");
+    refused(ln_bwd_plan(a, b, f, g, c, d, ptr(7), ptr(8), 1.f, ptr(9), ptr(10), 8, 8, ptr(11), k0), "dropout p=1", "ln_bwd p 1");
+    refused(ln_bwd_plan(a, b, f, g, c, d, ptr(7), ptr(8), nan, ptr(9), ptr(10), 8, 8, ptr(11), k0), "dropout p=", "ln_bwd p NaN");
+
+    // LayerNorm forward
+    struct LF { int M, D, two_rows_knob; bool two; int vpl, blocks; };
+    const LF lfs[] = {{4096, 768, 1, true, 3, 512}, {4095, 768, 1, false, 2, 1024}, {4096, 768, 0, false, 2, 1024}, {50176, 1024, 1, true, 4, 6272},
+                      {8192, 4096, 1, false, 8, 2048}, {8192, 512, 1, false, 1, 2048}, {5, 2048, 1, false, 4, 2}, {4097, 1024, 1, true, 4, 513}};
+    for (const LF &q : lfs) {
+        RowwiseKnobs k;
+        k.ln_fwd_two_rows = q.two_rows_knob;
+        const LnFwdPlan p = ln_fwd_plan(a, b, c, d, f, g, q.M, q.D, k);
+        CHECK(p.err == SFCVIT_OK && p.two_rows == q.two && p.vpl == q.vpl && p.blocks == q.blocks, "ln_fwd %d %d: %s two %d vpl %d blocks %d",
+              q.M, q.D, p.msg, int(p.two_rows), p.vpl, p.blocks);
+    }
+    refused(ln_fwd_plan(a, b, c, d, f, g, 8, 4104, k0), "D=4104", "ln_fwd D 4104");
+    refused(ln_fwd_plan(a, b, c, d, f, g, -1, 8, k0), "M=-1", "ln_fwd M -1");
+    refused(ln_fwd_plan(a, b, c, d, nullptr, g, 8, 8, k0), "null", "ln_fwd null mean");
+    refused(ln_fwd_plan(a, odd, c, d, f, g, 8, 8, k0), "alignment", "ln_fwd gamma");
+    {   // add_ln_path_plan takes the one-row form from the same helper
+        int vpl = 0, blocks = 0;
+        ln_fwd_rows(130, 768, vpl, blocks);
+        const AddLnPathPlan p = add_ln_path_plan(a, b, c, d, ptr(7), ptr(8), f, g, 2, 65, 768, 0.1f);
+        CHECK(p.err == SFCVIT_OK && p.vpl == vpl && p.blocks == blocks && vpl == 2 && blocks == 33, "add_ln_path: vpl %d blocks %d (%s)", p.vpl, p.blocks, p.msg);
+    }
+
+    // AdamW, and the same step with the EMA
+    sfcvit_adamw_args aa{};
+    auto far = [](int i) { return reinterpret_cast<float *>(uintptr_t(i + 1) << 36); };       // 64 GiB apart: no buffer reaches the next
+    aa.param = far(0); aa.grad = far(1); aa.master = far(2); aa.m = far(3); aa.v = far(4);
+    aa.lr = 3e-4f; aa.beta1 = 0.9f; aa.beta2 = 0.999f; aa.eps = 1e-8f; aa.grad_scale = 1.f; aa.step = 1;
+    const sfcvit_ema_args ee{far(5), 0.9999f, 1};
+    const int64_t per = 8 * ADAMW_THREADS;
+    const struct { int64_t n; int grid; } grids[] = {{1, 1}, {per - 1, 1}, {per, 1}, {per + 1, 2}, {5 * per - 1, 5}, {5 * per, 5}, {5 * per + 1, 6},
+                                                     {2047 * per, 2047}, {2047 * per + 1, 2048}, {2048 * per, 2048}, {2048 * per + 1, 2048},
+                                                     {int64_t(2049) * 2048, 2048}};
+    for (const auto &q : grids) {
+        aa.n = q.n;
+        const AdamwPlan p = adamw_plan(&aa, k0);
+        CHECK(p.err == SFCVIT_OK && p.grid == q.grid && p.nt == 3, "adamw n %lld: grid %d, want %d (%s)", (long long)q.n, p.grid, q.grid, p.msg);
+        const AdamwEmaPlan pe = adamw_ema_plan(&aa, &ee, k0);
+        CHECK(pe.err == SFCVIT_OK && pe.grid == p.grid && pe.nt == p.nt, "adamw_ema n %lld: grid %d, adamw's %d (%s)", (long long)q.n, pe.grid, p.grid, pe.msg);
+    }
+    aa.n = 4096;
+    const struct { int knob, nt; } nts[] = {{0, 0}, {1, 1}, {2, 2}, {3, 3}, {4, 0}, {7, 3}, {-1, 3}};
+    for (const auto &q : nts) {
+        RowwiseKnobs k;
+        k.adamw_nt = q.knob;
+        CHECK(adamw_plan(&aa, k).nt == q.nt && adamw_ema_plan(&aa, &ee, k).nt == q.nt, "adamw_nt %d: want %d", q.knob, q.nt);
+    }
+    refused(adamw_plan(nullptr, k0), "null", "adamw null a");
+    { sfcvit_adamw_args x = aa; x.m = nullptr; refused(adamw_plan(&x, k0), "null", "adamw null m"); }
+    { sfcvit_adamw_args x = aa; x.n = 0; refused(adamw_plan(&x, k0), "n=0", "adamw n 0"); }
+    { sfcvit_adamw_args x = aa; x.step = 0; refused(adamw_plan(&x, k0), "step=0", "adamw step 0"); float st[8] = {}; x.dev_state = st;
+      CHECK(adamw_plan(&x, k0).err == SFCVIT_OK, "adamw: step 0 with dev_state refused"); }
+    { sfcvit_adamw_args x = aa; x.grad = odd; refused(adamw_plan(&x, k0), "aligned", "adamw grad"); }
+
+    // column sums
+    const struct { int M, N, cb, rb, rpb; } cs[] = {{50176, 768, 3, 251, 200}, {50176, 2304, 9, 112, 448}, {8, 8, 1, 1, 8}};
+    for (const auto &q : cs) {
+        const int64_t ws = int64_t(q.rb) * q.N * 4;
+        const ColsumPlan p = colsum_plan(a, q.M, q.N, q.N, b, c, ws);
+        CHECK(p.err == SFCVIT_OK && p.col_blocks == q.cb && p.row_blocks == q.rb && p.rpb == q.rpb && p.ws_bytes == ws,
+              "colsum %d %d: (%d, %d, %d) ws %lld %s", q.M, q.N, p.col_blocks, p.row_blocks, p.rpb, (long long)p.ws_bytes, p.msg);
+        CHECK(int64_t(p.rpb) * p.row_blocks >= q.M && p.rpb % 8 == 0 && colsum_geometry(q.M, q.N).ws_bytes == ws, "colsum %d %d: cover", q.M, q.N);
+        refused(colsum_plan(a, q.M, q.N, q.N, b, c, ws - 1), "workspace", "colsum workspace one byte short");
+    }
+    refused(colsum_plan(a, 8, 8, 8, b, nullptr, 1 << 20), "workspace", "colsum null workspace");
+    refused(colsum_plan(nullptr, 8, 8, 8, b, c, 1 << 20), "null", "colsum null x");
+    refused(colsum_plan(a, 8, 12, 16, b, c, 1 << 20), "N=12", "colsum N 12");
+    refused(colsum_plan(a, 8, 16, 8, b, c, 1 << 20), "ld=8", "colsum ld < N");
+    refused(colsum_plan(odd, 8, 8, 8, b, c, 1 << 20), "alignment", "colsum x");
+
+    // the entry points whose plan is refusals + a grid
+    { const RowGridPlan p = transpose_plan(a, 768, 2304, 2304, b, 768); CHECK(p.err == SFCVIT_OK && p.grid == 36 && p.grid_y == 12, "transpose grid"); }
+    { const RowGridPlan p = transpose_plan(a, 8, 72, 72, b, 8); CHECK(p.err == SFCVIT_OK && p.grid == 2 && p.grid_y == 1, "transpose 8 x 72 grid"); }
+    refused(transpose_plan(a, 8, 8, 8, nullptr, 8), "null", "transpose null dst");
+    refused(transpose_plan(a, 8, 12, 16, b, 8), "C=12", "transpose C 12");
+    refused(transpose_plan(a, 16, 8, 8, b, 8), "ldd=8", "transpose ldd < R");
+    refused(transpose_plan(odd, 8, 8, 8, b, 8), "alignment", "transpose src");
+    CHECK(transpose_batched_plan(a, b, c, 77).grid == 77, "transpose_batched grid");
+    refused(transpose_batched_plan(a, b, nullptr, 4), "null", "transpose_batched null tiles");
+    refused(transpose_batched_plan(a, b, c, 0), "no tiles", "transpose_batched no tiles");
+    refused(transpose_batched_plan(a, odd, c, 4), "alignment", "transpose_batched dst");
+    CHECK(gelu_plan(false, nullptr, a, b, 8).err == SFCVIT_OK && gelu_plan(true, a, b, c, int64_t(50176) * 3072).err == SFCVIT_OK, "gelu refused");
+    refused(gelu_plan(false, nullptr, a, b, 12), "gelu_fwd: n=12", "gelu_fwd n 12");
+    refused(gelu_plan(false, nullptr, nullptr, b, 8), "gelu_fwd", "gelu_fwd null x");
+    refused(gelu_plan(true, nullptr, a, b, 8), "gelu_bwd", "gelu_bwd null dy");
+    refused(gelu_plan(true, a, b, c, 0), "gelu_bwd: n=0", "gelu_bwd n 0");
+    CHECK(gelu_drop_plan(false, nullptr, a, b, 37, 264, 0.1f).err == SFCVIT_OK && gelu_drop_plan(true, a, b, c, 50176, 3072, 0.f).err == SFCVIT_OK, "gelu_drop refused");
+    refused(gelu_drop_plan(true, nullptr, a, b, 8, 8, 0.1f), "gelu_drop_bwd: null", "gelu_drop_bwd null dy");
+    refused(gelu_drop_plan(false, nullptr, a, nullptr, 8, 8, 0.1f), "gelu_drop_fwd: rows=8", "gelu_drop_fwd null y");
+    refused(gelu_drop_plan(false, nullptr, a, b, 8, 12, 0.1f), "cols=12", "gelu_drop_fwd cols 12");
+    refused(gelu_drop_plan(true, a, b, c, 8, 8, 1.f), "gelu_drop_bwd: dropout p=1", "gelu_drop_bwd p 1");
+    refused(gelu_drop_plan(false, nullptr, a, b, 8, 8, nan), "dropout p=", "gelu_drop_fwd p NaN");
+    CHECK(dropout_mask_plan(a, 5, 7, 0.5f).err == SFCVIT_OK && dropout_mask_plan(a, 300, 5, 0.f).err == SFCVIT_OK, "dropout_mask refused");
+    refused(dropout_mask_plan(nullptr, 5, 7, 0.5f), "bad argument", "dropout_mask null out");
+    refused(dropout_mask_plan(a, 0, 7, 0.5f), "bad argument", "dropout_mask rows 0");
+    refused(dropout_mask_plan(a, 5, 7, 1.f), "bad argument", "dropout_mask p 1");
+    CHECK(soft_ce_plan(a, f, g, 256, 1000, 1024).grid == 64 && soft_ce_plan(a, f, g, 5, 10, 10).grid == 2, "soft_ce grid");
+    refused(soft_ce_plan(a, nullptr, g, 8, 8, 8), "null", "soft_ce null targets");
+    refused(soft_ce_plan(a, f, g, 8, 16, 8), "ld=8", "soft_ce ld < C");
+    static_assert(SFCVIT_SUMSQ_WORKSPACE_BYTES / 4 < ADAMW_MAX_BLOCKS, "the workspace, not the grid cap, bounds the sumsq grid");
+    const struct { int64_t n; int grid; } sq[] = {{1, 1}, {per, 1}, {per + 1, 2}, {1023 * per, 1023}, {1023 * per + 1, 1024}, {1024 * per + 1, 1024},
+                                                  {int64_t(86567656), SFCVIT_SUMSQ_WORKSPACE_BYTES / 4}};
+    for (const auto &q : sq) {
+        const RowGridPlan p = sumsq_plan(a, q.n, f, b);
+        CHECK(p.err == SFCVIT_OK && p.grid == q.grid, "sumsq n %lld: grid %d, want %d (%s)", (long long)q.n, p.grid, q.grid, p.msg);
+    }
+    refused(sumsq_plan(a, 0, f, b), "bad argument", "sumsq n 0");
+    refused(sumsq_plan(a, 8, f, nullptr), "bad argument", "sumsq null workspace");
+    refused(sumsq_plan(odd, 8, f, b), "alignment", "sumsq g");
+    CHECK(step_advance_plan(a).err == SFCVIT_OK && step_advance_plan(a).grid == 1, "step_advance");
+    refused(step_advance_plan(nullptr), "16-byte aligned", "step_advance null state");
+    refused(step_advance_plan(odd), "16-byte aligned", "step_advance state");
 }
 
 int main() {
@@ -987,6 +1159,7 @@ int main() {
     check_token_pool();
     check_dwconv();
     check_tokmix();
+    check_rowwise();
     check_drop_path();
     check_model_ema();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }

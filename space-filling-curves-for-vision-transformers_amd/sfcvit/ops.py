@@ -122,14 +122,14 @@ def _rows2d(t, dtype, name):
     return t
 
 
-def _grad_outs(what, out, shapes, wanted, device, expected):
+def _grad_outs(what, out, shapes, wanted, device, expected, name="out"):
     """The parameter gradients of a backward wrapper, one per entry of `shapes`: fp32, or -- with `out`, one tensor or a
     tuple with an entry per shape, e.g. views of a flat gradient buffer (None entries are allocated) -- bf16 written in
     place.  -> (the tensors, None where not wanted; whether they are bf16: the C calls' grad_bf16 flag)."""
     given = (None,) * len(shapes) if out is None else (out,) if torch.is_tensor(out) else out
     for t, shape in zip(given, shapes):
         if t is not None and (t.dtype != _BF16 or t.numel() != math.prod(shape) or not t.is_contiguous()):
-            raise ValueError(f"{what} out: {expected} expected")
+            raise ValueError(f"{what} {name}: {expected} expected")
     gdt = torch.float32 if out is None else _BF16
     grads = [None if not want else t if t is not None else torch.empty(tuple(shape), device=device, dtype=gdt)
              for t, shape, want in zip(given, shapes, wanted)]
@@ -390,39 +390,45 @@ def layernorm_fwd(x, gamma, beta, eps=1e-5):
     return y, mean, rstd
 
 
+def _layernorm_bwd(path, dy, x, mean, rstd, gamma, dx_add, drop_p, drop_seed, want_colsum, grad_out):
+    """layernorm_bwd (path = None) and layernorm_bwd_path (path = (rows_per_image, path_rate, path_seed)): the buffers, the
+    workspace of the one plan both C calls share, the call -> dx, dgamma, dbeta, dx_drop (None if not written), dcol (None if
+    not wanted)."""
+    what = "layernorm_bwd" if path is None else "layernorm_bwd_path"
+    _need(dy, _BF16, "layernorm dy", 2)
+    _need(x, _BF16, "layernorm x", 2)
+    M, D = x.shape
+    if path is not None and (path[0] <= 0 or M % path[0]):
+        raise ValueError(f"layernorm_bwd_path: {M} rows are not whole images of {path[0]}")
+    dx = torch.empty_like(x)
+    dx_drop = torch.empty_like(x) if path is not None or drop_p > 0 else None
+    (dg, db, dcol), bf16 = _grad_outs(what, grad_out, ((D,), (D,), (D,)), (True, True, want_colsum), x.device,
+                                      "contiguous bf16 [D] tensors", name="out" if path is not None else "grad_out")   # the words each had
+    ws = torch.empty(lib.sfcvit_layernorm_bwd_ws(M, D), device=x.device, dtype=torch.uint8)
+    if dx_add is not None:
+        _need(dx_add, _BF16, "layernorm dx_add", 2)
+    seed_off = _seed_off() if path is not None or drop_p > 0 else None
+    with _Deferring([dg, db] + ([dcol] if dcol is not None else []), [ws]):
+        if path is None:
+            rc = lib.sfcvit_layernorm_bwd_drop(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_add), _p(dx), _p(dx_drop), drop_p,
+                                               drop_seed, seed_off, _p(dg), _p(db), _p(dcol), int(bf16), M, D, _p(ws), _stream())
+        else:
+            rc = lib.sfcvit_layernorm_bwd_path(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_add), _p(dx), _p(dx_drop), drop_p,
+                                               drop_seed, seed_off, _p(dg), _p(db), _p(dcol), int(bf16), M // path[0], path[0], D,
+                                               _p(ws), path[1], path[2], _stream())
+        check(rc, "sfcvit_" + what)
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append(last_rowwise_kernel())
+    return dx, dg, db, dx_drop, dcol
+
+
 def layernorm_bwd(dy, x, mean, rstd, gamma, dx_add=None, drop_p=0.0, drop_seed=0, want_colsum=False, grad_out=None):
     """-> dx, dgamma, dbeta [, dx_drop when drop_p > 0] [, colsum of the outgoing gradient (dx_drop if
     drop_p > 0 else dx) when want_colsum].  dgamma / dbeta / colsum are fp32 [D], or -- with
     grad_out = (dgamma, dbeta, colsum-or-None) bf16 [D] tensors, e.g. views of a flat gradient buffer (None entries
     are allocated) -- written as bf16 in place."""
-    _need(dy, _BF16, "layernorm dy", 2)
-    _need(x, _BF16, "layernorm x", 2)
-    M, D = x.shape
-    dx = torch.empty_like(x)
-    dx_drop = torch.empty_like(x) if drop_p > 0 else None
-    gdt = torch.float32 if grad_out is None else _BF16
-    given = (None, None, None) if grad_out is None else grad_out
-    for t in given:
-        if t is not None and (t.dtype != _BF16 or t.numel() != D or not t.is_contiguous()):
-            raise ValueError("layernorm_bwd grad_out: contiguous bf16 [D] tensors expected")
-    dg = given[0] if given[0] is not None else torch.empty(D, device=x.device, dtype=gdt)
-    db = given[1] if given[1] is not None else torch.empty(D, device=x.device, dtype=gdt)
-    ws = torch.empty(lib.sfcvit_layernorm_bwd_ws(M, D), device=x.device, dtype=torch.uint8)
-    if dx_add is not None:
-        _need(dx_add, _BF16, "layernorm dx_add", 2)
-    dcol = None
-    if want_colsum:
-        dcol = given[2] if given[2] is not None else torch.empty(D, device=x.device, dtype=gdt)
-    with _Deferring([dg, db] + ([dcol] if dcol is not None else []), [ws]):
-        check(lib.sfcvit_layernorm_bwd_drop(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_add), _p(dx), _p(dx_drop),
-                                            drop_p, drop_seed, _seed_off() if drop_p > 0 else None, _p(dg), _p(db), _p(dcol),
-                                            int(gdt == _BF16), M, D, _p(ws),
-                                            _stream()),
-              "sfcvit_layernorm_bwd")
-    if KERNEL_LOG is not None:
-        KERNEL_LOG.append(last_rowwise_kernel())
-    out = (dx, dg, db) + ((dx_drop,) if drop_p > 0 else ()) + ((dcol,) if want_colsum else ())
-    return out
+    dx, dg, db, dx_drop, dcol = _layernorm_bwd(None, dy, x, mean, rstd, gamma, dx_add, drop_p, drop_seed, want_colsum, grad_out)
+    return (dx, dg, db) + ((dx_drop,) if drop_p > 0 else ()) + ((dcol,) if want_colsum else ())
 
 
 # ----------------------------------------------------------------------------
@@ -459,25 +465,8 @@ def layernorm_bwd_path(dy, x, mean, rstd, gamma, rows_per_image, path_rate, path
     gradient entering the sub-layer, is always returned (also at drop_p = 0): image b = row // rows_per_image gets
     dx * dropout mask / ((1 - drop_p)(1 - path_rate)) when the site of `path_seed` kept it, zeros otherwise.  dx (the residual
     path), dgamma and dbeta are those of layernorm_bwd; grad_out as there."""
-    _need(dy, _BF16, "layernorm dy", 2)
-    _need(x, _BF16, "layernorm x", 2)
-    M, D = x.shape
-    if rows_per_image <= 0 or M % rows_per_image:
-        raise ValueError(f"layernorm_bwd_path: {M} rows are not whole images of {rows_per_image}")
-    dx, dx_drop = torch.empty_like(x), torch.empty_like(x)
-    shapes = ((D,), (D,), (D,))
-    (dg, db, dcol), bf16 = _grad_outs("layernorm_bwd_path", grad_out, shapes, (True, True, want_colsum), x.device,
-                                      "contiguous bf16 [D] tensors")
-    ws = torch.empty(lib.sfcvit_layernorm_bwd_ws(M, D), device=x.device, dtype=torch.uint8)
-    if dx_add is not None:
-        _need(dx_add, _BF16, "layernorm dx_add", 2)
-    with _Deferring([dg, db] + ([dcol] if dcol is not None else []), [ws]):
-        check(lib.sfcvit_layernorm_bwd_path(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_add), _p(dx), _p(dx_drop),
-                                            drop_p, drop_seed, _seed_off(), _p(dg), _p(db), _p(dcol), int(bf16),
-                                            M // rows_per_image, rows_per_image, D, _p(ws), path_rate, path_seed, _stream()),
-              "sfcvit_layernorm_bwd_path")
-    if KERNEL_LOG is not None:
-        KERNEL_LOG.append(last_rowwise_kernel())
+    dx, dg, db, dx_drop, dcol = _layernorm_bwd((rows_per_image, path_rate, path_seed), dy, x, mean, rstd, gamma, dx_add, drop_p,
+                                               drop_seed, want_colsum, grad_out)
     return (dx, dg, db, dx_drop) + ((dcol,) if want_colsum else ())
 
 

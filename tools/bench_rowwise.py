@@ -55,3 +55,5 @@ for name, _, nbytes in cases:
     t = sorted(times[name])
     us = t[len(t) // 2]
     print(f"{name:34s} {us:8.1f} us [{t[0]:7.1f} .. {t[-1]:7.1f}]  {nbytes / us / 1e6:6.2f} TB/s")
+ops.layernorm_bwd(dy, x, mean, rstd, w)
+print("ln_bwd kernel:", ops.last_rowwise_kernel(), " SFCVIT_LN_COLS =", os.environ.get("SFCVIT_LN_COLS", "(default)"))
