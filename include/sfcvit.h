@@ -776,6 +776,28 @@ typedef struct sfcvit_ema_args {
 } sfcvit_ema_args;
 int sfcvit_adamw_ema_step(const sfcvit_adamw_args *a, const sfcvit_ema_args *e, void *stream);
 
+/* Gradient accumulation: K micro-batches per optimizer step.  The kernels of a backward pass overwrite the bf16 flat
+ * gradient, so the running sum lives next to the optimizer in one fp32 buffer `acc` [n]: after each of the first K - 1
+ * backward passes sfcvit_grad_accum folds the flat gradient into it (one elementwise pass, 6 bytes per parameter the first
+ * time, 10 after), and after the last one sfcvit_grad_accum_finish forms the averaged gradient in place, with the clip's sum
+ * of squares taken in the same pass (8 bytes per parameter; it replaces sfcvit_sumsq_accum's read of the gradient).
+ * sfcvit_adamw_step / sfcvit_adamw_ema_step then run as they are.  Every operation is a separate, correctly rounded fp32
+ * one; Inf and NaN propagate.
+ *
+ * acc[i] = float(grad[i])            when first != 0  (acc is not read)
+ * acc[i] = acc[i] + float(grad[i])   otherwise: ONE fp32 add per element and call
+ * Refused (SFCVIT_EINVAL, before any HIP call): a null grad or acc, n <= 0, a grad or acc that is not 16-byte aligned, an acc
+ * that shares a byte with grad. */
+int sfcvit_grad_accum(const void *grad /* bf16 [n] */, float *acc /* fp32 [n] */, int64_t n, int first, void *stream);
+
+/* grad[i] = bf16_rne( (acc[i] + float(grad[i])) * scale ): one fp32 add, one fp32 multiply, one rounding, in place.
+ * sumsq != NULL: *sumsq += sum_i float(grad_new[i])^2 -- the squares of the STORED bf16 values (what the AdamW kernel
+ * will read).  Block partials go through `workspace` (SFCVIT_SUMSQ_WORKSPACE_BYTES) and are added in a fixed order.
+ * No atomics: two runs, same bits.  sumsq == NULL: workspace may be NULL.
+ * Refused: what sfcvit_grad_accum refuses, a scale that is not finite or <= 0, a sumsq without a workspace, a sumsq or
+ * workspace that is not 4-byte aligned or shares a byte with grad or acc. */
+int sfcvit_grad_accum_finish(void *grad, const float *acc, int64_t n, float scale, float *sumsq, void *workspace, void *stream);
+
 /* Device-resident step state, 8 words (16-byte aligned): [0] dropout seed offset (uint32), [1] step (int32), [2] learning
  * rate (float, host-written), [3] 1 - beta1^step, [4] 1 / sqrt(1 - beta2^step).  sfcvit_step_advance increments the step
  * and refreshes [0], [3], [4]; run it once per training step before the forward (first node of a captured step).  The

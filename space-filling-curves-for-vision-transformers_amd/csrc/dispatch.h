@@ -24,7 +24,7 @@
 //     SFCVIT_LN_COLS           1        "0": 16-byte-vector LayerNorm backward also at D = 768 (ln_bwd_plan)
 //     SFCVIT_LN_BLOCKS         0 (auto) workgroups of the LayerNorm backward (ln_bwd_plan)
 //     SFCVIT_LN_FWD_TWO_ROWS   1        "0": one row per wave in the LayerNorm forward (ln_fwd_plan)
-//     SFCVIT_ADAMW_NT          3        nontemporal loads (1) / stores (2) of the optimizer state (adamw_plan)
+//     SFCVIT_ADAMW_NT          3        nontemporal loads (1) / stores (2) of the optimizer state (adamw_plan, grad_accum_plan)
 //     SFCVIT_GATHER_U          1        images per wave of the tile gather, 1 or 2 (patch_embed.hip)
 //     SFCVIT_GATHER_NT         3        nontemporal loads (1) / stores (2) of the tile gather (patch_embed.hip)
 #pragma once

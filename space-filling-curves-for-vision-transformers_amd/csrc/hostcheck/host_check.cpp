@@ -3,7 +3,7 @@
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
 //   host part), the error path of common.cpp, the mask validation and block map of attention_masked.cpp (check_mask_blocks),
 //   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv),
-//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), drop_path.cpp (check_drop_path) and model_ema.cpp (check_model_ema), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
+//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), drop_path.cpp (check_drop_path), model_ema.cpp (check_model_ema) and grad_accum.cpp (check_grad_accum), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
 //   and post passes each GEMM / attention shape of the benchmarked models gets).
 // Every buffer is a heap block of EXACTLY the documented size, so that an off-by-one in a generator or in the descriptor
 // writer is a heap-buffer-overflow report instead of silent corruption.
@@ -20,6 +20,7 @@
 #include "../../../include/sfcvit.h"
 #include "../dispatch.h"
 #include "../drop_path.h"
+#include "../grad_accum.h"
 #include "../model_ema.h"
 #include "../pos_embed.h"
 #include "../rowwise.h"
@@ -918,6 +919,74 @@ static void check_model_ema() {
     }
 }
 
+// grad_accum_plan / grad_accum_finish_plan (grad_accum.cpp): the grids at the sizes of the tests and the workloads -- adamw_plan's,
+// and with a sum of squares sumsq_plan's -- and every refusal, with heap buffers of exactly n bf16 (grad) and n fp32 (acc), one
+// float (sumsq) and SFCVIT_SUMSQ_WORKSPACE_BYTES (workspace).  The plans read no byte of any buffer.
+static void check_grad_accum() {
+    using namespace sfcvit;
+    const RowwiseKnobs k0;
+    const int max_parts = SFCVIT_SUMSQ_WORKSPACE_BYTES / 4;
+    const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+    const struct { int64_t n; int grid; } ok[] = {{1, 1}, {3, 1}, {4, 1}, {7, 1}, {2048, 1}, {2049, 2}, {2451, 2}, {5525002, 2048}, {4194304, 2048},
+                                                  {2097152, 1024}, {2097153, 1025}, {12582917, 2048}, {86567656, 2048}};
+    for (const auto &q : ok) {
+        const size_t n = size_t(q.n);
+        std::unique_ptr<char[]> gb(new char[n * 2 + 16]), ab(new char[n * 4 + 16]), sb(new char[4 + 16]), wb(new char[SFCVIT_SUMSQ_WORKSPACE_BYTES + 16]);
+        auto al = [](char *p) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(p) + 15) & ~uintptr_t(15)); };
+        char *g = al(gb.get()), *w = al(wb.get());
+        float *acc = reinterpret_cast<float *>(al(ab.get())), *sq = reinterpret_cast<float *>(al(sb.get()));
+        sfcvit_adamw_args aa{};
+        aa.param = g; aa.grad = g; aa.master = acc; aa.m = acc; aa.v = acc; aa.n = q.n; aa.step = 1;
+        const int adamw_grid = adamw_plan(&aa, k0).grid;
+        for (int first = 0; first < 2; first++) {
+            const GradAccumPlan p = grad_accum_plan(g, acc, q.n, k0);
+            CHECK(p.err == SFCVIT_OK && p.grid == q.grid && p.grid == adamw_grid && p.nt == 3, "grad_accum n %lld: grid %d, want %d (%s)", (long long)q.n, p.grid, q.grid, p.msg);
+        }
+        const GradAccumPlan f0 = grad_accum_finish_plan(g, acc, q.n, 0.25f, nullptr, nullptr, k0);
+        CHECK(f0.err == SFCVIT_OK && f0.grid == q.grid, "grad_accum_finish n %lld: grid %d, want %d (%s)", (long long)q.n, f0.grid, q.grid, f0.msg);
+        CHECK(grad_accum_finish_plan(g, acc, q.n, 0.25f, nullptr, w, k0).err == SFCVIT_OK, "grad_accum_finish: workspace without sumsq refused");
+        const GradAccumPlan f1 = grad_accum_finish_plan(g, acc, q.n, 0.25f, sq, w, k0);
+        const int want = q.grid > max_parts ? max_parts : q.grid;
+        CHECK(f1.err == SFCVIT_OK && f1.grid == want && f1.grid == sumsq_plan(g, q.n, sq, w).grid && f1.nt == 3,
+              "grad_accum_finish + sumsq n %lld: grid %d, want %d (%s)", (long long)q.n, f1.grid, want, f1.msg);
+        CHECK(int64_t(f1.grid) * 4 <= SFCVIT_SUMSQ_WORKSPACE_BYTES, "grad_accum_finish n %lld: %d partials leave the workspace", (long long)q.n, f1.grid);
+        { RowwiseKnobs k; k.adamw_nt = 0; CHECK(grad_accum_plan(g, acc, q.n, k).nt == 0 && grad_accum_finish_plan(g, acc, q.n, 1.f, sq, w, k).nt == 0, "grad_accum: adamw_nt 0"); }
+        auto bad = [&](const GradAccumPlan &r, const char *frag, const char *what) {
+            CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag) && r.grid == 0, "grad_accum %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
+        };
+        // what both entry points refuse
+        bad(grad_accum_plan(nullptr, acc, q.n, k0), "(grad)", "null grad");
+        bad(grad_accum_plan(g, nullptr, q.n, k0), "(acc)", "null acc");
+        bad(grad_accum_plan(g, acc, 0, k0), "n=0", "n = 0");
+        bad(grad_accum_plan(g, acc, -5, k0), "n=-5", "n < 0");
+        bad(grad_accum_plan(g, acc, INT64_MAX, k0), "address space", "n = 2^63 - 1");
+        bad(grad_accum_plan(g + 2, acc, q.n, k0), "grad must be 16-byte aligned", "misaligned grad");
+        bad(grad_accum_plan(g, acc + 1, q.n, k0), "acc must be 16-byte aligned", "misaligned acc");
+        bad(grad_accum_plan(g, reinterpret_cast<float *>(g), q.n, k0), "acc overlaps grad", "acc = grad");
+        bad(grad_accum_finish_plan(nullptr, acc, q.n, 0.5f, sq, w, k0), "grad_accum_finish: null pointer (grad)", "finish: null grad");
+        bad(grad_accum_finish_plan(g, nullptr, q.n, 0.5f, sq, w, k0), "(acc)", "finish: null acc");
+        bad(grad_accum_finish_plan(g, acc, 0, 0.5f, sq, w, k0), "n=0", "finish: n = 0");
+        bad(grad_accum_finish_plan(g + 8, acc, q.n, 0.5f, sq, w, k0), "grad must be 16-byte aligned", "finish: misaligned grad");
+        bad(grad_accum_finish_plan(g, acc + 2, q.n, 0.5f, sq, w, k0), "acc must be 16-byte aligned", "finish: misaligned acc");
+        bad(grad_accum_finish_plan(g, reinterpret_cast<float *>(g), q.n, 0.5f, sq, w, k0), "acc overlaps grad", "finish: acc = grad");
+        if (q.n >= 16) {      // acc starts in grad's last vector / grad starts in acc's last vector
+            bad(grad_accum_plan(g, reinterpret_cast<float *>(g + (q.n * 2 - 1) / 16 * 16), q.n, k0), "acc overlaps grad", "acc starts in grad's last vector");
+            bad(grad_accum_plan(reinterpret_cast<char *>(acc) + (q.n * 4 - 1) / 16 * 16, acc, q.n, k0), "acc overlaps grad", "grad starts in acc's last vector");
+        }
+        // what the finish adds
+        for (float sc : {0.f, -0.5f, nan, inf, -inf}) bad(grad_accum_finish_plan(g, acc, q.n, sc, nullptr, nullptr, k0), "scale=", "scale not finite or <= 0");
+        bad(grad_accum_finish_plan(g, acc, q.n, 0.5f, sq, nullptr, k0), "sumsq without workspace", "sumsq without workspace");
+        bad(grad_accum_finish_plan(g, acc, q.n, 0.5f, reinterpret_cast<float *>(reinterpret_cast<char *>(sq) + 2), w, k0), "sumsq must be 4-byte aligned", "misaligned sumsq");
+        bad(grad_accum_finish_plan(g, acc, q.n, 0.5f, sq, w + 1, k0), "workspace must be 4-byte aligned", "misaligned workspace");
+        bad(grad_accum_finish_plan(g, acc, q.n, 0.5f, acc, w, k0), "sumsq overlaps acc", "sumsq = acc");
+        bad(grad_accum_finish_plan(g, acc, q.n, 0.5f, reinterpret_cast<float *>(g), w, k0), "sumsq overlaps grad", "sumsq = grad");
+        bad(grad_accum_finish_plan(g, acc, q.n, 0.5f, acc + (q.n - 1), w, k0), "sumsq overlaps acc", "sumsq = acc's last element");
+        bad(grad_accum_finish_plan(g, acc, q.n, 0.5f, sq, acc, k0), "workspace overlaps", "workspace = acc");     // 4 KiB from a small acc may reach a neighbouring block first
+        bad(grad_accum_finish_plan(g, acc, q.n, 0.5f, sq, g, k0), "workspace overlaps grad", "workspace = grad");
+        bad(grad_accum_finish_plan(g, acc, q.n, 0.5f, sq, g - (SFCVIT_SUMSQ_WORKSPACE_BYTES - 4), k0), "workspace overlaps grad", "workspace ends in grad's first word");
+    }
+}
+
 // The plans of rowwise.cpp: which kernel, grid, LDS and workspace the LayerNorm, AdamW and column-sum shapes of the workloads
 // and the edge shapes get, what the four switches change, and one refusal of each kind per entry point.  The plans read no
 // pointer, so fake aligned ones serve.
@@ -1162,6 +1231,7 @@ int main() {
     check_rowwise();
     check_drop_path();
     check_model_ema();
+    check_grad_accum();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }
     std::printf("host_check ok\n");
     return 0;

@@ -1,7 +1,9 @@
 // The optimizer step for gfx950: sum of squares (gradient norm), the fused clip + AdamW step, the same with the model EMA in
-// it, and the device-resident step state.  HBM-bound: every global access is a 16-byte vector (8 bf16 or 4 fp32).  The
-// launchers run what the plans of rowwise.h / model_ema.h say.
+// it, gradient accumulation, and the device-resident step state.  HBM-bound: every global access is a 16-byte vector (8 bf16
+// or 4 fp32; the four-per-lane kernels pair an 8-byte bf16 access with it).  The launchers run what the plans of rowwise.h /
+// model_ema.h / grad_accum.h say.
 #include "common_host.h"
+#include "grad_accum.h"
 #include "model_ema.h"
 #include "rowwise_device.h"
 
@@ -239,6 +241,117 @@ __global__ __launch_bounds__(THREADS) void adamw_ema_kernel(sfcvit_adamw_args a,
 }
 
 // ---------------------------------------------------------------------------
+// Gradient accumulation (grad_accum.h): fp32 running sum of the micro-batch gradients, and on the last micro-batch the
+// average formed in place with the clip's sum of squares in the same pass.  adamw_kernel's layout: four parameters per lane
+// and group (an 8-byte bf16 access, a 16-byte fp32 one), two groups in flight, a remainder group and the under-4 tail.
+// Kernels of their own: sumsq_kernel and adamw_kernel keep their text (profiles/grad_accum/isa_identity.txt).
+// ---------------------------------------------------------------------------
+// acc = float(g) (FIRST: acc is not read) or acc + float(g): one fp32 add per element.  6 / 10 bytes per parameter, every
+// byte touched once: NT as adamw_kernel (bit 0 loads, bit 1 the store of acc, which nothing reads before the next pass).
+template <bool FIRST, int NT>
+__global__ __launch_bounds__(THREADS) void grad_accum_kernel(const uint16_t *__restrict__ g, float *__restrict__ acc, int64_t n) {
+    const int64_t nq = n >> 2, step = int64_t(gridDim.x) * THREADS;
+    auto load = [&](int64_t i, u32x2 &gq, f32x4 &av) __attribute__((always_inline)) {
+        if (NT & 1) {
+            gq = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(g) + i);
+            if (!FIRST) av = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(acc) + i);
+        } else {
+            gq = reinterpret_cast<const u32x2 *>(g)[i];
+            if (!FIRST) av = reinterpret_cast<const f32x4 *>(acc)[i];
+        }
+    };
+    auto update = [&](int64_t i, const u32x2 &gq, const f32x4 &av) __attribute__((always_inline)) {
+        const float gr[4] = {bf2f(uint16_t(gq[0])), bf2f(uint16_t(gq[0] >> 16)), bf2f(uint16_t(gq[1])), bf2f(uint16_t(gq[1] >> 16))};
+        f32x4 r;
+#pragma unroll
+        for (int j = 0; j < 4; j++) r[j] = FIRST ? gr[j] : av[j] + gr[j];
+        if (NT & 2) __builtin_nontemporal_store(r, reinterpret_cast<f32x4 *>(acc) + i);
+        else reinterpret_cast<f32x4 *>(acc)[i] = r;
+    };
+    int64_t i = blockIdx.x * int64_t(THREADS) + threadIdx.x;
+    for (; i + step < nq; i += 2 * step) {
+        u32x2 g0, g1;
+        f32x4 a0 = {}, a1 = {};
+        load(i, g0, a0);
+        load(i + step, g1, a1);
+        update(i, g0, a0);
+        update(i + step, g1, a1);
+    }
+    if (i < nq) {
+        u32x2 g0;
+        f32x4 a0 = {};
+        load(i, g0, a0);
+        update(i, g0, a0);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < int(n & 3)) {
+        const int64_t t = (nq << 2) + threadIdx.x;
+        acc[t] = FIRST ? bf2f(g[t]) : acc[t] + bf2f(g[t]);
+    }
+}
+
+// g = bf16((acc + float(g)) * scale) in place: one add, one multiply, one rounding (an add feeding a multiply cannot contract).
+// SUMSQ: part[block] = sum of the squares of the STORED bf16 values, the per-workgroup partials of sumsq_kernel, which
+// sumsq_reduce_kernel adds into *sumsq in a fixed order.  8 bytes per parameter: acc is read once (NT bit 0); g is stored
+// plainly, the AdamW kernel reads it next.
+template <bool SUMSQ, int NT>
+__global__ __launch_bounds__(THREADS) void grad_accum_finish_kernel(uint16_t *__restrict__ g, const float *__restrict__ acc, int64_t n,
+                                                                    float scale, float *__restrict__ part) {
+    __shared__ float red[WAVES];
+    float s = 0.f;
+    const int64_t nq = n >> 2, step = int64_t(gridDim.x) * THREADS;
+    auto load = [&](int64_t i, u32x2 &gq, f32x4 &av) __attribute__((always_inline)) {
+        gq = reinterpret_cast<const u32x2 *>(g)[i];
+        if (NT & 1) av = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(acc) + i);
+        else av = reinterpret_cast<const f32x4 *>(acc)[i];
+    };
+    auto update = [&](int64_t i, const u32x2 &gq, const f32x4 &av) __attribute__((always_inline)) {
+        const float gr[4] = {bf2f(uint16_t(gq[0])), bf2f(uint16_t(gq[0] >> 16)), bf2f(uint16_t(gq[1])), bf2f(uint16_t(gq[1] >> 16))};
+        float r[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) r[j] = (av[j] + gr[j]) * scale;
+        const u32x2 o = {pack2bf(r[0], r[1]), pack2bf(r[2], r[3])};
+        reinterpret_cast<u32x2 *>(g)[i] = o;
+        if (SUMSQ) {
+            const float q[4] = {bf2f(uint16_t(o[0])), bf2f(uint16_t(o[0] >> 16)), bf2f(uint16_t(o[1])), bf2f(uint16_t(o[1] >> 16))};
+#pragma unroll
+            for (int j = 0; j < 4; j++) s += q[j] * q[j];
+        }
+    };
+    int64_t i = blockIdx.x * int64_t(THREADS) + threadIdx.x;
+    for (; i + step < nq; i += 2 * step) {
+        u32x2 g0, g1;
+        f32x4 a0, a1;
+        load(i, g0, a0);
+        load(i + step, g1, a1);
+        update(i, g0, a0);
+        update(i + step, g1, a1);
+    }
+    if (i < nq) {
+        u32x2 g0;
+        f32x4 a0;
+        load(i, g0, a0);
+        update(i, g0, a0);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < int(n & 3)) {
+        const int64_t t = (nq << 2) + threadIdx.x;
+        const uint16_t o = f2bf((acc[t] + bf2f(g[t])) * scale);
+        g[t] = o;
+        if (SUMSQ) s += bf2f(o) * bf2f(o);
+    }
+    if (SUMSQ) {
+        s = wave_sum(s);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float t = 0.f;
+#pragma unroll
+            for (int w = 0; w < WAVES; w++) t += red[w];
+            part[blockIdx.x] = t;                          // partial[block]
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Device-resident step state: [0] dropout seed offset (uint32)  [1] step count (int32)  [2] learning rate (float,
 // written by the host, read by adamw)  [3] 1 - beta1^step  [4] 1 / sqrt(1 - beta2^step).  One thread advances it once
 // per training step -- as the first node of a captured step graph, so that every replay draws new dropout masks and
@@ -295,6 +408,38 @@ extern "C" int sfcvit_adamw_ema_step(const sfcvit_adamw_args *a, const sfcvit_em
     const AdamwEmaPlan p = adamw_ema_plan(a, e, read_rowwise_knobs());
     if (p.err) return fail(p.err, "%s", p.msg);
     return launch_adamw(p, a, e, stream);
+}
+
+extern "C" int sfcvit_grad_accum(const void *grad, float *acc, int64_t n, int first, void *stream) {
+    const GradAccumPlan p = grad_accum_plan(grad, acc, n, read_rowwise_knobs());
+    if (p.err) return fail(p.err, "%s", p.msg);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint16_t *g = static_cast<const uint16_t *>(grad);
+#define ACCUM(NT) do { \
+        if (first) hipLaunchKernelGGL((grad_accum_kernel<true, NT>), dim3(p.grid), dim3(THREADS), 0, s, g, acc, n); \
+        else hipLaunchKernelGGL((grad_accum_kernel<false, NT>), dim3(p.grid), dim3(THREADS), 0, s, g, acc, n); } while (0)
+    if (p.nt == 3) ACCUM(3); else if (p.nt == 2) ACCUM(2); else if (p.nt == 1) ACCUM(1); else ACCUM(0);
+#undef ACCUM
+    return check_launch("grad_accum");
+}
+
+extern "C" int sfcvit_grad_accum_finish(void *grad, const float *acc, int64_t n, float scale, float *sumsq, void *workspace, void *stream) {
+    const GradAccumPlan p = grad_accum_finish_plan(grad, acc, n, scale, sumsq, workspace, read_rowwise_knobs());
+    if (p.err) return fail(p.err, "%s", p.msg);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint16_t *g = static_cast<uint16_t *>(grad);
+    float *part = static_cast<float *>(workspace);
+    const bool nt = p.nt & 1;                              // the one stream of this kernel that is read once: acc
+    if (!sumsq) {
+        if (nt) hipLaunchKernelGGL((grad_accum_finish_kernel<false, 1>), dim3(p.grid), dim3(THREADS), 0, s, g, acc, n, scale, nullptr);
+        else hipLaunchKernelGGL((grad_accum_finish_kernel<false, 0>), dim3(p.grid), dim3(THREADS), 0, s, g, acc, n, scale, nullptr);
+        return check_launch("grad_accum_finish");
+    }
+    if (nt) hipLaunchKernelGGL((grad_accum_finish_kernel<true, 1>), dim3(p.grid), dim3(THREADS), 0, s, g, acc, n, scale, part);
+    else hipLaunchKernelGGL((grad_accum_finish_kernel<true, 0>), dim3(p.grid), dim3(THREADS), 0, s, g, acc, n, scale, part);
+    if (int rc = check_launch("grad_accum_finish")) return rc;
+    hipLaunchKernelGGL(sumsq_reduce_kernel, dim3(1), dim3(64), 0, s, part, p.grid, sumsq);
+    return check_launch("grad_accum_finish reduce");
 }
 
 extern "C" int sfcvit_step_advance(void *state, float beta1, float beta2, uint32_t seed_base, void *stream) {

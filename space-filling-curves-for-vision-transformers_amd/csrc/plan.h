@@ -1,5 +1,5 @@
 // The host scaffold every plan file shares (dispatch.cpp, attention_probe.cpp, token_agg.cpp, token_mix.cpp, pos_embed.cpp,
-// token_pool.cpp, rowwise.cpp, drop_path.cpp, model_ema.cpp): the status a plan carries, how it refuses, three small helpers and the "which kernel ran last" note.
+// token_pool.cpp, rowwise.cpp, drop_path.cpp, model_ema.cpp, grad_accum.cpp): the status a plan carries, how it refuses, three small helpers and the "which kernel ran last" note.
 // Plain host C++ with no HIP include; refuse, KernelNote::set and KernelNote::read are defined in common.cpp.
 #pragma once
 #include <cstdint>

@@ -10,13 +10,13 @@ namespace sfcvit {
 
 namespace {
 bool rate_ok(float p) { return p >= 0.f && p < 1.f; }      // false for NaN
+}  // namespace
 
 // Workgroups of the optimizer's grid-stride kernels over n >= 1 elements: one lane per 8, 1 .. ADAMW_MAX_BLOCKS (model_ema.h).
 int optim_grid(int64_t n) {
     const int64_t b = ceil_div((n - 1) / 8 + 1, ADAMW_THREADS);            // (n - 1) / 8 + 1: ceil(n / 8) without n + 7
     return int(b > ADAMW_MAX_BLOCKS ? ADAMW_MAX_BLOCKS : b);
 }
-}  // namespace
 
 // ---- LayerNorm ----
 void ln_fwd_rows(int M, int D, int &vpl, int &blocks) {

@@ -58,6 +58,7 @@ struct AdamwPlan : PlanStatus {
     int nt = 0;                             // adamw[_ema]_kernel<nt>
 };
 AdamwPlan adamw_plan(const sfcvit_adamw_args *a, const RowwiseKnobs &k, const char *what = "adamw");
+int optim_grid(int64_t n);                  // that grid for n >= 1 elements; sumsq_plan and grad_accum.cpp cap it further
 
 // ---- column sums ----
 struct ColsumPlan : PlanStatus {

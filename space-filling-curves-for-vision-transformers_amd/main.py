@@ -136,6 +136,11 @@ def build_parser():
                          "averaged in fp32 inside the AdamW kernel, evaluated after every epoch next to the raw weights (one "
                          "extra 'EMA Test Loss / EMA Test Acc' line) and checkpointed as model_ema_state_dict / ema_test_acc; "
                          "--resume continues the average.  Works with --graph, --device-mix and --device-augment")
+    ap.add_argument("--accum-steps", type=int, default=1, metavar="K",
+                    help="gradient accumulation: K consecutive batches of --batch-size form one optimizer step (effective batch "
+                         "K x --batch-size; fp32 running sum, the average formed inside the clip pass); the scheduler, the EMA "
+                         "and the clip advance once per optimizer step.  Works with --device-mix, --device-augment and data "
+                         "parallelism (one exchange per optimizer step); not with --graph")
     ap.add_argument("--model-ema-warmup", action="store_true",
                     help="with --model-ema: the decay of step t is min(DECAY, (1 + t) / (10 + t)), so that the average follows "
                          "the weights closely in the first steps")
@@ -160,8 +165,20 @@ def build_model(a, patch_embed, attn_mask=None):
                                pos_embed_std=a.pos_embed_std, pool=a.pool, drop_path_rate=a.drop_path)
 
 
+def parse_args(argv=None):
+    """The parsed arguments, with the combinations refused that no later code could honour."""
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.accum_steps < 1:
+        ap.error(f"--accum-steps {a.accum_steps}: a positive number of batches per optimizer step expected")
+    if a.graph and a.accum_steps > 1:
+        ap.error("--graph cannot be combined with --accum-steps > 1: a captured step does not accumulate (graphs serve "
+                 "launch-bound small models, accumulation serves models too large for the batch)")
+    return a
+
+
 def main():
-    a = build_parser().parse_args()
+    a = parse_args()
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     torch.cuda.set_device(local)
@@ -229,7 +246,11 @@ def main():
     optimizer = FusedAdamW(model.parameters(), lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=1.0,
                            ema_decay=a.model_ema, ema_warmup=a.model_ema_warmup)
     reducer = GradReducer(optimizer, overlap=not a.graph) if world > 1 else None    # --graph: collectives between two graphs
-    scheduler = WarmupCosine(optimizer, a.warmup_epochs * len(train_loader), a.epochs * len(train_loader))
+    steps_per_epoch = -(-len(train_loader) // a.accum_steps)        # optimizer steps: the last group of an epoch may be short
+    scheduler = WarmupCosine(optimizer, a.warmup_epochs * steps_per_epoch, a.epochs * steps_per_epoch)
+    if a.accum_steps > 1 and rank == 0:
+        print(f"gradient accumulation: {a.accum_steps} x {a.batch_size} = effective batch {a.accum_steps * a.batch_size}, "
+              f"{steps_per_epoch} optimizer steps per epoch")
     start_epoch, best = 0, 0.0
     if a.resume:
         ck = torch.load(a.resume, map_location=device, weights_only=True)
@@ -244,7 +265,7 @@ def main():
             start_epoch, best = ck["epoch"] + 1, ck.get("test_acc", 0.0)
             ssd = ck.get("scheduler_state_dict") or {}
             # ours: {"n": steps taken}; the reference's LambdaLR (transformers' cosine schedule): {"last_epoch": steps taken}
-            scheduler.n = ssd.get("n", ssd.get("last_epoch", start_epoch * len(train_loader)))
+            scheduler.n = ssd.get("n", ssd.get("last_epoch", start_epoch * steps_per_epoch))
             optimizer.lr = scheduler.lr_at(scheduler.n)
             if augment is not None and ck.get("augment_state_dict"):
                 augment.load_state_dict(ck["augment_state_dict"])       # the draw stream goes on where it stopped
@@ -282,7 +303,7 @@ def main():
     for epoch in range(start_epoch, a.epochs):
         tr_loss, tr_acc = train_with_mixup_or_cutmix(model, train_loader, train_criterion, optimizer, scheduler,
                                                      device, reducer=reducer, graphed=graphed, device_mix=a.device_mix,
-                                                     augment=augment)
+                                                     augment=augment, accum_steps=a.accum_steps)
         te_loss, te_acc = evaluate(model, test_loader, test_criterion, device, transform=test_transform)
         ema_loss = ema_acc = 0.0
         if a.model_ema is not None:

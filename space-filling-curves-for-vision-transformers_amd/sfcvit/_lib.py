@@ -189,6 +189,8 @@ SIGNATURES = {
     "sfcvit_sumsq_accum": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "sfcvit_adamw_step": (c_int, [ctypes.POINTER(AdamWArgs), c_void_p]),
     "sfcvit_adamw_ema_step": (c_int, [ctypes.POINTER(AdamWArgs), ctypes.POINTER(EmaArgs), c_void_p]),
+    "sfcvit_grad_accum": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "sfcvit_grad_accum_finish": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -1338,3 +1338,30 @@ def adamw_ema_step(param, master, grad, m, v, sumsq, ema, ema_decay, ema_warmup=
     e = _lib.EmaArgs()
     e.ema, e.decay, e.warmup = ema.data_ptr(), ema_decay, int(bool(ema_warmup))
     check(lib.sfcvit_adamw_ema_step(ctypes.byref(a), ctypes.byref(e), _stream()), "sfcvit_adamw_ema_step")
+
+
+def _accum_pair(what, grad, acc):
+    _need(grad, _BF16, f"{what} grad", 1)
+    _need(acc, torch.float32, f"{what} acc", 1)
+    if acc.numel() != grad.numel():
+        raise ValueError(f"{what}: acc has {acc.numel()} elements, grad {grad.numel()}")
+
+
+def grad_accum(grad, acc, first):
+    """acc = float(grad) (`first`: acc is not read) or acc + float(grad), one fp32 add per element: a micro-batch's bf16 flat
+    gradient folded into the fp32 running sum (sfcvit_grad_accum)."""
+    _accum_pair("grad_accum", grad, acc)
+    check(lib.sfcvit_grad_accum(_p(grad), _p(acc), grad.numel(), int(bool(first)), _stream()), "sfcvit_grad_accum")
+
+
+def grad_accum_finish(grad, acc, scale, sumsq=None):
+    """grad = bf16((acc + float(grad)) * scale) in place: the last micro-batch joins the sum and the average is formed in one
+    pass.  sumsq (fp32 [1], device): the sum of the squares of the stored values is ADDED to it in the same pass, in a fixed
+    order (sfcvit_grad_accum_finish) -- what sumsq_accum(grad, sumsq) would give afterwards, without its read of grad."""
+    _accum_pair("grad_accum_finish", grad, acc)
+    ws = None
+    if sumsq is not None:
+        _need(sumsq, torch.float32, "grad_accum_finish sumsq")
+        ws = torch.empty(4096, device=grad.device, dtype=torch.uint8)    # SFCVIT_SUMSQ_WORKSPACE_BYTES
+    check(lib.sfcvit_grad_accum_finish(_p(grad), _p(acc), grad.numel(), float(scale), _p(sumsq), _p(ws), _stream()),
+          "sfcvit_grad_accum_finish")

@@ -234,10 +234,20 @@ class GradReducer:
                 faulthandler.dump_traceback(file=sys.stderr, all_threads=True)
                 os._exit(4)
 
-    def finish(self):
+    def finish(self, deferred=False):
         """Block the compute stream on every outstanding collective.  On the first step (flat
         layout not built yet) the gradients are still separate tensors: build, reduce once,
-        install the hooks."""
+        install the hooks.
+
+        deferred=True: the exchange of a step that accumulated micro-batches -- ONE per optimizer step.  No begin_step() in
+        that step (the hooks of every backward pass are then no-ops); after the last backward the caller runs
+        optimizer.fold() and then this, which takes overlap=False's path whatever the reducer was built with: adopt_all,
+        launch every bucket, wait.  By linearity the result is the sum over the ranks of their averaged gradients;
+        grad_scale = 1 / world stays in the optimizer kernel.  The price is the overlap of the last micro-batch's collectives
+        with its backward pass."""
+        if deferred and self._pending is not None:
+            raise RuntimeError("GradReducer.finish(deferred=True) after begin_step(): the hooks of this step's backward passes "
+                               "have already launched buckets; a step that accumulates calls neither begin_step() nor them")
         if self.buckets is None:
             if self.opt.flat_grad is None:
                 self.opt._build()
@@ -247,7 +257,7 @@ class GradReducer:
             if self.world > 1:
                 for b in range(len(self.buckets)):
                     self._launch(b)
-        elif not self.overlap:
+        elif not self.overlap or deferred:
             self.opt.adopt_all()                 # gradients produced outside the slots move into the flat buffer first
             for b in range(len(self.buckets)):
                 self._launch(b)

@@ -4,12 +4,17 @@ optimizer + scheduler step per batch; evaluate = eval-mode forward + CE + accura
 Differences that do not change the math: no torch.autocast (the modules compute in bf16 with fp32
 accumulation themselves), running loss / accuracy stay on the device and are read once per epoch
 (the reference calls .item() twice per step, train.py:170-172), and FusedAdamW.step() does the
-clip_grad_norm_(1.0) inside the optimizer kernel (train.py:165-166)."""
+clip_grad_norm_(1.0) inside the optimizer kernel (train.py:165-166).
+
+accum_steps=K (every training loop): K consecutive loader batches form ONE optimizer step -- the loader's batch is the
+micro-batch, each draws its own mix, loss / accuracy bookkeeping stays per micro-batch, and the last group of an epoch steps
+with as many batches as it has (sfcvit.training.train.AccumSteps holds the sequence).  Needs len(train_loader)."""
 import numpy as np
 import torch
 import torch.nn.functional as TF
 
 from .optim import FusedAdamW
+from .train import AccumSteps
 
 
 def mixup_data(x, y, alpha=0.2):
@@ -55,42 +60,49 @@ def _augmented(images, augment, graphed=None):
     return augment(images, out=dst)
 
 
-def _plain_epoch(model, train_loader, criterion, optimizer, scheduler, device, augment=None):
+def _accum_seq(train_loader, optimizer, scheduler, reducer, accum_steps, clip=None):
+    return AccumSteps(optimizer, scheduler, reducer, n_batches=len(train_loader) if accum_steps != 1 else None,
+                      accum_steps=accum_steps, clip_params=clip)
+
+
+def _clip_params(model, optimizer):
+    """The loops of train.py:133-178 clip to 1.0; FusedAdamW does that inside its kernel."""
+    return None if isinstance(optimizer, FusedAdamW) else list(model.parameters())
+
+
+def _plain_epoch(model, train_loader, criterion, optimizer, scheduler, device, augment=None, accum_steps=1):
     model.train()
     total_loss = torch.zeros((), device=device)
     correct = torch.zeros((), device=device)
-    for images, labels in train_loader:
+    seq = _accum_seq(train_loader, optimizer, scheduler, None, accum_steps)
+    for i, (images, labels) in enumerate(train_loader):
         images, labels = images.to(device), labels.to(device)
         if augment is not None:
             images = _augmented(images, augment)
-        if hasattr(optimizer, "begin_step"):
-            optimizer.begin_step()
-        optimizer.zero_grad()
+        seq.begin(i)
         outputs = model(images)
         loss = criterion(outputs.float(), labels)
-        loss.backward()
-        optimizer.step()
-        if scheduler is not None:
-            scheduler.step()
+        seq.backward(loss)
+        seq.end()
         total_loss += loss.detach().float() * images.size(0)
         correct += (outputs.argmax(dim=1) == labels).sum()
     n = len(train_loader.dataset)
     return float(total_loss) / n, float(correct) / n
 
 
-def train(model, train_loader, criterion, optimizer, device, augment=None):
+def train(model, train_loader, criterion, optimizer, device, augment=None, accum_steps=1):
     """train.py:57-77: hard labels, no scheduler.  The reference does not clip here: construct
     FusedAdamW(..., max_grad_norm=None) for the same behaviour.  augment: see train_with_mixup_or_cutmix."""
-    return _plain_epoch(model, train_loader, criterion, optimizer, None, device, augment)
+    return _plain_epoch(model, train_loader, criterion, optimizer, None, device, augment, accum_steps)
 
 
-def train_with_scheduler(model, train_loader, criterion, optimizer, scheduler, device, augment=None):
-    """train.py:102-130: as `train` with a per-step scheduler."""
-    return _plain_epoch(model, train_loader, criterion, optimizer, scheduler, device, augment)
+def train_with_scheduler(model, train_loader, criterion, optimizer, scheduler, device, augment=None, accum_steps=1):
+    """train.py:102-130: as `train` with a per-step scheduler (one scheduler step per optimizer step)."""
+    return _plain_epoch(model, train_loader, criterion, optimizer, scheduler, device, augment, accum_steps)
 
 
 def _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_alpha, cutmix_alpha, mix_prob, reducer, graphed,
-                      augment=None):
+                      augment=None, accum_steps=1):
     """train_with_mixup_or_cutmix(device_mix=True): the same draws, but the batch is mixed where the tokenizer reads it
     (model(images, mix=bm)) and the loss / accuracy come from the label pair (F.mixed_target_cross_entropy)."""
     from .. import functional as F
@@ -100,7 +112,8 @@ def _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_a
     total_correct = torch.zeros((), device=device)
     total_samples = 0
     mixes = {}                                       # one record per batch size (the last batch of an epoch may be short)
-    for images, labels in train_loader:
+    seq = _accum_seq(train_loader, optimizer, scheduler, reducer, accum_steps, _clip_params(model, optimizer))
+    for i, (images, labels) in enumerate(train_loader):
         images, labels = images.to(device), labels.to(device)
         if augment is not None:
             images = _augmented(images, augment, graphed if graphed is not None and graphed.mix is not None else None)
@@ -121,21 +134,11 @@ def _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_a
             bm = mixes[B] = BatchMix(B, images.device)
         bm.draw(H, W, mixup_alpha, cutmix_alpha, mix_prob)
         y_a, y_b = labels, labels[bm.idx]
-        if hasattr(optimizer, "begin_step"):
-            optimizer.begin_step()
-        optimizer.zero_grad()
-        if reducer is not None:
-            reducer.begin_step()
+        seq.begin(i)
         outputs = model(images, mix=bm)
         loss, hits = F.mixed_target_cross_entropy(outputs, y_a, y_b, bm)
-        loss.backward()
-        if reducer is not None:
-            reducer.finish()
-        if not isinstance(optimizer, FusedAdamW):
-            torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0, foreach=False)
-        optimizer.step()
-        if scheduler is not None:
-            scheduler.step()
+        seq.backward(loss)
+        seq.end()
         total_correct += hits.sum()
         total_loss += loss.detach().float() * B
         total_samples += B
@@ -144,7 +147,7 @@ def _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_a
 
 def train_with_mixup_or_cutmix(model, train_loader, criterion, optimizer, scheduler, device,
                                mixup_alpha=0.2, cutmix_alpha=1.0, mix_prob=0.5, reducer=None, graphed=None, device_mix=False,
-                               augment=None):
+                               augment=None, accum_steps=1):
     """train.py:133-178.  `optimizer` is a FusedAdamW (clip inside) or any torch optimizer.
     graphed: a sfcvit.training.GraphedTrainStep built on this model / optimizer / scheduler with static buffers of the
     loader's batch shape -- the step (forward, soft-target CE, backward, clip, AdamW, scheduler) is then one hipGraph
@@ -157,15 +160,19 @@ def train_with_mixup_or_cutmix(model, train_loader, criterion, optimizer, schedu
     augment: a sfcvit.training.DeviceAugment -- the loader then yields the raw uint8 batches [B, C, H, W] and the
     reference's transform stack (main.py:169-188) runs on the device in front of the mix, one launch per batch; with a
     device-mix GraphedTrainStep the result is written straight into its static image buffer.  None = float batches, as
-    before."""
+    before.
+    accum_steps: K loader batches per optimizer step (the module docstring); not together with `graphed`."""
+    if graphed is not None and accum_steps != 1:
+        raise ValueError("accum_steps > 1 with a GraphedTrainStep: a captured step does not accumulate")
     if device_mix:
         return _device_mix_epoch(model, train_loader, optimizer, scheduler, device, mixup_alpha, cutmix_alpha, mix_prob,
-                                 reducer, graphed, augment)
+                                 reducer, graphed, augment, accum_steps)
     model.train()
     total_loss = torch.zeros((), device=device)
     total_correct = torch.zeros((), device=device)
     total_samples = 0
-    for images, labels in train_loader:
+    seq = _accum_seq(train_loader, optimizer, scheduler, reducer, accum_steps, _clip_params(model, optimizer))
+    for i, (images, labels) in enumerate(train_loader):
         images, labels = images.to(device), labels.to(device)
         if augment is not None:
             images = _augmented(images, augment)
@@ -184,23 +191,13 @@ def train_with_mixup_or_cutmix(model, train_loader, criterion, optimizer, schedu
             total_loss += loss.float() * images.size(0)
             total_samples += images.size(0)
             continue
-        if hasattr(optimizer, "begin_step"):
-            optimizer.begin_step()       # a batch the graph cannot replay (odd size): the device step state advances here
-        optimizer.zero_grad()
-        if reducer is not None:
-            reducer.begin_step()
+        seq.begin(i)                     # (also for a batch the graph cannot replay, odd size: the device step state advances here)
         outputs = model(images)
         num_classes = outputs.size(1)
         soft_targets = lam * TF.one_hot(y_a, num_classes).float() + (1 - lam) * TF.one_hot(y_b, num_classes).float()
         loss = criterion(outputs, soft_targets)
-        loss.backward()
-        if reducer is not None:
-            reducer.finish()
-        if not isinstance(optimizer, FusedAdamW):
-            torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0, foreach=False)
-        optimizer.step()
-        if scheduler is not None:
-            scheduler.step()
+        seq.backward(loss)
+        seq.end()
         preds = outputs.argmax(dim=1)
         total_correct += (lam * (preds == y_a).float() + (1 - lam) * (preds == y_b).float()).sum()
         total_loss += loss.detach().float() * images.size(0)

@@ -36,6 +36,8 @@ class FlatGradBuffer:
         self.offsets = None
         self.epoch = 0                          # bumped by zero_grad: one in-place gradient write per parameter and step
         self._wt = None                         # transposed(): (flat buffer of W^T, tile table, {id(p): view}, graph task id)
+        self.acc = None                         # accumulate(): fp32 running sum of the micro-batch gradients, allocated on first use
+        self.pending = 0                        # micro-batches folded into `acc` since the last fold()
 
     def _check(self, p):
         pass
@@ -53,6 +55,7 @@ class FlatGradBuffer:
             if p.dtype != dtype:
                 raise TypeError("all parameters must share one dtype")
         self._wt = None                              # (a rebuilt layout invalidates the transposed-weight table)
+        self.acc, self.pending = None, 0             # (and a running sum of the old one)
         self.offsets, off = [], 0
         for p in self.active:
             self.offsets.append(off)
@@ -122,7 +125,8 @@ class FlatGradBuffer:
         the flat buffer and autograd adopts those views (functional._slot); gradients that arrive as separate tensors are
         moved in by `adopt` before they are used, and the slot of a parameter that received none is zeroed there -- every
         slot is overwritten in full each step, so the buffer itself (218 MB at ViT-B: a 40-us fill per step) is not
-        cleared.  set_to_none=False keeps the views as p.grad and zeroes the buffer."""
+        cleared.  set_to_none=False keeps the views as p.grad and zeroes the buffer.  A pending sum of accumulate() lives in
+        `acc` and is left alone: zero_grad() is what runs between micro-batches."""
         if self.flat_grad is None:
             for p in self.params:
                 p.grad = None
@@ -151,6 +155,80 @@ class FlatGradBuffer:
         for p, o in zip(self.active, self.offsets):
             self.adopt(p, o)
 
+    # -- gradient accumulation: K micro-batches per optimizer step ---------------------------------------------------------
+    @torch.no_grad()
+    def accumulate(self):
+        """Call after the backward() of every micro-batch but the last: the flat gradient joins the fp32 running sum `acc`
+        (+4 bytes per parameter, allocated on first use; one fp32 add per element and call), then -- as
+        zero_grad(set_to_none=True) -- `epoch` advances and every p.grad is dropped, so that the next backward writes the
+        slots in place again.  A parameter that received no gradient in this micro-batch contributes zeros.
+
+        Needed because the kernels of a backward pass OVERWRITE the slots: backward() K times and then step(), torch's
+        idiom, would step on the last micro-batch alone.  Dropout / DropPath masks differ between the micro-batches of a step:
+        every site draws ops.next_seed() per forward pass, and in device-state mode the site counter keeps counting until the
+        next begin_step(), which -- like the scheduler and the EMA -- runs once per optimizer step, not per micro-batch."""
+        if self.flat_grad is None:
+            self._build()
+        else:
+            self.adopt_all()
+        if self.acc is None:
+            self.acc = torch.empty(self.flat_grad.numel(), device=self.flat_grad.device, dtype=torch.float32)
+        self._accumulate(self.pending == 0)
+        self.pending += 1
+        self.epoch += 1
+        for p in self.active:
+            p.grad = None
+
+    def _accumulate(self, first):
+        if first:
+            self.acc.copy_(self.flat_grad)                   # (acc is not read)
+        else:
+            self.acc.add_(self.flat_grad.float())
+
+    @torch.no_grad()
+    def fold(self, with_sumsq=False):
+        """After the LAST micro-batch's backward(): flat_grad = (acc + flat_grad) * float32(1 / K) for the K = pending + 1
+        micro-batches of this step -- one fp32 add, one fp32 multiply, one rounding to the buffer's dtype -- and the pending
+        count is cleared.  With nothing pending it does nothing and returns None.  with_sumsq: returns the fp32 sum of the
+        squares of the stored values (FusedAdamW takes it in the same pass, for the clip).
+
+        The result is the AVERAGE of the micro-batch gradients: every micro-batch's loss is its own mean, so the caller does
+        NOT divide the loss by K as with a torch optimizer; K equal micro-batches then give the gradient of the mean over
+        all their samples.  step() folds by itself; call fold() yourself only when something has to read the averaged
+        gradient first (GradReducer.finish(deferred=True))."""
+        if not self.pending:
+            return None
+        self.adopt_all()
+        scale = torch.tensor(1.0 / (self.pending + 1), dtype=torch.float32)       # float32(1 / K); a host scalar: no device sync
+        sumsq = self._fold(scale, with_sumsq)
+        self.pending = 0
+        return sumsq
+
+    def _fold(self, scale, with_sumsq):
+        self.flat_grad.copy_(((self.acc + self.flat_grad.float()) * scale).to(self.flat_grad.dtype))
+        return self.flat_grad.float().square().sum() if with_sumsq else None
+
+    def discard_accumulation(self):
+        """Drop a pending sum (a step abandoned half-way): the next accumulate() starts a new one."""
+        self.pending = 0
+
+    def _no_pending(self, what):
+        if self.pending:
+            raise RuntimeError(f"{what}: {self.pending} micro-batch(es) are accumulated but not stepped; step() or "
+                               "discard_accumulation() first (a running sum is not part of the optimizer state)")
+
+    def state_dict(self):
+        """The layout (FusedAdamW adds its state).  Refused while micro-batches are pending."""
+        self._no_pending("state_dict")
+        index = {id(p): i for i, p in enumerate(self.params)}
+        return {"active": None if self.active is None else [index[id(p)] for p in self.active]}
+
+    def load_state_dict(self, sd):
+        """Builds the layout if there is none yet; a pending sum is discarded."""
+        self.discard_accumulation()
+        if self.flat_grad is None and sd.get("active") is not None:
+            self._build([self.params[i] for i in sd["active"]])
+
 
 class FusedAdamW(FlatGradBuffer):
     """Not a torch.optim.Optimizer subclass on purpose: state is three flat fp32
@@ -164,7 +242,14 @@ class FusedAdamW(FlatGradBuffer):
     ema_weights() hand the average to evaluation and checkpoints.  Parameters outside the flat buffers never receive a
     gradient, so their average is their value.  Data parallel: every rank applies the same update to the same weights
     (GradReducer reduces the gradients and synchronises the replicas), so every rank holds the same average and the EMA
-    needs no collective of its own."""
+    needs no collective of its own.
+
+    Gradient accumulation (FlatGradBuffer.accumulate / fold, here on the kernels ops.grad_accum / ops.grad_accum_finish):
+    accumulate() after every micro-batch's backward() but the last, then step().  step() with micro-batches pending forms
+    the averaged gradient itself -- with the clip's sum of squares in the same pass when max_grad_norm is set -- and then
+    makes exactly the AdamW call it makes without accumulation: step_count, the device step state, the EMA, grad_norm()
+    (the norm of the averaged gradient) and the scheduler advance once per optimizer step.  An optimizer that never
+    accumulates allocates nothing (`acc is None`) and launches what it always did."""
 
     def __init__(self, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-5, max_grad_norm=1.0,
                  grad_scale=1.0, ema_decay=None, ema_warmup=False):
@@ -243,6 +328,17 @@ class FusedAdamW(FlatGradBuffer):
         if self.ema_decay is not None:
             self.ema = self.master.clone()       # the average starts at the weights (timm: a deep copy of the model)
 
+    def _accumulate(self, first):
+        ops.grad_accum(self.flat_grad, self.acc, first)
+
+    def _fold(self, scale, with_sumsq):
+        sumsq = None
+        if with_sumsq:
+            self._sumsq.zero_()
+            sumsq = self._sumsq
+        ops.grad_accum_finish(self.flat_grad, self.acc, float(scale), sumsq)
+        return sumsq
+
     @torch.no_grad()
     def step(self):
         if self._ema_swapped:
@@ -255,7 +351,9 @@ class FusedAdamW(FlatGradBuffer):
             self.step_count += 1         # device-state mode, captured: the replay's advance() counts and GraphedTrainStep mirrors it
             self._advanced_eagerly = False
         sumsq = None
-        if self.max_grad_norm is not None:
+        if self.pending:                 # micro-batches accumulated: the average, and the clip's sum of squares in the same pass
+            sumsq = self.fold(with_sumsq=self.max_grad_norm is not None)
+        elif self.max_grad_norm is not None:
             self._sumsq.zero_()
             ops.sumsq_accum(self.flat_grad, self._sumsq)
             sumsq = self._sumsq
@@ -276,6 +374,7 @@ class FusedAdamW(FlatGradBuffer):
         return self._sumsq.sqrt() * self.grad_scale
 
     def state_dict(self):
+        self._no_pending("state_dict")
         index = {id(p): i for i, p in enumerate(self.params)}
         sd = {"step": self.step_count, "lr": self.lr, "master": self.master, "m": self.m, "v": self.v,
               "active": [index[id(p)] for p in self.active]}
@@ -337,6 +436,7 @@ class FusedAdamW(FlatGradBuffer):
         step count, lr from its param group.  Parameters without a state entry there (never stepped: the token-mix branch
         the forward does not use, vit.py:269-272) stay outside the flat buffers, as here.  The fp32 master weights are
         taken from the model's (already loaded) parameters: torch.optim.AdamW keeps none."""
+        self.discard_accumulation()
         state, groups = sd["state"], sd["param_groups"]
         order = [i for g in groups for i in g["params"]]
         if len(order) != len(self.params):
@@ -369,6 +469,7 @@ class FusedAdamW(FlatGradBuffer):
     def load_state_dict(self, sd):
         if "param_groups" in sd and "state" in sd:           # a torch.optim optimizer's state (reference checkpoint)
             return self.load_torch_state_dict(sd)
+        self.discard_accumulation()
         if self.flat_grad is None:
             self._build([self.params[i] for i in sd["active"]])
         if self.master.numel() != sd["master"].numel():

@@ -167,8 +167,67 @@ class GraphedTrainStep:
         return False
 
 
-def train_step(model, images, soft_targets, optimizer, scheduler=None, reducer=None):
-    """One optimisation step; returns the (device, un-synchronised) loss."""
+class AccumSteps:
+    """The sequence around forward and backward when `accum_steps` consecutive micro-batches form one optimizer step, shared
+    by train_step and the epoch loops: begin(i) in front of the forward pass of micro-batch i (0-based, of `n_batches`),
+    backward(loss), end() after it.  The last group of an epoch steps with as many micro-batches as it has.
+
+    FusedAdamW (anything with accumulate()): every micro-batch's loss is its own mean and is NOT divided; all but the last of
+    a group end in optimizer.accumulate(), the last in optimizer.step(), which averages over the actual count.  With a
+    reducer there is one exchange per optimizer step: no reducer.begin_step(), and after the last backward
+    optimizer.fold() + reducer.finish(deferred=True).  torch optimizers: (loss / count).backward() and no zero_grad inside
+    a group.  begin_step(), zero_grad(), the clip, step() and scheduler.step() run once per group.  A group of one is the
+    sequence without accumulation, statement for statement."""
+
+    def __init__(self, optimizer, scheduler=None, reducer=None, n_batches=None, accum_steps=1, clip_params=None):
+        if int(accum_steps) != accum_steps or accum_steps < 1:
+            raise ValueError(f"accum_steps={accum_steps}: a positive integer expected")
+        self.opt, self.sched, self.reducer, self.k = optimizer, scheduler, reducer, int(accum_steps)
+        self.n = n_batches                    # only read with accum_steps > 1: how many micro-batches the last group has
+        self.clip_params = clip_params        # torch optimizers of the loops that clip to 1.0 outside the optimizer
+        self.fused = hasattr(optimizer, "accumulate")
+        self.j, self.count = 0, 1
+
+    def begin(self, i):
+        if self.k > 1:
+            self.j = i % self.k
+            self.count = min(self.k, self.n - (i - self.j))
+        if self.j == 0:
+            if hasattr(self.opt, "begin_step"):
+                self.opt.begin_step()        # device-resident step state: the counters advance once per optimizer step
+            self.opt.zero_grad()
+        if self.reducer is not None and self.count == 1:
+            self.reducer.begin_step()
+
+    def backward(self, loss):
+        (loss if self.fused or self.count == 1 else loss / self.count).backward()
+
+    def end(self):
+        """-> whether the optimizer stepped."""
+        if self.j < self.count - 1:
+            if self.fused:
+                self.opt.accumulate()
+            return False
+        if self.reducer is not None:
+            if self.count > 1:
+                self.opt.fold()              # the averaged gradient is what the ranks exchange, once
+                self.reducer.finish(deferred=True)
+            else:
+                self.reducer.finish()
+        if self.clip_params is not None:
+            torch.nn.utils.clip_grad_norm_(self.clip_params, 1.0, foreach=False)
+        self.opt.step()
+        if self.sched is not None:
+            self.sched.step()
+        return True
+
+
+def train_step(model, images, soft_targets, optimizer, scheduler=None, reducer=None, accum_steps=1):
+    """One optimisation step; returns the (device, un-synchronised) loss.
+    accum_steps=K > 1: `images` / `soft_targets` are split along dim 0 into K equal micro-batches that run one after the
+    other (AccumSteps) and the mean of their losses is returned; the batch size must be divisible by K."""
+    if accum_steps != 1:
+        return _train_step_accum(model, images, soft_targets, optimizer, scheduler, reducer, accum_steps)
     if hasattr(optimizer, "begin_step"):
         optimizer.begin_step()           # device-resident step state (after a GraphedTrainStep): counters advance here
     optimizer.zero_grad()
@@ -183,3 +242,18 @@ def train_step(model, images, soft_targets, optimizer, scheduler=None, reducer=N
     if scheduler is not None:
         scheduler.step()
     return loss.detach()
+
+
+def _train_step_accum(model, images, soft_targets, optimizer, scheduler, reducer, accum_steps):
+    seq = AccumSteps(optimizer, scheduler, reducer, n_batches=accum_steps, accum_steps=accum_steps)
+    B = images.size(0)
+    if B % seq.k:
+        raise ValueError(f"train_step: batch size {B} is not divisible by accum_steps={seq.k}")
+    losses = []
+    for i, (x, t) in enumerate(zip(images.chunk(seq.k), soft_targets.chunk(seq.k))):
+        seq.begin(i)
+        loss = F.soft_target_cross_entropy(model(x), t)
+        seq.backward(loss)
+        seq.end()
+        losses.append(loss.detach())
+    return torch.stack(losses).mean()
