@@ -230,25 +230,44 @@ __global__ __launch_bounds__(THREADS) void soft_ce_kernel(const uint16_t *__rest
     const uint16_t *l = logits + size_t(row) * ld;
     const float *t = targets + size_t(row) * C;
     float mx = -INFINITY;
-    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, bf2f(l[c]));
-    mx = wave_max(mx);
-    float se = 0.f, st = 0.f, stl = 0.f;
+    int am = C;                                       // this lane's first column that holds its maximum
     for (int c = lane; c < C; c += 64) {
         const float z = bf2f(l[c]);
-        se += __expf(z - mx);
+        if (z > mx) am = c;
+        mx = fmaxf(mx, z);
+    }
+    const float lane_mx = mx;
+    mx = wave_max(mx);
+    if (lane_mx != mx) am = C;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) am = min(am, __shfl_xor(am, o, 64));   // the row's first maximum
+    // se, and beside it the same sum without the term of the maximum (soft_ce_pair_kernel's remedy, mix.hip): at that column
+    // 1 - softmax is so / se, where 1 - exp(z - lse) loses every digit once the model is sure of the label
+    float se = 0.f, so = 0.f, st = 0.f, stl = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        const float z = bf2f(l[c]);
+        const float e = __expf(z - mx);
+        se += e;
+        so += c == am ? 0.f : e;
         st += t[c];
         stl += t[c] * z;
     }
     se = wave_sum(se);
+    so = wave_sum(so);
     st = wave_sum(st);
     stl = wave_sum(stl);
     const float lse = mx + __logf(se);
     if (lane == 0) loss_rows[row] = lse * st - stl;   // -sum t*(z - lse)
     if (dlogits) {
         uint16_t *d = dlogits + size_t(row) * ld;
+        const float omp_max = so / se;
         for (int c = lane; c < ld; c += 64) {
             float gr = 0.f;
-            if (c < C) gr = (__expf(bf2f(l[c]) - lse) * st - t[c]) * gscale;
+            if (c < C) {
+                // softmax * sum(t) - t, written as p * (sum(t) - t) - t * (1 - p): no cancellation in either factor
+                const float p = __expf(bf2f(l[c]) - lse), tc = t[c];
+                gr = (p * (st - tc) - tc * (c == am ? omp_max : 1.f - p)) * gscale;
+            }
             d[c] = f2bf(gr);
         }
     }
