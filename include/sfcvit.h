@@ -278,7 +278,7 @@ int sfcvit_hier_resample_concat_bwd(const void *dout, const int32_t *n_tokens, i
 /* HOST: name of the tokenizer kernel the calling thread launched last through any entry point of the three sections above
  * (patch embed, token gathers, hierarchical tokenizer), "none" before any -- what rocprofv3 would show, for tests that must
  * know which path ran: pe_fwd_kernel<fp32|bf16>, pe_bwd_kernel<..>, pe2_fwd_kernel<..>, pe2_bwd_kernel<..> (the tiled
- * forms; sfcvit_patch_embed_fwd / _bwd fall back to the generic ones when the descriptor, workspace or alignment do not
+ * forms; sfcvit_patch_embed_fwd / _bwd run the generic ones without a descriptor, or when P, D or its class count do not
  * fit), tokens_gather_kernel<fp32|bf16|mix>, tokens_gather_p256_kernel<..>, tokens_gather_tiles_kernel<C, fp32|mix>,
  * hier_fwd_kernel<fp32|bf16, fuse|levels>, hier_resample_concat_kernel, hier_resample_concat_bwd_kernel.  The helper
  * launches (weight permutation, split reduction, column sum) are not named.  SFCVIT_EINVAL for a null buffer or n <= 0. */

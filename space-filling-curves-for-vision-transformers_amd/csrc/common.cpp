@@ -1,5 +1,6 @@
 #include "common_host.h"
 #include "rowwise.h"
+#include "tokenizer.h"
 
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -13,7 +14,7 @@ thread_local char g_err[512] = "";
 thread_local GemmPlan g_gemm;
 thread_local bool g_gemm_noted = false;
 }
-thread_local KernelNote g_attn, g_rowwise, g_tokenizer;
+thread_local KernelNote g_attn, g_rowwise;
 
 int env_int(const char *name, int def) {
     const char *e = getenv(name);
@@ -65,6 +66,16 @@ const RowwiseKnobs &read_rowwise_knobs() {
         k.ln_blocks = env_int("SFCVIT_LN_BLOCKS", k.ln_blocks);
         k.ln_fwd_two_rows = env_int("SFCVIT_LN_FWD_TWO_ROWS", k.ln_fwd_two_rows);
         k.adamw_nt = env_int("SFCVIT_ADAMW_NT", k.adamw_nt);
+        return k;
+    }();
+    return once;
+}
+
+const TokenizerKnobs &read_tokenizer_knobs() {
+    static const TokenizerKnobs once = [] {
+        TokenizerKnobs k;
+        k.gather_u = env_int("SFCVIT_GATHER_U", k.gather_u);
+        k.gather_nt = env_int("SFCVIT_GATHER_NT", k.gather_nt);
         return k;
     }();
     return once;
@@ -167,8 +178,6 @@ extern "C" int sfcvit_last_gemm_kernel(char *buf, int n) {
 extern "C" int sfcvit_last_attn_kernel(char *buf, int n) { return sfcvit::g_attn.read(buf, n); }
 
 extern "C" int sfcvit_last_rowwise_kernel(char *buf, int n) { return sfcvit::g_rowwise.read(buf, n); }
-
-extern "C" int sfcvit_last_tokenizer_kernel(char *buf, int n) { return sfcvit::g_tokenizer.read(buf, n); }
 
 extern "C" int sfcvit_device_count(void) {
     int n = 0;

@@ -33,10 +33,8 @@ void note_attn_kernel(const AttnPlan &p);
 void note_attn_kernel(const ProbePlan &p);      // sfcvit_attention_probs / _stats report through sfcvit_last_attn_kernel too
 // g_attn: what note_attn_kernel formats into; the masked kernels (attention_masked.hip) have no plan and set it by name.
 // g_rowwise: which row-wise kernel the calling thread's last sfcvit_layernorm_bwd* / sfcvit_add_layernorm_path_fwd launched
-// (sfcvit_last_rowwise_kernel).
-// g_tokenizer: which tokenizer kernel (patch_embed.hip, patch_embed_tiled.hip, hier_tokenizer.hip) the calling thread launched
-// last (sfcvit_last_tokenizer_kernel): noted on the host just before the launch.
-extern thread_local KernelNote g_attn, g_rowwise, g_tokenizer;
+// (sfcvit_last_rowwise_kernel).  The other families keep theirs with their plans (g_tokenizer: tokenizer.h / tokenizer.cpp).
+extern thread_local KernelNote g_attn, g_rowwise;
 
 // rowwise.hip (layernorm.hip and the GEMM launchers call these too): out[n] = sum over `nparts` rows of part[nparts][N] in a
 // fixed order; out fp32 or bf16.

@@ -5,7 +5,8 @@
 // kernel (sfcvit_last_gemm_kernel / sfcvit_last_attn_kernel).
 //
 // Environment switches, for A/B measurements and tests (never needed in production).  Read by read_knobs and, the four of
-// the row-wise family (rowwise.h: RowwiseKnobs), read_rowwise_knobs (common.cpp):
+// the row-wise family (rowwise.h: RowwiseKnobs) and the two of the tokenizer family (tokenizer.h: TokenizerKnobs),
+// read_rowwise_knobs and read_tokenizer_knobs (common.cpp):
 //   read per call (tests flip them between calls)
 //     SFCVIT_GEMM_2PHASE       1        "0": four-phase k-tile schedule of the persistent GEMMs
 //     SFCVIT_GEMM_STAGGER      4,200    "slots,ticks" (10 ns) start-up stagger of the persistent GEMM; "1,0" = off
@@ -25,8 +26,8 @@
 //     SFCVIT_LN_BLOCKS         0 (auto) workgroups of the LayerNorm backward (ln_bwd_plan)
 //     SFCVIT_LN_FWD_TWO_ROWS   1        "0": one row per wave in the LayerNorm forward (ln_fwd_plan)
 //     SFCVIT_ADAMW_NT          3        nontemporal loads (1) / stores (2) of the optimizer state (adamw_plan, grad_accum_plan)
-//     SFCVIT_GATHER_U          1        images per wave of the tile gather, 1 or 2 (patch_embed.hip)
-//     SFCVIT_GATHER_NT         3        nontemporal loads (1) / stores (2) of the tile gather (patch_embed.hip)
+//     SFCVIT_GATHER_U          1        images per wave of the tile gather, 1 or 2 (gather_tiles_plan)
+//     SFCVIT_GATHER_NT         3        nontemporal loads (1) / stores (2) of the tile gather (gather_tiles_plan)
 #pragma once
 #include <cstddef>
 

@@ -22,12 +22,13 @@
 // SFCVIT_EINVAL (sfcvit_hier_tokenizer_supported says so beforehand); the caller then composes the level kernels, torch's interpolate and the fusion GEMM.
 #include "common_host.h"
 #include "device_common.h"
+#include "tokenizer.h"
 #include <hip/hip_runtime.h>
 
 namespace sfcvit {
 namespace {
 
-constexpr int HT_ROWS = 64, HT_THREADS = 256, HT_MAXL = 4, HT_RING = 4;
+constexpr int HT_RING = 4;               // HT_ROWS, HT_THREADS, HT_MAXL: tokenizer.h
 
 struct HierGeo {
     const void *x;
@@ -218,72 +219,45 @@ __global__ __launch_bounds__(HT_THREADS) void hier_fwd_kernel(const HierGeo g) {
     }
 }
 
-int hier_lds_bytes(int E, int kp_sum) { return HT_ROWS * (2 * E + 16) + HT_ROWS * (2 * kp_sum + 16); }
-
 }  // namespace
 }  // namespace sfcvit
 
 using namespace sfcvit;
 
 extern "C" int sfcvit_hier_tokenizer_supported(int L, int D, int C, const int32_t *P) {
-    if (L < 1 || L > HT_MAXL || D <= 0 || D % 64 || (L * D) % 256 || C <= 0 || !P) return 0;
-    int kp_sum = 0;
-    for (int l = 0; l < L; l++) {
-        const int K = P[l] * C;
-        if (P[l] <= 0 || K % 8) return 0;
-        kp_sum += (K + 31) & ~31;
-    }
-    return hier_lds_bytes(L * D, kp_sum) <= 160 * 1024;
+    int E = 0, kp_sum = 0;
+    return hier_envelope(L, D, C, P, E, kp_sum);
 }
 
 extern "C" int sfcvit_hier_tokenizer_fwd(const sfcvit_hier_args *a, void *stream) {
-    if (!a || !a->x || !a->h || (a->wf && !a->y)) return fail(SFCVIT_EINVAL, "hier_tokenizer_fwd: null pointer");
-    if (a->B <= 0 || a->C <= 0 || a->HW <= 0 || a->N <= 0)
-        return fail(SFCVIT_EINVAL, "hier_tokenizer_fwd: B=%d C=%d HW=%d N=%d", a->B, a->C, a->HW, a->N);
-    if (!sfcvit_hier_tokenizer_supported(a->L, a->D, a->C, a->P))
-        return fail(SFCVIT_EINVAL, "hier_tokenizer_fwd: L=%d D=%d C=%d outside the fused kernel's envelope "
-                    "(1..4 levels, D %% 64 == 0, L*D %% 256 == 0, P*C %% 8 == 0, 64 rows of L*D + sum K in 160 KiB LDS)",
-                    a->L, a->D, a->C);
-    if (int64_t(a->B) * a->N >= (int64_t(1) << 31) - HT_ROWS) return fail(SFCVIT_EINVAL, "hier_tokenizer_fwd: too many token rows");
+    const HierPlan p = hier_plan(a);
+    if (p.err) return fail(p.err, "%s", p.msg);
     HierGeo g{};
     g.x = a->x;
-    int kp_sum = 0;
     for (int l = 0; l < a->L; l++) {
-        if (!a->pix[l] || !a->w[l]) return fail(SFCVIT_EINVAL, "hier_tokenizer_fwd: level %d: null pointer", l);
-        if (int64_t(a->P[l]) * a->N != a->HW)
-            return fail(SFCVIT_EINVAL, "hier_tokenizer_fwd: level %d: N * P = %d * %d != H*W = %d (levels must share the token count)",
-                        l, a->N, a->P[l], a->HW);
-        if (!aligned16(a->w[l]) || (a->b[l] && (reinterpret_cast<uintptr_t>(a->b[l]) & 7)))
-            return fail(SFCVIT_EINVAL, "hier_tokenizer_fwd: level %d: weight / bias alignment", l);
         g.pix[l] = a->pix[l];
         g.w[l] = static_cast<const uint16_t *>(a->w[l]);
         g.b[l] = static_cast<const uint16_t *>(a->b[l]);
         g.P[l] = a->P[l];
-        kp_sum += (a->P[l] * a->C + 31) & ~31;
     }
-    const bool fuse = a->wf != nullptr;
-    if (!aligned16(a->wf) || !aligned16(a->h) || !aligned16(a->y) || (a->bf && (reinterpret_cast<uintptr_t>(a->bf) & 7)))
-        return fail(SFCVIT_EINVAL, "hier_tokenizer_fwd: fusion weight / output alignment");
     g.wf = static_cast<const uint16_t *>(a->wf);
     g.bf = static_cast<const uint16_t *>(a->bf);
     g.h = static_cast<uint16_t *>(a->h);
     g.y = static_cast<uint16_t *>(a->y);
     g.B = a->B; g.C = a->C; g.HW = a->HW; g.N = a->N; g.L = a->L; g.D = a->D;
-    g.E = a->L * a->D;
-    g.M = a->B * a->N;
-    g.h_stride = 2 * g.E + 16;
-    g.a_stride = 2 * kp_sum + 16;
-    const int lds = fuse ? hier_lds_bytes(g.E, kp_sum) : HT_ROWS * g.a_stride;
-    const int grid = (g.M + HT_ROWS - 1) / HT_ROWS;
+    g.E = p.E;
+    g.M = p.M;
+    g.h_stride = p.h_stride;
+    g.a_stride = p.a_stride;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const void *k = a->x_is_bf16 ? (fuse ? reinterpret_cast<const void *>(&hier_fwd_kernel<true, true>) : reinterpret_cast<const void *>(&hier_fwd_kernel<true, false>))
-                                 : (fuse ? reinterpret_cast<const void *>(&hier_fwd_kernel<false, true>) : reinterpret_cast<const void *>(&hier_fwd_kernel<false, false>));
-    if (int rc = raise_lds_limit(k, 160 * 1024, "hier_tokenizer_fwd attribute")) return rc;
-    g_tokenizer.set("hier_fwd_kernel<%s, %s>", a->x_is_bf16 ? "bf16" : "fp32", fuse ? "fuse" : "levels");
-    if (a->x_is_bf16 && fuse) hipLaunchKernelGGL((hier_fwd_kernel<true, true>), dim3(grid), dim3(HT_THREADS), lds, s, g);
-    else if (a->x_is_bf16) hipLaunchKernelGGL((hier_fwd_kernel<true, false>), dim3(grid), dim3(HT_THREADS), lds, s, g);
-    else if (fuse) hipLaunchKernelGGL((hier_fwd_kernel<false, true>), dim3(grid), dim3(HT_THREADS), lds, s, g);
-    else hipLaunchKernelGGL((hier_fwd_kernel<false, false>), dim3(grid), dim3(HT_THREADS), lds, s, g);
+    const void *k = p.x_bf16 ? (p.fuse ? reinterpret_cast<const void *>(&hier_fwd_kernel<true, true>) : reinterpret_cast<const void *>(&hier_fwd_kernel<true, false>))
+                             : (p.fuse ? reinterpret_cast<const void *>(&hier_fwd_kernel<false, true>) : reinterpret_cast<const void *>(&hier_fwd_kernel<false, false>));
+    if (int rc = raise_lds_limit(k, HT_LDS_LIMIT, "hier_tokenizer_fwd attribute")) return rc;
+    note_tokenizer_kernel(p);
+    if (p.x_bf16 && p.fuse) hipLaunchKernelGGL((hier_fwd_kernel<true, true>), dim3(p.grid), dim3(HT_THREADS), p.lds, s, g);
+    else if (p.x_bf16) hipLaunchKernelGGL((hier_fwd_kernel<true, false>), dim3(p.grid), dim3(HT_THREADS), p.lds, s, g);
+    else if (p.fuse) hipLaunchKernelGGL((hier_fwd_kernel<false, true>), dim3(p.grid), dim3(HT_THREADS), p.lds, s, g);
+    else hipLaunchKernelGGL((hier_fwd_kernel<false, false>), dim3(p.grid), dim3(HT_THREADS), p.lds, s, g);
     return check_launch("hier_tokenizer_fwd");
 }
 
@@ -299,7 +273,6 @@ extern "C" int sfcvit_hier_tokenizer_fwd(const sfcvit_hier_args *a, void *stream
 // ---------------------------------------------------------------------------------------------------------------------
 namespace sfcvit {
 namespace {
-constexpr int RS_MAXL = 8;
 struct ResampleArgs {
     const uint16_t *lev[RS_MAXL];       // forward: y_l [B, N_l, D];  backward: unused
     uint16_t *dlev[RS_MAXL];            // backward: d y_l
@@ -384,42 +357,31 @@ __global__ __launch_bounds__(256) void hier_resample_concat_bwd_kernel(const Res
     }
 }
 
-int rs_check(const void *const *lev, const int32_t *n_tokens, int L, int B, int N0, int D, const void *cat, const char *what) {
-    if (!lev || !n_tokens || !cat) return fail(SFCVIT_EINVAL, "%s: null pointer", what);
-    if (L < 1 || L > RS_MAXL || B <= 0 || N0 <= 0 || D <= 0 || D % 8) return fail(SFCVIT_EINVAL, "%s: L=%d B=%d N0=%d D=%d (1 <= L <= %d, D %% 8 == 0)", what, L, B, N0, D, RS_MAXL);
-    if (n_tokens[0] != N0) return fail(SFCVIT_EINVAL, "%s: the first level has %d tokens, not N0 = %d", what, n_tokens[0], N0);
-    if (!aligned16(cat)) return fail(SFCVIT_EINVAL, "%s: alignment", what);
-    for (int l = 0; l < L; l++)
-        if (!lev[l] || n_tokens[l] <= 0 || !aligned16(lev[l])) return fail(SFCVIT_EINVAL, "%s: level %d (pointer / token count / alignment)", what, l);
-    return SFCVIT_OK;
-}
 }  // namespace
 }  // namespace sfcvit
 
 extern "C" int sfcvit_hier_resample_concat(const void *const *levels, const int32_t *n_tokens, int L, int B, int N0, int D, void *out,
                                            void *stream) {
-    if (int rc = rs_check(levels, n_tokens, L, B, N0, D, out, "hier_resample_concat")) return rc;
+    const ResamplePlan p = resample_plan(false, levels, n_tokens, L, B, N0, D, out);
+    if (p.err) return fail(p.err, "%s", p.msg);
     ResampleArgs a{};
     for (int l = 0; l < L; l++) { a.lev[l] = static_cast<const uint16_t *>(levels[l]); a.n[l] = n_tokens[l]; }
     a.L = L; a.B = B; a.N0 = N0; a.D = D;
-    const int64_t total = int64_t(B) * N0 * L * (D / 8);
-    const unsigned blocks = unsigned(std::min<int64_t>((total + 255) / 256, 1 << 16));
-    g_tokenizer.set("hier_resample_concat_kernel");
-    hipLaunchKernelGGL(hier_resample_concat_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a, static_cast<uint16_t *>(out));
+    note_tokenizer_kernel(p);
+    hipLaunchKernelGGL(hier_resample_concat_kernel, dim3(p.blocks[0]), dim3(256), 0, static_cast<hipStream_t>(stream), a, static_cast<uint16_t *>(out));
     return check_launch("hier_resample_concat");
 }
 
 extern "C" int sfcvit_hier_resample_concat_bwd(const void *dout, const int32_t *n_tokens, int L, int B, int N0, int D, void *const *dlevels,
                                                void *stream) {
-    if (int rc = rs_check(const_cast<const void *const *>(dlevels), n_tokens, L, B, N0, D, dout, "hier_resample_concat_bwd")) return rc;
+    const ResamplePlan p = resample_plan(true, const_cast<const void *const *>(dlevels), n_tokens, L, B, N0, D, dout);
+    if (p.err) return fail(p.err, "%s", p.msg);
     ResampleArgs a{};
     for (int l = 0; l < L; l++) { a.dlev[l] = static_cast<uint16_t *>(dlevels[l]); a.n[l] = n_tokens[l]; }
     a.L = L; a.B = B; a.N0 = N0; a.D = D;
     for (int l = 0; l < L; l++) {
-        const int64_t total = int64_t(B) * n_tokens[l] * (D / 8);
-        const unsigned blocks = unsigned(std::min<int64_t>((total + 255) / 256, 1 << 16));
-        g_tokenizer.set("hier_resample_concat_bwd_kernel");
-        hipLaunchKernelGGL(hier_resample_concat_bwd_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a,
+        note_tokenizer_kernel(p);
+        hipLaunchKernelGGL(hier_resample_concat_bwd_kernel, dim3(p.blocks[l]), dim3(256), 0, static_cast<hipStream_t>(stream), a,
                            static_cast<const uint16_t *>(dout), l);
         if (int rc = check_launch("hier_resample_concat_bwd")) return rc;
     }

@@ -3,7 +3,7 @@
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
 //   host part), the error path of common.cpp, the mask validation and block map of attention_masked.cpp (check_mask_blocks),
 //   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv),
-//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), drop_path.cpp (check_drop_path), model_ema.cpp (check_model_ema) and grad_accum.cpp (check_grad_accum), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
+//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), tokenizer.cpp (check_tokenizer), drop_path.cpp (check_drop_path), model_ema.cpp (check_model_ema) and grad_accum.cpp (check_grad_accum), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
 //   and post passes each GEMM / attention shape of the benchmarked models gets).
 // Every buffer is a heap block of EXACTLY the documented size, so that an off-by-one in a generator or in the descriptor
 // writer is a heap-buffer-overflow report instead of silent corruption.
@@ -27,6 +27,7 @@
 #include "../token_agg.h"
 #include "../token_mix.h"
 #include "../token_pool.h"
+#include "../tokenizer.h"
 
 static int g_fail = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { std::fprintf(stderr, "host_check: " __VA_ARGS__); std::fprintf(stderr, " (%s:%d)\n", __FILE__, __LINE__); g_fail++; } } while (0)
@@ -1156,6 +1157,439 @@ static void check_rowwise() {
     refused(step_advance_plan(odd), "16-byte aligned", "step_advance state");
 }
 
+// The plans of tokenizer.cpp: form, grid, LDS and workspace of the token gathers, the fused patch embedding (generic and
+// tiled), the hierarchical tokenizer, the resampling concatenation and the two mix entry points at the benchmark shapes and at
+// every form boundary; every refusal with its text; the proof that the tiled forms never need more workspace than
+// sfcvit_patch_embed_workspace reports; and extents no tensor can have, so that UBSan sees the arithmetic.  Expected values are
+// the parent commit's (its library's answers to the queries, its formulas evaluated by hand for the grids).
+static std::vector<int32_t> tile_class_counts(int curve, int img) {
+    const int N = img * img / 256, cap = 16 + 2 * N + 2 * 8 * 256;
+    std::unique_ptr<int32_t[]> flat(new int32_t[img * img]), pix(new int32_t[img * img]), desc(new int32_t[cap]);
+    CHECK(sfcvit_curve_table(curve, img, flat.get()) == SFCVIT_OK && sfcvit_pixel_table(flat.get(), img, 1, 256, pix.get()) == SFCVIT_OK,
+          "tokenizer: tables of %d px", img);
+    CHECK(sfcvit_tile_descriptors(pix.get(), N, 256, img, desc.get(), cap) > 0, "tokenizer: %d px is not tiles", img);
+    std::vector<int32_t> cnt;
+    for (int c = 0; c < desc[1]; c++) cnt.push_back(desc[6 + c + 1] - desc[6 + c]);
+    return cnt;
+}
+
+static void check_tokenizer() {
+    using namespace sfcvit;
+    const TokenizerKnobs k0;
+    CHECK(k0.gather_u == 1 && k0.gather_nt == 3, "tokenizer: knob defaults");
+    void *a = ptr(0), *b = ptr(1), *odd = static_cast<char *>(ptr(4)) + 8, *odd4 = static_cast<char *>(ptr(4)) + 4;
+    const int32_t *ia = static_cast<const int32_t *>(ptr(2)), *ib = static_cast<const int32_t *>(ptr(3)), *ic = static_cast<const int32_t *>(ptr(5));
+    const uint32_t *rec = static_cast<const uint32_t *>(ptr(6));
+    const int big = INT32_MAX;
+    auto refused = [](const PlanStatus &p, const char *frag, const char *what) {
+        CHECK(p.err == SFCVIT_EINVAL && std::strstr(p.msg, frag), "tokenizer %s: want '%s', got %d '%s'", what, frag, p.err, p.msg);
+    };
+    auto named = [](const auto &p, const char *want, const char *what) {
+        char name[96];
+        kernel_name(p, name, sizeof(name));
+        CHECK(p.err == SFCVIT_OK && !std::strcmp(name, want), "tokenizer %s: '%s', want '%s' (%s)", what, name, want, p.msg);
+    };
+
+    // ---- token gathers ----
+    auto tiles = [&](int B, int C, int H, int W, int N, int ld, const int32_t *perm, const TokenizerKnobs &k) {
+        return gather_tiles_plan("tokens_gather_tiles", a, ia, ib, perm, B, C, H, W, N, b, ld, k);
+    };
+    {   // the benchmark shapes: ViT-B/16 at 224 with 256 images, ViT-L at 384 with 64
+        const GatherPlan p = tiles(256, 3, 224, 224, 196, 768, nullptr, k0);
+        named(p, "tokens_gather_tiles_kernel<3, fp32>", "tiles ViT-B");
+        CHECK(p.form == GatherForm::TILES && p.grid_x == 98 && p.grid_y == 64 && p.threads == 256 && p.lds == 13312 && p.upw == 1 && p.nt == 3 &&
+              p.HW == 50176 && p.wmagic == uint32_t((uint64_t(1) << 32) / 224) + 1, "tiles ViT-B: grid (%d, %d) lds %zu", p.grid_x, p.grid_y, p.lds);
+        const GatherPlan l = tiles(64, 3, 384, 384, 576, 768, nullptr, k0);
+        CHECK(l.err == SFCVIT_OK && l.grid_x == 288 && l.grid_y == 16 && l.lds == 13312, "tiles ViT-L: grid (%d, %d)", l.grid_x, l.grid_y);
+        TokenizerKnobs k2;
+        k2.gather_u = 2;
+        const GatherPlan u = tiles(256, 3, 224, 224, 196, 768, nullptr, k2);
+        CHECK(u.err == SFCVIT_OK && u.upw == 2 && u.grid_y == 32 && u.lds == 1024 + 8 * 3 * 1024, "tiles U = 2: grid y %d lds %zu", u.grid_y, u.lds);
+        const GatherPlan m = gather_mix_plan(a, ia, ib, ic, rec, 256, 3, 224, 224, 196, 256, b, 768, k2);
+        named(m, "tokens_gather_tiles_kernel<3, mix>", "tiles ViT-B mix");
+        CHECK(m.mix && m.upw == 1 && m.grid_x == 98 && m.grid_y == 64 && m.lds == 13312, "tiles mix: upw %d grid y %d", m.upw, m.grid_y);
+        const struct { int knob, u; } us[] = {{1, 1}, {2, 2}, {0, 1}, {3, 1}, {-2, 1}};
+        for (const auto &q : us) { TokenizerKnobs k; k.gather_u = q.knob; CHECK(tiles(8, 1, 16, 16, 1, 256, nullptr, k).upw == q.u, "gather_u %d", q.knob); }
+        const struct { int knob, nt; } nts[] = {{0, 0}, {1, 1}, {2, 2}, {3, 3}, {4, 0}, {-1, 0}, {7, 0}};
+        for (const auto &q : nts) { TokenizerKnobs k; k.gather_nt = q.knob; CHECK(tiles(8, 1, 16, 16, 1, 256, nullptr, k).nt == q.nt, "gather_nt %d", q.knob); }
+        for (int C = 1; C <= 4; C++) {
+            const GatherPlan ok = tiles(5, C, 32, 24, 3, 256 * C, nullptr, k0);
+            CHECK(ok.err == SFCVIT_OK && ok.C == C && ok.grid_x == 2 && ok.grid_y == 2 && ok.lds == size_t(1024 + 4 * C * 1024), "tiles C %d", C);
+        }
+    }
+    refused(gather_tiles_plan("tokens_gather_tiles", nullptr, ia, ib, nullptr, 1, 3, 32, 32, 4, b, 768, k0), "tokens_gather_tiles: null pointer", "tiles null x");
+    refused(gather_tiles_plan("tokens_gather_tiles", a, ia, nullptr, nullptr, 1, 3, 32, 32, 4, b, 768, k0), "tokens_gather_tiles: null pointer", "tiles null origin");
+    refused(gather_tiles_plan("tokens_gather_tiles", a, nullptr, ib, nullptr, 1, 3, 32, 32, 4, b, 768, k0), "null pointer", "tiles null pix");
+    refused(gather_tiles_plan("tokens_gather_tiles", a, ia, ib, nullptr, 1, 3, 32, 32, 4, nullptr, 768, k0), "null pointer", "tiles null tokens");
+    refused(tiles(0, 3, 32, 32, 4, 768, nullptr, k0), "B=0 C=3 H=32 W=32 N=4 (1 <= C <= 4", "tiles B 0");
+    refused(tiles(1, 5, 32, 32, 4, 1280, nullptr, k0), "C=5", "tiles C 5");
+    refused(tiles(1, 0, 32, 32, 4, 0, nullptr, k0), "C=0", "tiles C 0");
+    refused(tiles(1, 3, 32, 36, 4, 768, nullptr, k0), "W=36", "tiles W % 8");
+    refused(tiles(1, 3, 24, 32, 3, 768, nullptr, k0), "H=24", "tiles H % 16");
+    refused(tiles(1, 3, 32, 32, 5, 768, nullptr, k0), "N=5", "tiles N");
+    refused(tiles(1, 3, 32, 32, 4, 512, nullptr, k0), "ld=512 (must be 256 * C = 768)", "tiles ld");
+    refused(gather_tiles_plan("tokens_gather_tiles", odd, ia, ib, nullptr, 1, 3, 32, 32, 4, b, 768, k0), "x and tokens must be 16-byte aligned", "tiles x");
+    refused(gather_tiles_plan("tokens_gather_tiles", a, ia, ib, nullptr, 1, 3, 32, 32, 4, odd, 768, k0), "x and tokens must be 16-byte aligned", "tiles tokens");
+    refused(tiles(1, 1, 16, 16384, 1024, 256, nullptr, k0), "W=16384 too wide", "tiles W 16384");          // 16 W W = 2^32
+    CHECK(tiles(1, 1, 32, 16376, 2047, 256, nullptr, k0).err == SFCVIT_OK, "tiles W 16376 refused");       // the widest W % 8 == 0 below it
+    refused(tiles(65535 * 4 + 1, 1, 16, 16, 1, 256, nullptr, k0), "batch 262141 too large", "tiles grid y");
+    CHECK(tiles(65535 * 4, 1, 16, 16, 1, 256, nullptr, k0).grid_y == 65535, "tiles grid y 65535");
+    refused(tiles(65535 * 8, 1, 16, 16, 1, 256, nullptr, k0), "too large", "tiles B 65535 * 8");
+    refused(tiles(1, 1, 1 << 20, 8192, 1 << 25, 256, nullptr, k0), "H * W must fit 31 bits", "tiles H * W = 2^33");     // was an int product
+    refused(tiles(big, 1, 16, 16, 1, 256, nullptr, k0), "too large", "tiles B max");
+    refused(tiles(1, 1, big, big, big, 256, nullptr, k0), "tokens_gather_tiles: B=1", "tiles H W N max");
+    refused(tiles(1, big, 16, 16, 1, 256, nullptr, k0), "C=2147483647", "tiles C max");
+
+    auto rows = [&](int x_bf16, int B, int C, int HW, int N, int P, int ld, const int32_t *perm = nullptr) {
+        return gather_plan(perm ? "tokens_gather_mix" : "tokens_gather", a, x_bf16, ia, perm, B, C, HW, N, P, b, ld);
+    };
+    {   // form boundaries
+        const GatherPlan p = rows(0, 9, 4, 1024, 4, 256, 1024);                // 2 * 8 * 1024 * 2 = 32 KiB
+        named(p, "tokens_gather_p256_kernel<fp32>", "P 256 C 4");
+        CHECK(p.form == GatherForm::P256 && p.lds == 32768 && p.grid_x == 2 && p.grid_y == 2 && p.threads == 512, "P 256 C 4: lds %zu", p.lds);
+        const GatherPlan e = rows(1, 9, 4, 1024, 4, 256, 2048);                // 64 KiB: the last ld of this form
+        named(e, "tokens_gather_p256_kernel<bf16>", "ld 2048");
+        CHECK(e.lds == 65536, "ld 2048: lds %zu", e.lds);
+        const GatherPlan r = rows(0, 9, 4, 1024, 4, 256, 2056);                // the first ld above 2048 halfwords
+        named(r, "tokens_gather_kernel<fp32>", "ld 2056");
+        CHECK(r.form == GatherForm::ROWS && r.lds == 4112 && r.grid_x == 4 && r.grid_y == 2 && r.threads == 256, "ld 2056: lds %zu", r.lds);
+        named(rows(0, 1, 3, 1028, 4, 257, 776), "tokens_gather_kernel<fp32>", "P 257");
+        named(rows(1, 1, 5, 1024, 4, 256, 1280), "tokens_gather_kernel<bf16>", "C 5");
+        named(rows(0, 1, 5, 1024, 4, 256, 1280, ic), "tokens_gather_kernel<mix>", "C 5 mix");
+        named(rows(0, 1, 3, 1024, 64, 16, 48, ic), "tokens_gather_p256_kernel<mix>", "P 16 mix");
+        // a bf16 image with a tile table goes to sfcvit_tokens_gather (Python decides): ViT-B
+        const GatherPlan v = rows(1, 256, 3, 50176, 196, 256, 768);
+        named(v, "tokens_gather_p256_kernel<bf16>", "ViT-B bf16");
+        CHECK(v.grid_x == 98 && v.grid_y == 32 && v.lds == 24576, "ViT-B bf16: grid (%d, %d) lds %zu", v.grid_x, v.grid_y, v.lds);
+        const GatherPlan m = gather_mix_plan(a, ia, nullptr, ic, rec, 9, 3, 32, 32, 64, 16, b, 48, k0);
+        named(m, "tokens_gather_p256_kernel<mix>", "mix without origin");
+        CHECK(m.HW == 1024 && m.grid_x == 32 && m.grid_y == 2, "mix without origin: HW %d", m.HW);
+    }
+    refused(gather_plan("tokens_gather", nullptr, 0, ia, nullptr, 1, 3, 1024, 64, 16, b, 48), "tokens_gather: null pointer", "gather null x");
+    refused(gather_plan("tokens_gather", a, 0, nullptr, nullptr, 1, 3, 1024, 64, 16, b, 48), "tokens_gather: null pointer", "gather null pix");
+    refused(gather_plan("tokens_gather", a, 0, ia, nullptr, 1, 3, 1024, 64, 16, nullptr, 48), "tokens_gather: null pointer", "gather null tokens");
+    refused(rows(0, 0, 3, 1024, 64, 16, 48), "B=0 C=3 HW=1024 N=64 P=16 (N * P must equal H * W)", "gather B 0");
+    refused(rows(0, 1, 3, 1024, 64, 15, 48), "P=15", "gather N * P");
+    refused(rows(0, 1, 0, 1024, 64, 16, 48), "C=0", "gather C 0");
+    refused(rows(0, 1, 3, 1024, 64, 16, 40), "ld=40 (>= P * C = 48, multiple of 8, <= 32768)", "gather ld < K");
+    refused(rows(0, 1, 3, 1024, 64, 16, 52), "ld=52", "gather ld % 8");
+    refused(rows(0, 1, 1, 32776, 1, 32776, 32776), "ld=32776", "gather ld > 32768");
+    refused(gather_plan("tokens_gather", a, 0, ia, nullptr, 1, 3, 1024, 64, 16, odd, 48), "tokens must be 16-byte aligned", "gather tokens");
+    CHECK(gather_plan("tokens_gather", odd4, 0, ia, nullptr, 1, 3, 1024, 64, 16, b, 48).err == SFCVIT_OK, "gather: x needs no alignment");
+    refused(rows(0, 65535 * 8 + 1, 3, 1024, 64, 16, 48), "batch 524281 too large", "gather grid y");
+    CHECK(rows(0, 65535 * 8, 3, 1024, 64, 16, 48).grid_y == 65535, "gather B 65535 * 8");
+    refused(rows(0, big, 3, 1024, 64, 16, 48), "too large", "gather B max");
+    refused(rows(0, 1, big, big, 1, big, 32768), "P * C = 4611686014132420609", "gather P C max");        // was an int product
+    {
+        const GatherPlan p = gather_plan("tokens_gather", a, 0, ia, nullptr, 8, 1, big, big, 1, b, 8);    // N = HW = INT32_MAX, one pixel per token
+        CHECK(p.err == SFCVIT_OK && p.form == GatherForm::P256 && p.grid_x == (1 << 30) && p.grid_y == 1, "gather N max: grid x %d", p.grid_x);
+    }
+    refused(gather_mix_plan(a, ia, nullptr, nullptr, rec, 1, 3, 32, 32, 64, 16, b, 48, k0), "tokens_gather_mix: null perm / rec", "mix null perm");
+    refused(gather_mix_plan(a, ia, nullptr, ic, nullptr, 1, 3, 32, 32, 64, 16, b, 48, k0), "tokens_gather_mix: null perm / rec", "mix null rec");
+    refused(gather_mix_plan(a, ia, nullptr, ic, rec, 1, 3, 0, 32, 64, 16, b, 48, k0), "tokens_gather_mix: H=0 W=32", "mix H 0");
+    refused(gather_mix_plan(a, ia, nullptr, ic, rec, 1, 3, 65536, 32768, 64, 16, b, 48, k0), "tokens_gather_mix: H=65536 W=32768", "mix H W = 2^31");
+    refused(gather_mix_plan(a, ia, nullptr, ic, rec, 1, 3, big, big, 64, 16, b, 48, k0), "tokens_gather_mix: H=2147483647", "mix H W max");
+    refused(gather_mix_plan(odd, ia, nullptr, ic, rec, 1, 3, 32, 32, 64, 16, b, 48, k0), "tokens_gather_mix: x must be 16-byte aligned", "mix x");
+    refused(gather_mix_plan(a, ia, ib, ic, rec, 1, 3, 32, 32, 64, 16, b, 48, k0), "P=16 with a tile origin table", "mix P with origin");
+    refused(gather_mix_plan(a, ia, ib, ic, rec, 1, 3, 32, 32, 4, 256, b, 512, k0), "tokens_gather_mix: ld=512", "mix tiles ld");
+    refused(gather_mix_plan(a, ia, ib, ic, rec, 1, 5, 32, 32, 4, 256, b, 1280, k0), "tokens_gather_mix: B=1 C=5", "mix tiles C 5");
+    refused(gather_mix_plan(a, ia, nullptr, ic, rec, 1, 3, 32, 32, 64, 15, b, 48, k0), "tokens_gather_mix: B=1 C=3 HW=1024 N=64 P=15", "mix N * P");
+    refused(gather_mix_plan(nullptr, ia, nullptr, ic, rec, 1, 3, 32, 32, 64, 16, b, 48, k0), "tokens_gather_mix: null pointer", "mix null x");
+
+    // ---- patch embedding ----
+    auto pe_args = [&](int B, int C, int N, int P, int D, const std::vector<int32_t> &cnt) {
+        sfcvit_patch_embed_args q{};
+        q.x = a; q.pix = ia; q.w = ptr(7); q.bias = ptr(8); q.y = b; q.dw = ptr(9); q.dbias = ptr(10); q.workspace = ptr(11);
+        q.workspace_bytes = INT64_MAX;
+        q.B = B; q.C = C; q.N = N; q.P = P; q.D = D; q.HW = int(int64_t(N) * P);
+        if (!cnt.empty()) { q.desc = ib; q.desc_ncls = int(cnt.size()); for (size_t c = 0; c < cnt.size() && c < 8; c++) q.desc_cnt[c] = cnt[c]; }
+        return q;
+    };
+    {   // the benchmark shapes with the class counts of the real Hilbert tables
+        const std::vector<int32_t> cb = tile_class_counts(SFCVIT_CURVE_HILBERT, 224), cl = tile_class_counts(SFCVIT_CURVE_HILBERT, 384);
+        CHECK(cb == std::vector<int32_t>({49, 52, 49, 46}) && cl == std::vector<int32_t>({148, 144, 140, 144}), "hilbert class counts");
+        struct S { int B, N, D; const std::vector<int32_t> &cnt; int n_row_tiles, grid_f, KR, nz, grid_b; int64_t ws_f, ws_b, tiled_b; };
+        const S shapes[] = {{256, 196, 768, cb, 392, 1176, 2240, 24, 216, 9437184, 68419584, 56623104},
+                            {64, 576, 1024, cl, 288, 1152, 2368, 16, 192, 12582912, 69206016, 50331648}};
+        for (const S &q : shapes) {
+            sfcvit_patch_embed_args x = pe_args(q.B, 3, q.N, 256, q.D, q.cnt);
+            CHECK(patch_embed_geometry(q.B, 3, q.N, 256, q.D, false).ws_bytes == q.ws_f && patch_embed_geometry(q.B, 3, q.N, 256, q.D, true).ws_bytes == q.ws_b &&
+                  pe2_bwd_workspace(3, q.D) == q.tiled_b, "patch embed D %d: workspaces", q.D);
+            x.workspace_bytes = q.ws_f;
+            const PatchEmbedPlan f = patch_embed_plan(&x, false);
+            named(f, "pe2_fwd_kernel<fp32>", "tiled forward");
+            CHECK(f.form == PeForm::TILED && f.n_row_tiles == q.n_row_tiles && f.groups == q.n_row_tiles / 8 && f.grid == q.grid_f && f.lds == 100352 &&
+                  f.permute_grid == 1024 && f.wp_bytes == int64_t(4) * q.D * 768 * 2 && f.ws_bytes == q.ws_f && f.M == q.B * q.N && f.Kp == 768,
+                  "tiled forward D %d: row tiles %d grid %d lds %zu", q.D, f.n_row_tiles, f.grid, f.lds);
+            x.workspace_bytes = q.ws_f - 1;
+            refused(patch_embed_plan(&x, false), "patch_embed_fwd: workspace of", "forward workspace one byte short");
+            x.workspace_bytes = q.ws_b;
+            x.x_is_bf16 = 1;
+            const PatchEmbedPlan g = patch_embed_plan(&x, true);
+            named(g, "pe2_bwd_kernel<bf16>", "tiled backward");
+            CHECK(g.form == PeForm::TILED && g.KR == q.KR && g.nz == q.nz && g.grid == q.grid_b && g.lds == 131072 && g.dbias &&
+                  g.slab_bytes == int64_t(q.nz) * q.D * 768 * 4 && g.slab_bytes <= q.tiled_b && g.reduce_grid == q.D * 3 && g.ws_bytes == q.ws_b,
+                  "tiled backward D %d: KR %d nz %d grid %d", q.D, g.KR, g.nz, g.grid);
+            x.workspace_bytes = q.ws_b - 1;
+            refused(patch_embed_plan(&x, true), "patch_embed_bwd: workspace of", "backward workspace one byte short");
+            // without the descriptor: the generic kernels at the same shape
+            sfcvit_patch_embed_args y = pe_args(q.B, 3, q.N, 256, q.D, {});
+            const PatchEmbedPlan gf = patch_embed_plan(&y, false), gb = patch_embed_plan(&y, true);
+            named(gf, "pe_fwd_kernel<fp32>", "generic forward");
+            named(gb, "pe_bwd_kernel<fp32>", "generic backward");
+            const int tiles_d = q.D / 128, M = q.B * q.N, splits = (1024 + tiles_d * 6 - 1) / (tiles_d * 6), mps = ((M / 64 + splits - 1) / splits) * 64;
+            CHECK(gf.form == PeForm::GENERIC && gf.grid == tiles_d * (M / 128) && gf.lds == 65536 && gf.permute_grid == q.D * 3 && gf.wp_bytes == int64_t(q.D) * 768 * 2,
+                  "generic forward D %d: grid %d", q.D, gf.grid);
+            CHECK(gb.splits == splits && gb.m_per_split == mps && gb.zs == (M + mps - 1) / mps && gb.grid == 6 * tiles_d * gb.zs && gb.lds == 65536 &&
+                  gb.reduce_grid == q.D * 48 && gb.slab_bytes == int64_t(splits) * q.D * 768 * 4, "generic backward D %d: splits %d zs %d", q.D, gb.splits, gb.zs);
+        }
+        // form boundaries, forward and backward alike
+        struct F { int C, N, P, D, HW; int ncls; bool tiled; };
+        const F forms[] = {{3, 196, 256, 512, 50176, 4, true}, {3, 196, 256, 384, 50176, 4, false}, {3, 784, 64, 768, 50176, 4, false},
+                           {3, 196, 256, 768, 50176, 0, false}, {3, 196, 256, 768, 50176, 9, false}, {3, 196, 256, 768, 50176, 8, true},
+                           {1, 1, 256, 256, 256, 1, true}};
+        for (const F &q : forms)
+            for (int bwd = 0; bwd < 2; bwd++) {
+                sfcvit_patch_embed_args x = pe_args(4, q.C, q.N, q.P, q.D, std::vector<int32_t>(q.ncls > 0 ? q.ncls : 1, q.N / (q.ncls > 0 ? q.ncls : 1)));
+                x.desc_ncls = q.ncls;
+                const PatchEmbedPlan p = patch_embed_plan(&x, bwd);
+                CHECK(p.err == SFCVIT_OK && (p.form == PeForm::TILED) == q.tiled, "patch embed P %d D %d ncls %d: form (%s)", q.P, q.D, q.ncls, p.msg);
+            }
+        {   // H * W % 8 != 0 with P = 256 never reaches the choice of form: N * P == H * W is refused first
+            sfcvit_patch_embed_args x = pe_args(4, 3, 196, 256, 768, cb);
+            x.HW = 50180;
+            refused(patch_embed_plan(&x, false), "N*P=50176 must equal H*W=50180", "HW % 8");
+        }
+    }
+    {   // the query: the parent's values, and 0 where there is no such shape
+        const struct { int B, C, N, P, D; int64_t f, b; } ws[] = {{256, 3, 196, 256, 512, 6291456, 67633152}, {256, 3, 196, 256, 384, 4718592, 67239936},
+            {128, 3, 64, 16, 256, 196608, 6291456}, {8, 3, 16, 64, 192, 589824, 294912}, {2, 1, 27, 27, 104, 53248, 13312}, {4, 3, 4, 256, 256, 3145728, 62914560},
+            {1, 1, 1, 1, 8, 1024, 256}, {256, 3, 784, 64, 768, 2359296, 50724864}, {3, 4, 9, 256, 1280, 20971520, 41943040}, {512, 3, 4, 256, 2048, 25165824, 69206016}};
+        for (const auto &q : ws)
+            CHECK(patch_embed_geometry(q.B, q.C, q.N, q.P, q.D, false).ws_bytes == q.f && patch_embed_geometry(q.B, q.C, q.N, q.P, q.D, true).ws_bytes == q.b,
+                  "workspace %d %d %d %d %d: %lld / %lld", q.B, q.C, q.N, q.P, q.D, (long long)patch_embed_geometry(q.B, q.C, q.N, q.P, q.D, false).ws_bytes,
+                  (long long)patch_embed_geometry(q.B, q.C, q.N, q.P, q.D, true).ws_bytes);
+        for (int bwd = 0; bwd < 2; bwd++) {
+            CHECK(!patch_embed_geometry(0, 3, 4, 256, 256, bwd).ws_bytes && !patch_embed_geometry(1, -3, 4, 256, 256, bwd).ws_bytes &&
+                  !patch_embed_geometry(1, 3, 0, 256, 256, bwd).ws_bytes && !patch_embed_geometry(1, 3, 4, 0, 256, bwd).ws_bytes &&
+                  !patch_embed_geometry(1, 3, 4, 256, -8, bwd).ws_bytes, "workspace of a non-positive dimension");
+            // extents no tensor can have: singly and in pairs
+            const int v[] = {1, 8, big};
+            for (int B : v) for (int C : v) for (int N : v) for (int P : v) for (int D : v) {
+                const int64_t w = patch_embed_geometry(B, C, N, P, D, bwd).ws_bytes;
+                CHECK(w >= 0, "workspace %d %d %d %d %d negative", B, C, N, P, D);
+                sfcvit_patch_embed_args x = pe_args(B, C, N, P, D == big ? big - 7 : D, {4});
+                x.HW = int64_t(N) * P > big ? big : int(int64_t(N) * P);
+                const PatchEmbedPlan p = patch_embed_plan(&x, bwd);
+                CHECK(p.err == SFCVIT_OK || p.err == SFCVIT_EINVAL, "patch embed extents");
+            }
+        }
+        sfcvit_patch_embed_args x = pe_args(1, big, 1, 8, 8, {});
+        refused(patch_embed_plan(&x, false), "patch_embed_fwd: C*P=17179869176 D=8 too large", "C * P past int");          // was an int product
+        x = pe_args(1, 1 << 20, 1, 1 << 10, big - 7, {});
+        refused(patch_embed_plan(&x, true), "patch_embed_bwd: C*P=1073741824 D=2147483640 too large", "D * Kp past 2^35");
+        x = pe_args(1 << 15, 1, (1 << 15) - 1, 8, 1 << 16, {});               // 2^9 x (2^23 - 2^8) tiles
+        refused(patch_embed_plan(&x, false), "too many workgroups", "forward grid past int");                              // was an int product
+        CHECK(patch_embed_plan(&x, true).err == SFCVIT_OK, "backward at that shape refused");
+    }
+    {   // the two dead fall-backs: whatever the class counts, the tiled forms need no more than the query reports
+        uint32_t rng = 12345;
+        auto next = [&](uint32_t n) { rng = rng * 1664525u + 1013904223u; return (rng >> 8) % n; };
+        for (int it = 0; it < 4000; it++) {
+            const int C = 1 + int(next(4)), D = 256 * (1 + int(next(it % 8 ? 8 : 40))), ncls = 1 + int(next(8));
+            const int N = ncls + int(next(it % 3 ? 64 : 1100)), B = 1 + int(next(it % 5 ? 16 : 600));
+            std::vector<int32_t> cnt(ncls, 1);
+            for (int left = N - ncls; left > 0;) { const int take = 1 + int(next(left)); cnt[next(ncls)] += take; left -= take; }
+            sfcvit_patch_embed_args x = pe_args(B, C, N, 256, D, cnt);
+            const PatchEmbedPlan f = patch_embed_plan(&x, false), g = patch_embed_plan(&x, true);
+            const int tiles = (D / 256) * C, G = 8 * (32 / tiles > 1 ? 32 / tiles : 1);
+            CHECK(f.err == SFCVIT_OK && f.form == PeForm::TILED && f.wp_bytes == int64_t(ncls) * D * C * 256 * 2 && f.wp_bytes <= f.ws_bytes &&
+                  f.ws_bytes == patch_embed_geometry(B, C, N, 256, D, false).ws_bytes, "sweep forward B %d C %d N %d D %d ncls %d (%s)", B, C, N, D, ncls, f.msg);
+            CHECK(g.err == SFCVIT_OK && g.form == PeForm::TILED && g.nz >= 1 && g.nz <= G && g.KR % 64 == 0 && g.slab_bytes <= pe2_bwd_workspace(C, D) &&
+                  pe2_bwd_workspace(C, D) <= g.ws_bytes && g.ws_bytes == patch_embed_geometry(B, C, N, 256, D, true).ws_bytes,
+                  "sweep backward B %d C %d N %d D %d ncls %d: nz %d G %d (%s)", B, C, N, D, ncls, g.nz, G, g.msg);
+            int64_t rows_covered = 0, nz = 0;
+            for (int c = 0; c < ncls; c++) { const int64_t r = int64_t(cnt[c]) * B; nz += (r + g.KR - 1) / g.KR; rows_covered += r; }
+            CHECK(nz == g.nz && rows_covered == int64_t(B) * N, "sweep backward: nz %lld, the plan's %d", (long long)nz, g.nz);
+            x.desc = nullptr;                                        // the generic forms at the same shape: zs slabs within the query
+            const PatchEmbedPlan gb = patch_embed_plan(&x, true);
+            CHECK(gb.err == SFCVIT_OK && gb.zs >= 1 && gb.zs <= gb.splits && int64_t(gb.zs) * gb.m_per_split >= gb.M && gb.slab_bytes <= gb.ws_bytes, "sweep generic backward");
+        }
+    }
+    {   // refusals, in check order
+        const std::vector<int32_t> none;
+        auto bad = [&](bool bwd, const char *frag, const char *what, auto edit) {
+            sfcvit_patch_embed_args x = pe_args(1, 3, 8, 8, 8, none);
+            edit(x);
+            refused(patch_embed_plan(&x, bwd), frag, what);
+        };
+        refused(patch_embed_plan(nullptr, false), "patch_embed_fwd: null pointer", "pe null a");
+        refused(patch_embed_plan(nullptr, true), "patch_embed_bwd: null pointer", "pe null a");
+        bad(false, "patch_embed_fwd: null pointer", "pe null x", [](auto &x) { x.x = nullptr; });
+        bad(true, "patch_embed_bwd: null pointer", "pe null pix", [](auto &x) { x.pix = nullptr; });
+        bad(true, "patch_embed_bwd: null pointer", "pe null y", [](auto &x) { x.y = nullptr; });
+        bad(false, "patch_embed_fwd: non-positive dimension", "pe B 0", [](auto &x) { x.B = 0; });
+        bad(true, "patch_embed_bwd: non-positive dimension", "pe D -8", [](auto &x) { x.D = -8; });
+        bad(false, "patch_embed_fwd: N*P=64 must equal H*W=72", "pe HW", [](auto &x) { x.HW = 72; });
+        bad(false, "patch_embed_fwd: D=12 must be a multiple of 8", "pe D 12", [](auto &x) { x.D = 12; });
+        bad(true, "patch_embed_bwd: B*N too large", "pe B N", [](auto &x) { x.B = 1 << 28; });
+        bad(true, "patch_embed_bwd: B*N too large", "pe B max", [&](auto &x) { x.B = big; });
+        bad(false, "patch_embed_fwd: alignment", "pe x", [&](auto &x) { x.x = odd; });
+        bad(false, "patch_embed_fwd: alignment", "pe y", [&](auto &x) { x.y = odd; });
+        bad(true, "patch_embed_bwd: weight / bias alignment (w 16 bytes, bias 8 bytes)", "pe w", [&](auto &x) { x.w = odd; });
+        bad(false, "patch_embed_fwd: weight / bias alignment", "pe bias", [&](auto &x) { x.bias = odd4; });
+        bad(false, "patch_embed_fwd: null weight", "pe null w", [](auto &x) { x.w = nullptr; });
+        bad(true, "patch_embed_bwd: null dw", "pe null dw", [](auto &x) { x.dw = nullptr; });
+        bad(false, "patch_embed_fwd: workspace of 3072 bytes needed", "pe null workspace", [](auto &x) { x.workspace = nullptr; });
+        bad(false, "patch_embed_fwd: workspace of 3072 bytes needed", "pe short workspace", [](auto &x) { x.workspace_bytes = 3071; });
+        bad(true, "patch_embed_bwd: workspace of 768 bytes needed", "pe workspace alignment", [&](auto &x) { x.workspace = odd; });
+        sfcvit_patch_embed_args x = pe_args(1, 3, 8, 8, 8, none);
+        x.bias = static_cast<char *>(ptr(8)) + 8; x.dbias = nullptr; x.w = nullptr;
+        const PatchEmbedPlan p = patch_embed_plan(&x, true);
+        CHECK(p.err == SFCVIT_OK && !p.dbias && p.K == 24 && p.Kp == 24 && p.M == 8 && p.splits == 1 && p.zs == 1 && p.m_per_split == 64 && p.grid == 1,
+              "pe backward without w / dbias: %s", p.msg);
+    }
+
+    // ---- hierarchical tokenizer ----
+    auto hier_args = [&](int L, int D, int C, const std::vector<int32_t> &P, int N, int B, bool fuse) {
+        sfcvit_hier_args q{};
+        q.x = a; q.h = b; q.y = fuse ? ptr(7) : nullptr; q.wf = fuse ? ptr(8) : nullptr; q.bf = fuse ? ptr(9) : nullptr;
+        for (int l = 0; l < L && l < 4; l++) { q.pix[l] = ia; q.w[l] = ptr(10); q.b[l] = ptr(11); q.P[l] = P[l]; }
+        q.B = B; q.C = C; q.N = N; q.L = L; q.D = D; q.HW = int(int64_t(N) * P[0]);
+        return q;
+    };
+    {
+        struct H { int L, D, C; std::vector<int32_t> P; int N, B; int kp_sum, lds_fuse, lds_levels; };
+        const H hs[] = {{1, 256, 1, {8}, 5, 13, 32, 38912, 5120}, {2, 128, 3, {8, 8}, 8, 2, 64, 43008, 9216}, {4, 64, 3, {64, 64, 64, 64}, 16, 3, 768, 133120, 99328},
+                        {3, 256, 3, {16, 16, 16}, 64, 2, 192, 124928, 25600}, {4, 192, 3, {32, 32, 32, 32}, 4, 5, 384, 149504, 50176},
+                        {4, 192, 1, {96, 96, 96, 96}, 4, 5, 384, 149504, 50176}};
+        for (const H &q : hs) {
+            sfcvit_hier_args x = hier_args(q.L, q.D, q.C, q.P, q.N, q.B, true);
+            const HierPlan f = hier_plan(&x);
+            named(f, "hier_fwd_kernel<fp32, fuse>", "hier fuse");
+            CHECK(f.fuse && f.kp_sum == q.kp_sum && f.E == q.L * q.D && f.h_stride == 2 * f.E + 16 && f.a_stride == 2 * q.kp_sum + 16 && f.lds == q.lds_fuse &&
+                  f.M == q.B * q.N && f.grid == (q.B * q.N + 63) / 64, "hier L %d D %d: kp %d lds %d grid %d", q.L, q.D, f.kp_sum, f.lds, f.grid);
+            x = hier_args(q.L, q.D, q.C, q.P, q.N, q.B, false);
+            x.x_is_bf16 = 1;
+            const HierPlan l = hier_plan(&x);
+            named(l, "hier_fwd_kernel<bf16, levels>", "hier levels");
+            CHECK(!l.fuse && l.lds == q.lds_levels && l.lds == HT_ROWS * l.a_stride && l.grid == f.grid, "hier L %d D %d levels: lds %d", q.L, q.D, l.lds);
+        }
+        int E = 0, kp = 0;
+        auto sfcvit_hier_tokenizer_supported = [](int L, int D, int C, const int32_t *P) { int e = 0, k = 0; return hier_envelope(L, D, C, P, e, k); };   // the entry point's body
+        const int32_t inside[4] = {96, 96, 96, 192}, outside[4] = {96, 96, 128, 192}, k104[4] = {104, 104, 104, 104}, k768[4] = {256, 256, 256, 256};
+        CHECK(hier_envelope(4, 192, 1, inside, E, kp) && E == 768 && kp == 480 && 64 * (2 * E + 16) + 64 * (2 * kp + 16) == 161792, "hier: kp 480 is inside 160 KiB");
+        CHECK(!hier_envelope(4, 192, 1, outside, E, kp) && !hier_envelope(4, 192, 1, k104, E, kp) && !hier_envelope(4, 192, 3, k768, E, kp), "hier: kp 512 is outside");
+        const int32_t p16[5] = {16, 16, 16, 16, 16}, p4[2] = {4, 4}, pneg[2] = {16, -16}, pbig[4] = {big, big, big, big}, p8big[4] = {big - 7, 8, 8, 8};
+        CHECK(!sfcvit_hier_tokenizer_supported(3, 64, 3, p16) && !sfcvit_hier_tokenizer_supported(2, 96, 3, p16) && !sfcvit_hier_tokenizer_supported(2, 128, 3, p4) &&
+              !sfcvit_hier_tokenizer_supported(5, 256, 3, p16) && !sfcvit_hier_tokenizer_supported(0, 256, 3, p16) && !sfcvit_hier_tokenizer_supported(2, 128, 3, pneg) &&
+              !sfcvit_hier_tokenizer_supported(2, 128, 0, p16) && !sfcvit_hier_tokenizer_supported(2, 128, 3, nullptr) && !sfcvit_hier_tokenizer_supported(2, 0, 3, p16),
+              "hier envelope: refusals");
+        CHECK(!sfcvit_hier_tokenizer_supported(4, big - 63, big, pbig) && !sfcvit_hier_tokenizer_supported(4, 1 << 30, 8, p8big) &&
+              !sfcvit_hier_tokenizer_supported(4, 64, big, pbig) && !sfcvit_hier_tokenizer_supported(1, 256, 1, p8big), "hier envelope: extents");
+        const std::vector<int32_t> P3 = {16, 16, 16};
+        auto bad = [&](const char *frag, const char *what, auto edit) {
+            sfcvit_hier_args x = hier_args(3, 256, 3, P3, 64, 2, true);
+            edit(x);
+            refused(hier_plan(&x), frag, what);
+        };
+        refused(hier_plan(nullptr), "hier_tokenizer_fwd: null pointer", "hier null a");
+        bad("hier_tokenizer_fwd: null pointer", "hier null x", [](auto &x) { x.x = nullptr; });
+        bad("hier_tokenizer_fwd: null pointer", "hier null h", [](auto &x) { x.h = nullptr; });
+        bad("hier_tokenizer_fwd: null pointer", "hier wf without y", [](auto &x) { x.y = nullptr; });
+        bad("hier_tokenizer_fwd: B=0 C=3 HW=1024 N=64", "hier B 0", [](auto &x) { x.B = 0; });
+        bad("outside the fused kernel's envelope", "hier D 96", [](auto &x) { x.D = 96; });
+        bad("hier_tokenizer_fwd: L=5 D=256 C=3 outside", "hier L 5", [](auto &x) { x.L = 5; });
+        bad("hier_tokenizer_fwd: too many token rows", "hier rows", [](auto &x) { x.B = 1 << 25; });
+        bad("hier_tokenizer_fwd: too many token rows", "hier B N max", [&](auto &x) { x.B = big; x.N = big; });
+        bad("hier_tokenizer_fwd: level 1: null pointer", "hier null pix 1", [](auto &x) { x.pix[1] = nullptr; });
+        bad("hier_tokenizer_fwd: level 2: null pointer", "hier null w 2", [](auto &x) { x.w[2] = nullptr; });
+        bad("hier_tokenizer_fwd: level 1: N * P = 64 * 8 != H*W = 1024 (levels must share the token count)", "hier P 1", [](auto &x) { x.P[1] = 8; });
+        bad("hier_tokenizer_fwd: level 0: weight / bias alignment", "hier w 0", [&](auto &x) { x.w[0] = odd; });
+        bad("hier_tokenizer_fwd: level 2: weight / bias alignment", "hier b 2", [&](auto &x) { x.b[2] = odd4; });
+        bad("hier_tokenizer_fwd: fusion weight / output alignment", "hier wf", [&](auto &x) { x.wf = odd; });
+        bad("hier_tokenizer_fwd: fusion weight / output alignment", "hier h", [&](auto &x) { x.h = odd; });
+        bad("hier_tokenizer_fwd: fusion weight / output alignment", "hier bf", [&](auto &x) { x.bf = odd4; });
+        sfcvit_hier_args x = hier_args(1, 256, 8, {1}, big - 64, 1, false);            // the most rows it takes: 2^31 - 65
+        CHECK(hier_plan(&x).err == SFCVIT_OK && hier_plan(&x).grid == 33554431, "hier: B * N = %d refused (%s)", x.N, hier_plan(&x).msg);
+    }
+    {   // resampling: host arrays of exactly L entries
+        for (int bwd = 0; bwd < 2; bwd++) {
+            const char *name = bwd ? "hier_resample_concat_bwd_kernel" : "hier_resample_concat_kernel", *pre = bwd ? "hier_resample_concat_bwd: " : "hier_resample_concat: ";
+            std::unique_ptr<int32_t[]> n(new int32_t[3]{64, 16, 64});
+            std::unique_ptr<const void *[]> lev(new const void *[3]{ptr(7), ptr(8), ptr(9)});
+            const ResamplePlan p = resample_plan(bwd, lev.get(), n.get(), 3, 3, 64, 40, a);
+            named(p, name, "resample");
+            if (!bwd) CHECK(p.blocks[0] == (3 * 64 * 3 * 5 + 255) / 256 && p.blocks[1] == 0, "resample forward: %d workgroups", p.blocks[0]);
+            else CHECK(p.blocks[0] == 4 && p.blocks[1] == 1 && p.blocks[2] == 4, "resample backward: %d %d %d workgroups", p.blocks[0], p.blocks[1], p.blocks[2]);
+            const ResamplePlan v = resample_plan(bwd, lev.get(), n.get(), 1, 256, 64, 768, a);       // 256 x 64 rows of 96 vectors: 6144 workgroups
+            CHECK(v.err == SFCVIT_OK && v.blocks[0] == 6144, "resample 256 x 64 x 768: %d", v.blocks[0]);
+            n[0] = 1 << 20;
+            const ResamplePlan c = resample_plan(bwd, lev.get(), n.get(), 3, 64, 1 << 20, 1024, a);
+            CHECK(c.err == SFCVIT_OK && c.blocks[0] == 65536 && (!bwd || (c.blocks[1] == 512 && c.blocks[2] == 2048)), "resample cap: %d", c.blocks[0]);
+            n[0] = big; n[1] = big; n[2] = big - 1;
+            const ResamplePlan e = resample_plan(bwd, lev.get(), n.get(), 3, big, big, big - 7, a);
+            CHECK(e.err == SFCVIT_OK && e.blocks[0] == 65536 && (!bwd || (e.blocks[1] == 65536 && e.blocks[2] == 65536)), "resample extents: %s", e.msg);
+            n[0] = 64; n[1] = 16; n[2] = 64;
+            auto msg = [&](const char *rest) { static char buf[160]; std::snprintf(buf, sizeof(buf), "%s%s", pre, rest); return buf; };
+            refused(resample_plan(bwd, nullptr, n.get(), 3, 3, 64, 40, a), msg("null pointer"), "resample null levels");
+            refused(resample_plan(bwd, lev.get(), nullptr, 3, 3, 64, 40, a), msg("null pointer"), "resample null counts");
+            refused(resample_plan(bwd, lev.get(), n.get(), 3, 3, 64, 40, nullptr), msg("null pointer"), "resample null cat");
+            refused(resample_plan(bwd, lev.get(), n.get(), 0, 3, 64, 40, a), msg("L=0 B=3 N0=64 D=40 (1 <= L <= 8, D % 8 == 0)"), "resample L 0");
+            refused(resample_plan(bwd, lev.get(), n.get(), 9, 3, 64, 40, a), msg("L=9"), "resample L 9");
+            refused(resample_plan(bwd, lev.get(), n.get(), 3, 0, 64, 40, a), msg("L=3 B=0"), "resample B 0");
+            refused(resample_plan(bwd, lev.get(), n.get(), 3, 3, 64, 44, a), msg("L=3 B=3 N0=64 D=44"), "resample D 44");
+            refused(resample_plan(bwd, lev.get(), n.get(), 3, 3, 48, 40, a), msg("the first level has 64 tokens, not N0 = 48"), "resample N0");
+            refused(resample_plan(bwd, lev.get(), n.get(), 3, 3, 64, 40, odd), msg("alignment"), "resample cat");
+            n[1] = 0;
+            refused(resample_plan(bwd, lev.get(), n.get(), 3, 3, 64, 40, a), msg("level 1 (pointer / token count / alignment)"), "resample n 1");
+            n[1] = 16; lev[2] = nullptr;
+            refused(resample_plan(bwd, lev.get(), n.get(), 3, 3, 64, 40, a), msg("level 2 (pointer / token count / alignment)"), "resample null level 2");
+            lev[2] = ptr(9); lev[0] = odd;
+            refused(resample_plan(bwd, lev.get(), n.get(), 3, 3, 64, 40, a), msg("level 0 (pointer / token count / alignment)"), "resample level 0");
+        }
+    }
+
+    // ---- MixUp / CutMix ----
+    {
+        auto far = [](int i) { return reinterpret_cast<void *>(uintptr_t(i + 1) << 44); };         // 16 TiB apart
+        const MixPlan p = mix_images_plan(far(0), ia, rec, far(1), 256, 3, 224, 224);
+        CHECK(p.err == SFCVIT_OK && p.vec == 4 && p.HW == 50176 && p.grid == 49 && p.grid_y == 768, "mix_images ViT-B: vec %d grid (%d, %d)", p.vec, p.grid, p.grid_y);
+        const MixPlan q = mix_images_plan(far(0), ia, rec, far(1), 2048, 3, 27, 27);
+        CHECK(q.err == SFCVIT_OK && q.vec == 1 && q.HW == 729 && q.grid == 3 && q.grid_y == 4096, "mix_images 27 px: vec %d grid (%d, %d)", q.vec, q.grid, q.grid_y);
+        const MixPlan e = mix_images_plan(far(0), ia, rec, reinterpret_cast<void *>(uintptr_t(1) << 63), 1, 1, big, 1);
+        CHECK(e.err == SFCVIT_OK && e.vec == 1 && e.grid == (1 << 23), "mix_images H max: %s grid %d", e.msg, e.grid);
+        refused(mix_images_plan(nullptr, ia, rec, b, 1, 1, 4, 4), "mix_images: null pointer", "mix_images null x");
+        refused(mix_images_plan(a, nullptr, rec, b, 1, 1, 4, 4), "mix_images: null pointer", "mix_images null perm");
+        refused(mix_images_plan(a, ia, nullptr, b, 1, 1, 4, 4), "mix_images: null pointer", "mix_images null rec");
+        refused(mix_images_plan(a, ia, rec, nullptr, 1, 1, 4, 4), "mix_images: null pointer", "mix_images null out");
+        refused(mix_images_plan(a, ia, rec, b, 0, 1, 4, 4), "mix_images: B=0 C=1 H=4 W=4", "mix_images B 0");
+        refused(mix_images_plan(a, ia, rec, b, 1, 1, 65536, 32768), "mix_images: B=1 C=1 H=65536 W=32768", "mix_images H W = 2^31");
+        refused(mix_images_plan(a, ia, rec, b, 65536, 32768, 4, 4), "mix_images: B=65536 C=32768", "mix_images B C = 2^31");
+        refused(mix_images_plan(a, ia, rec, b, big, big, big, big), "mix_images: B=2147483647", "mix_images extents");
+        refused(mix_images_plan(a, ia, rec, a, 1, 1, 4, 4), "mix_images: out must not alias x", "mix_images out = x");
+        refused(mix_images_plan(a, ia, rec, static_cast<char *>(a) + 32, 1, 1, 4, 4), "must not alias", "mix_images overlap");
+        refused(mix_images_plan(a, ia, rec, b, big, 1, big, 1), "must not alias", "mix_images 2^64 bytes");
+        CHECK(mix_images_plan(a, ia, rec, static_cast<char *>(a) + 64, 1, 1, 4, 4).err == SFCVIT_OK, "mix_images: adjacent buffers refused");
+        refused(mix_images_plan(a, ia, rec, odd, 1, 1, 4, 4), "mix_images: x and out must be 16-byte aligned", "mix_images out");
+        const float *f = static_cast<const float *>(ptr(7));
+        const int64_t *ya = static_cast<const int64_t *>(ptr(8)), *yb = static_cast<const int64_t *>(ptr(9));
+        CHECK(soft_ce_pair_plan(a, ya, yb, rec, f, 256, 1000, 1024).grid == 64 && soft_ce_pair_plan(a, ya, yb, rec, f, 5, 10, 10).grid == 2 &&
+              soft_ce_pair_plan(a, ya, yb, rec, f, big, big, big).grid == (1 << 29), "soft_ce_pair grid");
+        refused(soft_ce_pair_plan(nullptr, ya, yb, rec, f, 1, 10, 16), "soft_ce_pair: null pointer", "soft_ce_pair null logits");
+        refused(soft_ce_pair_plan(a, nullptr, yb, rec, f, 1, 10, 16), "soft_ce_pair: null pointer", "soft_ce_pair null y_a");
+        refused(soft_ce_pair_plan(a, ya, nullptr, rec, f, 1, 10, 16), "soft_ce_pair: null pointer", "soft_ce_pair null y_b");
+        refused(soft_ce_pair_plan(a, ya, yb, nullptr, f, 1, 10, 16), "soft_ce_pair: null pointer", "soft_ce_pair null rec");
+        refused(soft_ce_pair_plan(a, ya, yb, rec, nullptr, 1, 10, 16), "soft_ce_pair: null pointer", "soft_ce_pair null loss");
+        refused(soft_ce_pair_plan(a, ya, yb, rec, f, 0, 10, 16), "soft_ce_pair: B=0 C=10 ld=16", "soft_ce_pair B 0");
+        refused(soft_ce_pair_plan(a, ya, yb, rec, f, 1, 0, 16), "soft_ce_pair: B=1 C=0", "soft_ce_pair C 0");
+        refused(soft_ce_pair_plan(a, ya, yb, rec, f, 1, 10, 8), "soft_ce_pair: B=1 C=10 ld=8", "soft_ce_pair ld");
+    }
+    char name[96];
+    CHECK(sfcvit_last_tokenizer_kernel(name, sizeof(name)) == SFCVIT_OK && !std::strcmp(name, "none"), "tokenizer: last kernel '%s'", name);
+    CHECK(sfcvit_last_tokenizer_kernel(nullptr, 4) == SFCVIT_EINVAL, "tokenizer: null name buffer accepted");
+}
+
 int main() {
     const int curves[] = {SFCVIT_CURVE_HILBERT, SFCVIT_CURVE_Z, SFCVIT_CURVE_MOORE, SFCVIT_CURVE_PEANO, SFCVIT_CURVE_RASTER,
                           SFCVIT_CURVE_SPIRAL, SFCVIT_CURVE_HILBERT_T};
@@ -1229,6 +1663,7 @@ int main() {
     check_dwconv();
     check_tokmix();
     check_rowwise();
+    check_tokenizer();
     check_drop_path();
     check_model_ema();
     check_grad_accum();

@@ -4,12 +4,12 @@
 // The mixing gather kernels themselves live with the gather in patch_embed.hip; mix.h is what the three share.
 #include "common_host.h"
 #include "mix.h"
+#include "tokenizer.h"
 
 namespace sfcvit {
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
+constexpr int THREADS = MIX_THREADS, WAVES = MIX_WAVES;
 
 // out[b, c, p] = mix(x[b, c, p], x[perm[b], c, p]): a thread owns V consecutive pixels of a plane (V = 4: one 16-byte
 // load of each image and one 16-byte store; V = 1 when H * W is not a multiple of 4) and walks the B * C planes with the
@@ -124,32 +124,24 @@ using namespace sfcvit;
 
 extern "C" int sfcvit_mix_images(const void *x, const int32_t *perm, const uint32_t *rec, void *out, int B, int C, int H, int W,
                                  void *stream) {
-    if (!x || !perm || !rec || !out) return fail(SFCVIT_EINVAL, "mix_images: null pointer");
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || int64_t(H) * W > 0x7fffffff || int64_t(B) * C > 0x7fffffff)
-        return fail(SFCVIT_EINVAL, "mix_images: B=%d C=%d H=%d W=%d", B, C, H, W);
-    const int64_t bytes = int64_t(B) * C * H * W * 4;
-    const char *xb = static_cast<const char *>(x), *ob = static_cast<const char *>(out);
-    if (xb < ob + bytes && ob < xb + bytes)
-        return fail(SFCVIT_EINVAL, "mix_images: out must not alias x (an image is also read as its partner's partner)");
-    if (!aligned16(x) || !aligned16(out)) return fail(SFCVIT_EINVAL, "mix_images: x and out must be 16-byte aligned");
-    const int HW = H * W, V = (HW & 3) ? 1 : 4;
-    const int64_t planes = int64_t(B) * C;
-    const dim3 grid(unsigned((HW / V + THREADS - 1) / THREADS), unsigned(planes < 4096 ? planes : 4096));
+    const MixPlan p = mix_images_plan(x, perm, rec, out, B, C, H, W);
+    if (p.err) return fail(p.err, "%s", p.msg);
+    const dim3 grid(p.grid, p.grid_y);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (V == 4)
+    if (p.vec == 4)
         hipLaunchKernelGGL(mix_images_kernel<4>, grid, dim3(THREADS), 0, s, static_cast<const float *>(x), perm, rec,
-                           static_cast<float *>(out), B, C, HW, W);
+                           static_cast<float *>(out), B, C, p.HW, W);
     else
         hipLaunchKernelGGL(mix_images_kernel<1>, grid, dim3(THREADS), 0, s, static_cast<const float *>(x), perm, rec,
-                           static_cast<float *>(out), B, C, HW, W);
+                           static_cast<float *>(out), B, C, p.HW, W);
     return check_launch("mix_images");
 }
 
 extern "C" int sfcvit_soft_ce_pair(const void *logits, const int64_t *y_a, const int64_t *y_b, const uint32_t *rec, float *loss_rows,
                                    void *dlogits, float *hit_rows, int B, int C, int ld, float gscale, void *stream) {
-    if (!logits || !y_a || !y_b || !rec || !loss_rows) return fail(SFCVIT_EINVAL, "soft_ce_pair: null pointer");
-    if (B <= 0 || C <= 0 || ld < C) return fail(SFCVIT_EINVAL, "soft_ce_pair: B=%d C=%d ld=%d", B, C, ld);
-    hipLaunchKernelGGL(soft_ce_pair_kernel, dim3((B + WAVES - 1) / WAVES), dim3(THREADS), 0, static_cast<hipStream_t>(stream),
+    const MixPlan p = soft_ce_pair_plan(logits, y_a, y_b, rec, loss_rows, B, C, ld);
+    if (p.err) return fail(p.err, "%s", p.msg);
+    hipLaunchKernelGGL(soft_ce_pair_kernel, dim3(p.grid), dim3(THREADS), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint16_t *>(logits), y_a, y_b, rec, loss_rows, static_cast<uint16_t *>(dlogits), hit_rows, B,
                        C, ld, gscale);
     return check_launch("soft_ce_pair");

@@ -16,11 +16,14 @@
 #include "common_host.h"
 #include "gemm_core.h"
 #include "mix.h"
+#include "tokenizer.h"
 
 namespace sfcvit {
 namespace {
 
 using namespace gemm_core;
+static_assert(BM == PATCH_BM && BN == PATCH_BN && BK == PATCH_BK && THREADS == PATCH_THREADS && TILE_BYTES == PATCH_TILE_BYTES,
+              "patch_embed_plan sizes the grids and the LDS of pe_fwd_kernel / pe_bwd_kernel from these");
 
 struct Geo {
     const void *x;
@@ -223,41 +226,12 @@ __global__ __launch_bounds__(1024) void pe_bwd_reduce(const float *__restrict__ 
     }
 }
 
-int bwd_splits(int M, int D, int K) {
-    const int tiles = ((D + BM - 1) / BM) * ((K + BN - 1) / BN);
-    int splits = (1024 + tiles - 1) / tiles;
-    const int ktiles = (M + BK - 1) / BK;
-    if (splits > ktiles) splits = ktiles;
-    if (splits < 1) splits = 1;
-    return splits;
-}
-
-int check_args(const sfcvit_patch_embed_args *a, const char *what) {
-    if (!a || !a->x || !a->pix || !a->y) return fail(SFCVIT_EINVAL, "%s: null pointer", what);
-    if (a->B <= 0 || a->C <= 0 || a->HW <= 0 || a->N <= 0 || a->P <= 0 || a->D <= 0)
-        return fail(SFCVIT_EINVAL, "%s: non-positive dimension", what);
-    if (int64_t(a->N) * a->P != a->HW) return fail(SFCVIT_EINVAL, "%s: N*P=%lld must equal H*W=%d", what, (long long)a->N * a->P, a->HW);
-    if (a->D % 8 != 0) return fail(SFCVIT_EINVAL, "%s: D=%d must be a multiple of 8", what, a->D);
-    if (int64_t(a->B) * a->N > 0x7fffffff / 2) return fail(SFCVIT_EINVAL, "%s: B*N too large", what);
-    if (!aligned16(a->x) || !aligned16(a->pix) || !aligned16(a->y)) return fail(SFCVIT_EINVAL, "%s: alignment", what);
-    // pe_fwd_kernel reads the bias with 8-byte loads; the same rule as sfcvit_hier_tokenizer_fwd
-    if (!aligned16(a->w) || (a->bias && (reinterpret_cast<uintptr_t>(a->bias) & 7)))
-        return fail(SFCVIT_EINVAL, "%s: weight / bias alignment (w 16 bytes, bias 8 bytes)", what);
-    return SFCVIT_OK;
-}
-
-Geo make_geo(const sfcvit_patch_embed_args *a) {
-    return Geo{a->x, a->pix, a->B, a->C, a->HW, a->N, a->P, a->B * a->N, a->C * a->P, (a->C * a->P + 7) / 8 * 8};
-}
-
 }  // namespace
-}  // namespace sfcvit
 
-namespace sfcvit {
-int pe2_fwd(const sfcvit_patch_embed_args &a, hipStream_t s);      // patch_embed_tiled.hip; -1 = not eligible
-int pe2_bwd(const sfcvit_patch_embed_args &a, hipStream_t s);
-int64_t pe2_bwd_workspace(int B, int C, int N, int D);
-}
+// patch_embed_tiled.hip: raise the LDS limit and launch what the plan says
+int launch_pe2_fwd(const PatchEmbedPlan &p, const sfcvit_patch_embed_args &a, hipStream_t s);
+int launch_pe2_bwd(const PatchEmbedPlan &p, const sfcvit_patch_embed_args &a, hipStream_t s);
+}  // namespace sfcvit
 
 using namespace sfcvit;
 
@@ -269,7 +243,7 @@ using namespace sfcvit;
 // ---------------------------------------------------------------------------------------------------------------------
 namespace sfcvit {
 namespace {
-constexpr int GT = 256, GIMG = 8;
+constexpr int GT = GATHER_THREADS, GIMG = GATHER_IMG;
 
 // MIX: image b is mixed with image perm[b] as the record says (mix.h) on the way to bf16; fp32 images only.
 template <bool XBF16, bool MIX>
@@ -400,7 +374,7 @@ __global__ __launch_bounds__(2 * GT) void tokens_gather_p256_kernel(const void *
 // image is read and the tokens are written with nontemporal accesses (see the launch code).  A third form -- one workgroup
 // per 16-row strip of the image, read front to back -- was built and dropped: 56 us warm against 38 (two barriers per image,
 // 132 registers).
-constexpr int TG_THREADS = 256;
+constexpr int TG_THREADS = GATHER_THREADS;
 
 // MIX: the wave loads the same lines of image perm[b] next to those of b and combines them in registers before pack2bf
 // (mix.h): MixUp everywhere, CutMix per pixel -- row and column follow from `line`, `chunk` and the tile origin -- and a
@@ -539,37 +513,18 @@ __global__ __launch_bounds__(TG_THREADS) void tokens_gather_tiles_kernel(const f
 namespace sfcvit {
 namespace {
 
-// perm / rec: the batch mix (both or neither); `what` names the entry point in messages.
-int gather_tiles_impl(const char *what, const void *x, const int32_t *pix, const int32_t *order, const int32_t *origin,
-                      const int32_t *perm, const uint32_t *rec, int B, int C, int H, int W, int N, void *tokens, int ld, void *stream) {
-    if (!x || !pix || !origin || !tokens) return fail(SFCVIT_EINVAL, "%s: null pointer", what);
-    if (B <= 0 || C < 1 || C > 4 || H <= 0 || W <= 0 || N <= 0 || int64_t(N) * 256 != int64_t(H) * W || (W & 7) || (H & 15))
-        return fail(SFCVIT_EINVAL, "%s: B=%d C=%d H=%d W=%d N=%d (1 <= C <= 4, W %% 8 == 0, H %% 16 == 0, N * 256 == H * W)", what, B, C, H, W, N);
-    if (ld != 256 * C) return fail(SFCVIT_EINVAL, "%s: ld=%d (must be 256 * C = %d)", what, ld, 256 * C);
-    if (!aligned16(x) || !aligned16(tokens)) return fail(SFCVIT_EINVAL, "%s: x and tokens must be 16-byte aligned", what);
-    if (int64_t(16) * W * W >= (int64_t(1) << 32)) return fail(SFCVIT_EINVAL, "%s: W=%d too wide", what, W);
+// perm / rec: the batch mix (both or neither, as p.mix says).
+int launch_gather_tiles(const GatherPlan &p, const char *what, const void *x, const int32_t *pix, const int32_t *order,
+                        const int32_t *origin, const int32_t *perm, const uint32_t *rec, int B, int W, int N, void *tokens, void *stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const auto *xp = static_cast<const float *>(x);
     auto *tp = static_cast<uint16_t *>(tokens);
-    const int HW = H * W;
-    // images per wave (A/B: 2 = fewer, longer workgroups); the mixing form holds twice the lines and exists for 1 only
-    static const int upw_env = env_int("SFCVIT_GATHER_U", 1) == 2 ? 2 : 1;
-    const int upw = perm ? 1 : upw_env;
-    const dim3 grid((N + 1) / 2, (B + 4 * upw - 1) / (4 * upw));
-    if (grid.y > 65535) return fail(SFCVIT_EINVAL, "%s: batch %d too large", what, B);
-    const uint32_t wmagic = uint32_t((uint64_t(1) << 32) / uint32_t(W)) + 1;
-    const size_t lds = 1024 + size_t(4 * upw) * C * 1024;
-    // nontemporal loads (1) and stores (2).  The gather is the first kernel of a step: L2 and the memory-side cache are full
-    // of the optimizer's dirty lines, and every line an ordinary load allocates evicts one of them -- a write-back that
-    // shares HBM with the gather (75.8 us against 42.1 us with clean caches; a plain fp32 -> bf16 cast of the image suffers
-    // the same: 69 vs 37 us).  Streaming loads do not allocate: 46.0 us; with streaming stores 43.2 us alone, 44.0 us in
-    // the step (profiles/r4/gather_ab.txt).  SFCVIT_GATHER_NT=0..3 for the A/B.
-    static const int nt = env_int("SFCVIT_GATHER_NT", 3);
-    g_tokenizer.set("tokens_gather_tiles_kernel<%d, %s>", C, perm ? "mix" : "fp32");
-#define TILES_K(CC, NTV, UU, MX) hipLaunchKernelGGL((tokens_gather_tiles_kernel<CC, NTV, UU, MX>), grid, dim3(TG_THREADS), lds, s, xp, pix, order, origin, tp, B, HW, W, wmagic, N, perm, rec)
-#define TILES(CC, NTV) do { if (perm) TILES_K(CC, NTV, 1, true); else if (upw == 2) TILES_K(CC, NTV, 2, false); else TILES_K(CC, NTV, 1, false); } while (0)
-#define TILES_C(CC) do { if (nt == 1) TILES(CC, 1); else if (nt == 2) TILES(CC, 2); else if (nt == 3) TILES(CC, 3); else TILES(CC, 0); } while (0)
-    switch (C) {
+    const dim3 grid(p.grid_x, p.grid_y);
+    note_tokenizer_kernel(p);
+#define TILES_K(CC, NTV, UU, MX) hipLaunchKernelGGL((tokens_gather_tiles_kernel<CC, NTV, UU, MX>), grid, dim3(p.threads), p.lds, s, xp, pix, order, origin, tp, B, p.HW, W, p.wmagic, N, perm, rec)
+#define TILES(CC, NTV) do { if (p.mix) TILES_K(CC, NTV, 1, true); else if (p.upw == 2) TILES_K(CC, NTV, 2, false); else TILES_K(CC, NTV, 1, false); } while (0)
+#define TILES_C(CC) do { if (p.nt == 1) TILES(CC, 1); else if (p.nt == 2) TILES(CC, 2); else if (p.nt == 3) TILES(CC, 3); else TILES(CC, 0); } while (0)
+    switch (p.C) {
     case 1: TILES_C(1); break;
     case 2: TILES_C(2); break;
     case 3: TILES_C(3); break;
@@ -582,36 +537,26 @@ int gather_tiles_impl(const char *what, const void *x, const int32_t *pix, const
 }
 
 // W is only read by the mixing kernels (pixel offset -> row, column).
-int gather_impl(const char *what, const void *x, int x_is_bf16, const int32_t *pix, const int32_t *order, const int32_t *perm,
-                const uint32_t *rec, int B, int C, int HW, int W, int N, int P, void *tokens, int ld, void *stream) {
-    if (!x || !pix || !tokens) return fail(SFCVIT_EINVAL, "%s: null pointer", what);
-    if (B <= 0 || C <= 0 || HW <= 0 || N <= 0 || P <= 0 || int64_t(N) * P != HW)
-        return fail(SFCVIT_EINVAL, "%s: B=%d C=%d HW=%d N=%d P=%d (N * P must equal H * W)", what, B, C, HW, N, P);
-    if (ld < P * C || ld % 8 || ld > 32768) return fail(SFCVIT_EINVAL, "%s: ld=%d (>= P * C = %d, multiple of 8, <= 32768)", what, ld, P * C);
-    if (!aligned16(tokens)) return fail(SFCVIT_EINVAL, "%s: tokens must be 16-byte aligned", what);
-    const dim3 grid(N, (B + GIMG - 1) / GIMG);
-    if (grid.y > 65535) return fail(SFCVIT_EINVAL, "%s: batch %d too large", what, B);
+int launch_gather(const GatherPlan &p, const char *what, const void *x, const int32_t *pix, const int32_t *order, const int32_t *perm,
+                  const uint32_t *rec, int B, int W, int N, int P, void *tokens, int ld, void *stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto *tp = static_cast<uint16_t *>(tokens);
-    if (P <= GT && C <= 4 && size_t(2) * GIMG * ld * 2 <= 64 * 1024) {
-        const dim3 grid2((N + 1) / 2, grid.y);
-        const size_t lds = size_t(2) * GIMG * ld * 2;
-        g_tokenizer.set("tokens_gather_p256_kernel<%s>", perm ? "mix" : x_is_bf16 ? "bf16" : "fp32");
-        if (perm)
-            hipLaunchKernelGGL((tokens_gather_p256_kernel<false, 4, true>), grid2, dim3(2 * GT), lds, s, x, pix, order, tp, B, C, HW, N, P, ld, W, perm, rec);
-        else if (x_is_bf16)
-            hipLaunchKernelGGL((tokens_gather_p256_kernel<true, 4, false>), grid2, dim3(2 * GT), lds, s, x, pix, order, tp, B, C, HW, N, P, ld, W, perm, rec);
+    const dim3 grid(p.grid_x, p.grid_y), block(p.threads);
+    note_tokenizer_kernel(p);
+    if (p.form == GatherForm::P256) {
+        if (p.mix)
+            hipLaunchKernelGGL((tokens_gather_p256_kernel<false, 4, true>), grid, block, p.lds, s, x, pix, order, tp, B, p.C, p.HW, N, P, ld, W, perm, rec);
+        else if (p.x_bf16)
+            hipLaunchKernelGGL((tokens_gather_p256_kernel<true, 4, false>), grid, block, p.lds, s, x, pix, order, tp, B, p.C, p.HW, N, P, ld, W, perm, rec);
         else
-            hipLaunchKernelGGL((tokens_gather_p256_kernel<false, 4, false>), grid2, dim3(2 * GT), lds, s, x, pix, order, tp, B, C, HW, N, P, ld, W, perm, rec);
-        return check_launch(what);
+            hipLaunchKernelGGL((tokens_gather_p256_kernel<false, 4, false>), grid, block, p.lds, s, x, pix, order, tp, B, p.C, p.HW, N, P, ld, W, perm, rec);
+    } else if (p.mix) {
+        hipLaunchKernelGGL((tokens_gather_kernel<false, true>), grid, block, p.lds, s, x, pix, tp, B, p.C, p.HW, N, P, ld, W, perm, rec);
+    } else if (p.x_bf16) {
+        hipLaunchKernelGGL((tokens_gather_kernel<true, false>), grid, block, p.lds, s, x, pix, tp, B, p.C, p.HW, N, P, ld, W, perm, rec);
+    } else {
+        hipLaunchKernelGGL((tokens_gather_kernel<false, false>), grid, block, p.lds, s, x, pix, tp, B, p.C, p.HW, N, P, ld, W, perm, rec);
     }
-    g_tokenizer.set("tokens_gather_kernel<%s>", perm ? "mix" : x_is_bf16 ? "bf16" : "fp32");
-    if (perm)
-        hipLaunchKernelGGL((tokens_gather_kernel<false, true>), grid, dim3(GT), size_t(ld) * 2, s, x, pix, tp, B, C, HW, N, P, ld, W, perm, rec);
-    else if (x_is_bf16)
-        hipLaunchKernelGGL((tokens_gather_kernel<true, false>), grid, dim3(GT), size_t(ld) * 2, s, x, pix, tp, B, C, HW, N, P, ld, W, perm, rec);
-    else
-        hipLaunchKernelGGL((tokens_gather_kernel<false, false>), grid, dim3(GT), size_t(ld) * 2, s, x, pix, tp, B, C, HW, N, P, ld, W, perm, rec);
     return check_launch(what);
 }
 
@@ -620,95 +565,68 @@ int gather_impl(const char *what, const void *x, int x_is_bf16, const int32_t *p
 
 extern "C" int sfcvit_tokens_gather_tiles(const void *x, const int32_t *pix, const int32_t *order, const int32_t *origin, int B, int C,
                                           int H, int W, int N, void *tokens, int ld, void *stream) {
-    return sfcvit::gather_tiles_impl("tokens_gather_tiles", x, pix, order, origin, nullptr, nullptr, B, C, H, W, N, tokens, ld, stream);
+    const GatherPlan p = gather_tiles_plan("tokens_gather_tiles", x, pix, origin, nullptr, B, C, H, W, N, tokens, ld, read_tokenizer_knobs());
+    if (p.err) return fail(p.err, "%s", p.msg);
+    return launch_gather_tiles(p, "tokens_gather_tiles", x, pix, order, origin, nullptr, nullptr, B, W, N, tokens, stream);
 }
 
 extern "C" int sfcvit_tokens_gather(const void *x, int x_is_bf16, const int32_t *pix, const int32_t *order, int B, int C, int HW, int N,
                                     int P, void *tokens, int ld, void *stream) {
-    return sfcvit::gather_impl("tokens_gather", x, x_is_bf16, pix, order, nullptr, nullptr, B, C, HW, 0, N, P, tokens, ld, stream);
+    const GatherPlan p = gather_plan("tokens_gather", x, x_is_bf16, pix, nullptr, B, C, HW, N, P, tokens, ld);
+    if (p.err) return fail(p.err, "%s", p.msg);
+    return launch_gather(p, "tokens_gather", x, pix, order, nullptr, nullptr, B, 0, N, P, tokens, ld, stream);
 }
 
 extern "C" int sfcvit_tokens_gather_mix(const void *x, const int32_t *pix, const int32_t *order, const int32_t *origin,
                                         const int32_t *perm, const uint32_t *rec, int B, int C, int H, int W, int N, int P,
                                         void *tokens, int ld, void *stream) {
-    using namespace sfcvit;
-    if (!perm || !rec) return fail(SFCVIT_EINVAL, "tokens_gather_mix: null perm / rec (the unmixed gather is sfcvit_tokens_gather)");
-    if (H <= 0 || W <= 0 || int64_t(H) * W > 0x7fffffff) return fail(SFCVIT_EINVAL, "tokens_gather_mix: H=%d W=%d", H, W);
-    if (!aligned16(x)) return fail(SFCVIT_EINVAL, "tokens_gather_mix: x must be 16-byte aligned");
-    if (origin) {
-        if (P != 256) return fail(SFCVIT_EINVAL, "tokens_gather_mix: P=%d with a tile origin table (16 x 16 tiles: P = 256)", P);
-        return gather_tiles_impl("tokens_gather_mix", x, pix, order, origin, perm, rec, B, C, H, W, N, tokens, ld, stream);
-    }
-    return gather_impl("tokens_gather_mix", x, 0, pix, order, perm, rec, B, C, H * W, W, N, P, tokens, ld, stream);
+    const GatherPlan p = gather_mix_plan(x, pix, origin, perm, rec, B, C, H, W, N, P, tokens, ld, read_tokenizer_knobs());
+    if (p.err) return fail(p.err, "%s", p.msg);
+    if (p.form == GatherForm::TILES) return launch_gather_tiles(p, "tokens_gather_mix", x, pix, order, origin, perm, rec, B, W, N, tokens, stream);
+    return launch_gather(p, "tokens_gather_mix", x, pix, order, perm, rec, B, W, N, P, tokens, ld, stream);
 }
 
 extern "C" int64_t sfcvit_patch_embed_workspace(int B, int C, int N, int P, int D, int bwd) {
-    if (B <= 0 || C <= 0 || N <= 0 || P <= 0 || D <= 0) return 0;
-    const int64_t K = (int64_t(C) * P + 7) / 8 * 8;
-    if (!bwd) return ((int64_t(D) * K * 2 * 8 + 15) / 16) * 16;      // up to 8 class-permuted copies of W (tiled forward)
-    const int64_t slabs = int64_t(bwd_splits(B * N, D, int(K))) * D * K * int64_t(sizeof(float));
-    const int64_t bias_ws = sfcvit_colsum_workspace(B * N, D);   // dbias reuses the buffer after the slabs are reduced
-    const int64_t tiled = (P == 256 && D % 256 == 0) ? pe2_bwd_workspace(B, C, N, D) : 0;
-    const int64_t m = slabs > bias_ws ? slabs : bias_ws;
-    return m > tiled ? m : tiled;
+    return patch_embed_geometry(B, C, N, P, D, bwd != 0).ws_bytes;
 }
 
 extern "C" int sfcvit_patch_embed_fwd(const sfcvit_patch_embed_args *a, void *stream) {
-    if (int rc = check_args(a, "patch_embed_fwd")) return rc;
-    if (!a->w) return fail(SFCVIT_EINVAL, "patch_embed_fwd: null weight");
-    const int64_t need = sfcvit_patch_embed_workspace(a->B, a->C, a->N, a->P, a->D, 0);
-    if (!a->workspace || a->workspace_bytes < need || !aligned16(a->workspace))
-        return fail(SFCVIT_EINVAL, "patch_embed_fwd: workspace of %lld bytes needed", (long long)need);
+    const PatchEmbedPlan p = patch_embed_plan(a, false);
+    if (p.err) return fail(p.err, "%s", p.msg);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = pe2_fwd(*a, s); rc >= 0) return rc;                 // tiles / strips: the coalesced kernel
-    const Geo g = make_geo(a);
+    if (p.form == PeForm::TILED) return launch_pe2_fwd(p, *a, s);      // tiles / strips: the coalesced kernel
+    const Geo g{a->x, a->pix, a->B, a->C, a->HW, a->N, a->P, p.M, p.K, p.Kp};
     uint16_t *wp = static_cast<uint16_t *>(a->workspace);
-    const int64_t nw = int64_t(a->D) * g.Kp;
-    hipLaunchKernelGGL(permute_w_kernel, dim3(unsigned((nw + 255) / 256)), dim3(256), 0, s,
-                       static_cast<const uint16_t *>(a->w), wp, a->D, a->C, a->P, g.Kp);
+    hipLaunchKernelGGL(permute_w_kernel, dim3(p.permute_grid), dim3(256), 0, s, static_cast<const uint16_t *>(a->w), wp, a->D, a->C, a->P, g.Kp);
     if (int rc = check_launch("patch_embed_fwd permute")) return rc;
-    dim3 grid(((a->D + BN - 1) / BN) * ((g.M + BM - 1) / BM)), block(THREADS);
-    const size_t lds = 4 * TILE_BYTES;
-    g_tokenizer.set("pe_fwd_kernel<%s>", a->x_is_bf16 ? "bf16" : "fp32");
-    if (a->x_is_bf16)
-        hipLaunchKernelGGL(pe_fwd_kernel<true>, grid, block, lds, s, g, wp, static_cast<const uint16_t *>(a->bias),
+    note_tokenizer_kernel(p);
+    if (p.x_bf16)
+        hipLaunchKernelGGL(pe_fwd_kernel<true>, dim3(p.grid), dim3(THREADS), p.lds, s, g, wp, static_cast<const uint16_t *>(a->bias),
                            static_cast<uint16_t *>(a->y), a->D);
     else
-        hipLaunchKernelGGL(pe_fwd_kernel<false>, grid, block, lds, s, g, wp, static_cast<const uint16_t *>(a->bias),
+        hipLaunchKernelGGL(pe_fwd_kernel<false>, dim3(p.grid), dim3(THREADS), p.lds, s, g, wp, static_cast<const uint16_t *>(a->bias),
                            static_cast<uint16_t *>(a->y), a->D);
     return check_launch("patch_embed_fwd");
 }
 
 extern "C" int sfcvit_patch_embed_bwd(const sfcvit_patch_embed_args *a, void *stream) {
-    if (int rc = check_args(a, "patch_embed_bwd")) return rc;
-    if (!a->dw) return fail(SFCVIT_EINVAL, "patch_embed_bwd: null dw");
-    const int64_t need = sfcvit_patch_embed_workspace(a->B, a->C, a->N, a->P, a->D, 1);
-    if (!a->workspace || a->workspace_bytes < need || !aligned16(a->workspace))
-        return fail(SFCVIT_EINVAL, "patch_embed_bwd: workspace of %lld bytes needed", (long long)need);
+    const PatchEmbedPlan p = patch_embed_plan(a, true);
+    if (p.err) return fail(p.err, "%s", p.msg);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = pe2_bwd(*a, s); rc >= 0) {                          // tiles / strips: the coalesced kernel
-        if (rc || !a->dbias) return rc;
-        return sfcvit_colsum(a->y, a->B * a->N, a->D, a->D, a->dbias, 0, a->workspace, a->workspace_bytes, stream);
+    if (p.form == PeForm::TILED) {                                     // tiles / strips: the coalesced kernel
+        if (int rc = launch_pe2_bwd(p, *a, s)) return rc;
+    } else {
+        const Geo g{a->x, a->pix, a->B, a->C, a->HW, a->N, a->P, p.M, p.K, p.Kp};
+        float *slabs = static_cast<float *>(a->workspace);
+        note_tokenizer_kernel(p);
+        if (p.x_bf16)
+            hipLaunchKernelGGL(pe_bwd_kernel<true>, dim3(p.grid), dim3(THREADS), p.lds, s, g, static_cast<const uint16_t *>(a->y), slabs, a->D, p.m_per_split);
+        else
+            hipLaunchKernelGGL(pe_bwd_kernel<false>, dim3(p.grid), dim3(THREADS), p.lds, s, g, static_cast<const uint16_t *>(a->y), slabs, a->D, p.m_per_split);
+        if (int rc = check_launch("patch_embed_bwd")) return rc;
+        hipLaunchKernelGGL(pe_bwd_reduce, dim3(p.reduce_grid), dim3(1024), 0, s, slabs, p.zs, static_cast<float *>(a->dw), a->D, a->C, a->P, g.Kp);
+        if (int rc = check_launch("patch_embed_bwd reduce")) return rc;
     }
-    const Geo g = make_geo(a);
-    const int splits = bwd_splits(g.M, a->D, g.Kp);
-    const int ktiles = (g.M + BK - 1) / BK;
-    const int m_per_split = ((ktiles + splits - 1) / splits) * BK;
-    const int zs = (g.M + m_per_split - 1) / m_per_split;
-    float *slabs = static_cast<float *>(a->workspace);
-    dim3 grid(((g.Kp + BN - 1) / BN) * ((a->D + BM - 1) / BM) * zs), block(THREADS);
-    const size_t lds = 4 * TILE_BYTES;
-    g_tokenizer.set("pe_bwd_kernel<%s>", a->x_is_bf16 ? "bf16" : "fp32");
-    if (a->x_is_bf16)
-        hipLaunchKernelGGL(pe_bwd_kernel<true>, grid, block, lds, s, g, static_cast<const uint16_t *>(a->y), slabs, a->D, m_per_split);
-    else
-        hipLaunchKernelGGL(pe_bwd_kernel<false>, grid, block, lds, s, g, static_cast<const uint16_t *>(a->y), slabs, a->D, m_per_split);
-    if (int rc = check_launch("patch_embed_bwd")) return rc;
-    const int64_t nw = int64_t(a->D) * g.Kp;
-    hipLaunchKernelGGL(pe_bwd_reduce, dim3(unsigned((nw + 15) / 16)), dim3(1024), 0, s, slabs, zs,
-                       static_cast<float *>(a->dw), a->D, a->C, a->P, g.Kp);
-    if (int rc = check_launch("patch_embed_bwd reduce")) return rc;
-    if (a->dbias)
-        return sfcvit_colsum(a->y, g.M, a->D, a->D, a->dbias, 0, a->workspace, a->workspace_bytes, stream);
+    if (p.dbias) return sfcvit_colsum(a->y, p.M, a->D, a->D, a->dbias, 0, a->workspace, a->workspace_bytes, stream);
     return SFCVIT_OK;
 }

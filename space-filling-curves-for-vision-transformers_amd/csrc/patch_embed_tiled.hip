@@ -24,16 +24,14 @@
 // (src/tokenizers/_1D/hilbert_embedding1D.py:30-44, morton_embedding1D.py:30-44, zigzag_embedding1D.py:30-39).
 #include "common_host.h"
 #include "device_common.h"
-#include <algorithm>
-#include <cstring>
-#include <vector>
+#include "tokenizer.h"
 
 namespace sfcvit {
 namespace {
 
-constexpr int TM = 128, TN = 256, BK = 64, PT = 512;       // token rows, output columns, k per step, threads
+constexpr int TM = PE2_TM, TN = PE2_TN, BK = 64, PT = PE2_PT;   // token rows, output columns, k per step, threads
 constexpr int A_BYTES = TM * 128, B_BYTES = TN * 128;       // one LDS k-tile of each operand (128-byte rows)
-using sfcvit::tile_desc::MAXCLS;
+static_assert(sfcvit::tile_desc::MAXCLS == PE2_MAXCLS, "the forward workspace holds PE2_MAXCLS copies of W");
 using sfcvit::tile_desc::DESC_HDR;      // layout: tile_descriptors.cpp
 
 typedef const __attribute__((address_space(1))) void *gptr_t;
@@ -56,6 +54,8 @@ struct RowInfo {              // one token row of the workgroup's tile
     int out_row;              // b * N + n, or -1 for a padding row
     int pad;
 };
+
+static_assert(sizeof(RowInfo) == 16 && PE2_FWD_LDS == 2 * A_BYTES + 2 * B_BYTES + TM * int(sizeof(RowInfo)), "pe2_fwd_kernel's LDS, as patch_embed_plan sizes it");
 
 template <bool XBF16>
 __global__ __launch_bounds__(PT) void pe2_fwd_kernel(const void *__restrict__ x, const int32_t *__restrict__ desc,
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(PT) void pe2_fwd_kernel(const void *__restrict__ x,
 // loop of the weight-gradient GEMM (gemm8p.hip) with the gather as its B loader.  fp32 partial tiles go to slabs
 // (deterministic fixed-order reduction, no atomics).
 // ----------------------------------------------------------------------------------------------------------------
-constexpr int BW_ROWS = 64, BW_IMG = BW_ROWS * 256;          // rows per step; one [64][128] st image
+constexpr int BW_ROWS = PE2_BW_ROWS, BW_IMG = BW_ROWS * 256;   // rows per step; one [64][128] st image
 
 template <bool XBF16>
 __global__ __launch_bounds__(PT) void pe2_bwd_kernel(const void *__restrict__ x, const int32_t *__restrict__ desc,
@@ -337,80 +337,40 @@ __global__ __launch_bounds__(256) void pe2_bwd_reduce(const float *__restrict__ 
     dw[i] = s;
 }
 
-constexpr int PE2_BWD_LDS = 2 * 4 * BW_IMG;
-
-// Rows per unit: the smallest multiple of 64 for which the row ranges of all classes number at most G = 8 x (32 / tiles):
-// every XCD then holds whole groups (the `tiles` output tiles of one row range) on its 32 CUs in ONE round.
-int pe2_bwd_row_range(int B, int ncls, const int32_t *cnt, int tiles, int *nz_out) {
-    const int G = 8 * std::max(1, 32 / tiles);
-    int64_t M = 0;
-    for (int c = 0; c < ncls; c++) M += int64_t(cnt[c]) * B;
-    int kr = int((M / G + BW_ROWS - 1) / BW_ROWS * BW_ROWS);
-    if (kr < BW_ROWS) kr = BW_ROWS;
-    for (;; kr += BW_ROWS) {
-        int nz = 0;
-        for (int c = 0; c < ncls; c++) nz += int((int64_t(cnt[c]) * B + kr - 1) / kr);
-        if (nz <= G) { *nz_out = nz; return kr; }
-    }
-}
-
-constexpr int PE2_LDS = 2 * A_BYTES + 2 * B_BYTES + TM * int(sizeof(RowInfo));
+static_assert(PE2_BWD_LDS == 2 * 4 * BW_IMG, "pe2_bwd_kernel's LDS, as patch_embed_plan sizes it");
 
 }  // namespace
 
-// Eligibility + launch of the tiled forward.  -1: not eligible (the caller uses the generic kernel).
-int pe2_fwd(const sfcvit_patch_embed_args &a, hipStream_t s) {
-    if (!a.desc || a.P != 256 || a.D % TN || a.desc_ncls <= 0 || a.desc_ncls > MAXCLS) return -1;
-    const int K = a.C * 256;
-    const int64_t need = int64_t(a.desc_ncls) * a.D * K * 2;
-    if (!a.workspace || a.workspace_bytes < need) return -1;
-    if ((reinterpret_cast<uintptr_t>(a.x) & 15) || (a.HW & 7)) return -1;
+// The tiled forward as patch_embed_plan laid it out: W' per class into the head of the workspace, then the GEMM.
+int launch_pe2_fwd(const PatchEmbedPlan &p, const sfcvit_patch_embed_args &a, hipStream_t s) {
     uint16_t *wp = static_cast<uint16_t *>(a.workspace);
-    hipLaunchKernelGGL(pe2_permute_w_kernel, dim3(1024), dim3(256), 0, s, static_cast<const uint16_t *>(a.w), a.desc + DESC_HDR + 2 * a.N,
-                       wp, a.D, a.C, a.desc_ncls);
+    hipLaunchKernelGGL(pe2_permute_w_kernel, dim3(p.permute_grid), dim3(256), 0, s, static_cast<const uint16_t *>(a.w),
+                       a.desc + DESC_HDR + 2 * a.N, wp, a.D, a.C, a.desc_ncls);
     if (int rc = check_launch("patch_embed_fwd (tiled) permute")) return rc;
     for (const void *k : {reinterpret_cast<const void *>(&pe2_fwd_kernel<false>), reinterpret_cast<const void *>(&pe2_fwd_kernel<true>)})
-        if (int rc = raise_lds_limit(k, PE2_LDS, "patch_embed_fwd (tiled) attribute")) return rc;
-    int n_row_tiles = 0;
-    for (int c = 0; c < a.desc_ncls; c++) n_row_tiles += int((int64_t(a.desc_cnt[c]) * a.B + TM - 1) / TM);
-    const int NCT = a.D / TN;
-    const int groups = (n_row_tiles + 7) / 8;                       // row tiles are dealt to the 8 XCD slots in groups of 8
-    dim3 grid(unsigned(groups) * 8u * unsigned(NCT)), block(PT);
-    g_tokenizer.set("pe2_fwd_kernel<%s>", a.x_is_bf16 ? "bf16" : "fp32");
-    if (a.x_is_bf16)
-        hipLaunchKernelGGL(pe2_fwd_kernel<true>, grid, block, PE2_LDS, s, a.x, a.desc, wp, static_cast<const uint16_t *>(a.bias),
-                           static_cast<uint16_t *>(a.y), a.B, a.C, a.HW, a.D, n_row_tiles);
+        if (int rc = raise_lds_limit(k, PE2_FWD_LDS, "patch_embed_fwd (tiled) attribute")) return rc;
+    note_tokenizer_kernel(p);
+    if (p.x_bf16)
+        hipLaunchKernelGGL(pe2_fwd_kernel<true>, dim3(p.grid), dim3(PT), p.lds, s, a.x, a.desc, wp, static_cast<const uint16_t *>(a.bias),
+                           static_cast<uint16_t *>(a.y), a.B, a.C, a.HW, a.D, p.n_row_tiles);
     else
-        hipLaunchKernelGGL(pe2_fwd_kernel<false>, grid, block, PE2_LDS, s, a.x, a.desc, wp, static_cast<const uint16_t *>(a.bias),
-                           static_cast<uint16_t *>(a.y), a.B, a.C, a.HW, a.D, n_row_tiles);
+        hipLaunchKernelGGL(pe2_fwd_kernel<false>, dim3(p.grid), dim3(PT), p.lds, s, a.x, a.desc, wp, static_cast<const uint16_t *>(a.bias),
+                           static_cast<uint16_t *>(a.y), a.B, a.C, a.HW, a.D, p.n_row_tiles);
     return check_launch("patch_embed_fwd (tiled)");
 }
 
-// Tiled backward: -1 = not eligible.  Workspace: fp32 slabs, one [D][C*256] per (class, row range).
-int64_t pe2_bwd_workspace(int B, int C, int N, int D) {
-    const int tiles = (D / 256) * C;
-    return int64_t(8 * std::max(1, 32 / tiles)) * D * C * 256 * int64_t(sizeof(float));      // at most G slabs
-}
-
-int pe2_bwd(const sfcvit_patch_embed_args &a, hipStream_t s) {
-    if (!a.desc || a.P != 256 || a.D % 256 || a.desc_ncls <= 0 || a.desc_ncls > MAXCLS) return -1;
-    if ((reinterpret_cast<uintptr_t>(a.x) & 15) || (a.HW & 7)) return -1;
-    int nz = 0;
-    const int KR = pe2_bwd_row_range(a.B, a.desc_ncls, a.desc_cnt, (a.D / 256) * a.C, &nz);
-    const int64_t need = int64_t(nz) * a.D * a.C * 256 * int64_t(sizeof(float));
-    if (!a.workspace || a.workspace_bytes < need) return -1;
+// The tiled backward: fp32 slabs in the workspace, one [D][C*256] per (class, row range), then their reduction into dW.
+int launch_pe2_bwd(const PatchEmbedPlan &p, const sfcvit_patch_embed_args &a, hipStream_t s) {
     for (const void *k : {reinterpret_cast<const void *>(&pe2_bwd_kernel<false>), reinterpret_cast<const void *>(&pe2_bwd_kernel<true>)})
         if (int rc = raise_lds_limit(k, PE2_BWD_LDS, "patch_embed_bwd (tiled) attribute")) return rc;
     float *slabs = static_cast<float *>(a.workspace);
-    dim3 grid(unsigned((nz + 7) / 8) * 8u * unsigned((a.D / 256) * a.C)), block(PT);      // row ranges dealt to the 8 XCD slots
-    g_tokenizer.set("pe2_bwd_kernel<%s>", a.x_is_bf16 ? "bf16" : "fp32");
-    if (a.x_is_bf16)
-        hipLaunchKernelGGL(pe2_bwd_kernel<true>, grid, block, PE2_BWD_LDS, s, a.x, a.desc, static_cast<const uint16_t *>(a.y), slabs, a.B, a.C, a.HW, a.D, KR);
+    note_tokenizer_kernel(p);
+    if (p.x_bf16)
+        hipLaunchKernelGGL(pe2_bwd_kernel<true>, dim3(p.grid), dim3(PT), p.lds, s, a.x, a.desc, static_cast<const uint16_t *>(a.y), slabs, a.B, a.C, a.HW, a.D, p.KR);
     else
-        hipLaunchKernelGGL(pe2_bwd_kernel<false>, grid, block, PE2_BWD_LDS, s, a.x, a.desc, static_cast<const uint16_t *>(a.y), slabs, a.B, a.C, a.HW, a.D, KR);
+        hipLaunchKernelGGL(pe2_bwd_kernel<false>, dim3(p.grid), dim3(PT), p.lds, s, a.x, a.desc, static_cast<const uint16_t *>(a.y), slabs, a.B, a.C, a.HW, a.D, p.KR);
     if (int rc = check_launch("patch_embed_bwd (tiled)")) return rc;
-    const int64_t nw = int64_t(a.D) * a.C * 256;
-    hipLaunchKernelGGL(pe2_bwd_reduce, dim3(unsigned((nw + 255) / 256)), dim3(256), 0, s, slabs, a.desc, static_cast<float *>(a.dw), a.B, a.C, a.D, KR);
+    hipLaunchKernelGGL(pe2_bwd_reduce, dim3(p.reduce_grid), dim3(256), 0, s, slabs, a.desc, static_cast<float *>(a.dw), a.B, a.C, a.D, p.KR);
     return check_launch("patch_embed_bwd (tiled) reduce");
 }
 

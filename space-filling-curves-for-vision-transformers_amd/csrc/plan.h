@@ -1,5 +1,5 @@
 // The host scaffold every plan file shares (dispatch.cpp, attention_probe.cpp, token_agg.cpp, token_mix.cpp, pos_embed.cpp,
-// token_pool.cpp, rowwise.cpp, drop_path.cpp, model_ema.cpp, grad_accum.cpp): the status a plan carries, how it refuses, three small helpers and the "which kernel ran last" note.
+// token_pool.cpp, rowwise.cpp, drop_path.cpp, model_ema.cpp, grad_accum.cpp, tokenizer.cpp): the status a plan carries, how it refuses, three small helpers and the "which kernel ran last" note.
 // Plain host C++ with no HIP include; refuse, KernelNote::set and KernelNote::read are defined in common.cpp.
 #pragma once
 #include <cstdint>
@@ -10,7 +10,7 @@ namespace sfcvit {
 
 struct PlanStatus {
     int err = SFCVIT_OK;                                     // else an error code; msg says why
-    char msg[160] = "";
+    char msg[256] = "";                                      // the longest refusal (the hierarchical envelope) is 200 characters
 };
 // Records the refusal in the plan; the entry point hands it to fail() (common_host.h) once the plan comes back.
 void refuse(PlanStatus &p, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));

@@ -151,7 +151,7 @@ class _PatchEmbed2(Function):
 class _PatchEmbed(Function):
     @staticmethod
     def forward(ctx, x, pix, w, b, desc):
-        tiled = desc is not None and pix.shape[1] == 256 and w.shape[0] % 256 == 0
+        tiled = ops.patch_embed_is_tiled(desc, pix.shape[1], w.shape[0])
         if tiled:
             # tiles / strips: the tiled kernel reads whole 16-pixel row segments of the image AS IT IS (fp32 from the
             # loader: one pass over 154 MB at ViT-B / 256 images; a bf16 copy first would cost that pass plus its own

@@ -84,7 +84,7 @@ def patch_embed_op(x: Tensor, pix: Tensor, w: Tensor, b: Optional[Tensor], desc_
 
 @patch_embed_op.register_fake
 def _(x, pix, w, b, desc_dev, desc_meta):
-    tiled = desc_dev is not None and pix.shape[1] == 256 and w.shape[0] % 256 == 0
+    tiled = ops.patch_embed_is_tiled(desc_dev, pix.shape[1], w.shape[0])
     keeps_x = x.is_contiguous() and (tiled or x.dtype == _BF16)
     y = x.new_empty((x.shape[0], pix.shape[0], w.shape[0]), dtype=_BF16)
     return y, (x.new_empty(0, dtype=_BF16) if keeps_x else x.new_empty(x.shape, dtype=x.dtype if tiled else _BF16))
@@ -95,7 +95,7 @@ def patch_embed_bwd_op(dy: Tensor, xs: Tensor, pix: Tensor, D: int, has_bias: bo
                        desc_meta: List[int]) -> Tuple[Tensor, Tensor]:
     ctx = _Ctx()
     ctx.saved_tensors, ctx.D, ctx.has_bias = (xs, pix), D, has_bias
-    tiled = desc_dev is not None and pix.shape[1] == 256 and D % 256 == 0
+    tiled = ops.patch_embed_is_tiled(desc_dev, pix.shape[1], D)
     ctx.desc = _desc_from(desc_dev, desc_meta) if tiled else None
     _, _, dw, db, _ = F._PatchEmbed.backward(ctx, dy)
     return dw, (db if db is not None else _e(dy))

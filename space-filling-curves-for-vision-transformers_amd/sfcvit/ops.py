@@ -877,9 +877,15 @@ def mix_images(x, mix):
     return out
 
 
+def patch_embed_is_tiled(desc, P, D):
+    """Whether patch_embed_fwd / _bwd run the tiled kernels (csrc/tokenizer.cpp: patch_embed_plan) for a tile descriptor
+    `desc` (or None), P pixels per token and D output columns."""
+    return desc is not None and P == 256 and D % 256 == 0
+
+
 def patch_embed_fwd(x, pix, w, bias, desc=None):
     """x [B,C,H,W] fp32/bf16, pix [N,P] int32 (device), w [D, P*C] bf16 -> [B, N, D] bf16.
-    desc: TileDesc (tile_descriptor) or None; with it the tiled kernel runs when P = 256 and D % 256 == 0."""
+    desc: TileDesc (tile_descriptor) or None; with it the tiled kernel runs where patch_embed_is_tiled says so."""
     N, P = pix.shape
     D = w.shape[0]
     _need(w, _BF16, "patch_embed w", 2)

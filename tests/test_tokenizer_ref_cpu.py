@@ -241,7 +241,7 @@ def test_guards_cover_a_stray_row_of_every_containment_shape():
         assert guard_bytes(shape, dtype) >= stray, (what, shape, guard_bytes(shape, dtype), stray)
 
 
-# ---- the query and the refusals --------------------------------------------------------------------------------------------
+# ---- the query (the refusals: tests/test_tokenizer_plans_cpu.py) ------------------------------------------------------------------
 def test_last_tokenizer_kernel_is_exported_and_says_none():
     from sfcvit import _lib, ops
     header = open(os.path.join(ROOT, "include", "sfcvit.h")).read()
@@ -256,28 +256,3 @@ def test_last_tokenizer_kernel_is_exported_and_says_none():
     assert _lib.lib.sfcvit_last_tokenizer_kernel(buf, 0) == EINVAL and _lib.lib.sfcvit_last_tokenizer_kernel(buf, -3) == EINVAL
     assert ops.last_tokenizer_kernel() == "none"
 
-
-def test_patch_embed_refuses_misaligned_weight_and_bias_before_any_launch():
-    """check_args returns SFCVIT_EINVAL before any HIP call (this machine has no GPU: a launch attempt would come back as
-    another status).  pe_fwd_kernel reads the bias with 8-byte loads; the weight must be 16-byte aligned, the rule of
-    sfcvit_hier_tokenizer_fwd.  With both aligned the next refusal is the workspace's, which shows the order."""
-    from sfcvit import _lib
-    lib = _lib.lib
-    raw = ctypes.create_string_buffer(1 << 12)
-    p = (ctypes.addressof(raw) + 15) // 16 * 16                # aligned host addresses: never dereferenced
-
-    def call(fn, w=p, bias=p + 8):
-        a = _lib.PatchEmbedArgs()
-        a.x, a.pix, a.y, a.dw, a.w, a.bias = p, p, p, p, w, bias
-        a.B, a.C, a.HW, a.N, a.P, a.D = 1, 3, 64, 8, 8, 8
-        rc = fn(ctypes.byref(a), None)
-        return rc, lib.sfcvit_last_error().decode()
-
-    for fn in (lib.sfcvit_patch_embed_fwd, lib.sfcvit_patch_embed_bwd):
-        for kw in (dict(bias=p + 4), dict(bias=p + 2), dict(w=p + 8), dict(w=p + 2)):
-            rc, msg = call(fn, **kw)
-            print(rc, msg)
-            assert rc == EINVAL and "weight / bias alignment" in msg, (kw, rc, msg)
-        for kw in (dict(), dict(bias=None)):
-            rc, msg = call(fn, **kw)
-            assert rc == EINVAL and "alignment" not in msg and ("workspace" in msg or "null" in msg), (kw, rc, msg)
