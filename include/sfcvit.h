@@ -541,6 +541,74 @@ int sfcvit_attention_masked_fwd(const sfcvit_attn_mask_args *a, void *stream);
 int sfcvit_attention_masked_bwd(const sfcvit_attn_mask_args *a, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Self-attention core with a learned relative position bias per head (head dim 64)
+ *   the bias of Swin / BEiT windows: softmax(q k^T / sqrt(hd) + b_h[offset(i, j)]) v
+ *
+ *       s[b,h,i,j]  = scale * q_i . k_j + bias(h,i,j)
+ *       bias(h,i,j) = table[h, index[i,j]]   if index[i,j] >= 0
+ *                   = -inf                   if index[i,j] == -1   (pair hidden: a window lives in the index itself)
+ *       P = softmax_j(s),   lse_i = log sum_j exp(s_ij)   (lse includes the bias)
+ *       dTable[h,t] = sum over b and over (i,j) with index[i,j] == t of  P_ij * (keep_ij * dP_ij - delta_i)
+ *   index: int32 [N, N], values in [-1, T), shared by all batches and heads, static.  table: fp32 [H, T].  Dropout acts on
+ *   P with the mask function of sfcvit_attn_args, keep_ij = 1 / (1 - p) or 0: an all-zero table over an all-visible index
+ *   drops what sfcvit_attention_fwd drops.  The bias sits after the scale: dTable carries no scale factor.  Preconditions
+ *   (enforced by sfcvit_attention_bias_blocks, assumed by the kernels): every entry in [-1, T), every row has an entry >= 0.
+ *
+ *   The kernels are the masked ones with head h's table row staged in LDS once per workgroup and looked up per score;
+ *   the block map says which 64 x 64 blocks hold a visible pair.  The table gradient takes no atomics: a workgroup owns
+ *   one visited block of one head and a chunk of the batch, recomputes S and dP per image, sums P (keep dP - delta) in
+ *   fp32 registers over its chunk and stores the block into the workspace [chunks][H][visited blocks][64][64]; the
+ *   chunks are summed in ascending order, and one wave per dTable element then sums its bucket's positions in the fixed
+ *   order of the inverted index.  Two runs give the same bits.
+ * ---------------------------------------------------------------------- */
+#define SFCVIT_BIAS_MAX_N 1024
+#define SFCVIT_BIAS_MAX_BUCKETS 4096 /* one head's table row in LDS: 16 KiB */
+/* HOST, no HIP call: validates index_host [N, N] and writes
+ *   map_host [nb][nb], nb = ceil(N / 64): 0 = every entry -1 (skipped), 1 = visited;
+ *   the inverted index as CSR: offsets_host [T + 1], positions_host [number of entries >= 0, at most N * N]:
+ *   positions_host[offsets_host[t] .. offsets_host[t + 1]) are the i * N + j with index[i,j] == t, ascending.
+ * SFCVIT_EINVAL (reason in sfcvit_last_error()): null pointer, N outside 1 .. 1024, T outside 1 .. 4096, an entry < -1 or
+ * >= T (the message names row and column), a row without an entry >= 0 (the message names the row). */
+int sfcvit_attention_bias_blocks(const int32_t *index_host, int N, int T, uint8_t *map_host, int32_t *offsets_host,
+                                 int32_t *positions_host);
+/* Bytes of the table gradient's workspace for a map with `visited_blocks` non-zero entries. */
+int64_t sfcvit_attention_bias_workspace(int B, int N, int H, int visited_blocks);
+typedef struct sfcvit_attn_bias_args {
+    /* the fields of sfcvit_attn_mask_args without the mask, same meaning */
+    const void *qkv;
+    void *out;
+    float *lse;
+    const void *dout;
+    void *dqkv;
+    float *delta;
+    int32_t B, N, H, hd; /* hd = 64 only, 1 <= N <= 1024 */
+    float scale;
+    float dropout_p;
+    uint32_t dropout_seed;
+    const uint32_t *seed_off;
+    float *colsum_part;
+    int64_t colsum_part_bytes;
+    void *colsum_out;
+    int32_t colsum_bf16;
+    const uint8_t *block_map; /* device, [nb][nb] as written by sfcvit_attention_bias_blocks for this index */
+    /* the bias */
+    const int32_t *index;     /* device, [N, N] */
+    const float *table;       /* device, [H, T] fp32 */
+    int32_t T;
+    int32_t visited_blocks;   /* bwd: number of non-zero entries of block_map */
+    const int32_t *offsets;   /* bwd: device, [T + 1] */
+    const int32_t *positions; /* bwd: device, [offsets[T]] */
+    float *dtable;            /* bwd: out, device, [H, T] fp32; every element is written.  NULL: a frozen table -- its gradient
+                                 is not computed, and visited_blocks, offsets, positions and the workspace are not looked at */
+    void *workspace;          /* bwd: sfcvit_attention_bias_workspace(B, N, H, visited_blocks) bytes, 16-byte aligned */
+    int64_t workspace_bytes;
+} sfcvit_attn_bias_args;
+/* Argument checks (null, alignment, N, T, hd, dropout_p, workspace size) run before any HIP call.
+ * sfcvit_last_attn_kernel reports "attn_bias_fwd_kernel" / "attn_bias_bwd_kv_kernel".  colsum_out as in the masked backward. */
+int sfcvit_attention_bias_fwd(const sfcvit_attn_bias_args *a, void *stream);
+int sfcvit_attention_bias_bwd(const sfcvit_attn_bias_args *a, void *stream);
+
+/* ------------------------------------------------------------------------
  * Attention maps and attention-distance statistics
  *   replaces the `(output, [attn_weights per layer])` path of CustomTransformerEncoderLayer / CustomTransformerEncoder
  *   (src/models/vit.py:48-174, commented out there; average_attn_weights=False) and the need_weights=True branch of

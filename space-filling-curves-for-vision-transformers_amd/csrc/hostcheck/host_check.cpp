@@ -2,6 +2,7 @@
 // available on this pool, so the native host code gets a CPU-side -fsanitize=address,undefined build of its own):
 //   sfcvit_curve_table / _rc (curves.cpp), sfcvit_pixel_table (curves.cpp), sfcvit_tile_descriptors (patch_embed_tiled.hip,
 //   host part), the error path of common.cpp, the mask validation and block map of attention_masked.cpp (check_mask_blocks),
+//   the index validation, inverted index, workspace and argument checks of attention_bias.cpp (check_attention_bias),
 //   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv),
 //   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), tokenizer.cpp (check_tokenizer), drop_path.cpp (check_drop_path), model_ema.cpp (check_model_ema) and grad_accum.cpp (check_grad_accum), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
 //   and post passes each GEMM / attention shape of the benchmarked models gets).
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "../../../include/sfcvit.h"
+#include "../attention_bias.h"
 #include "../dispatch.h"
 #include "../drop_path.h"
 #include "../grad_accum.h"
@@ -371,6 +373,114 @@ static void check_mask_blocks() {
     CHECK(sfcvit_attention_mask_blocks(&one, 0, &b) == SFCVIT_EINVAL, "mask blocks: N = 0 accepted");
     CHECK(sfcvit_attention_mask_blocks(&one, 4097, &b) == SFCVIT_EINVAL, "mask blocks: N = 4097 accepted");
     CHECK(sfcvit_attention_mask_blocks(&one, 1, &b) == SFCVIT_OK && b == 2, "mask blocks: N = 1, zero mask: %d", int(b));
+}
+
+// sfcvit_attention_bias_blocks / _workspace and attn_bias_check (attention_bias.cpp) with heap buffers of exactly N * N index
+// entries, nb * nb map bytes, T + 1 offsets and as many positions as the index has visible entries.
+static void check_attention_bias() {
+    struct W { int N, w, visited, total; };
+    const W windows[] = {{1, 0, 1, 1}, {4, 1, 1, 1}, {70, 1, 4, 4}, {130, 40, 7, 9}, {196, 32, 10, 16}, {576, 64, 25, 81}, {1024, 0, 16, 256}};
+    for (const W &q : windows) {
+        const int N = q.N, nb = (N + 63) / 64, T = 2 * q.w + 1;
+        std::unique_ptr<int32_t[]> idx(new int32_t[size_t(N) * N]);
+        std::unique_ptr<uint8_t[]> map(new uint8_t[size_t(nb) * nb]);
+        std::unique_ptr<int32_t[]> off(new int32_t[T + 1]);
+        int nnz = 0;
+        for (int i = 0; i < N; i++)
+            for (int j = 0; j < N; j++) nnz += (idx[size_t(i) * N + j] = (i - j <= q.w && j - i <= q.w) ? j - i + q.w : -1) >= 0;
+        std::unique_ptr<int32_t[]> pos(new int32_t[nnz]);
+        CHECK(sfcvit_attention_bias_blocks(idx.get(), N, T, map.get(), off.get(), pos.get()) == SFCVIT_OK, "bias blocks N %d w %d: %s", N, q.w,
+              sfcvit_last_error());
+        int visited = 0;
+        for (int i = 0; i < nb * nb; i++) visited += map[i] != 0;
+        CHECK(visited == q.visited && nb * nb == q.total, "bias blocks N %d w %d: %d / %d visited, want %d / %d", N, q.w, visited, nb * nb,
+              q.visited, q.total);
+        // the inverted index: bucket t holds the pairs with j - i = t - w, ascending, and every visible pair exactly once
+        bool ok = off[0] == 0 && off[T] == nnz;
+        for (int t = 0; t < T && ok; t++) {
+            const int d = t - q.w, want = N - (d < 0 ? -d : d);
+            ok = off[t + 1] - off[t] == (want > 0 ? want : 0);
+            for (int k = off[t]; k < off[t + 1] && ok; k++) {
+                const int i = pos[k] / N, j = pos[k] % N;
+                ok = j - i == d && (k == off[t] || pos[k] > pos[k - 1]);
+            }
+        }
+        CHECK(ok, "bias blocks N %d w %d: inverted index wrong", N, q.w);
+        const size_t last = size_t(N) * N - 1;
+        const int32_t keep = idx[last];
+        idx[last] = T;
+        CHECK(sfcvit_attention_bias_blocks(idx.get(), N, T, map.get(), off.get(), pos.get()) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "outside"),
+              "bias blocks: entry T accepted");
+        idx[last] = -2;
+        CHECK(sfcvit_attention_bias_blocks(idx.get(), N, T, map.get(), off.get(), pos.get()) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), "outside"),
+              "bias blocks: entry -2 accepted");
+        idx[last] = keep;
+        for (int j = 0; j < N; j++) idx[size_t(N - 1) * N + j] = -1;
+        char want[32];
+        std::snprintf(want, sizeof(want), "row %d ", N - 1);
+        CHECK(sfcvit_attention_bias_blocks(idx.get(), N, T, map.get(), off.get(), pos.get()) == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), want),
+              "bias blocks: hidden row %d accepted or not named: '%s'", N - 1, sfcvit_last_error());
+    }
+    int32_t one = 0, off2[2] = {0, 0}, pos1 = 0;
+    uint8_t b = 0;
+    CHECK(sfcvit_attention_bias_blocks(nullptr, 1, 1, &b, off2, &pos1) == SFCVIT_EINVAL, "bias blocks: null index accepted");
+    CHECK(sfcvit_attention_bias_blocks(&one, 1, 1, nullptr, off2, &pos1) == SFCVIT_EINVAL, "bias blocks: null map accepted");
+    CHECK(sfcvit_attention_bias_blocks(&one, 1, 1, &b, nullptr, &pos1) == SFCVIT_EINVAL, "bias blocks: null offsets accepted");
+    CHECK(sfcvit_attention_bias_blocks(&one, 1, 1, &b, off2, nullptr) == SFCVIT_EINVAL, "bias blocks: null positions accepted");
+    CHECK(sfcvit_attention_bias_blocks(&one, 0, 1, &b, off2, &pos1) == SFCVIT_EINVAL, "bias blocks: N = 0 accepted");
+    CHECK(sfcvit_attention_bias_blocks(&one, 1025, 1, &b, off2, &pos1) == SFCVIT_EINVAL, "bias blocks: N = 1025 accepted");
+    CHECK(sfcvit_attention_bias_blocks(&one, 1, 0, &b, off2, &pos1) == SFCVIT_EINVAL, "bias blocks: T = 0 accepted");
+    CHECK(sfcvit_attention_bias_blocks(&one, 1, 4097, &b, off2, &pos1) == SFCVIT_EINVAL, "bias blocks: T = 4097 accepted");
+    CHECK(sfcvit_attention_bias_blocks(&one, 1, 1, &b, off2, &pos1) == SFCVIT_OK && b == 1 && off2[1] == 1 && pos1 == 0, "bias blocks: N = 1");
+
+    // the workspace: 16 KiB per (chunk, head, visited block); the chunks cover the batch, at most 32, none empty
+    for (int B : {1, 2, 3, 40, 64, 256})
+        for (int H : {1, 2, 12, 16})
+            for (int vb : {1, 4, 10, 25, 81, 256}) {
+                const BiasChunks c = bias_chunks(B, H, vb);
+                CHECK(c.per >= 1 && c.chunks >= 1 && c.chunks <= 32 && c.per * c.chunks >= B && c.per * (c.chunks - 1) < B,
+                      "bias chunks B %d H %d vb %d: per %d chunks %d", B, H, vb, c.per, c.chunks);
+                CHECK(sfcvit_attention_bias_workspace(B, 64, H, vb) == int64_t(c.chunks) * H * vb * 16384, "bias workspace B %d H %d vb %d", B, H, vb);
+            }
+    CHECK(sfcvit_attention_bias_workspace(0, 64, 1, 1) == 0 && sfcvit_attention_bias_workspace(1, 1025, 1, 1) == 0, "bias workspace: bad shape");
+
+    // the entry points' checks: fake aligned pointers, nothing is dereferenced
+    sfcvit_attn_bias_args a{};
+    a.qkv = ptr(0); a.out = ptr(1); a.lse = static_cast<float *>(ptr(2)); a.dout = ptr(3); a.dqkv = ptr(4); a.delta = static_cast<float *>(ptr(5));
+    a.B = 2; a.N = 130; a.H = 2; a.hd = 64; a.scale = 0.125f;
+    a.block_map = static_cast<const uint8_t *>(ptr(6)); a.index = static_cast<const int32_t *>(ptr(7)); a.table = static_cast<const float *>(ptr(8));
+    a.T = 81; a.visited_blocks = 7; a.offsets = static_cast<const int32_t *>(ptr(9)); a.positions = static_cast<const int32_t *>(ptr(10));
+    a.dtable = static_cast<float *>(ptr(11)); a.workspace = ptr(12); a.workspace_bytes = sfcvit_attention_bias_workspace(2, 130, 2, 7);
+    CHECK(attn_bias_check(&a, false, "t") == SFCVIT_OK && attn_bias_check(&a, true, "t") == SFCVIT_OK, "bias check: good arguments refused: %s", sfcvit_last_error());
+    auto refused = [&](auto &&change, bool bwd, const char *word) {
+        sfcvit_attn_bias_args c = a;
+        change(c);
+        CHECK(attn_bias_check(&c, bwd, "t") == SFCVIT_EINVAL && std::strstr(sfcvit_last_error(), word), "bias check: '%s' not refused: '%s'", word,
+              sfcvit_last_error());
+    };
+    CHECK(attn_bias_check(nullptr, false, "t") == SFCVIT_EINVAL, "bias check: null arguments accepted");
+    refused([](sfcvit_attn_bias_args &c) { c.qkv = nullptr; }, false, "qkv / out / lse");
+    refused([](sfcvit_attn_bias_args &c) { c.dout = nullptr; }, true, "dout / dqkv / delta");
+    refused([](sfcvit_attn_bias_args &c) { c.index = nullptr; }, false, "index / table / block_map");
+    refused([](sfcvit_attn_bias_args &c) { c.table = nullptr; }, false, "index / table / block_map");
+    refused([](sfcvit_attn_bias_args &c) { c.offsets = nullptr; }, true, "offsets / positions");
+    {   // dtable == NULL is a frozen table: nothing of the table gradient is asked for
+        sfcvit_attn_bias_args c = a;
+        c.dtable = nullptr; c.offsets = nullptr; c.positions = nullptr; c.workspace = nullptr; c.workspace_bytes = 0; c.visited_blocks = 0;
+        CHECK(attn_bias_check(&c, true, "t") == SFCVIT_OK, "bias check: frozen table refused: %s", sfcvit_last_error());
+    }
+    refused([](sfcvit_attn_bias_args &c) { c.hd = 128; }, false, "head dim 128");
+    refused([](sfcvit_attn_bias_args &c) { c.dropout_p = 1.f; }, false, "dropout_p");
+    refused([](sfcvit_attn_bias_args &c) { c.B = 0; }, false, "B=0");
+    refused([](sfcvit_attn_bias_args &c) { c.N = 1025; }, false, "N=1025");
+    refused([](sfcvit_attn_bias_args &c) { c.T = 0; }, false, "T=0");
+    refused([](sfcvit_attn_bias_args &c) { c.T = 4097; }, false, "T=4097");
+    refused([](sfcvit_attn_bias_args &c) { c.qkv = static_cast<const char *>(c.qkv) + 2; }, false, "16-byte aligned");
+    refused([](sfcvit_attn_bias_args &c) { c.index = c.index + 1; }, false, "index must be 16-byte aligned");
+    refused([](sfcvit_attn_bias_args &c) { c.visited_blocks = 0; }, true, "visited_blocks=0");
+    refused([](sfcvit_attn_bias_args &c) { c.visited_blocks = 10; }, true, "visited_blocks=10");
+    refused([](sfcvit_attn_bias_args &c) { c.workspace = nullptr; }, true, "workspace");
+    refused([](sfcvit_attn_bias_args &c) { c.workspace_bytes -= 1; }, true, "workspace");
 }
 
 // pos_embed_plan / pos_embed_check_* (pos_embed.cpp): the geometry at the workload shapes and the edge shapes of the tests, and
@@ -1658,6 +1768,7 @@ int main() {
     CHECK(sfcvit_abi_version() == SFCVIT_ABI_VERSION, "abi version");
     check_dispatch();
     check_mask_blocks();
+    check_attention_bias();
     check_pos_embed();
     check_token_pool();
     check_dwconv();

@@ -151,18 +151,42 @@ def build_parser():
     win.add_argument("--attn-window-2d", type=float, default=None, metavar="R",
                      help="local attention in the image: every token attends to the tokens whose centres lie within R pixels "
                           "of its own in both axes (sfcvit.masks.image_window on the tokenizer's positions)")
+    ap.add_argument("--rel-pos-bias", choices=["curve", "image"], default=None,
+                    help="a learned relative position bias per head and encoder layer on the attention scores (Swin / BEiT), the "
+                         "offset taken along the curve (j - i) or in the image (the displacement of the token centres, whatever "
+                         "the curve); checkpoints then carry encoder.rel_pos_bias.<l> [heads, buckets].  --attn-window W (with "
+                         "curve) or --attn-window-2d R (with image) given with it becomes the window of the bias index instead "
+                         "of a mask.  Works with --graph, --accum-steps, --model-ema, --drop-path, --pool and --pos-embed")
+    ap.add_argument("--rel-pos-init-std", type=float, default=0.0,
+                    help="standard deviation of the bias tables' initial values (default 0: the model starts out computing "
+                         "what it computes without the bias)")
     ap.add_argument("--mean", type=float, nargs=3, default=[0.4914, 0.4822, 0.4465])      # main.py:176-177 (CIFAR)
     ap.add_argument("--std", type=float, nargs=3, default=[0.2023, 0.1994, 0.2010])
     return ap
 
 
+def rel_pos_window(a):
+    """The window of --rel-pos-bias's index, taken from the window option of its own kind (None: every pair visible);
+    SystemExit for the other kind's option."""
+    if a.rel_pos_bias == "curve" and a.attn_window_2d is not None:
+        raise SystemExit("--rel-pos-bias curve counts offsets along the curve: its window is --attn-window W (tokens), not "
+                         "--attn-window-2d")
+    if a.rel_pos_bias == "image" and a.attn_window is not None:
+        raise SystemExit("--rel-pos-bias image counts offsets in the image: its window is --attn-window-2d R (pixels), not "
+                         "--attn-window")
+    return a.attn_window if a.rel_pos_bias == "curve" else a.attn_window_2d
+
+
 def build_model(a, patch_embed, attn_mask=None):
     """The model of the parsed arguments `a` (fp32, on the CPU: main() moves and casts it)."""
+    rel = {}
+    if getattr(a, "rel_pos_bias", None) is not None:      # else: the call as it is without the option
+        rel = dict(rel_pos_bias=a.rel_pos_bias, rel_pos_window=rel_pos_window(a), rel_pos_init_std=a.rel_pos_init_std)
     return VisionTransformer1D(patch_embed=patch_embed, depth=a.depth, n_heads=a.heads, mlp_dim=a.mlp_dim,
                                num_classes=a.classes,
                                token_aggregator=a.token_aggregator or False, token_mix=a.token_mix,
                                attn_mask=attn_mask, pos_embed=a.pos_embed,
-                               pos_embed_std=a.pos_embed_std, pool=a.pool, drop_path_rate=a.drop_path)
+                               pos_embed_std=a.pos_embed_std, pool=a.pool, drop_path_rate=a.drop_path, **rel)
 
 
 def parse_args(argv=None):
@@ -226,7 +250,9 @@ def main():
 
     patch_embed = build_tokenizer(a)
     attn_mask = None
-    if a.attn_window is not None or a.attn_window_2d is not None:
+    if a.rel_pos_bias is not None:
+        rel_pos_window(a)                                       # a window of the other kind: refused before anything is built
+    elif a.attn_window is not None or a.attn_window_2d is not None:
         from sfcvit import masks
         from sfcvit.ops import AttentionMask
         if a.attn_window is not None:
@@ -240,6 +266,10 @@ def main():
             print(f"attention mask: {attn_mask.visited_blocks}/{attn_mask.total_blocks} blocks of 64 x 64 visited "
                   f"(N = {attn_mask.n_tokens})")
     model = build_model(a, patch_embed, attn_mask).to(device, dtype=torch.bfloat16)   # main.py:157: bf16 parameters
+    if a.rel_pos_bias is not None and rank == 0:
+        bi = model.encoder.rel_pos_index
+        print(f"relative position bias ({a.rel_pos_bias}): {bi.n_buckets} buckets per head, {bi.visited_blocks}/{bi.total_blocks} "
+              f"blocks of 64 x 64 visited (N = {bi.n_tokens})")
     train_criterion, test_criterion = SoftTargetCrossEntropy(), nn.CrossEntropyLoss()
     if a.model_ema_warmup and a.model_ema is None:
         raise SystemExit("--model-ema-warmup needs --model-ema")
@@ -271,6 +301,8 @@ def main():
                 augment.load_state_dict(ck["augment_state_dict"])       # the draw stream goes on where it stopped
     if a.attention_report and attn_mask is not None:
         raise SystemExit("--attention-report measures unmasked attention; it cannot be combined with --attn-window / --attn-window-2d")
+    if a.attention_report and a.rel_pos_bias is not None:
+        raise SystemExit("--attention-report measures attention without a bias; it cannot be combined with --rel-pos-bias")
     if a.attention_report and a.pool == "cls":
         raise SystemExit("--attention-report has no place in the image for the CLS token; it cannot be combined with --pool cls")
     if a.attention_report and rank == 0:

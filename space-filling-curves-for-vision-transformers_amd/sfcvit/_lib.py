@@ -54,6 +54,12 @@ class AttnMaskArgs(ctypes.Structure):
     _fields_ = AttnArgs._fields_ + [("mask", c_void_p), ("block_map", c_void_p)]
 
 
+class AttnBiasArgs(ctypes.Structure):
+    _fields_ = AttnArgs._fields_ + [("block_map", c_void_p), ("index", c_void_p), ("table", c_void_p), ("T", c_int32),
+                                    ("visited_blocks", c_int32), ("offsets", c_void_p), ("positions", c_void_p),
+                                    ("dtable", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64)]
+
+
 class AttnProbeArgs(ctypes.Structure):
     _fields_ = [("qkv", c_void_p), ("lse", c_void_p),
                 ("B", c_int32), ("N", c_int32), ("H", c_int32), ("hd", c_int32), ("scale", c_float),
@@ -158,6 +164,10 @@ SIGNATURES = {
     "sfcvit_attention_mask_blocks": (c_int, [c_void_p, c_int, c_void_p]),
     "sfcvit_attention_masked_fwd": (c_int, [ctypes.POINTER(AttnMaskArgs), c_void_p]),
     "sfcvit_attention_masked_bwd": (c_int, [ctypes.POINTER(AttnMaskArgs), c_void_p]),
+    "sfcvit_attention_bias_blocks": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sfcvit_attention_bias_workspace": (c_int64, [c_int, c_int, c_int, c_int]),
+    "sfcvit_attention_bias_fwd": (c_int, [ctypes.POINTER(AttnBiasArgs), c_void_p]),
+    "sfcvit_attention_bias_bwd": (c_int, [ctypes.POINTER(AttnBiasArgs), c_void_p]),
     "sfcvit_attention_probs": (c_int, [ctypes.POINTER(AttnProbeArgs), c_void_p]),
     "sfcvit_attention_stats": (c_int, [ctypes.POINTER(AttnProbeArgs), c_void_p]),
     "sfcvit_dwconv1d_out_len": (c_int, [c_int, c_int, c_int]),

@@ -148,6 +148,10 @@ def attention_report(model, images, layers=None, maps=False, head_mean=True, row
     if getattr(model, "attn_mask", None) is not None:
         raise NotImplementedError("attention_report: the model was built with attn_mask=; the probe kernels rebuild the attention "
                                   "map from q, k and lse WITHOUT a mask and would report wrong maps and distances")
+    if getattr(getattr(model, "encoder", None), "rel_pos_bias", None) is not None:
+        raise NotImplementedError("attention_report: the model was built with rel_pos_bias=; the probe kernels rebuild the attention "
+                                  "map from q, k and lse WITHOUT the bias and would report wrong maps and distances "
+                                  "(rel_pos_bias_tables reads the learned reach out of the tables themselves)")
     if isinstance(model, (VisionTransformer, VisionTransformer1D)):
         walk = _vit_layers
     elif isinstance(model, (altvit.SimpleViT, altvit.HilbertViT)):
@@ -189,3 +193,26 @@ def report_summary(report):
                         "sequence_distance": e["sequence_distance"].mean(dim=0).tolist(),
                         "entropy": e["entropy"].mean(dim=0).tolist(),
                         "mass_error": e["mass_error"]} for e in report["layers"]]}
+
+
+def rel_pos_bias_tables(model):
+    """The learned relative position bias of a model built with rel_pos_bias=: {"kind": "curve" | "image", "window": the
+    model's rel_pos_window, "cell": pixels per cell ("image" only), "offsets": what each bucket means (relpos.bucket_offsets:
+    j - i along the sequence, or (d_row, d_col) in cells; names for the three CLS buckets), "tables": per layer [H, T] fp32 on
+    the CPU}.  How far head h of layer l looks, in the geometry the model was given, is the shape of tables[l][h] over
+    `offsets`."""
+    from . import relpos
+    enc = getattr(model, "encoder", None)
+    tables = getattr(enc, "rel_pos_bias", None)
+    if tables is None:
+        raise ValueError("rel_pos_bias_tables: the model was built without rel_pos_bias=")
+    kind, window = model.rel_pos_kind, model.rel_pos_window
+    cls = hasattr(enc, "cls_token")
+    T = enc.rel_pos_index.n_buckets
+    out = {"kind": kind, "window": window,
+           "offsets": relpos.bucket_offsets(kind, T, n_tokens=enc.max_len, window=window if kind == "curve" else None, cls_token=cls),
+           "tables": [t.detach().to("cpu", torch.float32) for t in tables]}
+    if kind == "image":
+        from .models.vit import rel_pos_cell
+        out["cell"] = rel_pos_cell(model.patch_embed)
+    return out

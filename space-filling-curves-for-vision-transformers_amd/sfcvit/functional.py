@@ -419,6 +419,60 @@ def _attention_mask(mask, n_tokens, what):
     return ops.as_attention_mask(mask, n_tokens)
 
 
+def _table_grad(dtable, table):
+    """The fp32 table gradient of the bias kernels in the parameter's dtype: in its gradient slot when it has one."""
+    slot = _slot(table)
+    if slot is None:
+        return _like(dtable, table)
+    slot.copy_(dtable)
+    return slot
+
+
+class _BiasedAttention(Function):
+    """_Attention with a learned relative position bias per head: softmax(q k^T / sqrt(hd) + table[h, index]) v on the bias
+    kernels (ops.attention_bias_fwd / _bwd).  The table is cast to fp32 for the kernel per call."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_heads, scale, table, bias_index):
+        qkv = _c(qkv)
+        t32 = _c(table.detach().to(torch.float32))
+        out, lse = ops.attention_bias_fwd(qkv, n_heads, t32, bias_index, scale=scale)
+        ctx.save_for_backward(qkv, out, lse, t32)
+        ctx.n_heads, ctx.scale, ctx.bias_index, ctx.table = n_heads, scale, bias_index, table
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, t32 = ctx.saved_tensors
+        want = ctx.needs_input_grad[3]                          # a frozen table costs nothing
+        dqkv, dtable = ops.attention_bias_bwd(qkv, out, lse, _c(dout), ctx.n_heads, t32, ctx.bias_index, scale=ctx.scale, table_grad=want)
+        return dqkv, None, None, _table_grad(dtable, ctx.table) if want else None, None
+
+
+def _rel_bias(rel_bias, mask, n_tokens, n_heads, what):
+    """A layer call's rel_bias = (table [H, T], ops.AttentionBiasIndex), checked; None stays None.  Not together with a mask
+    (a window belongs in the index) and not under tracing (the torch.library ops have no biased form)."""
+    if rel_bias is None:
+        return None
+    if mask is not None:
+        raise ValueError(f"{what}: rel_bias and an attention mask cannot be combined: express the window in the bias index "
+                         "(sfcvit.relpos.curve_offsets(window=) / image_offsets(radius=)), where hidden pairs are -1")
+    if _traced():
+        raise NotImplementedError(f"{what}: a relative position bias is not supported under torch.compile / tracing (the "
+                                  "torch.library ops have no biased form); run the biased model eagerly")
+    try:
+        table, index = rel_bias
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: rel_bias must be (table [H, T], ops.AttentionBiasIndex)") from None
+    if not isinstance(index, ops.AttentionBiasIndex) or not isinstance(table, torch.Tensor):
+        raise ValueError(f"{what}: rel_bias must be (table [H, T], ops.AttentionBiasIndex)")
+    if tuple(table.shape) != (n_heads, index.n_buckets):
+        raise ValueError(f"{what}: rel_bias table must be [H, T] = {(n_heads, index.n_buckets)}, got {tuple(table.shape)}")
+    if index.n_tokens != n_tokens:
+        raise ValueError(f"{what}: rel_bias index for {index.n_tokens} tokens on a sequence of {n_tokens}")
+    return table, index
+
+
 class _Attention(Function):
     """softmax(q k^T / sqrt(hd)) v per head on a packed projection [B, N, 3 * H * hd] (q | k | v thirds, head h at
     columns h*hd.. of each third): the core of nn.MultiheadAttention and of altvit.Attention (altvit.py:131-142)."""
@@ -449,17 +503,23 @@ def _head_padding(D, n_heads):
     return hd, hp
 
 
-def attention(qkv, n_heads, mask=None):
+def attention(qkv, n_heads, mask=None, rel_bias=None):
     """Head dims the kernels do not have (32, 48, 96, ...) run zero-padded to the next one that exists: the padded
     q / k / v columns add nothing to q k^T or p v, the softmax scale stays 1 / sqrt(head dim).
     mask: None, or an additive attention mask [N, N] shared by all batches and heads (ops.AttentionMask, a float tensor,
     or a bool tensor with True = may not attend): scores q k^T / sqrt(hd) + mask on the masked kernels (kernel head dim
-    64: head dims up to 64).  Without a mask nothing changes."""
+    64: head dims up to 64).  Without a mask nothing changes.
+    rel_bias: None, or (table [H, T], ops.AttentionBiasIndex): a learned relative position bias per head, scores
+    q k^T / sqrt(hd) + table[h, index[i, j]] on the bias kernels (kernel head dim 64); the table receives a gradient.  Not
+    together with a mask: a window is part of the index (sfcvit.relpos)."""
     qkv = _bf(qkv)
     D = qkv.shape[-1] // 3
     hd, hp = _head_padding(D, n_heads)
+    rel_bias = _rel_bias(rel_bias, mask, qkv.shape[-2], n_heads, "attention")
     mask = _attention_mask(mask, qkv.shape[-2], "attention")
     core = _Attention.apply if mask is None else (lambda t, H, sc: _MaskedAttention.apply(t, H, sc, mask))
+    if rel_bias is not None:
+        core = lambda t, H, sc: _BiasedAttention.apply(t, H, sc, *rel_bias)      # noqa: E731
     if hp == hd:
         return core(qkv, n_heads, None)
     lead = qkv.shape[:-1]
@@ -791,7 +851,7 @@ class _EncoderLayer(Function):
 
     @staticmethod
     def launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale,
-                 attn_mask=None, drop_path=None):
+                 attn_mask=None, drop_path=None, rel_bias=None):
         """The forward's kernel launches, every intermediate returned (forward saves them; encoder_layer_probe reads the
         attention inputs out of the same sequence, so what it carries on is what forward computes)."""
         B, N, D = x.shape
@@ -799,7 +859,9 @@ class _EncoderLayer(Function):
         sa, s1_, sf, s2_ = seeds
         x2 = _c(x).view(B * N, D)
         qkv = ops.gemm(x2, in_w, bias=in_b)
-        if attn_mask is None:
+        if rel_bias is not None:                            # (fp32 table [H, T], ops.AttentionBiasIndex): the bias kernels
+            o, lse = ops.attention_bias_fwd(qkv.view(B, N, 3 * Da), n_heads, *rel_bias, p, sa, scale=scale)
+        elif attn_mask is None:
             o, lse = ops.attention_fwd(qkv.view(B, N, 3 * Da), n_heads, p, sa, scale=scale, any_length=True)
         else:                                               # an ops.AttentionMask: the masked kernels, and only then
             o, lse = ops.attention_masked_fwd(qkv.view(B, N, 3 * Da), n_heads, *attn_mask.on(x.device), p, sa, scale=scale)
@@ -824,11 +886,15 @@ class _EncoderLayer(Function):
 
     @staticmethod
     def forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale,
-                attn_mask=None, drop_path=None):
+                attn_mask=None, drop_path=None, rel_table=None, rel_index=None):
         B, N, D = x.shape
+        # the attention core's third form: the table parameter cast to fp32 for the kernels, once per call
+        rel_bias = None if rel_index is None else (_c(rel_table.detach().to(torch.float32)), rel_index)
         x2, qkv, o, lse, s1, mean1, rstd1, x1, hbits, h, s2, y, mean2, rstd2 = _EncoderLayer.launches(
-            x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale, attn_mask, drop_path)
+            x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale, attn_mask, drop_path,
+            rel_bias)
         ctx.hbits, ctx.attn_mask, ctx.drop_path = hbits, attn_mask, drop_path
+        ctx.rel_bias, ctx.rel_table = rel_bias, rel_table
         ctx.save_for_backward(x2, qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2,
                               in_w, out_w, n1_w, w1, w2, n2_w)
         ctx.n_heads, ctx.shape, ctx.p, ctx.seeds, ctx.scale = n_heads, (B, N, D), p, seeds, scale
@@ -887,7 +953,14 @@ class _EncoderLayer(Function):
         # the in_proj bias gradient (column sums of dqkv) comes out of the attention backward itself
         bi_slot = _slot(in_b)
         attn_mask = getattr(ctx, "attn_mask", None)         # library.py's traced backward builds its own ctx: never masked
-        if attn_mask is None:
+        rel_bias = getattr(ctx, "rel_bias", None)           # ... and never biased
+        dtable = None
+        if rel_bias is not None:
+            want = ctx.needs_input_grad[20]                     # a frozen table costs nothing
+            dqkv, dtable, dbi = ops.attention_bias_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), ctx.n_heads, *rel_bias, p, sa,
+                                                       colsum=bi_slot if bi_slot is not None else True, scale=ctx.scale, table_grad=want)
+            dtable = _table_grad(dtable, ctx.rel_table) if want else None
+        elif attn_mask is None:
             dqkv, dbi = ops.attention_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), ctx.n_heads, p, sa,
                                           colsum=bi_slot if bi_slot is not None else True, scale=ctx.scale, any_length=True)
         else:
@@ -901,9 +974,11 @@ class _EncoderLayer(Function):
         dx = ops.gemm_dx(dqkv, in_w, residual=ds1)
         if ss:
             ss.join(dw2, dw1, dwo, dwi)
-        # one gradient per argument of apply(): the mask is a 19th argument only when there is one, stochastic depth a 20th
+        # one gradient per argument of apply(): the mask is a 19th argument only when there is one, stochastic depth a 20th, the
+        # bias table and its index a 21st and 22nd
         return ((dx.view(B, N, D), dwi, dbi, dwo, dbo, dg1, dbt1, dw1, db1, dw2, db2, dg2, dbt2, None, None, None, None, None)
-                + ((None, None) if drop_path is not None else () if attn_mask is None else (None,)))
+                + ((None, None, dtable, None) if rel_bias is not None
+                   else (None, None) if drop_path is not None else () if attn_mask is None else (None,)))
 
 
 def _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads):
@@ -935,7 +1010,7 @@ def encoder_layer_probe(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2,
 
 
 def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5,
-                  dropout_p=0.0, attn_mask=None, drop_path=0.0):
+                  dropout_p=0.0, attn_mask=None, drop_path=0.0, rel_bias=None):
     """dropout_p > 0 = training-mode nn.TransformerEncoderLayer (fresh masks every call).
     attn_mask = nn.TransformerEncoderLayer's src_mask: None, or an additive [N, N] mask as in `attention` (build an
     ops.AttentionMask once when the layer runs more than once).  With None the launches and the bits are those of a call
@@ -947,11 +1022,17 @@ def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w,
     drop_path = r in (0, 1): stochastic depth for a layer in TRAINING mode (the caller passes 0 in eval, as it passes
     dropout_p = 0): each of the two residual branches is dropped per image with probability r and scaled by 1 / (1 - r)
     otherwise, the two sites drawing independently (timm's drop_path1 / drop_path2, scale_by_keep=True).  0 runs the launches
-    and gives the bits of a call without the argument.  Not under tracing."""
+    and gives the bits of a call without the argument.  Not under tracing.
+    rel_bias = (table [H, T] -- a parameter in any float dtype --, ops.AttentionBiasIndex): a learned relative position bias
+    per head on the attention scores, softmax(q k^T / sqrt(hd) + table[h, index[i, j]]), with dropout as without it; the
+    attention core alone changes, to the bias kernels, and the table receives its gradient (in its dtype, in its gradient
+    slot when it has one).  Not with attn_mask (a window is part of the index: sfcvit.relpos), not under tracing; None
+    runs the call as it is without the argument."""
     drop_path = float(drop_path)
     if not 0.0 <= drop_path < 1.0:
         raise ValueError(f"encoder_layer: drop_path={drop_path} outside [0, 1)")
     args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
+    rel_bias = _rel_bias(rel_bias, attn_mask, args[0].shape[1], n_heads, "encoder_layer")
     attn_mask = _attention_mask(attn_mask, args[0].shape[1], "encoder_layer")
     if drop_path > 0 and _traced():
         raise NotImplementedError("encoder_layer: drop_path > 0 has no traced form (torch.compile); run the layer eagerly")
@@ -959,8 +1040,10 @@ def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w,
         from . import library      # (dropout seeds are drawn inside the op: nothing data-dependent in the traced graph)
         return library.encoder_layer(args, n_heads, eps, float(dropout_p), scale)
     seeds = tuple(ops.next_seed() for _ in range(4)) if dropout_p > 0 else (0, 0, 0, 0)
+    path = (drop_path, (ops.next_seed(), ops.next_seed())) if drop_path > 0 else None
+    if rel_bias is not None:
+        return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale, None, path, *rel_bias)
     if drop_path > 0:
-        path = (drop_path, (ops.next_seed(), ops.next_seed()))
         return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale, attn_mask, path)
     if attn_mask is not None:
         return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale, attn_mask)

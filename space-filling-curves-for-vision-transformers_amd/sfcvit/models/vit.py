@@ -133,8 +133,11 @@ class TransformerSeqEncoder(nn.Module):
     vit.py:152-174).  A mask is not a parameter or a buffer: it never enters state_dict."""
 
     def __init__(self, input_dim, max_len, n_head, hidden_dim, method, dropout_p=0.1, n_layers=1, cls_token=False,
-                 drop_path_rate=0.0):
-        """drop_path_rate: stochastic depth (DropPath) in training mode.  Layer l of L drops each of its two residual branches
+                 drop_path_rate=0.0, rel_pos_bias=None):
+        """rel_pos_bias: None, or an ops.AttentionBiasIndex (or (index, init_std)): every layer adds a learned relative
+        position bias per head to its attention scores, one table `rel_pos_bias.<l>` [n_head, T] per layer in a ParameterList
+        (attach_rel_pos_bias; the models call it after everything else is constructed).
+        drop_path_rate: stochastic depth (DropPath) in training mode.  Layer l of L drops each of its two residual branches
         per image with probability drop_path_rates[l] = drop_path_rate * l / (L - 1) (0 for the first layer; a single layer
         gets drop_path_rate) and scales the kept ones by 1 / (1 - rate).  No parameter, buffer or state_dict key; eval mode and
         rate 0 run the launches they run without it.
@@ -158,6 +161,22 @@ class TransformerSeqEncoder(nn.Module):
                 raise ValueError(f"cls_token=True: input_dim={input_dim} must be a multiple of 8 (the kernels move 16-byte "
                                  "vectors of 8 channels)")
             self.cls_token = nn.Parameter(torch.zeros(1, 1, input_dim))
+        if rel_pos_bias is not None:
+            index, std = rel_pos_bias if isinstance(rel_pos_bias, tuple) else (rel_pos_bias, 0.0)
+            self.attach_rel_pos_bias(index, std)
+
+    def attach_rel_pos_bias(self, bias_index, init_std=0.0):
+        """One table [n_head, T] per layer, zeros or randn * init_std (init_std = 0 draws nothing: the model then computes
+        at initialisation what it computes without the bias).  The index is static and held outside state_dict."""
+        if not isinstance(bias_index, ops.AttentionBiasIndex):
+            raise ValueError("rel_pos_bias: an ops.AttentionBiasIndex is expected (sfcvit.relpos builds the index)")
+        n = self.max_len + (1 if hasattr(self, "cls_token") else 0)
+        if bias_index.n_tokens != n:
+            raise ValueError(f"rel_pos_bias: index for {bias_index.n_tokens} tokens on an encoder of {n}")
+        shape = (self.n_head, bias_index.n_buckets)
+        self.rel_pos_index = bias_index
+        self.rel_pos_bias = nn.ParameterList(
+            nn.Parameter(torch.randn(shape) * init_std if init_std > 0 else torch.zeros(shape)) for _ in self.transformer.layers)
 
     def _mask(self, mask):
         """The AttentionMask of `mask`; a tensor is validated and uploaded at its first use and remembered while the same
@@ -172,11 +191,17 @@ class TransformerSeqEncoder(nn.Module):
     def forward(self, x, mask=None):
         p = self.dropout_p if self.training else 0.0
         mask = self._mask(mask)
+        tables = getattr(self, "rel_pos_bias", None)
+        if tables is not None and mask is not None:
+            raise ValueError("TransformerSeqEncoder: rel_pos_bias and a mask cannot be combined; the window belongs in the "
+                             "bias index (rel_pos_window)")
         if hasattr(self, "cls_token"):
             x = F.cls_prepend(x, self.cls_token)                # vit.py:237-238
-        for layer, rate in zip(self.transformer.layers, self.drop_path_rates):
+        for l, (layer, rate) in enumerate(zip(self.transformer.layers, self.drop_path_rates)):
             a = layer.self_attn
             path = {"drop_path": rate} if self.training and rate > 0 else {}      # else: the call as it is without the feature
+            if tables is not None:
+                path["rel_bias"] = (tables[l], self.rel_pos_index)
             x = F.encoder_layer(x, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
                                 layer.norm1.weight, layer.norm1.bias, layer.linear1.weight, layer.linear1.bias,
                                 layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias,
@@ -319,6 +344,48 @@ def _model_mask(attn_mask, n_patches, pool):
     return ops.as_attention_mask(attn_mask, n)
 
 
+REL_POS_KINDS = ("curve", "image")
+
+
+def _attach_rel_pos_bias(model, kind, window, init_std, attn_mask, pool):
+    """The models' `rel_pos_bias` keyword, on request only and constructed LAST, after `ta`, `pos_embed` and `cls_token`:
+    every other parameter then draws the same initial values as without it, and the default module tree is today's.
+    "curve": the offset j - i along the token sequence, rel_pos_window in tokens; "image": the displacement of the token
+    centres in cells of sqrt(pixels per token) pixels, rel_pos_window in pixels.  One table per encoder layer,
+    `encoder.rel_pos_bias.<l>` [H, T]."""
+    if kind is None or kind is False:
+        if window is not None:
+            raise ValueError("rel_pos_window needs rel_pos_bias='curve' or 'image'")
+        return
+    if kind not in REL_POS_KINDS:
+        raise ValueError(f"rel_pos_bias={kind!r}: None, {', '.join(map(repr, REL_POS_KINDS))} expected")
+    if attn_mask is not None:
+        raise ValueError("rel_pos_bias and attn_mask cannot be combined: pass the window as rel_pos_window (tokens for 'curve', "
+                         "pixels for 'image'); the bias index then hides the pairs outside it")
+    from .. import relpos
+    pe = model.patch_embed
+    if kind == "curve":
+        index, T = relpos.curve_offsets(pe.n_patches, window)
+    else:
+        from ..analysis import token_positions                  # (analysis imports this module: resolved at call time)
+        pos = token_positions(pe)
+        index, T = relpos.image_offsets(pos, rel_pos_cell(pe), window)
+    if pool == "cls":
+        index, T = relpos.with_cls_token(index, T)
+    model.rel_pos_kind, model.rel_pos_window = kind, window
+    model.encoder.attach_rel_pos_bias(ops.AttentionBiasIndex(index, T), float(init_std))
+
+
+def rel_pos_cell(patch_embed):
+    """The pixel pitch image offsets are counted in: the square root of the pixels per token."""
+    levels = getattr(patch_embed, "levels", None)               # hierarchical: level 0 is the sequence (analysis.token_positions)
+    pe = levels[0] if levels is not None else patch_embed
+    geom = getattr(pe, "_geom", None)                           # (image side, pre-patch side, group)
+    if geom is None:
+        raise ValueError(f"rel_pos_bias='image': {type(pe).__name__} does not say how many pixels a token covers")
+    return math.sqrt(geom[0] * geom[0] / pe.n_patches)
+
+
 def _make_head(pool, embed_dim, n_patches, num_classes, head_dropout_p):
     if pool is None:
         return MultiLayerPredictor(embed_dim, n_patches, n_layers=2, num_classes=num_classes, dropout_p=head_dropout_p)
@@ -330,8 +397,17 @@ class VisionTransformer(nn.Module):
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, attn_mask=None,
-                 pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0):
-        """drop_path_rate: stochastic depth over the encoder layers (TransformerSeqEncoder; `encoder.drop_path_rates`).
+                 pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0, rel_pos_bias=None, rel_pos_window=None,
+                 rel_pos_init_std=0.0):
+        """rel_pos_bias: None (the model as it is without the keyword), "curve" or "image": every encoder layer adds a learned
+        relative position bias per head to its attention scores, softmax(q k^T / sqrt(hd) + b_h[offset(i, j)]), the offset taken
+        along the token sequence (j - i) or in the image (the displacement of the token centres in cells of sqrt(pixels per
+        token) pixels, whatever the curve).  rel_pos_window: None, or the window the index hides pairs beyond -- tokens for
+        "curve", pixels for "image" (the windows of sfcvit.masks); not together with attn_mask.  One table per layer,
+        `encoder.rel_pos_bias.<l>` [H, T], constructed last; rel_pos_init_std = 0 (zeros: the model starts out computing what
+        it computes without the bias) or the std of a normal draw.  With pool="cls" the CLS token gets three buckets of its own
+        (sfcvit.relpos.with_cls_token).
+        drop_path_rate: stochastic depth over the encoder layers (TransformerSeqEncoder; `encoder.drop_path_rates`).
         attn_mask: None, or a mask for every encoder layer (ops.as_attention_mask's forms; sfcvit.masks builds windows).
         Held outside state_dict: checkpoint keys are the reference's with or without it.
         pos_embed: None / False (the reference as shipped), "learned" (vit.py:360-361: a Parameter [1, N, D] = randn *
@@ -355,6 +431,7 @@ class VisionTransformer(nn.Module):
         self.mlp_head = _make_head(pool, embed_dim, self.patch_embed.n_patches, num_classes, head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)
+        _attach_rel_pos_bias(self, rel_pos_bias, rel_pos_window, rel_pos_init_std, self.attn_mask, pool)
 
     def forward(self, x, mix=None):
         """mix: a sfcvit.training.BatchMix applied to the image batch by the tokenizer, or None."""
@@ -374,8 +451,9 @@ class VisionTransformer1D(nn.Module):
 
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False, attn_mask=None,
-                 pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0):
-        """attn_mask, pos_embed, pos_embed_std, pool, drop_path_rate: as in VisionTransformer (the table is added directly after the tokenizer
+                 pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0, rel_pos_bias=None, rel_pos_window=None,
+                 rel_pos_init_std=0.0):
+        """attn_mask, pos_embed, pos_embed_std, pool, drop_path_rate, rel_pos_bias, rel_pos_window, rel_pos_init_std: as in VisionTransformer (the table is added directly after the tokenizer
         and, if present, `ta`: before `mlp_mixer`; with pool="cls" the token joins after `mlp_mixer`, whose weights stay sized
         for the N patch tokens)."""
         super().__init__()
@@ -392,6 +470,7 @@ class VisionTransformer1D(nn.Module):
         self.mlp_head = _make_head(pool, embed_dim, self.patch_embed.n_patches, num_classes, head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)
+        _attach_rel_pos_bias(self, rel_pos_bias, rel_pos_window, rel_pos_init_std, self.attn_mask, pool)
 
     def forward(self, x, mix=None):
         """mix: a sfcvit.training.BatchMix applied to the image batch by the tokenizer, or None."""

@@ -655,6 +655,118 @@ def attention_masked_bwd(qkv, out, lse, dout, n_heads, mask, block_map, dropout_
     return dqkv if cs is None else (dqkv, cs)
 
 
+class AttentionBiasIndex:
+    """The static half of a relative position bias: an int32 [N, N] bucket index (CPU; values in [-1, n_buckets), -1 = the
+    pair is hidden, shared by all batches and heads; sfcvit.relpos builds them) validated by sfcvit_attention_bias_blocks,
+    with its block map (one byte per 64 x 64 block: 0 skip, 1 visited) and its inverted index (CSR: offsets [T + 1],
+    positions = i * N + j ascending per bucket) for the table gradient.  Built once on the host; the device copies are made
+    once per device and stay put (graph capture replays them).  ValueError, with the library's message, for an entry outside
+    [-1, n_buckets), a row that hides every key, N outside 1 .. 1024 or n_buckets outside 1 .. 4096."""
+
+    def __init__(self, index, n_buckets):
+        if not isinstance(index, torch.Tensor) or index.is_cuda or index.dtype != torch.int32 or index.dim() != 2 \
+                or index.shape[0] != index.shape[1]:
+            raise ValueError("AttentionBiasIndex: a CPU int32 [N, N] tensor is expected (sfcvit.relpos builds them)")
+        self.index = index.contiguous()
+        self.n_tokens = N = int(index.shape[0])
+        self.n_buckets = T = int(n_buckets)
+        nb = (max(N, 1) + 63) // 64
+        self.block_map = torch.zeros((nb, nb), dtype=torch.uint8)
+        self.offsets = torch.zeros(max(T, 0) + 1, dtype=torch.int32)
+        positions = torch.zeros(max(N * N, 1), dtype=torch.int32)
+        rc = lib.sfcvit_attention_bias_blocks(ctypes.c_void_p(self.index.data_ptr()), N, T, ctypes.c_void_p(self.block_map.data_ptr()),
+                                              ctypes.c_void_p(self.offsets.data_ptr()), ctypes.c_void_p(positions.data_ptr()))
+        if rc != 0:
+            raise ValueError(lib.sfcvit_last_error().decode(errors="replace"))
+        self.positions = positions[:int(self.offsets[-1])].clone()
+        self.total_blocks = nb * nb
+        self.visited_blocks = int((self.block_map != 0).sum())
+        self._dev = {}
+
+    def on(self, device):
+        """(index, block map, offsets, positions) on `device`, uploaded at the first request."""
+        key = torch.device(device)
+        if key.type == "cuda" and key.index is None:
+            key = torch.device("cuda", torch.cuda.current_device())
+        if key not in self._dev:
+            self._dev[key] = tuple(t.to(key) for t in (self.index, self.block_map, self.offsets, self.positions))
+        return self._dev[key]
+
+    def __repr__(self):
+        return (f"AttentionBiasIndex(N={self.n_tokens}, buckets={self.n_buckets}, "
+                f"blocks {self.visited_blocks}/{self.total_blocks})")
+
+
+def _bias_args(qkv, n_heads, table, bias_index, dropout_p, dropout_seed, scale, what):
+    _need(qkv, _BF16, f"{what} qkv", 3)
+    if not isinstance(bias_index, AttentionBiasIndex):
+        raise ValueError(f"{what}: bias_index must be an ops.AttentionBiasIndex")
+    B, N, D3 = qkv.shape
+    if D3 % 3 or (D3 // 3) % n_heads:
+        raise ValueError(f"{what}: packed width {D3} is not 3 * n_heads * head_dim for n_heads = {n_heads}")
+    hd = D3 // 3 // n_heads
+    if bias_index.n_tokens != N:
+        raise ValueError(f"{what}: bias index for {bias_index.n_tokens} tokens on a sequence of {N}")
+    if tuple(_need(table, torch.float32, f"{what} table", 2).shape) != (n_heads, bias_index.n_buckets):
+        raise ValueError(f"{what}: table must be [H, T] = {(n_heads, bias_index.n_buckets)}, got {tuple(table.shape)}")
+    index, block_map, offsets, positions = bias_index.on(qkv.device)
+    a = _lib.AttnBiasArgs()
+    a.qkv, a.index, a.table, a.block_map = qkv.data_ptr(), index.data_ptr(), table.data_ptr(), block_map.data_ptr()
+    a.offsets, a.positions = offsets.data_ptr(), positions.data_ptr()
+    a.T, a.visited_blocks = bias_index.n_buckets, bias_index.visited_blocks
+    a.B, a.N, a.H, a.hd, a.scale = B, N, n_heads, hd, (1.0 / math.sqrt(hd) if scale is None else float(scale))
+    a.dropout_p, a.dropout_seed = dropout_p, dropout_seed
+    if dropout_p > 0.0 and STEP_STATE is not None:
+        a.seed_off = STEP_STATE.data_ptr()
+    return a, B, N, D3 // 3, hd
+
+
+def attention_bias_fwd(qkv, n_heads, table, bias_index, dropout_p=0.0, dropout_seed=0, scale=None):
+    """attention_fwd with a relative position bias per head: scores scale * q k^T + table[h, index[i, j]], hidden where the
+    index is -1.  table: fp32 [H, T] on the device; bias_index: an AttentionBiasIndex for N tokens and T buckets.  Head dim
+    64 only, 1 <= N <= 1024, T <= 4096.  -> out [B, N, D] bf16, lse [B, H, N] fp32 (the lse includes the bias)."""
+    a, B, N, D, hd = _bias_args(qkv, n_heads, table, bias_index, dropout_p, dropout_seed, scale, "attention_bias_fwd")
+    out = torch.empty((B, N, D), device=qkv.device, dtype=_BF16)
+    lse = torch.empty((B, n_heads, N), device=qkv.device, dtype=torch.float32)
+    a.out, a.lse = out.data_ptr(), lse.data_ptr()
+    check(_launch("attn_bias_fwd", 4.0 * B * n_heads * N * N * hd,
+                  lambda: lib.sfcvit_attention_bias_fwd(ctypes.byref(a), _stream())), "sfcvit_attention_bias_fwd")
+    return out, lse
+
+
+def attention_bias_bwd(qkv, out, lse, dout, n_heads, table, bias_index, dropout_p=0.0, dropout_seed=0, colsum=None, scale=None,
+                       table_grad=True):
+    """-> dqkv, dtable [H, T] fp32 [, column sums of dqkv as in attention_bwd].  table_grad=False (a frozen table): the
+    table-gradient kernels are not launched and dtable is None."""
+    a, B, N, D, hd = _bias_args(qkv, n_heads, table, bias_index, dropout_p, dropout_seed, scale, "attention_bias_bwd")
+    _need(dout, _BF16, "attention_bias_bwd dout", 3)
+    _need(out, _BF16, "attention_bias_bwd out", 3)
+    _need(lse, torch.float32, "attention_bias_bwd lse", 3)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty((B, n_heads, N), device=qkv.device, dtype=torch.float32)
+    a.out, a.lse, a.dout, a.dqkv, a.delta = out.data_ptr(), lse.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), delta.data_ptr()
+    dtable = None
+    if table_grad:
+        dtable = torch.empty((n_heads, bias_index.n_buckets), device=qkv.device, dtype=torch.float32)
+        nws = lib.sfcvit_attention_bias_workspace(B, N, n_heads, bias_index.visited_blocks)
+        workspace = torch.empty(nws, device=qkv.device, dtype=torch.uint8)
+        a.dtable, a.workspace, a.workspace_bytes = dtable.data_ptr(), workspace.data_ptr(), nws
+    cs = None
+    if colsum is not None and colsum is not False:
+        cs = torch.empty(3 * D, device=qkv.device, dtype=torch.float32) if colsum is True else colsum
+        if cs.numel() != 3 * D or not cs.is_contiguous() or cs.dtype not in (torch.float32, _BF16):
+            raise ValueError("attention_bias_bwd colsum: contiguous fp32 or bf16 [3D] expected")
+        nbytes = lib.sfcvit_attention_colsum_workspace(B, N, n_heads, hd)
+        ws = torch.empty(nbytes, device=qkv.device, dtype=torch.uint8)
+        a.colsum_part, a.colsum_part_bytes = ws.data_ptr(), nbytes
+        a.colsum_out, a.colsum_bf16 = cs.data_ptr(), int(cs.dtype == _BF16)
+    with _Deferring([colsum] if cs is not None and colsum is not True else [], [ws] if cs is not None else []):
+        # S and dP of every visited block are recomputed for the table gradient: 4 of the backward's 10 N^2 hd flops again
+        check(_launch("attn_bias_bwd", (14.0 if table_grad else 10.0) * B * n_heads * N * N * hd,
+                      lambda: lib.sfcvit_attention_bias_bwd(ctypes.byref(a), _stream())), "sfcvit_attention_bias_bwd")
+    return (dqkv, dtable) if cs is None else (dqkv, dtable, cs)
+
+
 def _probe_args(qkv, lse, n_heads, scale, what):
     _need(qkv, _BF16, f"{what} qkv", 3)
     _need(lse, torch.float32, f"{what} lse", 3)
