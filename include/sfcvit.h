@@ -444,6 +444,31 @@ int sfcvit_layernorm_bwd_path(const void *dy, const void *x, const float *mean, 
                               const uint32_t *seed_off, void *dgamma, void *dbeta, void *dcol, int grads_bf16, int B,
                               int rows_per_image, int D, void *ws, float path_rate, uint32_t path_seed, void *stream);
 
+/* LayerScale residual site (CaiT / DeiT-III) of the pre-norm encoder layer, with or without stochastic depth: the site above
+ * with a per-channel scale lam (bf16 [D], like gamma) on the branch,
+ *   s = bf16(x + (c[b] * lam[d]) * branch),  y = LayerNorm(s),  c[b] = keep(b) / (1 - rate).
+ * rate = 0: no DropPath, c = 1, no flag is evaluated (seed is unused).  Everything else is sfcvit_add_layernorm_path_fwd's
+ * contract: a dropped image's rows of branch are not read and its rows of s are the bits of x; mean / rstd are those of the
+ * rounded s; D % 8 == 0, D <= 4096; no in-place form.  Notes its kernel as "add_ln_scale_kernel<2>". */
+int sfcvit_add_layernorm_scale_fwd(const void *branch, const void *x, const void *lam, const void *gamma, const void *beta, void *s,
+                                   void *y, float *mean, float *rstd, int B, int N, int D, float eps, float rate, uint32_t seed,
+                                   const uint32_t *seed_off, void *stream);
+/* sfcvit_layernorm_bwd_path plus the channel scale.  dx = dx_add + LayerNorm backward is the gradient of s (and of x);
+ *   dx_drop[m, d] = keep_path(m / rows_per_image) && keep(m, d) ? dx * lam[d] / ((1 - p) (1 - path_rate)) : 0   (always written)
+ *   dcol[d] = sum_m dx_drop as stored (rounded);   dlam[d] = sum_m dx[m, d] as stored (rounded) * c[b] * branch[m, d]
+ * branch (bf16 [M, D]) is the forward's branch; rows of dropped images are not read and add nothing to dlam.  dlam is required
+ * (fp32 or bf16 [D] like the others: it may be a row of a [2, D] parameter's gradient slot); dcol may be NULL.  dgamma, dbeta
+ * and dx are those of sfcvit_layernorm_bwd_drop on the same grid.  path_rate = 0: no flag is evaluated.  Four reductions are
+ * queued under sfcvit_reduce_defer.  Workspace: sfcvit_layernorm_bwd_scale_ws(M, D) bytes (four partial rows per workgroup,
+ * 4/3 of sfcvit_layernorm_bwd_ws).  D % 8 == 0, D <= 2048.  The kernel form is sfcvit_layernorm_bwd_drop's for the width:
+ * "ln_bwd_scale_kernel<2, true>" (vectors per lane, dx_add given), "ln_bwd_cols_scale_kernel<3, false>" at D = 768 / 1024. */
+int sfcvit_layernorm_bwd_scale(const void *dy, const void *x, const float *mean, const float *rstd, const void *gamma,
+                               const void *dx_add, const void *branch, const void *lam, void *dx, void *dx_drop, float p,
+                               uint32_t seed, const uint32_t *seed_off, void *dgamma, void *dbeta, void *dcol, void *dlam,
+                               int grads_bf16, int B, int rows_per_image, int D, void *ws, float path_rate, uint32_t path_seed,
+                               void *stream);
+int64_t sfcvit_layernorm_bwd_scale_ws(int M, int D);
+
 /* ------------------------------------------------------------------------
  * Multi-head self-attention core (no mask; the masked form is the next section) on the packed projection
  *   replaces F.scaled_dot_product_attention as reached from nn.MultiheadAttention

@@ -4,7 +4,7 @@
 //   host part), the error path of common.cpp, the mask validation and block map of attention_masked.cpp (check_mask_blocks),
 //   the index validation, inverted index, workspace and argument checks of attention_bias.cpp (check_attention_bias),
 //   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv),
-//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), tokenizer.cpp (check_tokenizer), drop_path.cpp (check_drop_path), model_ema.cpp (check_model_ema) and grad_accum.cpp (check_grad_accum), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
+//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), tokenizer.cpp (check_tokenizer), drop_path.cpp (check_drop_path), layer_scale.cpp (check_layer_scale), model_ema.cpp (check_model_ema) and grad_accum.cpp (check_grad_accum), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
 //   and post passes each GEMM / attention shape of the benchmarked models gets).
 // Every buffer is a heap block of EXACTLY the documented size, so that an off-by-one in a generator or in the descriptor
 // writer is a heap-buffer-overflow report instead of silent corruption.
@@ -23,6 +23,7 @@
 #include "../dispatch.h"
 #include "../drop_path.h"
 #include "../grad_accum.h"
+#include "../layer_scale.h"
 #include "../model_ema.h"
 #include "../pos_embed.h"
 #include "../rowwise.h"
@@ -967,6 +968,116 @@ static void check_drop_path() {
     }
 }
 
+// add_ln_scale_plan / ln_bwd_scale_plan (layer_scale.cpp): form and vectors per lane per width, the four-row workspace against the
+// three-row one of the same grid, and every refusal, with heap buffers of exactly B N D bf16 (branch, x, s, y and the gradients),
+// D bf16 (lam, gamma, beta) and B N fp32 (mean, rstd).  The plans read no byte of them.
+static void check_layer_scale() {
+    using namespace sfcvit;
+    const RowwiseKnobs k0;
+    const struct { int B, N, D, vpl; } ok[] = {{1, 1, 8, 1}, {2, 1, 8, 1}, {5, 3, 72, 1}, {2, 65, 200, 1}, {3, 7, 520, 2}, {2, 9, 1536, 4},
+                                               {2, 3, 2048, 4}, {22, 197, 768, 2}, {8, 577, 1024, 2}, {1, 2, 4096, 8},
+                                               {256, 196, 768, 2}, {64, 576, 1024, 2}};
+    for (const auto &q : ok) {
+        const size_t rows = size_t(q.B) * q.N, bytes = rows * q.D * 2;
+        std::unique_ptr<char[]> a(new char[bytes + 16]), x(new char[bytes + 16]), s(new char[bytes + 16]), y(new char[bytes + 16]);
+        std::unique_ptr<char[]> g(new char[q.D * 2 + 16]), b(new char[q.D * 2 + 16]), l(new char[q.D * 2 + 16]);
+        std::unique_ptr<float[]> mean(new float[rows]), rstd(new float[rows]);
+        auto al = [](char *p) { return reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(p) + 15) & ~uintptr_t(15)); };
+        void *ap = al(a.get()), *xp = al(x.get()), *sp = al(s.get()), *yp = al(y.get()), *gp = al(g.get()), *bp = al(b.get()), *lp = al(l.get());
+        float *mp = mean.get(), *rp = rstd.get();
+        const AddLnScalePlan p = add_ln_scale_plan(ap, xp, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f);
+        CHECK(p.err == SFCVIT_OK, "layer_scale fwd %d %d %d refused: %s", q.B, q.N, q.D, p.msg);
+        CHECK(p.M == int(rows) && p.vpl == q.vpl && p.vpl * 512 >= q.D, "layer_scale fwd %d %d %d: M %d vpl %d", q.B, q.N, q.D, p.M, p.vpl);
+        CHECK(int64_t(p.blocks) * ROW_WAVES >= p.M && int64_t(p.blocks - 1) * ROW_WAVES < p.M, "layer_scale fwd blocks %d for %d rows", p.blocks, p.M);
+        CHECK(add_ln_scale_plan(ap, xp, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.f).err == SFCVIT_OK, "layer_scale fwd: rate 0 refused");
+        auto fwd = [&](const void *a_, const void *x_, const void *l_, const void *g_, const void *b_, const void *s_, const void *y_,
+                       const float *m_, const float *r_, int B, int N, int D, float rate, const char *frag, const char *what) {
+            const AddLnScalePlan r = add_ln_scale_plan(a_, x_, l_, g_, b_, s_, y_, m_, r_, B, N, D, rate);
+            CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag), "layer_scale fwd %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
+        };
+        fwd(nullptr, xp, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null branch");
+        fwd(ap, nullptr, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null x");
+        fwd(ap, xp, nullptr, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null lam");
+        fwd(ap, xp, lp, nullptr, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null gamma");
+        fwd(ap, xp, lp, gp, nullptr, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null beta");
+        fwd(ap, xp, lp, gp, bp, nullptr, yp, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null s");
+        fwd(ap, xp, lp, gp, bp, sp, nullptr, mp, rp, q.B, q.N, q.D, 0.1f, "null", "null y");
+        fwd(ap, xp, lp, gp, bp, sp, yp, nullptr, rp, q.B, q.N, q.D, 0.1f, "null", "null mean");
+        fwd(ap, xp, lp, gp, bp, sp, yp, mp, nullptr, q.B, q.N, q.D, 0.1f, "null", "null rstd");
+        fwd(ap, xp, lp, gp, bp, sp, yp, mp, rp, 0, q.N, q.D, 0.1f, "B=0", "B = 0");
+        fwd(ap, xp, lp, gp, bp, sp, yp, mp, rp, q.B, -1, q.D, 0.1f, "N=-1", "N = -1");
+        fwd(ap, xp, lp, gp, bp, sp, yp, mp, rp, 65536, 32768, q.D, 0.1f, "leave int", "B * N = 2^31");
+        fwd(ap, xp, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, 0, 0.1f, "D=0", "D = 0");
+        fwd(ap, xp, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, 12, 0.1f, "D=12", "D = 12");
+        fwd(ap, xp, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, 4104, 0.1f, "D=4104", "D = 4104");
+        fwd(static_cast<char *>(ap) + 2, xp, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "aligned", "misaligned branch");
+        fwd(ap, xp, static_cast<char *>(lp) + 8, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "aligned", "misaligned lam");
+        fwd(ap, xp, lp, gp, bp, static_cast<char *>(sp) + 8, yp, mp, rp, q.B, q.N, q.D, 0.1f, "aligned", "misaligned s");
+        fwd(ap, xp, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, 1.f, "rate=1", "rate 1");
+        fwd(ap, xp, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, -0.25f, "rate=-0.25", "rate < 0");
+        fwd(ap, xp, lp, gp, bp, sp, yp, mp, rp, q.B, q.N, q.D, std::numeric_limits<float>::quiet_NaN(), "rate=", "rate NaN");
+        fwd(ap, xp, lp, gp, bp, xp, yp, mp, rp, q.B, q.N, q.D, 0.1f, "overlaps", "s = x");
+        fwd(ap, xp, lp, gp, bp, sp, ap, mp, rp, q.B, q.N, q.D, 0.1f, "overlaps", "y = branch");
+        fwd(ap, xp, lp, gp, bp, sp, sp, mp, rp, q.B, q.N, q.D, 0.1f, "overlaps", "y = s");
+
+        if (q.D > LN_BWD_MAX_D) continue;
+        std::unique_ptr<float[]> ws(new float[4 * q.D]);
+        const void *w = ws.get();
+        const LnBwdScalePlan pb = ln_bwd_scale_plan(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, k0);
+        const LnBwdPlan three = ln_bwd_geometry(int(rows), q.D, false, k0);
+        const bool cols = q.D == 768 || q.D == 1024;
+        CHECK(pb.err == SFCVIT_OK && pb.M == int(rows) && pb.cols == cols && !pb.add, "layer_scale bwd %d %d %d refused: %s", q.B, q.N, q.D, pb.msg);
+        CHECK(pb.inst == (cols ? q.D / 256 : q.D <= 512 ? 1 : q.D <= 1024 ? 2 : 4), "layer_scale bwd D %d: form %d inst %d", q.D, int(pb.cols), pb.inst);
+        RowwiseKnobs kv;
+        kv.ln_cols = 0;                                       // SFCVIT_LN_COLS=0: the 16-byte-vector form at every width
+        const LnBwdScalePlan pv = ln_bwd_scale_geometry(int(rows), q.D, false, kv);
+        CHECK(!pv.cols && pv.inst == (q.D <= 512 ? 1 : q.D <= 1024 ? 2 : 4) && pv.ws_bytes == int64_t(pv.blocks) * 4 * q.D * 4, "layer_scale bwd D %d without cols: inst %d", q.D, pv.inst);
+        CHECK(pb.blocks == three.blocks && pb.lds == three.lds, "layer_scale bwd %d %d: grid %d / lds %zu are not ln_bwd_geometry's", int(rows), q.D, pb.blocks, pb.lds);
+        CHECK(pb.ws_bytes * 3 == three.ws_bytes * 4 && pb.ws_bytes == int64_t(pb.blocks) * 4 * q.D * 4, "layer_scale bwd: workspace %lld", (long long)pb.ws_bytes);
+        CHECK(ln_bwd_scale_geometry(int(rows), q.D, false, k0).ws_bytes == pb.ws_bytes, "layer_scale bwd: the workspace query disagrees");
+        char name[96], want[96];
+        scale_kernel_name(pb, name, sizeof(name));
+        std::snprintf(want, sizeof(want), "ln_bwd%s_scale_kernel<%d, false>", cols ? "_cols" : "", pb.inst);
+        CHECK(!std::strcmp(name, want), "layer_scale bwd name '%s'", name);
+        const LnBwdScalePlan pa = ln_bwd_scale_plan(ap, xp, mp, rp, gp, ap, ap, lp, sp, yp, 0.f, mp, rp, mp, q.B, q.N, q.D, w, 0.f, k0);
+        scale_kernel_name(pa, name, sizeof(name));
+        std::snprintf(want, sizeof(want), "ln_bwd%s_scale_kernel<%d, true>", cols ? "_cols" : "", pa.inst);
+        CHECK(pa.err == SFCVIT_OK && pa.add && !std::strcmp(name, want), "layer_scale bwd: dx_add, p = 0, rate = 0: '%s' %s", name, pa.msg);
+        auto bwd = [&](const void *dy_, const void *x_, const float *m_, const float *r_, const void *g_, const void *add_, const void *br_,
+                       const void *l_, const void *dx_, const void *dd_, float dp, const void *dg_, const void *db_, const void *dl_, int B,
+                       int N, int D, const void *ws_, float rate, const char *frag, const char *what) {
+            const LnBwdScalePlan r = ln_bwd_scale_plan(dy_, x_, m_, r_, g_, add_, br_, l_, dx_, dd_, dp, dg_, db_, dl_, B, N, D, ws_, rate, k0);
+            CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag), "layer_scale bwd %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
+        };
+        bwd(nullptr, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "null", "null dy");
+        bwd(ap, nullptr, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "null", "null x");
+        bwd(ap, xp, nullptr, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "null", "null mean");
+        bwd(ap, xp, mp, nullptr, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "null", "null rstd");
+        bwd(ap, xp, mp, rp, nullptr, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "null", "null gamma");
+        bwd(ap, xp, mp, rp, gp, nullptr, nullptr, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "null", "null branch");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, nullptr, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "null", "null lam");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, nullptr, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "null", "null dx");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, nullptr, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "dx_drop", "missing dx_drop");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, nullptr, rp, mp, q.B, q.N, q.D, w, 0.5f, "null", "null dgamma");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, nullptr, mp, q.B, q.N, q.D, w, 0.5f, "null", "null dbeta");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, nullptr, q.B, q.N, q.D, w, 0.5f, "null", "null dlam");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, nullptr, 0.5f, "null", "null workspace");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, 0, q.N, q.D, w, 0.5f, "B=0", "B = 0");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, 0, q.D, w, 0.5f, "N=0", "rows_per_image = 0");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, 46341, 46341, q.D, w, 0.5f, "leave int", "B * N > int");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, 2056, w, 0.5f, "D=2056", "D = 2056");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, 4, w, 0.5f, "D=4", "D = 4");
+        bwd(ap, xp, mp, rp, gp, static_cast<char *>(ap) + 8, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "aligned", "misaligned dx_add");
+        bwd(ap, xp, mp, rp, gp, nullptr, static_cast<char *>(ap) + 4, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "aligned", "misaligned branch");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, static_cast<char *>(lp) + 2, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "aligned", "misaligned lam");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, static_cast<char *>(yp) + 2, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "aligned", "misaligned dx_drop");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 1.f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "dropout p=1", "dropout p = 1");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, -0.5f, mp, rp, mp, q.B, q.N, q.D, w, 0.5f, "dropout p=-0.5", "dropout p < 0");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, 1.f, "rate=1", "rate 1");
+        bwd(ap, xp, mp, rp, gp, nullptr, ap, lp, sp, yp, 0.1f, mp, rp, mp, q.B, q.N, q.D, w, -1.f, "rate=-1", "rate < 0");
+    }
+}
+
 // adamw_ema_plan (model_ema.cpp): the grid at the sizes of the tests and the workloads, and every refusal, with heap buffers of
 // exactly n bf16 (param, grad) and n fp32 (master, m, v, ema).  The plan reads the two structs and no byte of the buffers.
 static void check_model_ema() {
@@ -1776,6 +1887,7 @@ int main() {
     check_rowwise();
     check_tokenizer();
     check_drop_path();
+    check_layer_scale();
     check_model_ema();
     check_grad_accum();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }

@@ -131,6 +131,17 @@ def build_parser():
                     help="stochastic depth (DropPath, the DeiT recipe's drop_path_rate): in training every encoder layer drops "
                          "each of its two residual branches per image, with a probability that grows linearly with depth from 0 "
                          "to R, and scales the kept ones up; 0 <= R < 1, default 0 (off).  Works with --graph; no checkpoint key")
+    ap.add_argument("--pre-norm", action="store_true",
+                    help="pre-norm encoder layers, x + f(LN(x)), with a final LayerNorm after the last one (torch's "
+                         "norm_first=True under nn.TransformerEncoder(norm=): the DeiT / timm block); checkpoints then carry "
+                         "encoder.transformer.norm.*.  Works with --graph, --accum-steps, --model-ema, --drop-path, --device-mix, "
+                         "--device-augment and the model options")
+    ap.add_argument("--activation", choices=["relu", "gelu"], default="relu",
+                    help="the encoder MLP's activation; gelu (erf) needs --pre-norm")
+    ap.add_argument("--layer-scale", type=float, nargs="?", const=1e-4, default=None, metavar="INIT",
+                    help="LayerScale (CaiT / DeiT-III): a learned per-channel scale on each residual branch of every encoder "
+                         "layer, initialised to INIT (1e-4 when the value is omitted); needs --pre-norm; checkpoints then carry "
+                         "encoder.layer_scale.<l> [2, embed dim]")
     ap.add_argument("--model-ema", type=float, nargs="?", const=0.9999, default=None, metavar="DECAY",
                     help="keep an exponential moving average of the weights (timm's --model-ema; DECAY defaults to 0.9999): "
                          "averaged in fp32 inside the AdamW kernel, evaluated after every epoch next to the raw weights (one "
@@ -182,6 +193,8 @@ def build_model(a, patch_embed, attn_mask=None):
     rel = {}
     if getattr(a, "rel_pos_bias", None) is not None:      # else: the call as it is without the option
         rel = dict(rel_pos_bias=a.rel_pos_bias, rel_pos_window=rel_pos_window(a), rel_pos_init_std=a.rel_pos_init_std)
+    if getattr(a, "pre_norm", False) or getattr(a, "activation", "relu") != "relu" or getattr(a, "layer_scale", None) is not None:
+        rel.update(norm_first=a.pre_norm, activation=a.activation, layer_scale=a.layer_scale)
     return VisionTransformer1D(patch_embed=patch_embed, depth=a.depth, n_heads=a.heads, mlp_dim=a.mlp_dim,
                                num_classes=a.classes,
                                token_aggregator=a.token_aggregator or False, token_mix=a.token_mix,
@@ -195,6 +208,10 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.accum_steps < 1:
         ap.error(f"--accum-steps {a.accum_steps}: a positive number of batches per optimizer step expected")
+    if a.activation != "relu" and not a.pre_norm:
+        ap.error(f"--activation {a.activation} needs --pre-norm: the post-norm layer has the ReLU MLP only")
+    if a.layer_scale is not None and not a.pre_norm:
+        ap.error("--layer-scale needs --pre-norm: the post-norm layer has no LayerScale")
     if a.graph and a.accum_steps > 1:
         ap.error("--graph cannot be combined with --accum-steps > 1: a captured step does not accumulate (graphs serve "
                  "launch-bound small models, accumulation serves models too large for the batch)")

@@ -151,6 +151,12 @@ SIGNATURES = {
     "sfcvit_layernorm_bwd_path": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_float, ctypes.c_uint32, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, ctypes.c_uint32, c_void_p]),
+    "sfcvit_add_layernorm_scale_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_int, c_int, c_int, c_float, c_float, ctypes.c_uint32, c_void_p, c_void_p]),
+    "sfcvit_layernorm_bwd_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_float, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, ctypes.c_uint32, c_void_p]),
+    "sfcvit_layernorm_bwd_scale_ws": (c_int64, [c_int, c_int]),
     "sfcvit_gelu_drop_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, ctypes.c_uint32, c_void_p, c_void_p]),
     "sfcvit_gelu_drop_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, ctypes.c_uint32, c_void_p, c_void_p]),
     "sfcvit_step_advance": (c_int, [c_void_p, c_float, c_float, ctypes.c_uint32, c_void_p]),

@@ -89,6 +89,11 @@ def _vit_layers(model, images):
     if isinstance(model, VisionTransformer1D):
         x = model.mlp_mixer(x)
     enc = model.encoder
+    if getattr(enc, "norm_first", False):    # pre-norm layers: the encoder's own stack on the probe launches, the final norm last
+        for _, x, qkv, lse, scale in enc.pre_norm_layers(x, probe=True):
+            yield qkv, lse, enc.n_head, scale
+        yield _head_eval(model.mlp_head, x)
+        return
     for layer in enc.transformer.layers:
         a = layer.self_attn
         x, qkv, lse, scale = F.encoder_layer_probe(x, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,

@@ -11,6 +11,7 @@ needs is local to one function:
   token_pool     x[:, 0] / x[:, a:b].mean(dim=1)        (the read-out of a pooled classifier head)
   pooled_head    LayerNorm + Linear on the pooled token
   encoder_layer  nn.TransformerEncoderLayer, post-norm  (torch:nn/modules/transformer.py:951-982)
+  pre_norm_layer nn.TransformerEncoderLayer(norm_first=True) + the following norm, GELU, LayerScale (same file, the norm_first branch)
   predictor_head MultiLayerPredictor(n_layers=2)        (src/models/vit.py:295-319)
   linear, layer_norm, gelu                              generic pieces
   soft_target_cross_entropy                             main.py:45-51
@@ -1048,6 +1049,255 @@ def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w,
     if attn_mask is not None:
         return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale, attn_mask)
     return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale)
+
+
+# ----------------------------------------------------------------------------
+class _PreNormCfg:
+    """The non-tensor arguments of _PreNormLayer, one object so that apply() has a fixed argument list."""
+
+    def __init__(self, n_heads, eps, p, seeds, scale, act, attn_mask=None, drop_path=None, rel_index=None):
+        self.n_heads, self.eps, self.p, self.seeds, self.scale, self.act = n_heads, eps, p, seeds, scale, act
+        self.attn_mask, self.drop_path, self.rel_index = attn_mask, drop_path, rel_index
+
+
+class _PreNormLayer(Function):
+    """Pre-norm transformer encoder layer (torch:nn/modules/transformer.py, norm_first=True) as "residual site + the LayerNorm
+    after it", twice.  In: the residual stream s and n = LN1(s).  Out: s' and n' = LN_next(s'), LN_next being the next layer's
+    norm1 or the encoder's final norm:
+         a  = drop1(out_proj(attention(in_proj(n))));    s1 = s  + c1[b] lam1 * a;   n1 = LN2(s1)
+         f  = drop2(W2 drop(act(W1 n1 + b1)) + b2);      s' = s1 + c2[b] lam2 * f;   n' = LN_next(s')
+    act is ReLU or erf-GELU; lam = None is no LayerScale, drop_path = None no stochastic depth.  Which kernels a site runs:
+      no lam, no drop_path   the branch GEMM's residual= epilogue + ops.layernorm_fwd;   ops.layernorm_bwd(dx_add=)
+      drop_path alone        ops.add_layernorm_path_fwd;                                 ops.layernorm_bwd_path(dx_add=)
+      lam                    ops.add_layernorm_scale_fwd;                                ops.layernorm_bwd_scale(dx_add=)
+    The LayerNorm backward after a site applies that site's dropout mask and DropPath flag to the gradient it hands the branch,
+    and adds the gradient of s arriving on the residual path (dx_add).  The ReLU MLP is _EncoderLayer's (bit matrix included);
+    the GELU MLP is _Mixer's recipe: pre-activation GEMM, one element-wise pass (with the dropout), b1's gradient a column sum."""
+
+    @staticmethod
+    def site(branch_in, w, b, res, lam_row, g_w, g_b, B, eps, p, seed, drop_path, site):
+        """One residual site + the LayerNorm after it -> (branch or None, s, n, mean, rstd)."""
+        if lam_row is None and drop_path is None:
+            s = ops.gemm(branch_in, w, bias=b, residual=res, dropout_p=p, dropout_seed=seed)
+            return (None, s) + tuple(ops.layernorm_fwd(s, g_w, g_b, eps))
+        a = ops.gemm(branch_in, w, bias=b, dropout_p=p, dropout_seed=seed)
+        rate, pseed = (drop_path[0], drop_path[1][site]) if drop_path is not None else (0.0, 0)
+        if lam_row is None:
+            return (None,) + tuple(ops.add_layernorm_path_fwd(a, res, g_w, g_b, B, rate, pseed, eps))
+        return (a,) + tuple(ops.add_layernorm_scale_fwd(a, res, lam_row, g_w, g_b, B, rate, pseed, eps))
+
+    @staticmethod
+    def launches(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_bias, cfg):
+        """The forward's kernel launches, every intermediate returned (forward saves them; pre_norm_layer_probe reads the attention
+        inputs out of the same sequence)."""
+        B, N, D = s.shape
+        Da = in_w.shape[0] // 3
+        p, H = cfg.p, cfg.n_heads
+        sa, s1_, sf, s2_ = cfg.seeds
+        s0, n0 = _c(s).view(B * N, D), _c(n).view(B * N, D)
+        qkv = ops.gemm(n0, in_w, bias=in_b)
+        if rel_bias is not None:
+            o, lse = ops.attention_bias_fwd(qkv.view(B, N, 3 * Da), H, *rel_bias, p, sa, scale=cfg.scale)
+        elif cfg.attn_mask is None:
+            o, lse = ops.attention_fwd(qkv.view(B, N, 3 * Da), H, p, sa, scale=cfg.scale, any_length=True)
+        else:
+            o, lse = ops.attention_masked_fwd(qkv.view(B, N, 3 * Da), H, *cfg.attn_mask.on(s.device), p, sa, scale=cfg.scale)
+        lam1, lam2 = (lam[0], lam[1]) if lam is not None else (None, None)
+        a, s1, n1, mean1, rstd1 = _PreNormLayer.site(o.view(B * N, Da), out_w, out_b, s0, lam1, n2_w, n2_b, B, cfg.eps, p, s1_,
+                                                     cfg.drop_path, 0)
+        hbits = u = None
+        if cfg.act == "relu":
+            hbits = (torch.empty((B * N, w1.shape[0] // 8), device=s.device, dtype=torch.uint8)
+                     if USE_ACTMASK and w1.shape[0] % 16 == 0 else None)
+            h = ops.gemm(n1, w1, bias=b1, act=ops.ACT_RELU, dropout_p=p, dropout_seed=sf, actmask=hbits)
+        else:
+            u = ops.gemm(n1, w1, bias=b1)
+            h = ops.gelu_drop_fwd(u, p, sf) if p > 0 else ops.gelu_fwd(u)
+        f, s2, n2, mean2, rstd2 = _PreNormLayer.site(h, w2, b2, s1, lam2, nf_w, nf_b, B, cfg.eps, p, s2_, cfg.drop_path, 1)
+        return dict(n0=n0, qkv=qkv, o=o, lse=lse, a=a, s1=s1, n1=n1, mean1=mean1, rstd1=rstd1, hbits=hbits, u=u, h=h, f=f, s2=s2,
+                    n2=n2, mean2=mean2, rstd2=rstd2)
+
+    @staticmethod
+    def forward(ctx, s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_table, cfg):
+        B, N, D = s.shape
+        rel_bias = None if cfg.rel_index is None else (_c(rel_table.detach().to(torch.float32)), cfg.rel_index)
+        t = _PreNormLayer.launches(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_bias, cfg)
+        ctx.cfg, ctx.shape, ctx.rel_bias, ctx.rel_table, ctx.hbits = cfg, (B, N, D), rel_bias, rel_table, t["hbits"]
+        ctx.lam_param = lam                                     # for its gradient slot: both rows are written in one backward
+        ctx.small = (in_b, out_b, n2_b, b1, b2, nf_b)          # parameters only needed for their gradient slots
+        ctx.has = tuple(t[k] is not None for k in ("a", "u", "f"))
+        opt = [t[k] for k in ("a", "u", "f") if t[k] is not None] + ([lam] if lam is not None else [])
+        ctx.save_for_backward(t["n0"], t["qkv"], t["o"], t["lse"], t["s1"], t["n1"], t["mean1"], t["rstd1"], t["h"], t["s2"],
+                              t["mean2"], t["rstd2"], in_w, out_w, n2_w, w1, w2, nf_w, *opt)
+        ctx.set_materialize_grads(False)
+        return t["s2"].view(B, N, D), t["n2"].view(B, N, D)
+
+    @staticmethod
+    def backward(ctx, ds_out, dn_out):
+        (n0, qkv, o, lse, s1, n1, mean1, rstd1, h, s2, mean2, rstd2, in_w, out_w, n2_w, w1, w2, nf_w, *opt) = ctx.saved_tensors
+        opt = list(opt)
+        a, u, f = (opt.pop(0) if has else None for has in ctx.has)
+        lam = opt.pop(0) if opt else None
+        cfg = ctx.cfg
+        B, N, D = ctx.shape
+        p, drop_path = cfg.p, cfg.drop_path
+        sa, s1_, sf, s2_ = cfg.seeds
+        in_b, out_b, n2_b, b1, b2, nf_b = ctx.small
+        ds_out = None if ds_out is None else _c(ds_out).view(B * N, D)
+        dn_out = torch.zeros_like(s2) if dn_out is None else _c(dn_out).view(B * N, D)
+        ss = _SideStream(dn_out.device) if SIDE_STREAM_WGRAD else None
+        wg = (lambda a_, b_, w_: ss.run(lambda: _wgrad(a_, b_, w_), a_, b_)) if ss else _wgrad
+        lam_slot = _slot(ctx.lam_param) if lam is not None else None
+        dlam = [None, None]
+
+        def ln_bwd(dyv, sv, mean, rstd, g_w, g_b, prev_bias, seed, site, add, branch):
+            """The LayerNorm backward after a site -> (gradient of s, dgamma, dbeta, gradient entering the branch, column sums of
+            that = the bias gradient of linear2 / out_proj).  Gradients go straight into their slots when every parameter of
+            the call has one."""
+            slots = (_slot(g_w), _slot(g_b), _slot(prev_bias))
+            ok = all(t is not None for t in slots) and (lam is None or lam_slot is not None)
+            if lam is not None:
+                row = None
+                if ok:
+                    row = lam_slot[site]
+                    row._sfcvit_deferrable = True
+                rate, pseed = (drop_path[0], drop_path[1][site]) if drop_path is not None else (0.0, 0)
+                dsv, dg, dbt, dsub, dl, dcol = ops.layernorm_bwd_scale(dyv, sv, mean, rstd, g_w, branch, lam[site], N, rate, pseed, dx_add=add,
+                                                                       drop_p=p, drop_seed=seed, want_colsum=True,
+                                                                       grad_out=slots + (row,) if ok else None)
+                dlam[site] = dl
+            elif drop_path is not None:
+                dsv, dg, dbt, dsub, dcol = ops.layernorm_bwd_path(dyv, sv, mean, rstd, g_w, N, drop_path[0], drop_path[1][site], dx_add=add,
+                                                                  drop_p=p, drop_seed=seed, want_colsum=True, grad_out=slots if ok else None)
+            elif p > 0:
+                dsv, dg, dbt, dsub, dcol = ops.layernorm_bwd(dyv, sv, mean, rstd, g_w, dx_add=add, drop_p=p, drop_seed=seed,
+                                                             want_colsum=True, grad_out=slots if ok else None)
+            else:
+                dsv, dg, dbt, dcol = ops.layernorm_bwd(dyv, sv, mean, rstd, g_w, dx_add=add, want_colsum=True, grad_out=slots if ok else None)
+                dsub = dsv
+            if not ok:
+                dg, dbt, dcol = dg.to(_BF16), dbt.to(_BF16), dcol.to(_BF16)
+            return dsv, dg, dbt, dsub, dcol
+
+        ds2, dgf, dbtf, df, db2 = ln_bwd(dn_out, s2, mean2, rstd2, nf_w, nf_b, b2, s2_, 1, ds_out, f)
+        dw2 = wg(df, h, w2)
+        b1_slot = _slot(b1)
+        if cfg.act == "relu":
+            # h is stored after relu + dropout: (h > 0) is the joint mask, 1/(1-p) the dropout scale; b1's gradient is the column
+            # sum of dh, fused into that GEMM's epilogue
+            dh, db1 = ops.gemm_dx(df, w2, aux_in=h, dact=ops.ACT_RELU, dact_scale=1.0 / (1.0 - p),
+                                  colsum=b1_slot if b1_slot is not None else True, actmask=ctx.hbits)
+            if b1_slot is None:
+                db1 = db1.to(_BF16)
+        else:
+            dh = ops.gemm_dx(df, w2)
+            dh = ops.gelu_drop_bwd(dh, u, p, sf) if p > 0 else ops.gelu_bwd(dh, u)
+            db1 = ops.colsum(dh, out=b1_slot) if b1_slot is not None else ops.colsum(dh).to(_BF16)
+        dw1 = wg(dh, n1, w1)
+        dn1 = ops.gemm_dx(dh, w1)
+        ds1, dg2, dbt2, da, dbo = ln_bwd(dn1, s1, mean1, rstd1, n2_w, n2_b, out_b, s1_, 0, ds2, a)
+        Da = in_w.shape[0] // 3
+        dwo = wg(da, o.view(B * N, Da), out_w)
+        do = ops.gemm_dx(da, out_w)
+        bi_slot = _slot(in_b)
+        dtable = None
+        col = bi_slot if bi_slot is not None else True
+        if ctx.rel_bias is not None:
+            want = ctx.needs_input_grad[15]                     # a frozen table costs nothing
+            dqkv, dtable, dbi = ops.attention_bias_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, *ctx.rel_bias, p, sa,
+                                                       colsum=col, scale=cfg.scale, table_grad=want)
+            dtable = _table_grad(dtable, ctx.rel_table) if want else None
+        elif cfg.attn_mask is None:
+            dqkv, dbi = ops.attention_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, p, sa, colsum=col,
+                                          scale=cfg.scale, any_length=True)
+        else:
+            dqkv, dbi = ops.attention_masked_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads,
+                                                 *cfg.attn_mask.on(dn_out.device), p, sa, colsum=col, scale=cfg.scale)
+        dqkv = dqkv.view(B * N, 3 * Da)
+        if bi_slot is None:
+            dbi = dbi.to(_BF16)
+        dwi = wg(dqkv, n0, in_w)
+        dn_in = ops.gemm_dx(dqkv, in_w)
+        if ss:
+            ss.join(dw2, dw1, dwo, dwi)
+        if lam is None:
+            dl = None
+        elif lam_slot is not None and all(d.dtype == _BF16 and d.data_ptr() == lam_slot[i].data_ptr() for i, d in enumerate(dlam)):
+            dl = lam_slot                                       # both rows were written in place
+        else:
+            if lam_slot is not None:                            # one row sits in the slot, its reduction perhaps still queued
+                ops.flush_deferred(end=False)
+            dl = torch.stack([dlam[0].to(_BF16), dlam[1].to(_BF16)])
+        return (ds1.view(B, N, D), dn_in.view(B, N, D), dwi, dbi, dwo, dbo, dg2, dbt2, dw1, db1, dw2, db2, dgf, dbtf, dl, dtable, None)
+
+
+def _layer_scale_arg(layer_scale, D, what):
+    """layer_scale = None, (lam1, lam2) with [D] each, or one [2, D] tensor (row 0: the attention branch) -> bf16 [2, D] or None.
+    A [2, D] bf16 parameter passes as it is, so its gradient can be written into its slot."""
+    if layer_scale is None:
+        return None
+    if isinstance(layer_scale, (tuple, list)):
+        if len(layer_scale) != 2 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != (D,) for t in layer_scale):
+            raise ValueError(f"{what}: layer_scale must be (lam1, lam2) with [D] = [{D}] each, or one [2, D] tensor")
+        layer_scale = torch.stack([_bf(layer_scale[0]), _bf(layer_scale[1])])
+    if not isinstance(layer_scale, torch.Tensor) or tuple(layer_scale.shape) != (2, D):
+        raise ValueError(f"{what}: layer_scale must be (lam1, lam2) with [D] = [{D}] each, or one [2, D] tensor")
+    return _c(_bf(layer_scale))
+
+
+def _check_pre_norm_width(D, what="pre_norm_layer"):
+    if D % 8 or D > 2048:
+        raise ValueError(f"{what}: width {D} is not supported by the pre-norm kernels (a multiple of 8, at most 2048)")
+
+
+def _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads, activation, layer_scale, what):
+    if activation not in ("relu", "gelu"):
+        raise ValueError(f"{what}: activation={activation!r} (relu or gelu)")
+    if tuple(n.shape) != tuple(s.shape) or s.dim() != 3:
+        raise ValueError(f"{what}: s and n = LayerNorm(s) must be equal [B, N, D], got {tuple(s.shape)} and {tuple(n.shape)}")
+    _check_pre_norm_width(s.shape[-1], what)
+    args, scale = _encoder_layer_args(s, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads)
+    return args, scale, _bf(n), _layer_scale_arg(layer_scale, s.shape[-1], what)
+
+
+def pre_norm_layer(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads, eps=1e-5, dropout_p=0.0,
+                   attn_mask=None, drop_path=0.0, rel_bias=None, activation="relu", layer_scale=None):
+    """One pre-norm encoder layer (nn.TransformerEncoderLayer(norm_first=True)) on the HIP path, as "residual site + the
+    LayerNorm after it": takes the residual stream s [B, N, D] and n = norm1(s), returns (s', n') with n' = LayerNorm(s') by
+    the FOLLOWING norm (next_w, next_b): the next layer's norm1, or the encoder's final norm after the last layer.  The first
+    layer's n comes from layer_norm(s, norm1).  n2_w / n2_b are the layer's own norm2.
+    activation: "relu" or "gelu" (erf).  layer_scale: None, or (lam1, lam2) / a [2, D] tensor: the per-channel scales of the
+    attention and MLP branches (CaiT / DeiT-III), s1 = s + c1[b] lam1 * a.  dropout_p, attn_mask, drop_path, rel_bias and the
+    zero padding of head dims the kernels do not have: as in encoder_layer, with its masks, flags and seeds.  Not under tracing."""
+    what = "pre_norm_layer"
+    drop_path = float(drop_path)
+    if not 0.0 <= drop_path < 1.0:
+        raise ValueError(f"{what}: drop_path={drop_path} outside [0, 1)")
+    args, scale, n, lam = _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads,
+                                         activation, layer_scale, what)
+    rel_bias = _rel_bias(rel_bias, attn_mask, args[0].shape[1], n_heads, what)
+    if _traced():
+        raise NotImplementedError(f"{what}: the pre-norm layer has no traced form (torch.compile); run the model eagerly")
+    attn_mask = _attention_mask(attn_mask, args[0].shape[1], what)
+    seeds = tuple(ops.next_seed() for _ in range(4)) if dropout_p > 0 else (0, 0, 0, 0)
+    path = (drop_path, (ops.next_seed(), ops.next_seed())) if drop_path > 0 else None
+    table, index = rel_bias if rel_bias is not None else (None, None)
+    cfg = _PreNormCfg(n_heads, eps, float(dropout_p), seeds, scale, activation, attn_mask, path, index)
+    return _PreNormLayer.apply(args[0], n, *args[1:], lam, table, cfg)
+
+
+def pre_norm_layer_probe(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads, eps=1e-5,
+                         activation="relu", layer_scale=None):
+    """The eval-mode (dropout 0) pre-norm layer with its attention inputs exposed: (s', n', qkv [B, N, 3 * H * kernel head dim],
+    lse [B, H, N], softmax scale or None).  Same launches as pre_norm_layer(dropout_p=0): s' and n' have its bits.  For
+    sfcvit.analysis; no autograd graph is built."""
+    with torch.no_grad():
+        args, scale, n, lam = _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads,
+                                             activation, layer_scale, "pre_norm_layer_probe")
+        B, N, D = args[0].shape
+        cfg = _PreNormCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, activation)
+        t = _PreNormLayer.launches(args[0], n, *args[1:], lam, None, cfg)
+        return t["s2"].view(B, N, D), t["n2"].view(B, N, D), t["qkv"].view(B, N, -1), t["lse"], scale
 
 
 # ----------------------------------------------------------------------------

@@ -133,8 +133,15 @@ class TransformerSeqEncoder(nn.Module):
     vit.py:152-174).  A mask is not a parameter or a buffer: it never enters state_dict."""
 
     def __init__(self, input_dim, max_len, n_head, hidden_dim, method, dropout_p=0.1, n_layers=1, cls_token=False,
-                 drop_path_rate=0.0, rel_pos_bias=None):
-        """rel_pos_bias: None, or an ops.AttentionBiasIndex (or (index, init_std)): every layer adds a learned relative
+                 drop_path_rate=0.0, rel_pos_bias=None, norm_first=False, activation="relu", layer_scale=None):
+        """norm_first=True: pre-norm layers, x + f(LN(x)), and a final LayerNorm after the last one -- torch's
+        nn.TransformerEncoderLayer(norm_first=True, activation=...) under nn.TransformerEncoder(norm=nn.LayerNorm(D)), so the
+        state_dict keys are torch's own (`transformer.layers.<l>.*`, `transformer.norm.weight|bias`); F.pre_norm_layer runs them.
+        activation: "relu" or "gelu" (erf) in the MLP; "gelu" needs norm_first.  layer_scale: None, or the initial value
+        (e.g. 1e-4) of LayerScale (CaiT / DeiT-III): `layer_scale`, a ParameterList of one [2, input_dim] tensor per layer, row 0
+        scaling the attention branch and row 1 the MLP branch per channel; needs norm_first.  The final norm and LayerScale are
+        constructed last and draw no random number; with norm_first=False the encoder is what it is without the three keywords.
+        rel_pos_bias: None, or an ops.AttentionBiasIndex (or (index, init_std)): every layer adds a learned relative
         position bias per head to its attention scores, one table `rel_pos_bias.<l>` [n_head, T] per layer in a ParameterList
         (attach_rel_pos_bias; the models call it after everything else is constructed).
         drop_path_rate: stochastic depth (DropPath) in training mode.  Layer l of L drops each of its two residual branches
@@ -150,9 +157,21 @@ class TransformerSeqEncoder(nn.Module):
         self.n_head = n_head
         self.dropout_p = dropout_p
         self.drop_path_rates = drop_path_rates(drop_path_rate, n_layers)
+        self.norm_first, self.activation = bool(norm_first), activation
+        if activation not in ("relu", "gelu"):
+            raise ValueError(f"activation={activation!r} must be 'relu' or 'gelu'")
+        if not norm_first and activation != "relu":
+            raise ValueError(f"activation={activation!r} needs norm_first=True: the post-norm layer has the ReLU MLP only")
+        if not norm_first and layer_scale is not None:
+            raise ValueError("layer_scale needs norm_first=True: the post-norm layer has no LayerScale")
+        if norm_first:
+            F._check_pre_norm_width(input_dim, "norm_first=True")
+            if layer_scale is not None and not math.isfinite(float(layer_scale)):
+                raise ValueError(f"layer_scale={layer_scale} must be a finite initial value")
+        extra = dict(norm_first=True, activation=activation) if norm_first else {}      # else: the constructor call as it was
         encoder_layer = nn.TransformerEncoderLayer(d_model=input_dim, nhead=n_head,
                                                    dim_feedforward=hidden_dim, dropout=dropout_p,
-                                                   batch_first=True)
+                                                   batch_first=True, **extra)
         self.transformer = nn.TransformerEncoder(encoder_layer, num_layers=n_layers,
                                                  enable_nested_tensor=False)
         self.to_patch_embedding = method
@@ -164,6 +183,11 @@ class TransformerSeqEncoder(nn.Module):
         if rel_pos_bias is not None:
             index, std = rel_pos_bias if isinstance(rel_pos_bias, tuple) else (rel_pos_bias, 0.0)
             self.attach_rel_pos_bias(index, std)
+        if norm_first:
+            self.transformer.norm = nn.LayerNorm(input_dim)     # nn.TransformerEncoder(norm=): ones and zeros, no draw
+            if layer_scale is not None:
+                self.layer_scale = nn.ParameterList(nn.Parameter(torch.full((2, input_dim), float(layer_scale)))
+                                                    for _ in range(n_layers))
 
     def attach_rel_pos_bias(self, bias_index, init_std=0.0):
         """One table [n_head, T] per layer, zeros or randn * init_std (init_std = 0 draws nothing: the model then computes
@@ -197,6 +221,10 @@ class TransformerSeqEncoder(nn.Module):
                              "bias index (rel_pos_window)")
         if hasattr(self, "cls_token"):
             x = F.cls_prepend(x, self.cls_token)                # vit.py:237-238
+        if self.norm_first:
+            for out in self.pre_norm_layers(x, mask, p):
+                pass
+            return out[1]
         for l, (layer, rate) in enumerate(zip(self.transformer.layers, self.drop_path_rates)):
             a = layer.self_attn
             path = {"drop_path": rate} if self.training and rate > 0 else {}      # else: the call as it is without the feature
@@ -207,6 +235,34 @@ class TransformerSeqEncoder(nn.Module):
                                 layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias,
                                 self.n_head, layer.norm1.eps, dropout_p=p, attn_mask=mask, **path)
         return x
+
+    def pre_norm_layers(self, x, mask=None, p=0.0, probe=False):
+        """The pre-norm stack, one F.pre_norm_layer per layer: each takes the residual stream s and n = norm1(s) and returns s'
+        and the FOLLOWING norm of s' (the next layer's norm1, the final norm after the last layer).  Yields (s', n') per layer
+        -- the last n' is the encoder's output -- or, with probe=True (eval launches, no autograd), F.pre_norm_layer_probe's
+        (s', n', qkv, lse, scale)."""
+        if F._traced():                                         # before the first launch: layer 0's norm1 runs ahead of its layer
+            raise NotImplementedError("pre_norm_layer: the pre-norm layer has no traced form (torch.compile); run the model eagerly")
+        layers = list(self.transformer.layers)
+        follow =[l.norm1 for l in layers[1:]] + [self.transformer.norm]
+        tables, scales = getattr(self, "rel_pos_bias", None), getattr(self, "layer_scale", None)
+        s = x
+        n = F.layer_norm(s, layers[0].norm1.weight, layers[0].norm1.bias, layers[0].norm1.eps)
+        for l, (layer, nxt, rate) in enumerate(zip(layers, follow, self.drop_path_rates)):
+            a = layer.self_attn
+            w = (a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, layer.norm2.weight, layer.norm2.bias,
+                 layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, nxt.weight, nxt.bias)
+            kw = dict(activation=self.activation, layer_scale=scales[l] if scales is not None else None)
+            if probe:
+                out = F.pre_norm_layer_probe(s, n, *w, self.n_head, layer.norm2.eps, **kw)
+            else:
+                if self.training and rate > 0:
+                    kw["drop_path"] = rate
+                if tables is not None:
+                    kw["rel_bias"] = (tables[l], self.rel_pos_index)
+                out = F.pre_norm_layer(s, n, *w, self.n_head, layer.norm2.eps, dropout_p=p, attn_mask=mask, **kw)
+            s, n = out[0], out[1]
+            yield out
 
 
 class MixerBlock(nn.Module):
@@ -398,7 +454,7 @@ class VisionTransformer(nn.Module):
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, attn_mask=None,
                  pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0, rel_pos_bias=None, rel_pos_window=None,
-                 rel_pos_init_std=0.0):
+                 rel_pos_init_std=0.0, norm_first=False, activation="relu", layer_scale=None):
         """rel_pos_bias: None (the model as it is without the keyword), "curve" or "image": every encoder layer adds a learned
         relative position bias per head to its attention scores, softmax(q k^T / sqrt(hd) + b_h[offset(i, j)]), the offset taken
         along the token sequence (j - i) or in the image (the displacement of the token centres in cells of sqrt(pixels per
@@ -408,6 +464,8 @@ class VisionTransformer(nn.Module):
         it computes without the bias) or the std of a normal draw.  With pool="cls" the CLS token gets three buckets of its own
         (sfcvit.relpos.with_cls_token).
         drop_path_rate: stochastic depth over the encoder layers (TransformerSeqEncoder; `encoder.drop_path_rates`).
+        norm_first, activation, layer_scale: pre-norm encoder layers with a final norm, a GELU MLP and LayerScale
+        (TransformerSeqEncoder: the DeiT / timm block; `encoder.transformer.norm`, `encoder.layer_scale.<l>` [2, D]).
         attn_mask: None, or a mask for every encoder layer (ops.as_attention_mask's forms; sfcvit.masks builds windows).
         Held outside state_dict: checkpoint keys are the reference's with or without it.
         pos_embed: None / False (the reference as shipped), "learned" (vit.py:360-361: a Parameter [1, N, D] = randn *
@@ -427,7 +485,8 @@ class VisionTransformer(nn.Module):
         self.encoder = TransformerSeqEncoder(input_dim=embed_dim, max_len=self.patch_embed.n_patches,
                                              method=self.patch_embed, n_head=n_heads, hidden_dim=mlp_dim,
                                              n_layers=depth, dropout_p=dropout_p, cls_token=pool == "cls",
-                                             drop_path_rate=drop_path_rate)
+                                             drop_path_rate=drop_path_rate, norm_first=norm_first, activation=activation,
+                                             layer_scale=layer_scale)
         self.mlp_head = _make_head(pool, embed_dim, self.patch_embed.n_patches, num_classes, head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)
@@ -452,8 +511,8 @@ class VisionTransformer1D(nn.Module):
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False, attn_mask=None,
                  pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0, rel_pos_bias=None, rel_pos_window=None,
-                 rel_pos_init_std=0.0):
-        """attn_mask, pos_embed, pos_embed_std, pool, drop_path_rate, rel_pos_bias, rel_pos_window, rel_pos_init_std: as in VisionTransformer (the table is added directly after the tokenizer
+                 rel_pos_init_std=0.0, norm_first=False, activation="relu", layer_scale=None):
+        """attn_mask, pos_embed, pos_embed_std, pool, drop_path_rate, rel_pos_bias, rel_pos_window, rel_pos_init_std, norm_first, activation, layer_scale: as in VisionTransformer (the table is added directly after the tokenizer
         and, if present, `ta`: before `mlp_mixer`; with pool="cls" the token joins after `mlp_mixer`, whose weights stay sized
         for the N patch tokens)."""
         super().__init__()
@@ -466,7 +525,8 @@ class VisionTransformer1D(nn.Module):
         self.encoder = TransformerSeqEncoder(input_dim=embed_dim, max_len=self.patch_embed.n_patches,
                                              n_head=n_heads, hidden_dim=mlp_dim, n_layers=depth,
                                              method=self.patch_embed, dropout_p=dropout_p, cls_token=pool == "cls",
-                                             drop_path_rate=drop_path_rate)
+                                             drop_path_rate=drop_path_rate, norm_first=norm_first, activation=activation,
+                                             layer_scale=layer_scale)
         self.mlp_head = _make_head(pool, embed_dim, self.patch_embed.n_patches, num_classes, head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)

@@ -471,6 +471,68 @@ def layernorm_bwd_path(dy, x, mean, rstd, gamma, rows_per_image, path_rate, path
 
 
 # ----------------------------------------------------------------------------
+# LayerScale residual site (pre-norm layers): the site above with a per-channel scale on the branch
+# ----------------------------------------------------------------------------
+def add_layernorm_scale_fwd(branch, x, lam, gamma, beta, B, rate=0.0, seed=0, eps=1e-5):
+    """s = bf16(x + (c[b] * lam[d]) * branch), LayerNorm(s) -> (s, y, mean, rstd); lam bf16 [D]; c[b] = keep(b) / (1 - rate) per
+    image b = row // (M / B), 1 at rate = 0 (no flag is drawn).  branch, x: bf16 [M, D], M = B * tokens.  A dropped image's rows
+    of s are the bits of x."""
+    _need(branch, _BF16, "add_layernorm_scale branch", 2)
+    _need(x, _BF16, "add_layernorm_scale x", 2)
+    M, D = x.shape
+    if branch.shape != x.shape or B <= 0 or M % B:
+        raise ValueError(f"add_layernorm_scale: branch {tuple(branch.shape)} and x {tuple(x.shape)} must be equal [B * N, D] with B = {B}")
+    if _need(lam, _BF16, "lam", 1).numel() != D:
+        raise ValueError(f"add_layernorm_scale: lam must be [D] = [{D}], got {tuple(lam.shape)}")
+    s, y = torch.empty_like(x), torch.empty_like(x)
+    mean = torch.empty(M, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(M, device=x.device, dtype=torch.float32)
+    check(lib.sfcvit_add_layernorm_scale_fwd(_p(branch), _p(x), _p(lam), _p(_need(gamma, _BF16, "gamma", 1)),
+                                             _p(_need(beta, _BF16, "beta", 1)), _p(s), _p(y), _p(mean), _p(rstd), B, M // B, D, eps,
+                                             rate, seed, _seed_off() if rate > 0 else None, _stream()),
+          "sfcvit_add_layernorm_scale_fwd")
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append(last_rowwise_kernel())
+    return s, y, mean, rstd
+
+
+def layernorm_bwd_scale(dy, x, mean, rstd, gamma, branch, lam, rows_per_image, path_rate=0.0, path_seed=0, dx_add=None, drop_p=0.0,
+                        drop_seed=0, want_colsum=False, grad_out=None):
+    """layernorm_bwd_path with the channel scale of a LayerScale site -> dx, dgamma, dbeta, dx_drop, dlam [, colsum of dx_drop].
+    dx is the gradient of s (and of the residual input); dx_drop = dx * lam * dropout mask / ((1 - drop_p)(1 - path_rate)) for
+    kept images, zeros for dropped ones, is the gradient entering the sub-layer; dlam[d] = sum over rows of the stored dx * c[b]
+    * branch.  grad_out = (dgamma, dbeta, colsum-or-None, dlam) bf16 [D] tensors (None entries are allocated): written in place
+    as bf16, e.g. views of a flat gradient buffer -- dlam may be a row of a [2, D] parameter's slot."""
+    what = "layernorm_bwd_scale"
+    _need(dy, _BF16, "layernorm dy", 2)
+    _need(x, _BF16, "layernorm x", 2)
+    _need(branch, _BF16, "layernorm_bwd_scale branch", 2)
+    M, D = x.shape
+    if rows_per_image <= 0 or M % rows_per_image:
+        raise ValueError(f"{what}: {M} rows are not whole images of {rows_per_image}")
+    if branch.shape != x.shape or dy.shape != x.shape or _need(lam, _BF16, "lam", 1).numel() != D:
+        raise ValueError(f"{what}: dy, x and branch must be equal [M, D] and lam [D], got {tuple(dy.shape)} {tuple(x.shape)} "
+                         f"{tuple(branch.shape)} {tuple(lam.shape)}")
+    dx, dx_drop = torch.empty_like(x), torch.empty_like(x)
+    if grad_out is not None and len(grad_out) == 4:
+        grad_out = (grad_out[0], grad_out[1], grad_out[3], grad_out[2])      # the optional entry last, as _grad_outs' callers have it
+    (dg, db, dl, dcol), bf16 = _grad_outs(what, grad_out, ((D,), (D,), (D,), (D,)), (True, True, True, want_colsum), x.device,
+                                          "contiguous bf16 [D] tensors (dgamma, dbeta, colsum or None, dlam)")
+    ws = torch.empty(lib.sfcvit_layernorm_bwd_scale_ws(M, D), device=x.device, dtype=torch.uint8)
+    if dx_add is not None:
+        _need(dx_add, _BF16, "layernorm dx_add", 2)
+    seed_off = _seed_off() if path_rate > 0 or drop_p > 0 else None
+    with _Deferring([dg, db, dl] + ([dcol] if dcol is not None else []), [ws]):
+        check(lib.sfcvit_layernorm_bwd_scale(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_add), _p(branch), _p(lam), _p(dx),
+                                             _p(dx_drop), drop_p, drop_seed, seed_off, _p(dg), _p(db), _p(dcol), _p(dl), int(bf16),
+                                             M // rows_per_image, rows_per_image, D, _p(ws), path_rate, path_seed, _stream()),
+              "sfcvit_" + what)
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append(last_rowwise_kernel())
+    return (dx, dg, db, dx_drop, dl) + ((dcol,) if want_colsum else ())
+
+
+# ----------------------------------------------------------------------------
 # attention
 # ----------------------------------------------------------------------------
 SUPPORTED_HEAD_DIMS = (64, 128, 192, 256)
