@@ -392,24 +392,6 @@ def gelu_dropout(x, p):
     return _GeluDrop.apply(_bf(x), float(p), ops.next_seed())
 
 
-class _MaskedAttention(Function):
-    """_Attention with an additive mask (ops.AttentionMask): softmax(q k^T / sqrt(hd) + M) v on the masked kernels."""
-
-    @staticmethod
-    def forward(ctx, qkv, n_heads, scale, mask):
-        qkv = _c(qkv)
-        m, bm = mask.on(qkv.device)
-        out, lse = ops.attention_masked_fwd(qkv, n_heads, m, bm, scale=scale)
-        ctx.save_for_backward(qkv, out, lse, m, bm)
-        ctx.n_heads, ctx.scale = n_heads, scale
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, out, lse, m, bm = ctx.saved_tensors
-        return ops.attention_masked_bwd(qkv, out, lse, _c(dout), ctx.n_heads, m, bm, scale=ctx.scale), None, None, None
-
-
 def _attention_mask(mask, n_tokens, what):
     """ops.as_attention_mask for a layer call.  Under tracing a mask is refused: the torch.library ops have no masked form."""
     if mask is None:
@@ -429,25 +411,44 @@ def _table_grad(dtable, table):
     return slot
 
 
-class _BiasedAttention(Function):
-    """_Attention with a learned relative position bias per head: softmax(q k^T / sqrt(hd) + table[h, index]) v on the bias
-    kernels (ops.attention_bias_fwd / _bwd).  The table is cast to fp32 for the kernel per call."""
+def _fp32_bias(rel_table, rel_index):
+    """The attention core's third form as the kernels take it: (the table parameter cast to fp32, once per call; the index)."""
+    return None if rel_index is None else (_c(rel_table.detach().to(torch.float32)), rel_index)
 
-    @staticmethod
-    def forward(ctx, qkv, n_heads, scale, table, bias_index):
-        qkv = _c(qkv)
-        t32 = _c(table.detach().to(torch.float32))
-        out, lse = ops.attention_bias_fwd(qkv, n_heads, t32, bias_index, scale=scale)
-        ctx.save_for_backward(qkv, out, lse, t32)
-        ctx.n_heads, ctx.scale, ctx.bias_index, ctx.table = n_heads, scale, bias_index, table
-        return out
 
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, out, lse, t32 = ctx.saved_tensors
-        want = ctx.needs_input_grad[3]                          # a frozen table costs nothing
-        dqkv, dtable = ops.attention_bias_bwd(qkv, out, lse, _c(dout), ctx.n_heads, t32, ctx.bias_index, scale=ctx.scale, table_grad=want)
-        return dqkv, None, None, _table_grad(dtable, ctx.table) if want else None, None
+def _attn_fwd(qkv3, n_heads, p, seed, scale, attn_mask, rel_bias):
+    """The attention core of a layer and of `attention` on qkv3 [B, N, 3 * H * hd] -> (o, lse): the bias kernels with rel_bias =
+    (fp32 table [H, T], ops.AttentionBiasIndex), the masked kernels with an ops.AttentionMask, and only then; the plain ones
+    otherwise.  This and _attn_bwd are the only place that chooses."""
+    if rel_bias is not None:
+        return ops.attention_bias_fwd(qkv3, n_heads, *rel_bias, p, seed, scale=scale)
+    if attn_mask is not None:
+        return ops.attention_masked_fwd(qkv3, n_heads, *attn_mask.on(qkv3.device), p, seed, scale=scale)
+    return ops.attention_fwd(qkv3, n_heads, p, seed, scale=scale, any_length=True)
+
+
+def _attn_bwd(qkv3, o, lse, do3, n_heads, p, seed, scale, attn_mask, rel_bias, want_colsum, in_b, rel_table, want_table):
+    """-> (dqkv, dbi or None, dtable or None).  want_colsum: the in_proj bias gradient (column sums of dqkv) comes out of the
+    attention backward itself, into in_b's gradient slot when it has one.  want_table = False (a frozen table) costs nothing;
+    otherwise the table gradient comes back as _table_grad leaves it."""
+    col = None
+    if want_colsum:
+        bi_slot = _slot(in_b)
+        col = bi_slot if bi_slot is not None else True
+    dtable = None
+    if rel_bias is not None:
+        dqkv, dtable, *dbi = ops.attention_bias_bwd(qkv3, o, lse, do3, n_heads, *rel_bias, p, seed, colsum=col, scale=scale,
+                                                    table_grad=want_table)
+        dtable = _table_grad(dtable, rel_table) if want_table else None
+    else:
+        if attn_mask is not None:
+            got = ops.attention_masked_bwd(qkv3, o, lse, do3, n_heads, *attn_mask.on(qkv3.device), p, seed, colsum=col, scale=scale)
+        else:
+            got = ops.attention_bwd(qkv3, o, lse, do3, n_heads, p, seed, colsum=col, scale=scale, any_length=True)
+        dqkv, *dbi = got if want_colsum else (got,)
+    if not want_colsum:
+        return dqkv, None, dtable
+    return dqkv, (dbi[0].to(_BF16) if col is True else dbi[0]), dtable
 
 
 def _rel_bias(rel_bias, mask, n_tokens, n_heads, what):
@@ -476,20 +477,26 @@ def _rel_bias(rel_bias, mask, n_tokens, n_heads, what):
 
 class _Attention(Function):
     """softmax(q k^T / sqrt(hd)) v per head on a packed projection [B, N, 3 * H * hd] (q | k | v thirds, head h at
-    columns h*hd.. of each third): the core of nn.MultiheadAttention and of altvit.Attention (altvit.py:131-142)."""
+    columns h*hd.. of each third): the core of nn.MultiheadAttention and of altvit.Attention (altvit.py:131-142).  With an
+    additive mask (ops.AttentionMask) softmax(q k^T / sqrt(hd) + M) v on the masked kernels; with a learned relative position
+    bias per head (rel_table [H, T], rel_index) softmax(q k^T / sqrt(hd) + table[h, index]) v on the bias kernels."""
 
     @staticmethod
-    def forward(ctx, qkv, n_heads, scale):
+    def forward(ctx, qkv, n_heads, scale, mask, rel_table, rel_index):
         qkv = _c(qkv)
-        out, lse = ops.attention_fwd(qkv, n_heads, scale=scale, any_length=True)
+        rel_bias = _fp32_bias(rel_table, rel_index)
+        out, lse = _attn_fwd(qkv, n_heads, 0.0, 0, scale, mask, rel_bias)
         ctx.save_for_backward(qkv, out, lse)
-        ctx.n_heads, ctx.scale = n_heads, scale
+        ctx.n_heads, ctx.scale, ctx.mask, ctx.rel_bias, ctx.rel_table = n_heads, scale, mask, rel_bias, rel_table
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
-        return ops.attention_bwd(qkv, out, lse, _c(dout), ctx.n_heads, scale=ctx.scale, any_length=True), None, None
+        want = ctx.rel_bias is not None and ctx.needs_input_grad[4]          # a frozen table costs nothing
+        dqkv, _, dtable = _attn_bwd(qkv, out, lse, _c(dout), ctx.n_heads, 0.0, 0, ctx.scale, ctx.mask, ctx.rel_bias, False, None,
+                                    ctx.rel_table, want)
+        return dqkv, None, None, None, dtable, None
 
 
 def _head_padding(D, n_heads):
@@ -518,14 +525,12 @@ def attention(qkv, n_heads, mask=None, rel_bias=None):
     hd, hp = _head_padding(D, n_heads)
     rel_bias = _rel_bias(rel_bias, mask, qkv.shape[-2], n_heads, "attention")
     mask = _attention_mask(mask, qkv.shape[-2], "attention")
-    core = _Attention.apply if mask is None else (lambda t, H, sc: _MaskedAttention.apply(t, H, sc, mask))
-    if rel_bias is not None:
-        core = lambda t, H, sc: _BiasedAttention.apply(t, H, sc, *rel_bias)      # noqa: E731
+    table, index = rel_bias if rel_bias is not None else (None, None)
     if hp == hd:
-        return core(qkv, n_heads, None)
+        return _Attention.apply(qkv, n_heads, None, mask, table, index)
     lead = qkv.shape[:-1]
     padded = torch.nn.functional.pad(qkv.reshape(*lead, 3, n_heads, hd), (0, hp - hd)).reshape(*lead, 3 * n_heads * hp)
-    out = core(padded, n_heads, 1.0 / math.sqrt(hd))
+    out = _Attention.apply(padded, n_heads, 1.0 / math.sqrt(hd), mask, table, index)
     return out.reshape(*lead, n_heads, hp)[..., :hd].reshape(*lead, D)
 
 
@@ -839,147 +844,169 @@ def pooled_head(x, ln_w, ln_b, w, b, eps=1e-5):
 
 
 # ----------------------------------------------------------------------------
+# The two encoder layers (post-norm _EncoderLayer, pre-norm _PreNormLayer) are "residual site + the LayerNorm after it", twice,
+# around one attention core (_attn_fwd / _attn_bwd above) and one MLP: the pieces below, shared by both.
+# ----------------------------------------------------------------------------
+class _LayerCfg:
+    """The non-tensor arguments of _EncoderLayer and _PreNormLayer, one object so that apply() has a fixed argument list.
+    seeds: the four dropout seeds (attention, dropout1, the MLP's, dropout2); drop_path: None or (rate, (seed1, seed2))."""
+
+    def __init__(self, n_heads, eps, p, seeds, scale, act, attn_mask=None, drop_path=None, rel_index=None):
+        self.n_heads, self.eps, self.p, self.seeds, self.scale, self.act = n_heads, eps, p, seeds, scale, act
+        self.attn_mask, self.drop_path, self.rel_index = attn_mask, drop_path, rel_index
+
+
+_PreNormCfg = _LayerCfg     # the name callers that build a _PreNormLayer by hand knew it by: same constructor
+
+
+def _site_fwd(branch_in, w, b, res, lam_row, g_w, g_b, B, eps, p, seed, drop_path, site):
+    """One residual site + the LayerNorm after it -> (branch or None, s, n, mean, rstd).  Which kernels it runs:
+      no lam, no drop_path   the branch GEMM's residual= epilogue + ops.layernorm_fwd
+      drop_path alone        the branch GEMM stores drop(a) without the residual; ops.add_layernorm_path_fwd adds, rounds once, normalises
+      lam                    the same with ops.add_layernorm_scale_fwd; the branch is returned (the backward needs it for dlam)"""
+    if lam_row is None and drop_path is None:
+        s = ops.gemm(branch_in, w, bias=b, residual=res, dropout_p=p, dropout_seed=seed)
+        return (None, s) + tuple(ops.layernorm_fwd(s, g_w, g_b, eps))
+    a = ops.gemm(branch_in, w, bias=b, dropout_p=p, dropout_seed=seed)
+    rate, pseed = (drop_path[0], drop_path[1][site]) if drop_path is not None else (0.0, 0)
+    if lam_row is None:
+        return (None,) + tuple(ops.add_layernorm_path_fwd(a, res, g_w, g_b, B, rate, pseed, eps))
+    return (a,) + tuple(ops.add_layernorm_scale_fwd(a, res, lam_row, g_w, g_b, B, rate, pseed, eps))
+
+
+def _site_bwd(dyv, sv, mean, rstd, g_w, g_b, prev_bias, N, p, seed, drop_path, site, add=None, branch=None, lam_row=None, lam_out=None):
+    """The LayerNorm backward after a site -> (gradient of s, dgamma, dbeta, gradient entering the branch, column sums of that =
+    the bias gradient of linear2 / out_proj, for free in the same pass; dlam or None).  It applies the site's dropout mask and
+    DropPath flag (riding on the dropout multiplier) to the gradient it hands the branch and adds `add`, the gradient of s arriving
+    on the residual path:  ops.layernorm_bwd / ops.layernorm_bwd_path / with lam_row ops.layernorm_bwd_scale (branch: the site's
+    stored branch).  Gradients go straight into their slots when every parameter of the call has one (lam_out: the site's row of
+    the LayerScale parameter's slot, or None)."""
+    slots = (_slot(g_w), _slot(g_b), _slot(prev_bias))
+    ok = all(t is not None for t in slots) and (lam_row is None or lam_out is not None)
+    go = slots if ok else None
+    dl = None
+    if lam_row is not None:
+        if ok:
+            lam_out._sfcvit_deferrable = True
+            go = slots + (lam_out,)
+        rate, pseed = (drop_path[0], drop_path[1][site]) if drop_path is not None else (0.0, 0)
+        dsv, dg, dbt, dsub, dl, dcol = ops.layernorm_bwd_scale(dyv, sv, mean, rstd, g_w, branch, lam_row, N, rate, pseed, dx_add=add,
+                                                               drop_p=p, drop_seed=seed, want_colsum=True, grad_out=go)
+    elif drop_path is not None:
+        dsv, dg, dbt, dsub, dcol = ops.layernorm_bwd_path(dyv, sv, mean, rstd, g_w, N, drop_path[0], drop_path[1][site], dx_add=add,
+                                                          drop_p=p, drop_seed=seed, want_colsum=True, grad_out=go)
+    elif p > 0:
+        dsv, dg, dbt, dsub, dcol = ops.layernorm_bwd(dyv, sv, mean, rstd, g_w, dx_add=add, drop_p=p, drop_seed=seed, want_colsum=True,
+                                                     grad_out=go)
+    else:
+        dsv, dg, dbt, dcol = ops.layernorm_bwd(dyv, sv, mean, rstd, g_w, dx_add=add, want_colsum=True, grad_out=go)
+        dsub = dsv
+    if not ok:
+        dg, dbt, dcol = dg.to(_BF16), dbt.to(_BF16), dcol.to(_BF16)
+    return dsv, dg, dbt, dsub, dcol, dl
+
+
+def _mlp_fwd(n1, w1, b1, act, p, seed):
+    """h = drop(act(W1 n1 + b1)) -> (hbits, u, h).  relu: one GEMM; the dX GEMM through ReLU + dropout needs only the sign
+    pattern of h, a bit matrix hbits written by linear1's epilogue (19 MB instead of 308 MB per ViT-B layer read back in
+    backward; sfcvit_gemm_args.actmask).  gelu (erf): _Mixer's recipe, the pre-activation u from the GEMM and one element-wise
+    pass with the dropout."""
+    if act == "relu":
+        hbits = (torch.empty((n1.shape[0], w1.shape[0] // 8), device=n1.device, dtype=torch.uint8)
+                 if USE_ACTMASK and w1.shape[0] % 16 == 0 else None)
+        return hbits, None, ops.gemm(n1, w1, bias=b1, act=ops.ACT_RELU, dropout_p=p, dropout_seed=seed, actmask=hbits)
+    u = ops.gemm(n1, w1, bias=b1)
+    return None, u, (ops.gelu_drop_fwd(u, p, seed) if p > 0 else ops.gelu_fwd(u))
+
+
+def _mlp_bwd(df, h, u, hbits, w2, b1, act, p, seed):
+    """df = the gradient of linear2's output -> (dh, the gradient of linear1's output; db1, in b1's slot when it has one)."""
+    b1_slot = _slot(b1)
+    if act == "relu":
+        # h is stored after relu + dropout: (h > 0) is the joint mask, 1/(1-p) the dropout scale; b1's gradient is the column
+        # sum of dh, fused into that GEMM's epilogue
+        dh, db1 = ops.gemm_dx(df, w2, aux_in=h, dact=ops.ACT_RELU, dact_scale=1.0 / (1.0 - p),
+                              colsum=b1_slot if b1_slot is not None else True, actmask=hbits)
+        return dh, (db1 if b1_slot is not None else db1.to(_BF16))
+    dh = ops.gemm_dx(df, w2)
+    dh = ops.gelu_drop_bwd(dh, u, p, seed) if p > 0 else ops.gelu_bwd(dh, u)
+    return dh, (ops.colsum(dh, out=b1_slot) if b1_slot is not None else ops.colsum(dh).to(_BF16))
+
+
+def _wgrad_runner(device):
+    """(wg, join): wg(dy2, x2, w) = _wgrad, on the side stream with SFCVIT_SIDE_STREAM=1; join(*dws) before they are returned."""
+    if not SIDE_STREAM_WGRAD:
+        return _wgrad, lambda *dws: None
+    ss = _SideStream(device)
+    return (lambda a_, b_, w_: ss.run(lambda: _wgrad(a_, b_, w_), a_, b_)), ss.join
+
+
 class _EncoderLayer(Function):
     """Post-norm transformer encoder layer (torch:nn/modules/transformer.py:951-982):
          a  = out_proj(attention(in_proj(x)));  x1 = LN1(x + drop1(a))
          f  = W2 drop(relu(W1 x1 + b1)) + b2;   y  = LN2(x1 + drop2(f))
     with dropout p on the attention probabilities as well.  p = 0 (eval) makes every mask the
     identity.  Masks are functions of (seed, element index), regenerated in backward.
-    drop_path = (rate, (seed1, seed2)), rate > 0: stochastic depth on the two residual sites,
+    cfg.drop_path = (rate, (seed1, seed2)), rate > 0: stochastic depth on the two residual sites,
          x1 = LN1(x + c1[b] drop1(a));  y = LN2(x1 + c2[b] drop2(f)),  c[b] = keep[b] / (1 - rate), one flag per image and site
-    (functions of (seed, image index), regenerated in backward): the branch GEMMs store drop(a) / drop(f) without the residual and
-    ops.add_layernorm_path_fwd adds, rounds once to s1 / s2 and normalises."""
+    (functions of (seed, image index), regenerated in backward): _site_fwd's second form.  Arguments: the 13 tensors, the bias
+    table parameter (None without cfg.rel_index), a _LayerCfg (act "relu")."""
 
     @staticmethod
-    def launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale,
-                 attn_mask=None, drop_path=None, rel_bias=None):
+    def launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, rel_bias, cfg):
         """The forward's kernel launches, every intermediate returned (forward saves them; encoder_layer_probe reads the
         attention inputs out of the same sequence, so what it carries on is what forward computes)."""
         B, N, D = x.shape
         Da = in_w.shape[0] // 3                             # attention width: D, or n_heads * padded head dim (encoder_layer)
-        sa, s1_, sf, s2_ = seeds
+        p = cfg.p
+        sa, s1_, sf, s2_ = cfg.seeds
         x2 = _c(x).view(B * N, D)
         qkv = ops.gemm(x2, in_w, bias=in_b)
-        if rel_bias is not None:                            # (fp32 table [H, T], ops.AttentionBiasIndex): the bias kernels
-            o, lse = ops.attention_bias_fwd(qkv.view(B, N, 3 * Da), n_heads, *rel_bias, p, sa, scale=scale)
-        elif attn_mask is None:
-            o, lse = ops.attention_fwd(qkv.view(B, N, 3 * Da), n_heads, p, sa, scale=scale, any_length=True)
-        else:                                               # an ops.AttentionMask: the masked kernels, and only then
-            o, lse = ops.attention_masked_fwd(qkv.view(B, N, 3 * Da), n_heads, *attn_mask.on(x.device), p, sa, scale=scale)
-        if drop_path is None:
-            s1 = ops.gemm(o.view(B * N, Da), out_w, bias=out_b, residual=x2, dropout_p=p, dropout_seed=s1_)
-            x1, mean1, rstd1 = ops.layernorm_fwd(s1, n1_w, n1_b, eps)
-        else:
-            a = ops.gemm(o.view(B * N, Da), out_w, bias=out_b, dropout_p=p, dropout_seed=s1_)
-            s1, x1, mean1, rstd1 = ops.add_layernorm_path_fwd(a, x2, n1_w, n1_b, B, drop_path[0], drop_path[1][0], eps)
-        # The dX GEMM through ReLU + dropout needs only the sign pattern of h: a bit matrix written by linear1's epilogue
-        # (19 MB instead of 308 MB per ViT-B layer read back in backward; sfcvit_gemm_args.actmask)
-        hbits = (torch.empty((B * N, w1.shape[0] // 8), device=x.device, dtype=torch.uint8)
-                 if USE_ACTMASK and w1.shape[0] % 16 == 0 else None)
-        h = ops.gemm(x1, w1, bias=b1, act=ops.ACT_RELU, dropout_p=p, dropout_seed=sf, actmask=hbits)
-        if drop_path is None:
-            s2 = ops.gemm(h, w2, bias=b2, residual=x1, dropout_p=p, dropout_seed=s2_)
-            y, mean2, rstd2 = ops.layernorm_fwd(s2, n2_w, n2_b, eps)
-        else:
-            f = ops.gemm(h, w2, bias=b2, dropout_p=p, dropout_seed=s2_)
-            s2, y, mean2, rstd2 = ops.add_layernorm_path_fwd(f, x1, n2_w, n2_b, B, drop_path[0], drop_path[1][1], eps)
-        return x2, qkv, o, lse, s1, mean1, rstd1, x1, hbits, h, s2, y, mean2, rstd2
+        o, lse = _attn_fwd(qkv.view(B, N, 3 * Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask, rel_bias)
+        _, s1, x1, mean1, rstd1 = _site_fwd(o.view(B * N, Da), out_w, out_b, x2, None, n1_w, n1_b, B, cfg.eps, p, s1_, cfg.drop_path, 0)
+        hbits, _, h = _mlp_fwd(x1, w1, b1, cfg.act, p, sf)
+        _, s2, y, mean2, rstd2 = _site_fwd(h, w2, b2, x1, None, n2_w, n2_b, B, cfg.eps, p, s2_, cfg.drop_path, 1)
+        return dict(x2=x2, qkv=qkv, o=o, lse=lse, s1=s1, mean1=mean1, rstd1=rstd1, x1=x1, hbits=hbits, h=h, s2=s2, y=y, mean2=mean2,
+                    rstd2=rstd2)
 
     @staticmethod
-    def forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale,
-                attn_mask=None, drop_path=None, rel_table=None, rel_index=None):
-        B, N, D = x.shape
-        # the attention core's third form: the table parameter cast to fp32 for the kernels, once per call
-        rel_bias = None if rel_index is None else (_c(rel_table.detach().to(torch.float32)), rel_index)
-        x2, qkv, o, lse, s1, mean1, rstd1, x1, hbits, h, s2, y, mean2, rstd2 = _EncoderLayer.launches(
-            x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p, seeds, scale, attn_mask, drop_path,
-            rel_bias)
-        ctx.hbits, ctx.attn_mask, ctx.drop_path = hbits, attn_mask, drop_path
-        ctx.rel_bias, ctx.rel_table = rel_bias, rel_table
-        ctx.save_for_backward(x2, qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2,
-                              in_w, out_w, n1_w, w1, w2, n2_w)
-        ctx.n_heads, ctx.shape, ctx.p, ctx.seeds, ctx.scale = n_heads, (B, N, D), p, seeds, scale
+    def forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, rel_table, cfg):
+        rel_bias = _fp32_bias(rel_table, cfg.rel_index)
+        t = _EncoderLayer.launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, rel_bias, cfg)
+        ctx.cfg, ctx.shape, ctx.rel_bias, ctx.rel_table, ctx.hbits = cfg, tuple(x.shape), rel_bias, rel_table, t["hbits"]
         ctx.small = (in_b, out_b, n1_b, b1, b2, n2_b)      # parameters only needed for their gradient slots
-        return y.view(B, N, D)
+        ctx.save_for_backward(t["x2"], t["qkv"], t["o"], t["lse"], t["s1"], t["mean1"], t["rstd1"], t["x1"], t["h"], t["s2"],
+                              t["mean2"], t["rstd2"], in_w, out_w, n1_w, w1, w2, n2_w)
+        return t["y"].view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
         (x2, qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2,
          in_w, out_w, n1_w, w1, w2, n2_w) = ctx.saved_tensors
+        cfg = ctx.cfg
         B, N, D = ctx.shape
-        p = ctx.p
-        sa, s1_, sf, s2_ = ctx.seeds
+        p, drop_path = cfg.p, cfg.drop_path
+        sa, s1_, sf, s2_ = cfg.seeds
         dy2 = _c(dy).view(B * N, D)
         in_b, out_b, n1_b, b1, b2, n2_b = ctx.small
-        ss = _SideStream(dy2.device) if SIDE_STREAM_WGRAD else None
-        wg = (lambda a_, b_, w_: ss.run(lambda: _wgrad(a_, b_, w_), a_, b_)) if ss else _wgrad
-
-        drop_path = getattr(ctx, "drop_path", None)         # (library.py's traced backward builds its own ctx: never set)
-
-        def ln_bwd(dyv, s, mean, rstd, g_w, g_b, prev_bias, seed, site):
-            """LayerNorm backward; also returns the column sums of the gradient it hands to the sub-layer = the bias
-            gradient of linear2 / out_proj, for free in the same pass.  Gradients go straight into their slots when
-            all three parameters have one."""
-            slots = (_slot(g_w), _slot(g_b), _slot(prev_bias))
-            go = slots if all(t is not None for t in slots) else None
-            if drop_path is not None:                       # the per-image branch scale rides on the dropout multiplier
-                dsv, dg, dbt, dsub, dcol = ops.layernorm_bwd_path(dyv, s, mean, rstd, g_w, N, drop_path[0], drop_path[1][site],
-                                                                  drop_p=p, drop_seed=seed, want_colsum=True, grad_out=go)
-            elif p > 0:
-                dsv, dg, dbt, dsub, dcol = ops.layernorm_bwd(dyv, s, mean, rstd, g_w, drop_p=p, drop_seed=seed,
-                                                             want_colsum=True, grad_out=go)
-            else:
-                dsv, dg, dbt, dcol = ops.layernorm_bwd(dyv, s, mean, rstd, g_w, want_colsum=True, grad_out=go)
-                dsub = dsv
-            if go is None:
-                dg, dbt, dcol = dg.to(_BF16), dbt.to(_BF16), dcol.to(_BF16)
-            return dsv, dg, dbt, dsub, dcol
-
-        ds2, dg2, dbt2, df, db2 = ln_bwd(dy2, s2, mean2, rstd2, n2_w, n2_b, b2, s2_, 1)
+        wg, join = _wgrad_runner(dy2.device)
+        ds2, dg2, dbt2, df, db2, _ = _site_bwd(dy2, s2, mean2, rstd2, n2_w, n2_b, b2, N, p, s2_, drop_path, 1)
         dw2 = wg(df, h, w2)
-        # h is stored after relu + dropout: (h > 0) is the joint mask, 1/(1-p) the dropout scale
-        # ... and the bias gradient of linear1 is the column sum of dh: fused into that GEMM's epilogue
-        b1_slot = _slot(b1)
-        dh, db1 = ops.gemm_dx(df, w2, aux_in=h, dact=ops.ACT_RELU, dact_scale=1.0 / (1.0 - p),
-                              colsum=b1_slot if b1_slot is not None else True, actmask=ctx.hbits)
-        if b1_slot is None:
-            db1 = db1.to(_BF16)
+        dh, db1 = _mlp_bwd(df, h, None, ctx.hbits, w2, b1, cfg.act, p, sf)
         dw1 = wg(dh, x1, w1)
         dx1 = ops.gemm_dx(dh, w1, residual=ds2)
-        ds1, dg1, dbt1, da, dbo = ln_bwd(dx1, s1, mean1, rstd1, n1_w, n1_b, out_b, s1_, 0)
+        ds1, dg1, dbt1, da, dbo, _ = _site_bwd(dx1, s1, mean1, rstd1, n1_w, n1_b, out_b, N, p, s1_, drop_path, 0)
         Da = in_w.shape[0] // 3
-        o2 = o.view(B * N, Da)
-        dwo = wg(da, o2, out_w)
+        dwo = wg(da, o.view(B * N, Da), out_w)
         do = ops.gemm_dx(da, out_w)
-        # the in_proj bias gradient (column sums of dqkv) comes out of the attention backward itself
-        bi_slot = _slot(in_b)
-        attn_mask = getattr(ctx, "attn_mask", None)         # library.py's traced backward builds its own ctx: never masked
-        rel_bias = getattr(ctx, "rel_bias", None)           # ... and never biased
-        dtable = None
-        if rel_bias is not None:
-            want = ctx.needs_input_grad[20]                     # a frozen table costs nothing
-            dqkv, dtable, dbi = ops.attention_bias_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), ctx.n_heads, *rel_bias, p, sa,
-                                                       colsum=bi_slot if bi_slot is not None else True, scale=ctx.scale, table_grad=want)
-            dtable = _table_grad(dtable, ctx.rel_table) if want else None
-        elif attn_mask is None:
-            dqkv, dbi = ops.attention_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), ctx.n_heads, p, sa,
-                                          colsum=bi_slot if bi_slot is not None else True, scale=ctx.scale, any_length=True)
-        else:
-            dqkv, dbi = ops.attention_masked_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), ctx.n_heads,
-                                                 *attn_mask.on(dy2.device), p, sa,
-                                                 colsum=bi_slot if bi_slot is not None else True, scale=ctx.scale)
+        want = ctx.rel_bias is not None and ctx.needs_input_grad[13]        # a frozen table costs nothing
+        dqkv, dbi, dtable = _attn_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask,
+                                      ctx.rel_bias, True, in_b, ctx.rel_table, want)
         dqkv = dqkv.view(B * N, 3 * Da)
-        if bi_slot is None:
-            dbi = dbi.to(_BF16)
         dwi = wg(dqkv, x2, in_w)
         dx = ops.gemm_dx(dqkv, in_w, residual=ds1)
-        if ss:
-            ss.join(dw2, dw1, dwo, dwi)
-        # one gradient per argument of apply(): the mask is a 19th argument only when there is one, stochastic depth a 20th, the
-        # bias table and its index a 21st and 22nd
-        return ((dx.view(B, N, D), dwi, dbi, dwo, dbo, dg1, dbt1, dw1, db1, dw2, db2, dg2, dbt2, None, None, None, None, None)
-                + ((None, None, dtable, None) if rel_bias is not None
-                   else (None, None) if drop_path is not None else () if attn_mask is None else (None,)))
+        join(dw2, dw1, dwo, dwi)
+        return dx.view(B, N, D), dwi, dbi, dwo, dbo, dg1, dbt1, dw1, db1, dw2, db2, dg2, dbt2, dtable, None
 
 
 def _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads):
@@ -1006,8 +1033,34 @@ def encoder_layer_probe(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2,
     with torch.no_grad():
         args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
         B, N, D = args[0].shape
-        t = _EncoderLayer.launches(*args, n_heads, eps, 0.0, (0, 0, 0, 0), scale)
-        return t[11].view(B, N, D), t[1].view(B, N, -1), t[3], scale
+        t = _EncoderLayer.launches(*args, None, _LayerCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, "relu"))
+        return t["y"].view(B, N, D), t["qkv"].view(B, N, -1), t["lse"], scale
+
+
+def _path_rate(what, drop_path):
+    """A layer call's drop_path as a float in [0, 1): checked first, before the tensors are looked at."""
+    drop_path = float(drop_path)
+    if not 0.0 <= drop_path < 1.0:
+        raise ValueError(f"{what}: drop_path={drop_path} outside [0, 1)")
+    return drop_path
+
+
+def _layer_options(what, n_tokens, n_heads, attn_mask, rel_bias, no_traced_form=None):
+    """The attention options both layers take, checked -> (ops.AttentionMask or None, (table, ops.AttentionBiasIndex) or None).
+    no_traced_form: a layer without a traced form says so here: after the bias refusals, before the mask's."""
+    rel_bias = _rel_bias(rel_bias, attn_mask, n_tokens, n_heads, what)
+    if no_traced_form is not None and _traced():
+        raise NotImplementedError(f"{what}: {no_traced_form}")
+    return _attention_mask(attn_mask, n_tokens, what), rel_bias
+
+
+def _layer_cfg(n_heads, eps, dropout_p, scale, act, attn_mask, drop_path, rel_bias):
+    """An eager layer call's (_LayerCfg, bias table or None).  The seeds are drawn here, on the host, in this order: four dropout
+    seeds when dropout_p > 0, then two path seeds when drop_path > 0."""
+    seeds = tuple(ops.next_seed() for _ in range(4)) if dropout_p > 0 else (0, 0, 0, 0)
+    path = (drop_path, (ops.next_seed(), ops.next_seed())) if drop_path > 0 else None
+    table, index = rel_bias if rel_bias is not None else (None, None)
+    return _LayerCfg(n_heads, eps, float(dropout_p), seeds, scale, act, attn_mask, path, index), table
 
 
 def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5,
@@ -1029,62 +1082,28 @@ def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w,
     attention core alone changes, to the bias kernels, and the table receives its gradient (in its dtype, in its gradient
     slot when it has one).  Not with attn_mask (a window is part of the index: sfcvit.relpos), not under tracing; None
     runs the call as it is without the argument."""
-    drop_path = float(drop_path)
-    if not 0.0 <= drop_path < 1.0:
-        raise ValueError(f"encoder_layer: drop_path={drop_path} outside [0, 1)")
+    drop_path = _path_rate("encoder_layer", drop_path)
     args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
-    rel_bias = _rel_bias(rel_bias, attn_mask, args[0].shape[1], n_heads, "encoder_layer")
-    attn_mask = _attention_mask(attn_mask, args[0].shape[1], "encoder_layer")
+    attn_mask, rel_bias = _layer_options("encoder_layer", args[0].shape[1], n_heads, attn_mask, rel_bias)
     if drop_path > 0 and _traced():
         raise NotImplementedError("encoder_layer: drop_path > 0 has no traced form (torch.compile); run the layer eagerly")
     if _traced():
         from . import library      # (dropout seeds are drawn inside the op: nothing data-dependent in the traced graph)
         return library.encoder_layer(args, n_heads, eps, float(dropout_p), scale)
-    seeds = tuple(ops.next_seed() for _ in range(4)) if dropout_p > 0 else (0, 0, 0, 0)
-    path = (drop_path, (ops.next_seed(), ops.next_seed())) if drop_path > 0 else None
-    if rel_bias is not None:
-        return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale, None, path, *rel_bias)
-    if drop_path > 0:
-        return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale, attn_mask, path)
-    if attn_mask is not None:
-        return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale, attn_mask)
-    return _EncoderLayer.apply(*args, n_heads, eps, float(dropout_p), seeds, scale)
+    cfg, table = _layer_cfg(n_heads, eps, dropout_p, scale, "relu", attn_mask, drop_path, rel_bias)
+    return _EncoderLayer.apply(*args, table, cfg)
 
 
 # ----------------------------------------------------------------------------
-class _PreNormCfg:
-    """The non-tensor arguments of _PreNormLayer, one object so that apply() has a fixed argument list."""
-
-    def __init__(self, n_heads, eps, p, seeds, scale, act, attn_mask=None, drop_path=None, rel_index=None):
-        self.n_heads, self.eps, self.p, self.seeds, self.scale, self.act = n_heads, eps, p, seeds, scale, act
-        self.attn_mask, self.drop_path, self.rel_index = attn_mask, drop_path, rel_index
-
-
 class _PreNormLayer(Function):
     """Pre-norm transformer encoder layer (torch:nn/modules/transformer.py, norm_first=True) as "residual site + the LayerNorm
     after it", twice.  In: the residual stream s and n = LN1(s).  Out: s' and n' = LN_next(s'), LN_next being the next layer's
     norm1 or the encoder's final norm:
          a  = drop1(out_proj(attention(in_proj(n))));    s1 = s  + c1[b] lam1 * a;   n1 = LN2(s1)
          f  = drop2(W2 drop(act(W1 n1 + b1)) + b2);      s' = s1 + c2[b] lam2 * f;   n' = LN_next(s')
-    act is ReLU or erf-GELU; lam = None is no LayerScale, drop_path = None no stochastic depth.  Which kernels a site runs:
-      no lam, no drop_path   the branch GEMM's residual= epilogue + ops.layernorm_fwd;   ops.layernorm_bwd(dx_add=)
-      drop_path alone        ops.add_layernorm_path_fwd;                                 ops.layernorm_bwd_path(dx_add=)
-      lam                    ops.add_layernorm_scale_fwd;                                ops.layernorm_bwd_scale(dx_add=)
-    The LayerNorm backward after a site applies that site's dropout mask and DropPath flag to the gradient it hands the branch,
-    and adds the gradient of s arriving on the residual path (dx_add).  The ReLU MLP is _EncoderLayer's (bit matrix included);
-    the GELU MLP is _Mixer's recipe: pre-activation GEMM, one element-wise pass (with the dropout), b1's gradient a column sum."""
-
-    @staticmethod
-    def site(branch_in, w, b, res, lam_row, g_w, g_b, B, eps, p, seed, drop_path, site):
-        """One residual site + the LayerNorm after it -> (branch or None, s, n, mean, rstd)."""
-        if lam_row is None and drop_path is None:
-            s = ops.gemm(branch_in, w, bias=b, residual=res, dropout_p=p, dropout_seed=seed)
-            return (None, s) + tuple(ops.layernorm_fwd(s, g_w, g_b, eps))
-        a = ops.gemm(branch_in, w, bias=b, dropout_p=p, dropout_seed=seed)
-        rate, pseed = (drop_path[0], drop_path[1][site]) if drop_path is not None else (0.0, 0)
-        if lam_row is None:
-            return (None,) + tuple(ops.add_layernorm_path_fwd(a, res, g_w, g_b, B, rate, pseed, eps))
-        return (a,) + tuple(ops.add_layernorm_scale_fwd(a, res, lam_row, g_w, g_b, B, rate, pseed, eps))
+    cfg.act is ReLU or erf-GELU (_mlp_fwd); lam = None is no LayerScale, cfg.drop_path = None no stochastic depth (_site_fwd /
+    _site_bwd: which kernels a site runs).  Arguments: s, n, the 12 parameters, lam [2, D] or None, the bias table parameter or
+    None, a _LayerCfg."""
 
     @staticmethod
     def launches(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_bias, cfg):
@@ -1092,35 +1111,22 @@ class _PreNormLayer(Function):
         inputs out of the same sequence)."""
         B, N, D = s.shape
         Da = in_w.shape[0] // 3
-        p, H = cfg.p, cfg.n_heads
+        p = cfg.p
         sa, s1_, sf, s2_ = cfg.seeds
         s0, n0 = _c(s).view(B * N, D), _c(n).view(B * N, D)
         qkv = ops.gemm(n0, in_w, bias=in_b)
-        if rel_bias is not None:
-            o, lse = ops.attention_bias_fwd(qkv.view(B, N, 3 * Da), H, *rel_bias, p, sa, scale=cfg.scale)
-        elif cfg.attn_mask is None:
-            o, lse = ops.attention_fwd(qkv.view(B, N, 3 * Da), H, p, sa, scale=cfg.scale, any_length=True)
-        else:
-            o, lse = ops.attention_masked_fwd(qkv.view(B, N, 3 * Da), H, *cfg.attn_mask.on(s.device), p, sa, scale=cfg.scale)
+        o, lse = _attn_fwd(qkv.view(B, N, 3 * Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask, rel_bias)
         lam1, lam2 = (lam[0], lam[1]) if lam is not None else (None, None)
-        a, s1, n1, mean1, rstd1 = _PreNormLayer.site(o.view(B * N, Da), out_w, out_b, s0, lam1, n2_w, n2_b, B, cfg.eps, p, s1_,
-                                                     cfg.drop_path, 0)
-        hbits = u = None
-        if cfg.act == "relu":
-            hbits = (torch.empty((B * N, w1.shape[0] // 8), device=s.device, dtype=torch.uint8)
-                     if USE_ACTMASK and w1.shape[0] % 16 == 0 else None)
-            h = ops.gemm(n1, w1, bias=b1, act=ops.ACT_RELU, dropout_p=p, dropout_seed=sf, actmask=hbits)
-        else:
-            u = ops.gemm(n1, w1, bias=b1)
-            h = ops.gelu_drop_fwd(u, p, sf) if p > 0 else ops.gelu_fwd(u)
-        f, s2, n2, mean2, rstd2 = _PreNormLayer.site(h, w2, b2, s1, lam2, nf_w, nf_b, B, cfg.eps, p, s2_, cfg.drop_path, 1)
+        a, s1, n1, mean1, rstd1 = _site_fwd(o.view(B * N, Da), out_w, out_b, s0, lam1, n2_w, n2_b, B, cfg.eps, p, s1_, cfg.drop_path, 0)
+        hbits, u, h = _mlp_fwd(n1, w1, b1, cfg.act, p, sf)
+        f, s2, n2, mean2, rstd2 = _site_fwd(h, w2, b2, s1, lam2, nf_w, nf_b, B, cfg.eps, p, s2_, cfg.drop_path, 1)
         return dict(n0=n0, qkv=qkv, o=o, lse=lse, a=a, s1=s1, n1=n1, mean1=mean1, rstd1=rstd1, hbits=hbits, u=u, h=h, f=f, s2=s2,
                     n2=n2, mean2=mean2, rstd2=rstd2)
 
     @staticmethod
     def forward(ctx, s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_table, cfg):
         B, N, D = s.shape
-        rel_bias = None if cfg.rel_index is None else (_c(rel_table.detach().to(torch.float32)), cfg.rel_index)
+        rel_bias = _fp32_bias(rel_table, cfg.rel_index)
         t = _PreNormLayer.launches(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_bias, cfg)
         ctx.cfg, ctx.shape, ctx.rel_bias, ctx.rel_table, ctx.hbits = cfg, (B, N, D), rel_bias, rel_table, t["hbits"]
         ctx.lam_param = lam                                     # for its gradient slot: both rows are written in one backward
@@ -1145,89 +1151,34 @@ class _PreNormLayer(Function):
         in_b, out_b, n2_b, b1, b2, nf_b = ctx.small
         ds_out = None if ds_out is None else _c(ds_out).view(B * N, D)
         dn_out = torch.zeros_like(s2) if dn_out is None else _c(dn_out).view(B * N, D)
-        ss = _SideStream(dn_out.device) if SIDE_STREAM_WGRAD else None
-        wg = (lambda a_, b_, w_: ss.run(lambda: _wgrad(a_, b_, w_), a_, b_)) if ss else _wgrad
+        wg, join = _wgrad_runner(dn_out.device)
         lam_slot = _slot(ctx.lam_param) if lam is not None else None
-        dlam = [None, None]
-
-        def ln_bwd(dyv, sv, mean, rstd, g_w, g_b, prev_bias, seed, site, add, branch):
-            """The LayerNorm backward after a site -> (gradient of s, dgamma, dbeta, gradient entering the branch, column sums of
-            that = the bias gradient of linear2 / out_proj).  Gradients go straight into their slots when every parameter of
-            the call has one."""
-            slots = (_slot(g_w), _slot(g_b), _slot(prev_bias))
-            ok = all(t is not None for t in slots) and (lam is None or lam_slot is not None)
-            if lam is not None:
-                row = None
-                if ok:
-                    row = lam_slot[site]
-                    row._sfcvit_deferrable = True
-                rate, pseed = (drop_path[0], drop_path[1][site]) if drop_path is not None else (0.0, 0)
-                dsv, dg, dbt, dsub, dl, dcol = ops.layernorm_bwd_scale(dyv, sv, mean, rstd, g_w, branch, lam[site], N, rate, pseed, dx_add=add,
-                                                                       drop_p=p, drop_seed=seed, want_colsum=True,
-                                                                       grad_out=slots + (row,) if ok else None)
-                dlam[site] = dl
-            elif drop_path is not None:
-                dsv, dg, dbt, dsub, dcol = ops.layernorm_bwd_path(dyv, sv, mean, rstd, g_w, N, drop_path[0], drop_path[1][site], dx_add=add,
-                                                                  drop_p=p, drop_seed=seed, want_colsum=True, grad_out=slots if ok else None)
-            elif p > 0:
-                dsv, dg, dbt, dsub, dcol = ops.layernorm_bwd(dyv, sv, mean, rstd, g_w, dx_add=add, drop_p=p, drop_seed=seed,
-                                                             want_colsum=True, grad_out=slots if ok else None)
-            else:
-                dsv, dg, dbt, dcol = ops.layernorm_bwd(dyv, sv, mean, rstd, g_w, dx_add=add, want_colsum=True, grad_out=slots if ok else None)
-                dsub = dsv
-            if not ok:
-                dg, dbt, dcol = dg.to(_BF16), dbt.to(_BF16), dcol.to(_BF16)
-            return dsv, dg, dbt, dsub, dcol
-
-        ds2, dgf, dbtf, df, db2 = ln_bwd(dn_out, s2, mean2, rstd2, nf_w, nf_b, b2, s2_, 1, ds_out, f)
+        lam1, lam2 = (lam[0], lam[1]) if lam is not None else (None, None)
+        out1, out2 = (lam_slot[0], lam_slot[1]) if lam_slot is not None else (None, None)
+        ds2, dgf, dbtf, df, db2, dlam2 = _site_bwd(dn_out, s2, mean2, rstd2, nf_w, nf_b, b2, N, p, s2_, drop_path, 1, ds_out, f, lam2, out2)
         dw2 = wg(df, h, w2)
-        b1_slot = _slot(b1)
-        if cfg.act == "relu":
-            # h is stored after relu + dropout: (h > 0) is the joint mask, 1/(1-p) the dropout scale; b1's gradient is the column
-            # sum of dh, fused into that GEMM's epilogue
-            dh, db1 = ops.gemm_dx(df, w2, aux_in=h, dact=ops.ACT_RELU, dact_scale=1.0 / (1.0 - p),
-                                  colsum=b1_slot if b1_slot is not None else True, actmask=ctx.hbits)
-            if b1_slot is None:
-                db1 = db1.to(_BF16)
-        else:
-            dh = ops.gemm_dx(df, w2)
-            dh = ops.gelu_drop_bwd(dh, u, p, sf) if p > 0 else ops.gelu_bwd(dh, u)
-            db1 = ops.colsum(dh, out=b1_slot) if b1_slot is not None else ops.colsum(dh).to(_BF16)
+        dh, db1 = _mlp_bwd(df, h, u, ctx.hbits, w2, b1, cfg.act, p, sf)
         dw1 = wg(dh, n1, w1)
         dn1 = ops.gemm_dx(dh, w1)
-        ds1, dg2, dbt2, da, dbo = ln_bwd(dn1, s1, mean1, rstd1, n2_w, n2_b, out_b, s1_, 0, ds2, a)
+        ds1, dg2, dbt2, da, dbo, dlam1 = _site_bwd(dn1, s1, mean1, rstd1, n2_w, n2_b, out_b, N, p, s1_, drop_path, 0, ds2, a, lam1, out1)
         Da = in_w.shape[0] // 3
         dwo = wg(da, o.view(B * N, Da), out_w)
         do = ops.gemm_dx(da, out_w)
-        bi_slot = _slot(in_b)
-        dtable = None
-        col = bi_slot if bi_slot is not None else True
-        if ctx.rel_bias is not None:
-            want = ctx.needs_input_grad[15]                     # a frozen table costs nothing
-            dqkv, dtable, dbi = ops.attention_bias_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, *ctx.rel_bias, p, sa,
-                                                       colsum=col, scale=cfg.scale, table_grad=want)
-            dtable = _table_grad(dtable, ctx.rel_table) if want else None
-        elif cfg.attn_mask is None:
-            dqkv, dbi = ops.attention_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, p, sa, colsum=col,
-                                          scale=cfg.scale, any_length=True)
-        else:
-            dqkv, dbi = ops.attention_masked_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads,
-                                                 *cfg.attn_mask.on(dn_out.device), p, sa, colsum=col, scale=cfg.scale)
+        want = ctx.rel_bias is not None and ctx.needs_input_grad[15]        # a frozen table costs nothing
+        dqkv, dbi, dtable = _attn_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask,
+                                      ctx.rel_bias, True, in_b, ctx.rel_table, want)
         dqkv = dqkv.view(B * N, 3 * Da)
-        if bi_slot is None:
-            dbi = dbi.to(_BF16)
         dwi = wg(dqkv, n0, in_w)
         dn_in = ops.gemm_dx(dqkv, in_w)
-        if ss:
-            ss.join(dw2, dw1, dwo, dwi)
+        join(dw2, dw1, dwo, dwi)
         if lam is None:
             dl = None
-        elif lam_slot is not None and all(d.dtype == _BF16 and d.data_ptr() == lam_slot[i].data_ptr() for i, d in enumerate(dlam)):
+        elif lam_slot is not None and all(d.dtype == _BF16 and d.data_ptr() == r.data_ptr() for d, r in ((dlam1, out1), (dlam2, out2))):
             dl = lam_slot                                       # both rows were written in place
         else:
             if lam_slot is not None:                            # one row sits in the slot, its reduction perhaps still queued
                 ops.flush_deferred(end=False)
-            dl = torch.stack([dlam[0].to(_BF16), dlam[1].to(_BF16)])
+            dl = torch.stack([dlam1.to(_BF16), dlam2.to(_BF16)])
         return (ds1.view(B, N, D), dn_in.view(B, N, D), dwi, dbi, dwo, dbo, dg2, dbt2, dw1, db1, dw2, db2, dgf, dbtf, dl, dtable, None)
 
 
@@ -1270,19 +1221,12 @@ def pre_norm_layer(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, n
     attention and MLP branches (CaiT / DeiT-III), s1 = s + c1[b] lam1 * a.  dropout_p, attn_mask, drop_path, rel_bias and the
     zero padding of head dims the kernels do not have: as in encoder_layer, with its masks, flags and seeds.  Not under tracing."""
     what = "pre_norm_layer"
-    drop_path = float(drop_path)
-    if not 0.0 <= drop_path < 1.0:
-        raise ValueError(f"{what}: drop_path={drop_path} outside [0, 1)")
+    drop_path = _path_rate(what, drop_path)
     args, scale, n, lam = _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads,
                                          activation, layer_scale, what)
-    rel_bias = _rel_bias(rel_bias, attn_mask, args[0].shape[1], n_heads, what)
-    if _traced():
-        raise NotImplementedError(f"{what}: the pre-norm layer has no traced form (torch.compile); run the model eagerly")
-    attn_mask = _attention_mask(attn_mask, args[0].shape[1], what)
-    seeds = tuple(ops.next_seed() for _ in range(4)) if dropout_p > 0 else (0, 0, 0, 0)
-    path = (drop_path, (ops.next_seed(), ops.next_seed())) if drop_path > 0 else None
-    table, index = rel_bias if rel_bias is not None else (None, None)
-    cfg = _PreNormCfg(n_heads, eps, float(dropout_p), seeds, scale, activation, attn_mask, path, index)
+    attn_mask, rel_bias = _layer_options(what, args[0].shape[1], n_heads, attn_mask, rel_bias,
+                                         no_traced_form="the pre-norm layer has no traced form (torch.compile); run the model eagerly")
+    cfg, table = _layer_cfg(n_heads, eps, dropout_p, scale, activation, attn_mask, drop_path, rel_bias)
     return _PreNormLayer.apply(args[0], n, *args[1:], lam, table, cfg)
 
 
@@ -1295,7 +1239,7 @@ def pre_norm_layer_probe(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2,
         args, scale, n, lam = _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads,
                                              activation, layer_scale, "pre_norm_layer_probe")
         B, N, D = args[0].shape
-        cfg = _PreNormCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, activation)
+        cfg = _LayerCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, activation)
         t = _PreNormLayer.launches(args[0], n, *args[1:], lam, None, cfg)
         return t["s2"].view(B, N, D), t["n2"].view(B, N, D), t["qkv"].view(B, N, -1), t["lse"], scale
 

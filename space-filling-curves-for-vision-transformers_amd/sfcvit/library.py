@@ -521,13 +521,13 @@ def encoder_layer_op(x: Tensor, in_w: Tensor, in_b: Tensor, out_w: Tensor, out_b
     ctx = _Ctx()
     if p > 0 and not seeds:
         seeds = [ops.next_seed() for _ in range(4)]
-    y = F._EncoderLayer.forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps, p,
-                                tuple(seeds) if seeds else (0, 0, 0, 0), scale)
+    cfg = F._LayerCfg(n_heads, eps, p, tuple(seeds) if seeds else (0, 0, 0, 0), scale, "relu")     # no mask, DropPath or bias when traced
+    y = F._EncoderLayer.forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, None, cfg)
     saved = list(ctx.saved_tensors[1:_ENC_SAVED])
     hbits = ctx.hbits if ctx.hbits is not None else _e(x, torch.uint8)
     # what backward regenerates the masks from: a CPU tensor (read back without a device sync); without dropout an empty
     # DEVICE tensor, so that an inference / evaluation graph holds no CPU tensor and "reduce-overhead" can capture it
-    seed_t = torch.tensor(list(ctx.seeds), dtype=torch.int64) if p > 0 else _e(x, torch.int64)
+    seed_t = torch.tensor(list(cfg.seeds), dtype=torch.int64) if p > 0 else _e(x, torch.int64)
     return [y] + saved + [hbits, seed_t]
 
 
@@ -551,9 +551,9 @@ def encoder_layer_bwd_op(dy: Tensor, x: Tensor, saved: List[Tensor], weights: Li
     ctx = _Ctx()
     B, N, D = x.shape
     ctx.saved_tensors = (F._c(x).view(B * N, D), qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2, in_w, out_w, n1_w, w1, w2, n2_w)
-    ctx.hbits = _opt(hbits)
-    ctx.n_heads, ctx.shape, ctx.p, ctx.scale = n_heads, (B, N, D), p, scale
-    ctx.seeds = tuple(int(v) for v in seed_t.tolist()) if p > 0 else (0, 0, 0, 0)
+    # what _EncoderLayer.forward sets (eps is the forward's alone)
+    seeds = tuple(int(v) for v in seed_t.tolist()) if p > 0 else (0, 0, 0, 0)
+    ctx.cfg, ctx.shape, ctx.rel_bias, ctx.rel_table, ctx.hbits = F._LayerCfg(n_heads, None, p, seeds, scale, "relu"), (B, N, D), None, None, _opt(hbits)
     ctx.small = (None,) * 6
     with _no_slots():
         return list(F._EncoderLayer.backward(ctx, dy)[:13])

@@ -390,36 +390,55 @@ def layernorm_fwd(x, gamma, beta, eps=1e-5):
     return y, mean, rstd
 
 
-def _layernorm_bwd(path, dy, x, mean, rstd, gamma, dx_add, drop_p, drop_seed, want_colsum, grad_out):
-    """layernorm_bwd (path = None) and layernorm_bwd_path (path = (rows_per_image, path_rate, path_seed)): the buffers, the
-    workspace of the one plan both C calls share, the call -> dx, dgamma, dbeta, dx_drop (None if not written), dcol (None if
-    not wanted)."""
-    what = "layernorm_bwd" if path is None else "layernorm_bwd_path"
+def _layernorm_bwd(path, dy, x, mean, rstd, gamma, dx_add, drop_p, drop_seed, want_colsum, grad_out, scale=None):
+    """layernorm_bwd (path = None), layernorm_bwd_path (path = (rows_per_image, path_rate, path_seed)) and layernorm_bwd_scale
+    (path and scale = (branch, lam)): the checks, the buffers, the workspace of the plan the C call uses, the call -> dx, dgamma,
+    dbeta, dx_drop (None if not written), dcol (None if not wanted) [, dlam with scale]."""
+    what = "layernorm_bwd" if path is None else "layernorm_bwd_path" if scale is None else "layernorm_bwd_scale"
     _need(dy, _BF16, "layernorm dy", 2)
     _need(x, _BF16, "layernorm x", 2)
+    if scale is not None:
+        branch, lam = scale
+        _need(branch, _BF16, "layernorm_bwd_scale branch", 2)
     M, D = x.shape
     if path is not None and (path[0] <= 0 or M % path[0]):
-        raise ValueError(f"layernorm_bwd_path: {M} rows are not whole images of {path[0]}")
+        raise ValueError(f"{what}: {M} rows are not whole images of {path[0]}")
+    if scale is not None and (branch.shape != x.shape or dy.shape != x.shape or _need(lam, _BF16, "lam", 1).numel() != D):
+        raise ValueError(f"{what}: dy, x and branch must be equal [M, D] and lam [D], got {tuple(dy.shape)} {tuple(x.shape)} "
+                         f"{tuple(branch.shape)} {tuple(lam.shape)}")
     dx = torch.empty_like(x)
     dx_drop = torch.empty_like(x) if path is not None or drop_p > 0 else None
-    (dg, db, dcol), bf16 = _grad_outs(what, grad_out, ((D,), (D,), (D,)), (True, True, want_colsum), x.device,
-                                      "contiguous bf16 [D] tensors", name="out" if path is not None else "grad_out")   # the words each had
-    ws = torch.empty(lib.sfcvit_layernorm_bwd_ws(M, D), device=x.device, dtype=torch.uint8)
+    if scale is None:
+        (dg, db, dcol), bf16 = _grad_outs(what, grad_out, ((D,), (D,), (D,)), (True, True, want_colsum), x.device,
+                                          "contiguous bf16 [D] tensors", name="out" if path is not None else "grad_out")   # the words each had
+        dl = ()
+    else:
+        if grad_out is not None and len(grad_out) == 4:
+            grad_out = (grad_out[0], grad_out[1], grad_out[3], grad_out[2])      # the optional entry last, as _grad_outs' callers have it
+        (dg, db, *dl, dcol), bf16 = _grad_outs(what, grad_out, ((D,), (D,), (D,), (D,)), (True, True, True, want_colsum), x.device,
+                                               "contiguous bf16 [D] tensors (dgamma, dbeta, colsum or None, dlam)")
+    ws_bytes = lib.sfcvit_layernorm_bwd_ws if scale is None else lib.sfcvit_layernorm_bwd_scale_ws
+    ws = torch.empty(ws_bytes(M, D), device=x.device, dtype=torch.uint8)
     if dx_add is not None:
         _need(dx_add, _BF16, "layernorm dx_add", 2)
-    seed_off = _seed_off() if path is not None or drop_p > 0 else None
-    with _Deferring([dg, db] + ([dcol] if dcol is not None else []), [ws]):
+    # (the scale form draws no flag at rate 0; the path form passes the offset whatever the rate)
+    seed_off = _seed_off() if drop_p > 0 or (path is not None and (scale is None or path[1] > 0)) else None
+    with _Deferring([dg, db, *dl] + ([dcol] if dcol is not None else []), [ws]):
         if path is None:
             rc = lib.sfcvit_layernorm_bwd_drop(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_add), _p(dx), _p(dx_drop), drop_p,
                                                drop_seed, seed_off, _p(dg), _p(db), _p(dcol), int(bf16), M, D, _p(ws), _stream())
-        else:
+        elif scale is None:
             rc = lib.sfcvit_layernorm_bwd_path(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_add), _p(dx), _p(dx_drop), drop_p,
                                                drop_seed, seed_off, _p(dg), _p(db), _p(dcol), int(bf16), M // path[0], path[0], D,
                                                _p(ws), path[1], path[2], _stream())
+        else:
+            rc = lib.sfcvit_layernorm_bwd_scale(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_add), _p(branch), _p(lam), _p(dx),
+                                                _p(dx_drop), drop_p, drop_seed, seed_off, _p(dg), _p(db), _p(dcol), _p(dl[0]), int(bf16),
+                                                M // path[0], path[0], D, _p(ws), path[1], path[2], _stream())
         check(rc, "sfcvit_" + what)
     if KERNEL_LOG is not None:
         KERNEL_LOG.append(last_rowwise_kernel())
-    return dx, dg, db, dx_drop, dcol
+    return (dx, dg, db, dx_drop, dcol, *dl)
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, dx_add=None, drop_p=0.0, drop_seed=0, want_colsum=False, grad_out=None):
@@ -440,23 +459,37 @@ def drop_path_keep(B, rate, seed, device="cuda"):
     return dropout_mask(B, 8, rate, seed, device)[:, 0] > 0
 
 
-def add_layernorm_path_fwd(branch, x, gamma, beta, B, rate, seed, eps=1e-5):
-    """s = bf16(x + c[b] * branch), LayerNorm(s) -> (s, y, mean, rstd); c[b] = keep(b) / (1 - rate) per image b = row // (M / B).
-    branch, x: bf16 [M, D], M = B * tokens.  A dropped image's rows of s are the bits of x."""
-    _need(branch, _BF16, "add_layernorm_path branch", 2)
-    _need(x, _BF16, "add_layernorm_path x", 2)
+def _add_layernorm_fwd(what, branch, x, lam, gamma, beta, B, rate, seed, eps):
+    """add_layernorm_path_fwd and add_layernorm_scale_fwd (what = "add_layernorm_scale", with lam): the checks, the buffers, the
+    call -> (s, y, mean, rstd)."""
+    scaled = what == "add_layernorm_scale"
+    _need(branch, _BF16, f"{what} branch", 2)
+    _need(x, _BF16, f"{what} x", 2)
     M, D = x.shape
     if branch.shape != x.shape or B <= 0 or M % B:
-        raise ValueError(f"add_layernorm_path: branch {tuple(branch.shape)} and x {tuple(x.shape)} must be equal [B * N, D] with B = {B}")
+        raise ValueError(f"{what}: branch {tuple(branch.shape)} and x {tuple(x.shape)} must be equal [B * N, D] with B = {B}")
+    if scaled and _need(lam, _BF16, "lam", 1).numel() != D:
+        raise ValueError(f"{what}: lam must be [D] = [{D}], got {tuple(lam.shape)}")
     s, y = torch.empty_like(x), torch.empty_like(x)
     mean = torch.empty(M, device=x.device, dtype=torch.float32)
     rstd = torch.empty(M, device=x.device, dtype=torch.float32)
-    check(lib.sfcvit_add_layernorm_path_fwd(_p(branch), _p(x), _p(_need(gamma, _BF16, "gamma", 1)), _p(_need(beta, _BF16, "beta", 1)),
-                                            _p(s), _p(y), _p(mean), _p(rstd), B, M // B, D, eps, rate, seed, _seed_off(), _stream()),
-          "sfcvit_add_layernorm_path_fwd")
+    head = (_p(branch), _p(x)) + ((_p(lam),) if scaled else ())
+    tail = (_p(_need(gamma, _BF16, "gamma", 1)), _p(_need(beta, _BF16, "beta", 1)), _p(s), _p(y), _p(mean), _p(rstd), B, M // B, D, eps,
+            rate, seed)
+    if scaled:                                  # no flag is drawn at rate 0: the device seed offset only with one
+        rc = lib.sfcvit_add_layernorm_scale_fwd(*head, *tail, _seed_off() if rate > 0 else None, _stream())
+    else:
+        rc = lib.sfcvit_add_layernorm_path_fwd(*head, *tail, _seed_off(), _stream())
+    check(rc, f"sfcvit_{what}_fwd")
     if KERNEL_LOG is not None:
         KERNEL_LOG.append(last_rowwise_kernel())
     return s, y, mean, rstd
+
+
+def add_layernorm_path_fwd(branch, x, gamma, beta, B, rate, seed, eps=1e-5):
+    """s = bf16(x + c[b] * branch), LayerNorm(s) -> (s, y, mean, rstd); c[b] = keep(b) / (1 - rate) per image b = row // (M / B).
+    branch, x: bf16 [M, D], M = B * tokens.  A dropped image's rows of s are the bits of x."""
+    return _add_layernorm_fwd("add_layernorm_path", branch, x, None, gamma, beta, B, rate, seed, eps)
 
 
 def layernorm_bwd_path(dy, x, mean, rstd, gamma, rows_per_image, path_rate, path_seed, dx_add=None, drop_p=0.0, drop_seed=0,
@@ -477,23 +510,7 @@ def add_layernorm_scale_fwd(branch, x, lam, gamma, beta, B, rate=0.0, seed=0, ep
     """s = bf16(x + (c[b] * lam[d]) * branch), LayerNorm(s) -> (s, y, mean, rstd); lam bf16 [D]; c[b] = keep(b) / (1 - rate) per
     image b = row // (M / B), 1 at rate = 0 (no flag is drawn).  branch, x: bf16 [M, D], M = B * tokens.  A dropped image's rows
     of s are the bits of x."""
-    _need(branch, _BF16, "add_layernorm_scale branch", 2)
-    _need(x, _BF16, "add_layernorm_scale x", 2)
-    M, D = x.shape
-    if branch.shape != x.shape or B <= 0 or M % B:
-        raise ValueError(f"add_layernorm_scale: branch {tuple(branch.shape)} and x {tuple(x.shape)} must be equal [B * N, D] with B = {B}")
-    if _need(lam, _BF16, "lam", 1).numel() != D:
-        raise ValueError(f"add_layernorm_scale: lam must be [D] = [{D}], got {tuple(lam.shape)}")
-    s, y = torch.empty_like(x), torch.empty_like(x)
-    mean = torch.empty(M, device=x.device, dtype=torch.float32)
-    rstd = torch.empty(M, device=x.device, dtype=torch.float32)
-    check(lib.sfcvit_add_layernorm_scale_fwd(_p(branch), _p(x), _p(lam), _p(_need(gamma, _BF16, "gamma", 1)),
-                                             _p(_need(beta, _BF16, "beta", 1)), _p(s), _p(y), _p(mean), _p(rstd), B, M // B, D, eps,
-                                             rate, seed, _seed_off() if rate > 0 else None, _stream()),
-          "sfcvit_add_layernorm_scale_fwd")
-    if KERNEL_LOG is not None:
-        KERNEL_LOG.append(last_rowwise_kernel())
-    return s, y, mean, rstd
+    return _add_layernorm_fwd("add_layernorm_scale", branch, x, lam, gamma, beta, B, rate, seed, eps)
 
 
 def layernorm_bwd_scale(dy, x, mean, rstd, gamma, branch, lam, rows_per_image, path_rate=0.0, path_seed=0, dx_add=None, drop_p=0.0,
@@ -503,32 +520,8 @@ def layernorm_bwd_scale(dy, x, mean, rstd, gamma, branch, lam, rows_per_image, p
     kept images, zeros for dropped ones, is the gradient entering the sub-layer; dlam[d] = sum over rows of the stored dx * c[b]
     * branch.  grad_out = (dgamma, dbeta, colsum-or-None, dlam) bf16 [D] tensors (None entries are allocated): written in place
     as bf16, e.g. views of a flat gradient buffer -- dlam may be a row of a [2, D] parameter's slot."""
-    what = "layernorm_bwd_scale"
-    _need(dy, _BF16, "layernorm dy", 2)
-    _need(x, _BF16, "layernorm x", 2)
-    _need(branch, _BF16, "layernorm_bwd_scale branch", 2)
-    M, D = x.shape
-    if rows_per_image <= 0 or M % rows_per_image:
-        raise ValueError(f"{what}: {M} rows are not whole images of {rows_per_image}")
-    if branch.shape != x.shape or dy.shape != x.shape or _need(lam, _BF16, "lam", 1).numel() != D:
-        raise ValueError(f"{what}: dy, x and branch must be equal [M, D] and lam [D], got {tuple(dy.shape)} {tuple(x.shape)} "
-                         f"{tuple(branch.shape)} {tuple(lam.shape)}")
-    dx, dx_drop = torch.empty_like(x), torch.empty_like(x)
-    if grad_out is not None and len(grad_out) == 4:
-        grad_out = (grad_out[0], grad_out[1], grad_out[3], grad_out[2])      # the optional entry last, as _grad_outs' callers have it
-    (dg, db, dl, dcol), bf16 = _grad_outs(what, grad_out, ((D,), (D,), (D,), (D,)), (True, True, True, want_colsum), x.device,
-                                          "contiguous bf16 [D] tensors (dgamma, dbeta, colsum or None, dlam)")
-    ws = torch.empty(lib.sfcvit_layernorm_bwd_scale_ws(M, D), device=x.device, dtype=torch.uint8)
-    if dx_add is not None:
-        _need(dx_add, _BF16, "layernorm dx_add", 2)
-    seed_off = _seed_off() if path_rate > 0 or drop_p > 0 else None
-    with _Deferring([dg, db, dl] + ([dcol] if dcol is not None else []), [ws]):
-        check(lib.sfcvit_layernorm_bwd_scale(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_add), _p(branch), _p(lam), _p(dx),
-                                             _p(dx_drop), drop_p, drop_seed, seed_off, _p(dg), _p(db), _p(dcol), _p(dl), int(bf16),
-                                             M // rows_per_image, rows_per_image, D, _p(ws), path_rate, path_seed, _stream()),
-              "sfcvit_" + what)
-    if KERNEL_LOG is not None:
-        KERNEL_LOG.append(last_rowwise_kernel())
+    dx, dg, db, dx_drop, dcol, dl = _layernorm_bwd((rows_per_image, path_rate, path_seed), dy, x, mean, rstd, gamma, dx_add, drop_p,
+                                                   drop_seed, want_colsum, grad_out, scale=(branch, lam))
     return (dx, dg, db, dx_drop, dl) + ((dcol,) if want_colsum else ())
 
 

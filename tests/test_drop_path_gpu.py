@@ -272,7 +272,7 @@ def test_encoder_layer_against_the_masked_reference(ops, masked):
     leaves = [x.clone().requires_grad_(True)] + [P[k].clone().requires_grad_(True) for k in ORDER]
     ops.KERNEL_LOG = []
     try:
-        y = F._EncoderLayer.apply(*leaves, H, 1e-5, p, seeds, None, am, (rate, pseeds))
+        y = F._EncoderLayer.apply(*leaves, None, F._LayerCfg(H, 1e-5, p, seeds, None, "relu", am, (rate, pseeds)))
         kept = [t.detach() for t in y.grad_fn.saved_tensors[:10]]
         y.backward(dy)
         ran = list(ops.KERNEL_LOG)

@@ -134,7 +134,7 @@ def test_encoder_layer_training_mode_against_masked_reference(ops, B, N, D, H, F
     leaves = [x.clone().requires_grad_(True)] + [P[k].clone().requires_grad_(True) for k in order]
     ops.KERNEL_LOG = []
     try:
-        y = F._EncoderLayer.apply(*leaves, H, 1e-5, p, seeds, None)        # scale None = 1 / sqrt(head dim)
+        y = F._EncoderLayer.apply(*leaves, None, F._LayerCfg(H, 1e-5, p, seeds, None, "relu"))        # scale None = 1 / sqrt(head dim)
         kept = [t.detach() for t in y.grad_fn.saved_tensors[:10]]           # (freed by backward)
         y.backward(dy)
         ran = set(ops.KERNEL_LOG)

@@ -339,7 +339,7 @@ def _run_layer(ops, act, with_lam, rate, masked=False, biased=False):
         table = (0.5 * torch.randn(H, T, device="cuda", generator=torch.Generator(device="cuda").manual_seed(9))).requires_grad_(True)
     leaves = [s.clone().requires_grad_(True), n.clone().requires_grad_(True)] + [P[k].clone().requires_grad_(True) for k in prenorm_ref.ORDER]
     lam_leaf = lam.clone().requires_grad_(True) if with_lam else None
-    cfg = F._PreNormCfg(H, 1e-5, p, seeds, None, act, am, (rate, pseeds) if rate > 0 else None, index)
+    cfg = F._LayerCfg(H, 1e-5, p, seeds, None, act, am, (rate, pseeds) if rate > 0 else None, index)
     ops.KERNEL_LOG = []
     try:
         s2, n2 = F._PreNormLayer.apply(*leaves, lam_leaf, table, cfg)
