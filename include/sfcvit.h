@@ -469,6 +469,31 @@ int sfcvit_layernorm_bwd_scale(const void *dy, const void *x, const float *mean,
                                void *stream);
 int64_t sfcvit_layernorm_bwd_scale_ws(int M, int D);
 
+/* QK-norm (ViT-22B; timm's qk_norm=True): a LayerNorm over the head dim on the queries and keys of every head of a packed
+ * projection qkv [M, 3 * H * hp] bf16 (q | k | v thirds, head h at columns h * hp .. of each third), IN PLACE, before q k^T:
+ *   q[m, h, :hd] <- LayerNorm_hd(q[m, h, :hd]; P[0], P[1], eps),  k likewise with P[2], P[3];  q, k[m, h, hd:hp] <- +0;  v untouched
+ * hp: the kernel head dim (64 / 128 / 192 / 256); 1 <= hd <= hp: the model's head dim, columns hd .. hp - 1 being zero padding
+ * that stays out of the statistics.  params P: bf16 [4, hd], rows q_weight, q_bias, k_weight, k_bias, shared by all heads.
+ * Biased variance, centred, fp32 from the bf16 inputs; one rounding to bf16.  eps >= 0, finite.  raw [M, 2 * H * hp] bf16
+ * receives the bits of q | k as they were: the backward recomputes mean and rstd from it with the forward's own device
+ * function, nothing else is stored.  Notes its kernel ("qk_norm_fwd_kernel<64>") for sfcvit_last_rowwise_kernel. */
+int sfcvit_qk_norm_fwd(void *qkv, void *raw, const void *params, int M, int H, int hd, int hp, float eps, void *stream);
+/* Its backward, in place on the q and k thirds of dqkv [M, 3 * H * hp] as the attention backward left them (v untouched):
+ *   dx = rstd * (g - mean(g) - xh * mean(g * xh)),  g = dy * gamma, over the hd real columns; padded columns are written +0
+ * whatever they held.  dparams [4, hd] (fp32, or bf16 with dparams_is_bf16: a gradient slot): dgamma = sum dy * xh and dbeta =
+ * sum dy over all M * H head rows, q and k apart.  colsum (optional; fp32 or bf16) [2 * H * hp]: the column sums of the stored
+ * dq | dk over the M rows, the q and k part of the in_proj bias gradient.  vsum (optional, needs colsum): fp32 [H * hp], the v
+ * third's column sums from the attention backward; colsum is then [3 * H * hp] and its last third receives them, so one slot
+ * ends up holding the whole bias gradient.  Deterministic: per-workgroup partials in ws (sfcvit_qk_norm_bwd_ws(M, H, hp)
+ * bytes), one fixed-order second-stage launch, no atomics, a grid that depends on the shape alone.  Never queued under
+ * sfcvit_reduce_defer.  Notes "qk_norm_bwd_kernel<64>". */
+int sfcvit_qk_norm_bwd(void *dqkv, const void *raw, const void *params, void *dparams, int dparams_is_bf16, void *colsum,
+                       int colsum_is_bf16, const float *vsum, void *ws, int M, int H, int hd, int hp, float eps, void *stream);
+int64_t sfcvit_qk_norm_bwd_ws(int M, int H, int hp);
+/* HOST: the launch geometry of both directions: out[0] = token rows per workgroup, out[1] = slot groups (of 8 head slots) per
+ * row, out[2] = workgroups = out[1] * ceil(M / out[0]), out[3] = 16-byte vectors per lane. */
+int sfcvit_qk_norm_plan(int M, int H, int hp, int32_t *out);
+
 /* ------------------------------------------------------------------------
  * Multi-head self-attention core (no mask; the masked form is the next section) on the packed projection
  *   replaces F.scaled_dot_product_attention as reached from nn.MultiheadAttention

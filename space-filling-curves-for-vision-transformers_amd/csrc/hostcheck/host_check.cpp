@@ -4,7 +4,7 @@
 //   host part), the error path of common.cpp, the mask validation and block map of attention_masked.cpp (check_mask_blocks),
 //   the index validation, inverted index, workspace and argument checks of attention_bias.cpp (check_attention_bias),
 //   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv),
-//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), tokenizer.cpp (check_tokenizer), drop_path.cpp (check_drop_path), layer_scale.cpp (check_layer_scale), model_ema.cpp (check_model_ema) and grad_accum.cpp (check_grad_accum), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
+//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), tokenizer.cpp (check_tokenizer), drop_path.cpp (check_drop_path), layer_scale.cpp (check_layer_scale), qk_norm.cpp (check_qk_norm), model_ema.cpp (check_model_ema) and grad_accum.cpp (check_grad_accum), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
 //   and post passes each GEMM / attention shape of the benchmarked models gets).
 // Every buffer is a heap block of EXACTLY the documented size, so that an off-by-one in a generator or in the descriptor
 // writer is a heap-buffer-overflow report instead of silent corruption.
@@ -26,6 +26,7 @@
 #include "../layer_scale.h"
 #include "../model_ema.h"
 #include "../pos_embed.h"
+#include "../qk_norm.h"
 #include "../rowwise.h"
 #include "../token_agg.h"
 #include "../token_mix.h"
@@ -1080,6 +1081,86 @@ static void check_layer_scale() {
 
 // adamw_ema_plan (model_ema.cpp): the grid at the sizes of the tests and the workloads, and every refusal, with heap buffers of
 // exactly n bf16 (param, grad) and n fp32 (master, m, v, ema).  The plan reads the two structs and no byte of the buffers.
+// qk_norm_fwd_plan / qk_norm_bwd_plan (qk_norm.cpp): the grid and the workspace per shape, and every refusal.
+static void check_qk_norm() {
+    // (the buffers of the largest shapes are terabytes: raw sits 2^46 bytes above qkv so that none of them overlaps)
+    void *qkv = ptr(8), *raw = reinterpret_cast<void *>(uintptr_t(1) << 46), *P = ptr(3), *dP = ptr(4), *cs = ptr(5), *ws = ptr(6);
+    const float *vs = static_cast<const float *>(ptr(7));
+    struct Q { int M, H, hd, hp; };
+    for (const Q &q : {Q{10, 4, 64, 64}, Q{10, 3, 64, 64}, Q{394, 12, 64, 64}, Q{10, 4, 48, 64}, Q{10, 4, 20, 64}, Q{7, 2, 128, 128},
+                       Q{7, 2, 96, 128}, Q{7, 1, 192, 192}, Q{7, 1, 256, 256}, Q{50176, 12, 64, 64}, Q{36864, 16, 64, 64}, Q{1, 1, 1, 64},
+                       Q{INT_MAX, 1, 64, 64}}) {
+        const QkNormPlan f = qk_norm_fwd_plan(qkv, raw, P, q.M, q.H, q.hd, q.hp, 1e-6f);
+        const QkNormPlan b = qk_norm_bwd_plan(qkv, raw, P, dP, cs, vs, ws, q.M, q.H, q.hd, q.hp, 0.f);
+        CHECK(f.err == SFCVIT_OK && b.err == SFCVIT_OK, "qk_norm %d %d %d %d refused: %s %s", q.M, q.H, q.hd, q.hp, f.msg, b.msg);
+        const int sgs = (2 * q.H + 7) / 8, chunks = int((int64_t(q.M) + QK_ROWS_PER_WG - 1) / QK_ROWS_PER_WG);
+        CHECK(f.vpl == q.hp / 64 && f.slot_groups == sgs && f.rows_per_wg == QK_ROWS_PER_WG && f.chunks == chunks && f.blocks == sgs * chunks,
+              "qk_norm fwd %d %d %d: vpl %d groups %d chunks %d blocks %d", q.M, q.H, q.hp, f.vpl, f.slot_groups, f.chunks, f.blocks);
+        CHECK(b.blocks == f.blocks && b.chunks == f.chunks && b.part_ld == 12 * q.hp && b.ws_bytes == int64_t(b.blocks) * 12 * q.hp * 4,
+              "qk_norm bwd %d %d %d: blocks %d ws %lld", q.M, q.H, q.hp, b.blocks, (long long)b.ws_bytes);
+        CHECK(int64_t(f.chunks) * f.rows_per_wg >= q.M && int64_t(f.chunks - 1) * f.rows_per_wg < q.M, "qk_norm chunks %d for %d rows", f.chunks, q.M);
+        CHECK(qk_norm_geometry(q.M, q.H, q.hp, "t").ws_bytes == b.ws_bytes, "qk_norm: the workspace query disagrees");
+        const int Da = q.H * q.hp;
+        CHECK(b.reduce_blocks == 2 * Da / 16 + 4 * q.hp / 16 + (Da + 1023) / 1024, "qk_norm bwd reduce blocks %d", b.reduce_blocks);
+        const QkNormPlan n = qk_norm_bwd_plan(qkv, raw, P, dP, nullptr, nullptr, ws, q.M, q.H, q.hd, q.hp, 1e-5f);
+        CHECK(n.err == SFCVIT_OK && n.reduce_blocks == 4 * q.hp / 16, "qk_norm bwd without colsum: %s, %d reduce blocks", n.msg, n.reduce_blocks);
+    }
+    const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+    auto fwd = [&](const char *what, const char *frag, void *q_, void *r_, void *p_, int M, int H, int hd, int hp, float eps) {
+        const QkNormPlan r = qk_norm_fwd_plan(q_, r_, p_, M, H, hd, hp, eps);
+        CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag), "qk_norm fwd %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
+    };
+    auto bwd = [&](const char *what, const char *frag, void *q_, void *r_, void *p_, void *d_, void *c_, const float *v_, void *w_, int M,
+                   int H, int hd, int hp, float eps) {
+        const QkNormPlan r = qk_norm_bwd_plan(q_, r_, p_, d_, c_, v_, w_, M, H, hd, hp, eps);
+        CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag), "qk_norm bwd %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
+    };
+    auto off8 = [](const void *p) { return reinterpret_cast<void *>(reinterpret_cast<uintptr_t>(p) + 8); };
+    fwd("null qkv", "null", nullptr, raw, P, 10, 4, 64, 64, 1e-6f);
+    fwd("null raw", "null", qkv, nullptr, P, 10, 4, 64, 64, 1e-6f);
+    fwd("null params", "null", qkv, raw, nullptr, 10, 4, 64, 64, 1e-6f);
+    fwd("qkv + 8", "aligned", off8(qkv), raw, P, 10, 4, 64, 64, 1e-6f);
+    fwd("raw + 8", "aligned", qkv, off8(raw), P, 10, 4, 64, 64, 1e-6f);
+    fwd("params + 8", "aligned", qkv, raw, off8(P), 10, 4, 64, 64, 1e-6f);
+    fwd("raw in qkv", "overlaps", qkv, reinterpret_cast<char *>(qkv) + 1024, P, 10, 4, 64, 64, 1e-6f);
+    bwd("null dqkv", "null", nullptr, raw, P, dP, cs, vs, ws, 10, 4, 64, 64, 1e-6f);
+    bwd("null raw", "null", qkv, nullptr, P, dP, cs, vs, ws, 10, 4, 64, 64, 1e-6f);
+    bwd("null params", "null", qkv, raw, nullptr, dP, cs, vs, ws, 10, 4, 64, 64, 1e-6f);
+    bwd("null dparams", "null", qkv, raw, P, nullptr, cs, vs, ws, 10, 4, 64, 64, 1e-6f);
+    bwd("null ws", "workspace", qkv, raw, P, dP, cs, vs, nullptr, 10, 4, 64, 64, 1e-6f);
+    bwd("vsum alone", "vsum without colsum", qkv, raw, P, dP, nullptr, vs, ws, 10, 4, 64, 64, 1e-6f);
+    bwd("dqkv + 8", "aligned", off8(qkv), raw, P, dP, cs, vs, ws, 10, 4, 64, 64, 1e-6f);
+    bwd("dparams + 8", "aligned", qkv, raw, P, off8(dP), cs, vs, ws, 10, 4, 64, 64, 1e-6f);
+    bwd("colsum + 8", "aligned", qkv, raw, P, dP, off8(cs), vs, ws, 10, 4, 64, 64, 1e-6f);
+    bwd("vsum + 8", "aligned", qkv, raw, P, dP, cs, static_cast<const float *>(off8(vs)), ws, 10, 4, 64, 64, 1e-6f);
+    bwd("ws + 8", "aligned", qkv, raw, P, dP, cs, vs, off8(ws), 10, 4, 64, 64, 1e-6f);
+    bwd("raw in dqkv", "overlaps", qkv, reinterpret_cast<char *>(qkv) + 1024, P, dP, cs, vs, ws, 10, 4, 64, 64, 1e-6f);
+    for (int hp : {0, 32, 96, 65, 512, -64}) {
+        fwd("hp", "not a kernel head dim", qkv, raw, P, 10, 4, 8, hp, 1e-6f);
+        bwd("hp", "not a kernel head dim", qkv, raw, P, dP, cs, vs, ws, 10, 4, 8, hp, 1e-6f);
+    }
+    for (int hd : {0, -1, 65, 1000}) {
+        fwd("hd", "hd=", qkv, raw, P, 10, 4, hd, 64, 1e-6f);
+        bwd("hd", "hd=", qkv, raw, P, dP, cs, vs, ws, 10, 4, hd, 64, 1e-6f);
+    }
+    fwd("hd > hp", "hd=129", qkv, raw, P, 10, 4, 129, 128, 1e-6f);
+    for (int z : {0, -5}) {
+        fwd("M", "M=", qkv, raw, P, z, 4, 64, 64, 1e-6f);
+        fwd("H", "H=", qkv, raw, P, 10, z, 64, 64, 1e-6f);
+        bwd("M", "M=", qkv, raw, P, dP, cs, vs, ws, z, 4, 64, 64, 1e-6f);
+        bwd("H", "H=", qkv, raw, P, dP, cs, vs, ws, 10, z, 64, 64, 1e-6f);
+    }
+    fwd("row width", "leaves int", qkv, raw, P, 10, 11184811, 64, 64, 1e-6f);               // 3 * H * 64 = 2^31 + 64
+    bwd("row width", "leaves int", qkv, raw, P, dP, cs, vs, ws, 10, INT_MAX, 64, 256, 1e-6f);
+    CHECK(qk_norm_fwd_plan(qkv, raw, P, 10, 11184810, 64, 64, 1e-6f).err == SFCVIT_OK, "qk_norm: the widest row that fits is refused");
+    fwd("grid", "leaves int", qkv, raw, P, INT_MAX, 256, 64, 64, 1e-6f);                   // 64 slot groups * 2^25 chunks
+    for (float eps : {-1e-6f, nan, inf, -inf}) {
+        fwd("eps", "eps=", qkv, raw, P, 10, 4, 64, 64, eps);
+        bwd("eps", "eps=", qkv, raw, P, dP, cs, vs, ws, 10, 4, 64, 64, eps);
+    }
+    CHECK(qk_norm_fwd_plan(qkv, raw, P, 10, 4, 64, 64, 0.f).err == SFCVIT_OK, "qk_norm: eps = 0 refused");
+}
+
 static void check_model_ema() {
     using namespace sfcvit;
     const RowwiseKnobs k0;
@@ -1888,6 +1969,7 @@ int main() {
     check_tokenizer();
     check_drop_path();
     check_layer_scale();
+    check_qk_norm();
     check_model_ema();
     check_grad_accum();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }

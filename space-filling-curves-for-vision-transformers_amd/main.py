@@ -142,6 +142,13 @@ def build_parser():
                     help="LayerScale (CaiT / DeiT-III): a learned per-channel scale on each residual branch of every encoder "
                          "layer, initialised to INIT (1e-4 when the value is omitted); needs --pre-norm; checkpoints then carry "
                          "encoder.layer_scale.<l> [2, embed dim]")
+    ap.add_argument("--qk-norm", type=float, nargs="?", const=1e-6, default=None, metavar="EPS",
+                    help="QK-norm (ViT-22B; timm's qk_norm): a LayerNorm over the head dim on the queries and keys of every head "
+                         "before q k^T, with epsilon EPS (1e-6 when the value is omitted): keeps the attention logits of deep and "
+                         "wide models bounded in bf16; checkpoints then carry encoder.qk_norm.<l> [4, head dim] (q weight, q "
+                         "bias, k weight, k bias).  Works with post- and pre-norm layers, --rel-pos-bias, --attn-window*, "
+                         "--drop-path, --layer-scale, --graph, --accum-steps, --model-ema, --pool, --pos-embed and "
+                         "--attention-report")
     ap.add_argument("--model-ema", type=float, nargs="?", const=0.9999, default=None, metavar="DECAY",
                     help="keep an exponential moving average of the weights (timm's --model-ema; DECAY defaults to 0.9999): "
                          "averaged in fp32 inside the AdamW kernel, evaluated after every epoch next to the raw weights (one "
@@ -195,6 +202,8 @@ def build_model(a, patch_embed, attn_mask=None):
         rel = dict(rel_pos_bias=a.rel_pos_bias, rel_pos_window=rel_pos_window(a), rel_pos_init_std=a.rel_pos_init_std)
     if getattr(a, "pre_norm", False) or getattr(a, "activation", "relu") != "relu" or getattr(a, "layer_scale", None) is not None:
         rel.update(norm_first=a.pre_norm, activation=a.activation, layer_scale=a.layer_scale)
+    if getattr(a, "qk_norm", None) is not None:
+        rel.update(qk_norm=True, qk_norm_eps=a.qk_norm)
     return VisionTransformer1D(patch_embed=patch_embed, depth=a.depth, n_heads=a.heads, mlp_dim=a.mlp_dim,
                                num_classes=a.classes,
                                token_aggregator=a.token_aggregator or False, token_mix=a.token_mix,
@@ -212,6 +221,8 @@ def parse_args(argv=None):
         ap.error(f"--activation {a.activation} needs --pre-norm: the post-norm layer has the ReLU MLP only")
     if a.layer_scale is not None and not a.pre_norm:
         ap.error("--layer-scale needs --pre-norm: the post-norm layer has no LayerScale")
+    if a.qk_norm is not None and not (a.qk_norm >= 0.0 and a.qk_norm < float("inf")):
+        ap.error(f"--qk-norm {a.qk_norm}: a finite epsilon >= 0 expected")
     if a.graph and a.accum_steps > 1:
         ap.error("--graph cannot be combined with --accum-steps > 1: a captured step does not accumulate (graphs serve "
                  "launch-bound small models, accumulation serves models too large for the batch)")

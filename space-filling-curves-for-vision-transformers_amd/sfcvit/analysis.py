@@ -94,12 +94,14 @@ def _vit_layers(model, images):
             yield qkv, lse, enc.n_head, scale
         yield _head_eval(model.mlp_head, x)
         return
-    for layer in enc.transformer.layers:
+    for l, layer in enumerate(enc.transformer.layers):
         a = layer.self_attn
+        # QK-norm: the probe returns the normalised q, k -- what the attention kernels consumed
+        qk = dict(qk_norm=enc.qk_norm[l], qk_norm_eps=enc.qk_norm_eps) if hasattr(enc, "qk_norm") else {}
         x, qkv, lse, scale = F.encoder_layer_probe(x, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
                                                    layer.norm1.weight, layer.norm1.bias, layer.linear1.weight,
                                                    layer.linear1.bias, layer.linear2.weight, layer.linear2.bias,
-                                                   layer.norm2.weight, layer.norm2.bias, enc.n_head, layer.norm1.eps)
+                                                   layer.norm2.weight, layer.norm2.bias, enc.n_head, layer.norm1.eps, **qk)
         yield qkv, lse, enc.n_head, scale
     yield _head_eval(model.mlp_head, x)
 

@@ -427,13 +427,15 @@ def _attn_fwd(qkv3, n_heads, p, seed, scale, attn_mask, rel_bias):
     return ops.attention_fwd(qkv3, n_heads, p, seed, scale=scale, any_length=True)
 
 
-def _attn_bwd(qkv3, o, lse, do3, n_heads, p, seed, scale, attn_mask, rel_bias, want_colsum, in_b, rel_table, want_table):
+def _attn_bwd(qkv3, o, lse, do3, n_heads, p, seed, scale, attn_mask, rel_bias, want_colsum, in_b, rel_table, want_table,
+              fp32_sums=False):
     """-> (dqkv, dbi or None, dtable or None).  want_colsum: the in_proj bias gradient (column sums of dqkv) comes out of the
     attention backward itself, into in_b's gradient slot when it has one.  want_table = False (a frozen table) costs nothing;
-    otherwise the table gradient comes back as _table_grad leaves it."""
+    otherwise the table gradient comes back as _table_grad leaves it.  fp32_sums (_qk_norm_bwd): the column sums come back as a
+    fresh fp32 tensor and no slot is touched."""
     col = None
     if want_colsum:
-        bi_slot = _slot(in_b)
+        bi_slot = None if fp32_sums else _slot(in_b)
         col = bi_slot if bi_slot is not None else True
     dtable = None
     if rel_bias is not None:
@@ -448,7 +450,89 @@ def _attn_bwd(qkv3, o, lse, do3, n_heads, p, seed, scale, attn_mask, rel_bias, w
         dqkv, *dbi = got if want_colsum else (got,)
     if not want_colsum:
         return dqkv, None, dtable
-    return dqkv, (dbi[0].to(_BF16) if col is True else dbi[0]), dtable
+    return dqkv, (dbi[0].to(_BF16) if col is True and not fp32_sums else dbi[0]), dtable
+
+
+def _qk_norm_fwd(qkv, qk, cfg):
+    """QK-norm of a layer, between the projection GEMM and the attention core: with qk [4, hd] (q_weight, q_bias, k_weight,
+    k_bias) the q and k thirds of qkv [M, 3 * H * hp] are normalised per head IN PLACE and the raw q | k, which the backward
+    needs, is returned; with qk = None nothing is launched.  This and _qk_norm_bwd are the only place that decides."""
+    if qk is None:
+        return None
+    return ops.qk_norm_fwd(qkv, qk, cfg.n_heads, qk.shape[1], cfg.qk_eps)
+
+
+def _qk_norm_bwd(attn_bwd, raw, qk, qk_param, in_b, cfg):
+    """The attention backward of a layer with the mirror of _qk_norm_fwd behind it -> (dqkv, dbi, dtable, dqk or None).
+    attn_bwd(fp32_sums): _attn_bwd with the layer's arguments.  Without QK-norm that is all.  With it, the attention backward's
+    column sums are the bias gradient for the v third alone: they come back as fp32, never into the slot, and ops.qk_norm_bwd
+    -- which rewrites dq | dk in place -- writes its own q | k sums and carries the v sums over, into in_b's slot when it has
+    one, so the slot holds one kernel's complete answer whatever reductions are queued.  dqk goes into qk_param's slot."""
+    if raw is None:
+        return attn_bwd(False) + (None,)
+    dqkv, sums, dtable = attn_bwd(True)
+    Da = raw.shape[1] // 2
+    bi_slot, qk_slot = _slot(in_b), _slot(qk_param)
+    dbi = bi_slot if bi_slot is not None else torch.empty(3 * Da, device=raw.device, dtype=_BF16)
+    _, dqk, _ = ops.qk_norm_bwd(dqkv, raw, qk, cfg.n_heads, qk.shape[1], cfg.qk_eps, colsum=dbi, grad_out=qk_slot, vsum=sums[2 * Da:])
+    return dqkv, dbi, dtable, (dqk if qk_slot is not None else dqk.to(_BF16))
+
+
+def _qk_norm_arg(qk_norm, qk_norm_eps, hd, what):
+    """A layer call's qk_norm = None or a [4, head_dim] tensor (rows q_weight, q_bias, k_weight, k_bias; the model's head dim,
+    not the padded one) -> (bf16 tensor or None, eps).  A bf16 parameter passes as it is, so its gradient can be written into its
+    slot.  Refused under tracing: the torch.library ops have no QK-norm form."""
+    if qk_norm is None:
+        return None, float(qk_norm_eps)
+    if _traced():
+        raise NotImplementedError(f"{what}: qk_norm is not supported under torch.compile / tracing (the torch.library ops have "
+                                  "no QK-norm form); run the model eagerly")
+    if not isinstance(qk_norm, torch.Tensor) or tuple(qk_norm.shape) != (4, hd):
+        got = tuple(qk_norm.shape) if isinstance(qk_norm, torch.Tensor) else type(qk_norm).__name__
+        raise ValueError(f"{what}: qk_norm must be a [4, head_dim] = [4, {hd}] tensor (q_weight, q_bias, k_weight, k_bias), got {got}")
+    eps = float(qk_norm_eps)
+    if not (eps >= 0.0 and math.isfinite(eps)):
+        raise ValueError(f"{what}: qk_norm_eps={qk_norm_eps} must be finite and >= 0")
+    return _c(_bf(qk_norm)), eps
+
+
+class _QkNorm(Function):
+    """qk_norm: the stand-alone differentiable form on a copy of the packed projection (the layers use the in-place kernels)."""
+
+    @staticmethod
+    def forward(ctx, qkv, params, n_heads, eps):
+        out = qkv.clone(memory_format=torch.contiguous_format)
+        raw = ops.qk_norm_fwd(out, params, n_heads, params.shape[1], eps)
+        ctx.save_for_backward(raw, params)
+        ctx.n_heads, ctx.eps = n_heads, eps
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        raw, params = ctx.saved_tensors
+        dqkv = dout.clone(memory_format=torch.contiguous_format)
+        _, dP, _ = ops.qk_norm_bwd(dqkv, raw, params, ctx.n_heads, params.shape[1], ctx.eps)
+        return dqkv, dP.to(_BF16), None, None
+
+
+def qk_norm(qkv, n_heads, params, eps=1e-6, head_dim=None):
+    """QK-norm (ViT-22B; timm's qk_norm=True) of a packed projection qkv [.., 3 * H * hp] (q | k | v thirds, head h at columns
+    h * hp .. of each third): a LayerNorm over the head dim on every query and key head row, v unchanged -> a new tensor.
+    params: [4, head_dim], rows q_weight, q_bias, k_weight, k_bias, shared by all heads.  head_dim: the model's head dim when hp
+    is a zero-padded kernel head dim (the padded columns stay out of the statistics and come out +0); default hp, which must
+    then be 64, 128, 192 or 256."""
+    qkv = _bf(qkv)
+    if n_heads <= 0 or qkv.shape[-1] % (3 * n_heads):
+        raise ValueError(f"qk_norm: packed width {qkv.shape[-1]} is not 3 * n_heads * head_dim for n_heads = {n_heads}")
+    hp = qkv.shape[-1] // (3 * n_heads)
+    hd = hp if head_dim is None else int(head_dim)
+    if hp not in ops.SUPPORTED_HEAD_DIMS or not 1 <= hd <= hp:
+        raise ValueError(f"qk_norm: head dim {hd} on a packed head width of {hp}: the width must be one of {ops.SUPPORTED_HEAD_DIMS} "
+                         "and 1 <= head_dim <= width")
+    params, eps = _qk_norm_arg(params, eps, hd, "qk_norm")
+    if params is None:
+        raise ValueError("qk_norm: params must be a [4, head_dim] tensor")
+    return _QkNorm.apply(qkv, params, n_heads, eps)
 
 
 def _rel_bias(rel_bias, mask, n_tokens, n_heads, what):
@@ -851,9 +935,9 @@ class _LayerCfg:
     """The non-tensor arguments of _EncoderLayer and _PreNormLayer, one object so that apply() has a fixed argument list.
     seeds: the four dropout seeds (attention, dropout1, the MLP's, dropout2); drop_path: None or (rate, (seed1, seed2))."""
 
-    def __init__(self, n_heads, eps, p, seeds, scale, act, attn_mask=None, drop_path=None, rel_index=None):
+    def __init__(self, n_heads, eps, p, seeds, scale, act, attn_mask=None, drop_path=None, rel_index=None, qk_eps=1e-6):
         self.n_heads, self.eps, self.p, self.seeds, self.scale, self.act = n_heads, eps, p, seeds, scale, act
-        self.attn_mask, self.drop_path, self.rel_index = attn_mask, drop_path, rel_index
+        self.attn_mask, self.drop_path, self.rel_index, self.qk_eps = attn_mask, drop_path, rel_index, qk_eps
 
 
 _PreNormCfg = _LayerCfg     # the name callers that build a _PreNormLayer by hand knew it by: same constructor
@@ -953,7 +1037,7 @@ class _EncoderLayer(Function):
     table parameter (None without cfg.rel_index), a _LayerCfg (act "relu")."""
 
     @staticmethod
-    def launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, rel_bias, cfg):
+    def launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, rel_bias, cfg, qk=None):
         """The forward's kernel launches, every intermediate returned (forward saves them; encoder_layer_probe reads the
         attention inputs out of the same sequence, so what it carries on is what forward computes)."""
         B, N, D = x.shape
@@ -962,27 +1046,31 @@ class _EncoderLayer(Function):
         sa, s1_, sf, s2_ = cfg.seeds
         x2 = _c(x).view(B * N, D)
         qkv = ops.gemm(x2, in_w, bias=in_b)
+        raw = _qk_norm_fwd(qkv, qk, cfg)
         o, lse = _attn_fwd(qkv.view(B, N, 3 * Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask, rel_bias)
         _, s1, x1, mean1, rstd1 = _site_fwd(o.view(B * N, Da), out_w, out_b, x2, None, n1_w, n1_b, B, cfg.eps, p, s1_, cfg.drop_path, 0)
         hbits, _, h = _mlp_fwd(x1, w1, b1, cfg.act, p, sf)
         _, s2, y, mean2, rstd2 = _site_fwd(h, w2, b2, x1, None, n2_w, n2_b, B, cfg.eps, p, s2_, cfg.drop_path, 1)
-        return dict(x2=x2, qkv=qkv, o=o, lse=lse, s1=s1, mean1=mean1, rstd1=rstd1, x1=x1, hbits=hbits, h=h, s2=s2, y=y, mean2=mean2,
+        return dict(x2=x2, qkv=qkv, raw=raw, o=o, lse=lse, s1=s1, mean1=mean1, rstd1=rstd1, x1=x1, hbits=hbits, h=h, s2=s2, y=y, mean2=mean2,
                     rstd2=rstd2)
 
     @staticmethod
-    def forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, rel_table, cfg):
+    def forward(ctx, x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, rel_table, cfg, qk=None):
         rel_bias = _fp32_bias(rel_table, cfg.rel_index)
-        t = _EncoderLayer.launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, rel_bias, cfg)
+        t = _EncoderLayer.launches(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, rel_bias, cfg, qk)
         ctx.cfg, ctx.shape, ctx.rel_bias, ctx.rel_table, ctx.hbits = cfg, tuple(x.shape), rel_bias, rel_table, t["hbits"]
         ctx.small = (in_b, out_b, n1_b, b1, b2, n2_b)      # parameters only needed for their gradient slots
+        ctx.qk_param = qk                                   # QK-norm: for its gradient slot; raw q | k and qk are saved last
+        opt = [t["raw"], qk] if qk is not None else []
         ctx.save_for_backward(t["x2"], t["qkv"], t["o"], t["lse"], t["s1"], t["mean1"], t["rstd1"], t["x1"], t["h"], t["s2"],
-                              t["mean2"], t["rstd2"], in_w, out_w, n1_w, w1, w2, n2_w)
+                              t["mean2"], t["rstd2"], in_w, out_w, n1_w, w1, w2, n2_w, *opt)
         return t["y"].view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
         (x2, qkv, o, lse, s1, mean1, rstd1, x1, h, s2, mean2, rstd2,
-         in_w, out_w, n1_w, w1, w2, n2_w) = ctx.saved_tensors
+         in_w, out_w, n1_w, w1, w2, n2_w, *opt) = ctx.saved_tensors
+        raw, qk = opt if opt else (None, None)
         cfg = ctx.cfg
         B, N, D = ctx.shape
         p, drop_path = cfg.p, cfg.drop_path
@@ -1000,13 +1088,14 @@ class _EncoderLayer(Function):
         dwo = wg(da, o.view(B * N, Da), out_w)
         do = ops.gemm_dx(da, out_w)
         want = ctx.rel_bias is not None and ctx.needs_input_grad[13]        # a frozen table costs nothing
-        dqkv, dbi, dtable = _attn_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask,
-                                      ctx.rel_bias, True, in_b, ctx.rel_table, want)
+        dqkv, dbi, dtable, dqk = _qk_norm_bwd(
+            lambda fp32: _attn_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask,
+                                   ctx.rel_bias, True, in_b, ctx.rel_table, want, fp32), raw, qk, getattr(ctx, "qk_param", None), in_b, cfg)
         dqkv = dqkv.view(B * N, 3 * Da)
         dwi = wg(dqkv, x2, in_w)
         dx = ops.gemm_dx(dqkv, in_w, residual=ds1)
         join(dw2, dw1, dwo, dwi)
-        return dx.view(B, N, D), dwi, dbi, dwo, dbo, dg1, dbt1, dw1, db1, dw2, db2, dg2, dbt2, dtable, None
+        return dx.view(B, N, D), dwi, dbi, dwo, dbo, dg1, dbt1, dw1, db1, dw2, db2, dg2, dbt2, dtable, None, dqk
 
 
 def _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads):
@@ -1026,14 +1115,16 @@ def _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2,
     return args, scale
 
 
-def encoder_layer_probe(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5):
+def encoder_layer_probe(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5, qk_norm=None,
+                        qk_norm_eps=1e-6):
     """The eval-mode (dropout 0) encoder layer with its attention inputs exposed: (y, qkv [B, N, 3 * H * kernel head dim],
-    lse [B, H, N], softmax scale or None).  Same launches as encoder_layer(dropout_p=0): y has its bits.  For
-    sfcvit.analysis; no autograd graph is built."""
+    lse [B, H, N], softmax scale or None).  Same launches as encoder_layer(dropout_p=0): y has its bits.  With qk_norm the
+    qkv returned is the NORMALISED one: what the attention kernels consumed.  For sfcvit.analysis; no autograd graph is built."""
     with torch.no_grad():
         args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
         B, N, D = args[0].shape
-        t = _EncoderLayer.launches(*args, None, _LayerCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, "relu"))
+        qk, qk_eps = _qk_norm_arg(qk_norm, qk_norm_eps, D // n_heads, "encoder_layer_probe")
+        t = _EncoderLayer.launches(*args, None, _LayerCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, "relu", qk_eps=qk_eps), qk)
         return t["y"].view(B, N, D), t["qkv"].view(B, N, -1), t["lse"], scale
 
 
@@ -1054,17 +1145,17 @@ def _layer_options(what, n_tokens, n_heads, attn_mask, rel_bias, no_traced_form=
     return _attention_mask(attn_mask, n_tokens, what), rel_bias
 
 
-def _layer_cfg(n_heads, eps, dropout_p, scale, act, attn_mask, drop_path, rel_bias):
+def _layer_cfg(n_heads, eps, dropout_p, scale, act, attn_mask, drop_path, rel_bias, qk_eps=1e-6):
     """An eager layer call's (_LayerCfg, bias table or None).  The seeds are drawn here, on the host, in this order: four dropout
-    seeds when dropout_p > 0, then two path seeds when drop_path > 0."""
+    seeds when dropout_p > 0, then two path seeds when drop_path > 0.  (QK-norm draws nothing.)"""
     seeds = tuple(ops.next_seed() for _ in range(4)) if dropout_p > 0 else (0, 0, 0, 0)
     path = (drop_path, (ops.next_seed(), ops.next_seed())) if drop_path > 0 else None
     table, index = rel_bias if rel_bias is not None else (None, None)
-    return _LayerCfg(n_heads, eps, float(dropout_p), seeds, scale, act, attn_mask, path, index), table
+    return _LayerCfg(n_heads, eps, float(dropout_p), seeds, scale, act, attn_mask, path, index, qk_eps), table
 
 
 def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5,
-                  dropout_p=0.0, attn_mask=None, drop_path=0.0, rel_bias=None):
+                  dropout_p=0.0, attn_mask=None, drop_path=0.0, rel_bias=None, qk_norm=None, qk_norm_eps=1e-6):
     """dropout_p > 0 = training-mode nn.TransformerEncoderLayer (fresh masks every call).
     attn_mask = nn.TransformerEncoderLayer's src_mask: None, or an additive [N, N] mask as in `attention` (build an
     ops.AttentionMask once when the layer runs more than once).  With None the launches and the bits are those of a call
@@ -1081,17 +1172,23 @@ def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w,
     per head on the attention scores, softmax(q k^T / sqrt(hd) + table[h, index[i, j]]), with dropout as without it; the
     attention core alone changes, to the bias kernels, and the table receives its gradient (in its dtype, in its gradient
     slot when it has one).  Not with attn_mask (a window is part of the index: sfcvit.relpos), not under tracing; None
-    runs the call as it is without the argument."""
+    runs the call as it is without the argument.
+    qk_norm = a [4, head_dim] tensor, rows q_weight, q_bias, k_weight, k_bias (timm's attn.q_norm / attn.k_norm, shared by all
+    heads; head_dim = embed_dim / n_heads, not the padded one): QK-norm, a LayerNorm(head_dim, eps=qk_norm_eps) on the queries
+    and keys of every head before q k^T, one in-place kernel between the projection GEMM and the attention core and its mirror
+    in the backward; the softmax scale, mask, bias and dropout are untouched and the tensor receives its gradient (in its slot
+    when it has one).  Combines with every other option; not under tracing.  None runs the call as it is without the argument."""
     drop_path = _path_rate("encoder_layer", drop_path)
     args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
+    qk, qk_eps = _qk_norm_arg(qk_norm, qk_norm_eps, args[0].shape[-1] // n_heads, "encoder_layer")
     attn_mask, rel_bias = _layer_options("encoder_layer", args[0].shape[1], n_heads, attn_mask, rel_bias)
     if drop_path > 0 and _traced():
         raise NotImplementedError("encoder_layer: drop_path > 0 has no traced form (torch.compile); run the layer eagerly")
     if _traced():
         from . import library      # (dropout seeds are drawn inside the op: nothing data-dependent in the traced graph)
         return library.encoder_layer(args, n_heads, eps, float(dropout_p), scale)
-    cfg, table = _layer_cfg(n_heads, eps, dropout_p, scale, "relu", attn_mask, drop_path, rel_bias)
-    return _EncoderLayer.apply(*args, table, cfg)
+    cfg, table = _layer_cfg(n_heads, eps, dropout_p, scale, "relu", attn_mask, drop_path, rel_bias, qk_eps)
+    return _EncoderLayer.apply(*args, table, cfg) if qk is None else _EncoderLayer.apply(*args, table, cfg, qk)
 
 
 # ----------------------------------------------------------------------------
@@ -1106,7 +1203,7 @@ class _PreNormLayer(Function):
     None, a _LayerCfg."""
 
     @staticmethod
-    def launches(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_bias, cfg):
+    def launches(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_bias, cfg, qk=None):
         """The forward's kernel launches, every intermediate returned (forward saves them; pre_norm_layer_probe reads the attention
         inputs out of the same sequence)."""
         B, N, D = s.shape
@@ -1115,24 +1212,28 @@ class _PreNormLayer(Function):
         sa, s1_, sf, s2_ = cfg.seeds
         s0, n0 = _c(s).view(B * N, D), _c(n).view(B * N, D)
         qkv = ops.gemm(n0, in_w, bias=in_b)
+        raw = _qk_norm_fwd(qkv, qk, cfg)
         o, lse = _attn_fwd(qkv.view(B, N, 3 * Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask, rel_bias)
         lam1, lam2 = (lam[0], lam[1]) if lam is not None else (None, None)
         a, s1, n1, mean1, rstd1 = _site_fwd(o.view(B * N, Da), out_w, out_b, s0, lam1, n2_w, n2_b, B, cfg.eps, p, s1_, cfg.drop_path, 0)
         hbits, u, h = _mlp_fwd(n1, w1, b1, cfg.act, p, sf)
         f, s2, n2, mean2, rstd2 = _site_fwd(h, w2, b2, s1, lam2, nf_w, nf_b, B, cfg.eps, p, s2_, cfg.drop_path, 1)
-        return dict(n0=n0, qkv=qkv, o=o, lse=lse, a=a, s1=s1, n1=n1, mean1=mean1, rstd1=rstd1, hbits=hbits, u=u, h=h, f=f, s2=s2,
+        return dict(n0=n0, qkv=qkv, raw=raw, o=o, lse=lse, a=a, s1=s1, n1=n1, mean1=mean1, rstd1=rstd1, hbits=hbits, u=u, h=h, f=f, s2=s2,
                     n2=n2, mean2=mean2, rstd2=rstd2)
 
     @staticmethod
-    def forward(ctx, s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_table, cfg):
+    def forward(ctx, s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_table, cfg, qk=None):
         B, N, D = s.shape
         rel_bias = _fp32_bias(rel_table, cfg.rel_index)
-        t = _PreNormLayer.launches(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_bias, cfg)
+        t = _PreNormLayer.launches(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, nf_w, nf_b, lam, rel_bias, cfg, qk)
+        ctx.qk_param = qk                                       # QK-norm: for its gradient slot; raw q | k and qk are saved last
         ctx.cfg, ctx.shape, ctx.rel_bias, ctx.rel_table, ctx.hbits = cfg, (B, N, D), rel_bias, rel_table, t["hbits"]
         ctx.lam_param = lam                                     # for its gradient slot: both rows are written in one backward
         ctx.small = (in_b, out_b, n2_b, b1, b2, nf_b)          # parameters only needed for their gradient slots
         ctx.has = tuple(t[k] is not None for k in ("a", "u", "f"))
+        ctx.has_lam = lam is not None
         opt = [t[k] for k in ("a", "u", "f") if t[k] is not None] + ([lam] if lam is not None else [])
+        opt += [t["raw"], qk] if qk is not None else []
         ctx.save_for_backward(t["n0"], t["qkv"], t["o"], t["lse"], t["s1"], t["n1"], t["mean1"], t["rstd1"], t["h"], t["s2"],
                               t["mean2"], t["rstd2"], in_w, out_w, n2_w, w1, w2, nf_w, *opt)
         ctx.set_materialize_grads(False)
@@ -1143,7 +1244,8 @@ class _PreNormLayer(Function):
         (n0, qkv, o, lse, s1, n1, mean1, rstd1, h, s2, mean2, rstd2, in_w, out_w, n2_w, w1, w2, nf_w, *opt) = ctx.saved_tensors
         opt = list(opt)
         a, u, f = (opt.pop(0) if has else None for has in ctx.has)
-        lam = opt.pop(0) if opt else None
+        lam = opt.pop(0) if ctx.has_lam else None
+        raw, qk = opt if opt else (None, None)
         cfg = ctx.cfg
         B, N, D = ctx.shape
         p, drop_path = cfg.p, cfg.drop_path
@@ -1165,8 +1267,9 @@ class _PreNormLayer(Function):
         dwo = wg(da, o.view(B * N, Da), out_w)
         do = ops.gemm_dx(da, out_w)
         want = ctx.rel_bias is not None and ctx.needs_input_grad[15]        # a frozen table costs nothing
-        dqkv, dbi, dtable = _attn_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask,
-                                      ctx.rel_bias, True, in_b, ctx.rel_table, want)
+        dqkv, dbi, dtable, dqk = _qk_norm_bwd(
+            lambda fp32: _attn_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask,
+                                   ctx.rel_bias, True, in_b, ctx.rel_table, want, fp32), raw, qk, getattr(ctx, "qk_param", None), in_b, cfg)
         dqkv = dqkv.view(B * N, 3 * Da)
         dwi = wg(dqkv, n0, in_w)
         dn_in = ops.gemm_dx(dqkv, in_w)
@@ -1179,7 +1282,7 @@ class _PreNormLayer(Function):
             if lam_slot is not None:                            # one row sits in the slot, its reduction perhaps still queued
                 ops.flush_deferred(end=False)
             dl = torch.stack([dlam1.to(_BF16), dlam2.to(_BF16)])
-        return (ds1.view(B, N, D), dn_in.view(B, N, D), dwi, dbi, dwo, dbo, dg2, dbt2, dw1, db1, dw2, db2, dgf, dbtf, dl, dtable, None)
+        return (ds1.view(B, N, D), dn_in.view(B, N, D), dwi, dbi, dwo, dbo, dg2, dbt2, dw1, db1, dw2, db2, dgf, dbtf, dl, dtable, None, dqk)
 
 
 def _layer_scale_arg(layer_scale, D, what):
@@ -1212,35 +1315,40 @@ def _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, n
 
 
 def pre_norm_layer(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads, eps=1e-5, dropout_p=0.0,
-                   attn_mask=None, drop_path=0.0, rel_bias=None, activation="relu", layer_scale=None):
+                   attn_mask=None, drop_path=0.0, rel_bias=None, activation="relu", layer_scale=None, qk_norm=None, qk_norm_eps=1e-6):
     """One pre-norm encoder layer (nn.TransformerEncoderLayer(norm_first=True)) on the HIP path, as "residual site + the
     LayerNorm after it": takes the residual stream s [B, N, D] and n = norm1(s), returns (s', n') with n' = LayerNorm(s') by
     the FOLLOWING norm (next_w, next_b): the next layer's norm1, or the encoder's final norm after the last layer.  The first
     layer's n comes from layer_norm(s, norm1).  n2_w / n2_b are the layer's own norm2.
     activation: "relu" or "gelu" (erf).  layer_scale: None, or (lam1, lam2) / a [2, D] tensor: the per-channel scales of the
     attention and MLP branches (CaiT / DeiT-III), s1 = s + c1[b] lam1 * a.  dropout_p, attn_mask, drop_path, rel_bias and the
-    zero padding of head dims the kernels do not have: as in encoder_layer, with its masks, flags and seeds.  Not under tracing."""
+    zero padding of head dims the kernels do not have: as in encoder_layer, with its masks, flags and seeds; qk_norm, qk_norm_eps
+    (QK-norm) as there too.  Not under tracing."""
     what = "pre_norm_layer"
     drop_path = _path_rate(what, drop_path)
     args, scale, n, lam = _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads,
                                          activation, layer_scale, what)
+    qk, qk_eps = _qk_norm_arg(qk_norm, qk_norm_eps, args[0].shape[-1] // n_heads, what)
     attn_mask, rel_bias = _layer_options(what, args[0].shape[1], n_heads, attn_mask, rel_bias,
                                          no_traced_form="the pre-norm layer has no traced form (torch.compile); run the model eagerly")
-    cfg, table = _layer_cfg(n_heads, eps, dropout_p, scale, activation, attn_mask, drop_path, rel_bias)
-    return _PreNormLayer.apply(args[0], n, *args[1:], lam, table, cfg)
+    cfg, table = _layer_cfg(n_heads, eps, dropout_p, scale, activation, attn_mask, drop_path, rel_bias, qk_eps)
+    if qk is None:
+        return _PreNormLayer.apply(args[0], n, *args[1:], lam, table, cfg)
+    return _PreNormLayer.apply(args[0], n, *args[1:], lam, table, cfg, qk)
 
 
 def pre_norm_layer_probe(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads, eps=1e-5,
-                         activation="relu", layer_scale=None):
+                         activation="relu", layer_scale=None, qk_norm=None, qk_norm_eps=1e-6):
     """The eval-mode (dropout 0) pre-norm layer with its attention inputs exposed: (s', n', qkv [B, N, 3 * H * kernel head dim],
-    lse [B, H, N], softmax scale or None).  Same launches as pre_norm_layer(dropout_p=0): s' and n' have its bits.  For
-    sfcvit.analysis; no autograd graph is built."""
+    lse [B, H, N], softmax scale or None).  Same launches as pre_norm_layer(dropout_p=0): s' and n' have its bits.  With qk_norm
+    the qkv returned is the NORMALISED one: what the attention kernels consumed.  For sfcvit.analysis; no autograd graph is built."""
     with torch.no_grad():
         args, scale, n, lam = _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads,
                                              activation, layer_scale, "pre_norm_layer_probe")
         B, N, D = args[0].shape
-        cfg = _LayerCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, activation)
-        t = _PreNormLayer.launches(args[0], n, *args[1:], lam, None, cfg)
+        qk, qk_eps = _qk_norm_arg(qk_norm, qk_norm_eps, D // n_heads, "pre_norm_layer_probe")
+        cfg = _LayerCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, activation, qk_eps=qk_eps)
+        t = _PreNormLayer.launches(args[0], n, *args[1:], lam, None, cfg, qk)
         return t["s2"].view(B, N, D), t["n2"].view(B, N, D), t["qkv"].view(B, N, -1), t["lse"], scale
 
 

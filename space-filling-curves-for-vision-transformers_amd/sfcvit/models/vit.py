@@ -133,7 +133,8 @@ class TransformerSeqEncoder(nn.Module):
     vit.py:152-174).  A mask is not a parameter or a buffer: it never enters state_dict."""
 
     def __init__(self, input_dim, max_len, n_head, hidden_dim, method, dropout_p=0.1, n_layers=1, cls_token=False,
-                 drop_path_rate=0.0, rel_pos_bias=None, norm_first=False, activation="relu", layer_scale=None):
+                 drop_path_rate=0.0, rel_pos_bias=None, norm_first=False, activation="relu", layer_scale=None, qk_norm=False,
+                 qk_norm_eps=1e-6):
         """norm_first=True: pre-norm layers, x + f(LN(x)), and a final LayerNorm after the last one -- torch's
         nn.TransformerEncoderLayer(norm_first=True, activation=...) under nn.TransformerEncoder(norm=nn.LayerNorm(D)), so the
         state_dict keys are torch's own (`transformer.layers.<l>.*`, `transformer.norm.weight|bias`); F.pre_norm_layer runs them.
@@ -141,6 +142,11 @@ class TransformerSeqEncoder(nn.Module):
         (e.g. 1e-4) of LayerScale (CaiT / DeiT-III): `layer_scale`, a ParameterList of one [2, input_dim] tensor per layer, row 0
         scaling the attention branch and row 1 the MLP branch per channel; needs norm_first.  The final norm and LayerScale are
         constructed last and draw no random number; with norm_first=False the encoder is what it is without the three keywords.
+        qk_norm=True: QK-norm (ViT-22B; timm's qk_norm=True), a LayerNorm(head_dim, eps=qk_norm_eps) on the queries and keys of
+        every head before q k^T, in post- and pre-norm layers alike: `qk_norm`, a ParameterList of one [4, head_dim] tensor per
+        layer with rows q_weight, q_bias, k_weight, k_bias = 1, 0, 1, 0 (timm's blocks.<l>.attn.q_norm.weight | .bias and
+        k_norm.weight | .bias), shared by the heads of a layer.  Constructed after everything else of the encoder, no draw;
+        False: the encoder as it is without the keyword.
         rel_pos_bias: None, or an ops.AttentionBiasIndex (or (index, init_std)): every layer adds a learned relative
         position bias per head to its attention scores, one table `rel_pos_bias.<l>` [n_head, T] per layer in a ParameterList
         (attach_rel_pos_bias; the models call it after everything else is constructed).
@@ -158,6 +164,15 @@ class TransformerSeqEncoder(nn.Module):
         self.dropout_p = dropout_p
         self.drop_path_rates = drop_path_rates(drop_path_rate, n_layers)
         self.norm_first, self.activation = bool(norm_first), activation
+        self.qk_norm_eps = float(qk_norm_eps)
+        if qk_norm:
+            if input_dim % n_head:
+                raise ValueError(f"qk_norm=True: input_dim={input_dim} is not a multiple of n_head={n_head}")
+            if not (self.qk_norm_eps >= 0.0 and math.isfinite(self.qk_norm_eps)):
+                raise ValueError(f"qk_norm_eps={qk_norm_eps} must be finite and >= 0")
+            if ops.padded_head_dim(input_dim // n_head) is None:
+                raise ValueError(f"qk_norm=True: head dim {input_dim // n_head} exceeds the largest supported one, "
+                                 f"{max(ops.SUPPORTED_HEAD_DIMS)}")
         if activation not in ("relu", "gelu"):
             raise ValueError(f"activation={activation!r} must be 'relu' or 'gelu'")
         if not norm_first and activation != "relu":
@@ -188,6 +203,9 @@ class TransformerSeqEncoder(nn.Module):
             if layer_scale is not None:
                 self.layer_scale = nn.ParameterList(nn.Parameter(torch.full((2, input_dim), float(layer_scale)))
                                                     for _ in range(n_layers))
+        if qk_norm:
+            row = torch.tensor([1.0, 0.0, 1.0, 0.0]).unsqueeze(1)
+            self.qk_norm = nn.ParameterList(nn.Parameter(row.expand(4, input_dim // n_head).clone()) for _ in range(n_layers))
 
     def attach_rel_pos_bias(self, bias_index, init_std=0.0):
         """One table [n_head, T] per layer, zeros or randn * init_std (init_std = 0 draws nothing: the model then computes
@@ -215,7 +233,7 @@ class TransformerSeqEncoder(nn.Module):
     def forward(self, x, mask=None):
         p = self.dropout_p if self.training else 0.0
         mask = self._mask(mask)
-        tables = getattr(self, "rel_pos_bias", None)
+        tables, qks = getattr(self, "rel_pos_bias", None), getattr(self, "qk_norm", None)
         if tables is not None and mask is not None:
             raise ValueError("TransformerSeqEncoder: rel_pos_bias and a mask cannot be combined; the window belongs in the "
                              "bias index (rel_pos_window)")
@@ -230,6 +248,8 @@ class TransformerSeqEncoder(nn.Module):
             path = {"drop_path": rate} if self.training and rate > 0 else {}      # else: the call as it is without the feature
             if tables is not None:
                 path["rel_bias"] = (tables[l], self.rel_pos_index)
+            if qks is not None:
+                path["qk_norm"], path["qk_norm_eps"] = qks[l], self.qk_norm_eps
             x = F.encoder_layer(x, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
                                 layer.norm1.weight, layer.norm1.bias, layer.linear1.weight, layer.linear1.bias,
                                 layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias,
@@ -253,6 +273,8 @@ class TransformerSeqEncoder(nn.Module):
             w = (a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, layer.norm2.weight, layer.norm2.bias,
                  layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, nxt.weight, nxt.bias)
             kw = dict(activation=self.activation, layer_scale=scales[l] if scales is not None else None)
+            if hasattr(self, "qk_norm"):
+                kw["qk_norm"], kw["qk_norm_eps"] = self.qk_norm[l], self.qk_norm_eps
             if probe:
                 out = F.pre_norm_layer_probe(s, n, *w, self.n_head, layer.norm2.eps, **kw)
             else:
@@ -454,7 +476,7 @@ class VisionTransformer(nn.Module):
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, attn_mask=None,
                  pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0, rel_pos_bias=None, rel_pos_window=None,
-                 rel_pos_init_std=0.0, norm_first=False, activation="relu", layer_scale=None):
+                 rel_pos_init_std=0.0, norm_first=False, activation="relu", layer_scale=None, qk_norm=False, qk_norm_eps=1e-6):
         """rel_pos_bias: None (the model as it is without the keyword), "curve" or "image": every encoder layer adds a learned
         relative position bias per head to its attention scores, softmax(q k^T / sqrt(hd) + b_h[offset(i, j)]), the offset taken
         along the token sequence (j - i) or in the image (the displacement of the token centres in cells of sqrt(pixels per
@@ -466,6 +488,8 @@ class VisionTransformer(nn.Module):
         drop_path_rate: stochastic depth over the encoder layers (TransformerSeqEncoder; `encoder.drop_path_rates`).
         norm_first, activation, layer_scale: pre-norm encoder layers with a final norm, a GELU MLP and LayerScale
         (TransformerSeqEncoder: the DeiT / timm block; `encoder.transformer.norm`, `encoder.layer_scale.<l>` [2, D]).
+        qk_norm, qk_norm_eps: QK-norm, a LayerNorm over the head dim on the queries and keys of every head
+        (TransformerSeqEncoder; `encoder.qk_norm.<l>` [4, head_dim]).
         attn_mask: None, or a mask for every encoder layer (ops.as_attention_mask's forms; sfcvit.masks builds windows).
         Held outside state_dict: checkpoint keys are the reference's with or without it.
         pos_embed: None / False (the reference as shipped), "learned" (vit.py:360-361: a Parameter [1, N, D] = randn *
@@ -486,7 +510,7 @@ class VisionTransformer(nn.Module):
                                              method=self.patch_embed, n_head=n_heads, hidden_dim=mlp_dim,
                                              n_layers=depth, dropout_p=dropout_p, cls_token=pool == "cls",
                                              drop_path_rate=drop_path_rate, norm_first=norm_first, activation=activation,
-                                             layer_scale=layer_scale)
+                                             layer_scale=layer_scale, qk_norm=qk_norm, qk_norm_eps=qk_norm_eps)
         self.mlp_head = _make_head(pool, embed_dim, self.patch_embed.n_patches, num_classes, head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)
@@ -511,8 +535,8 @@ class VisionTransformer1D(nn.Module):
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False, attn_mask=None,
                  pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0, rel_pos_bias=None, rel_pos_window=None,
-                 rel_pos_init_std=0.0, norm_first=False, activation="relu", layer_scale=None):
-        """attn_mask, pos_embed, pos_embed_std, pool, drop_path_rate, rel_pos_bias, rel_pos_window, rel_pos_init_std, norm_first, activation, layer_scale: as in VisionTransformer (the table is added directly after the tokenizer
+                 rel_pos_init_std=0.0, norm_first=False, activation="relu", layer_scale=None, qk_norm=False, qk_norm_eps=1e-6):
+        """attn_mask, pos_embed, pos_embed_std, pool, drop_path_rate, rel_pos_bias, rel_pos_window, rel_pos_init_std, norm_first, activation, layer_scale, qk_norm, qk_norm_eps: as in VisionTransformer (the table is added directly after the tokenizer
         and, if present, `ta`: before `mlp_mixer`; with pool="cls" the token joins after `mlp_mixer`, whose weights stay sized
         for the N patch tokens)."""
         super().__init__()
@@ -526,7 +550,7 @@ class VisionTransformer1D(nn.Module):
                                              n_head=n_heads, hidden_dim=mlp_dim, n_layers=depth,
                                              method=self.patch_embed, dropout_p=dropout_p, cls_token=pool == "cls",
                                              drop_path_rate=drop_path_rate, norm_first=norm_first, activation=activation,
-                                             layer_scale=layer_scale)
+                                             layer_scale=layer_scale, qk_norm=qk_norm, qk_norm_eps=qk_norm_eps)
         self.mlp_head = _make_head(pool, embed_dim, self.patch_embed.n_patches, num_classes, head_dropout_p)
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)

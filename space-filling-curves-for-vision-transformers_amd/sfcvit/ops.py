@@ -526,6 +526,78 @@ def layernorm_bwd_scale(dy, x, mean, rstd, gamma, branch, lam, rows_per_image, p
 
 
 # ----------------------------------------------------------------------------
+# QK-norm: LayerNorm over the head dim on the q and k thirds of a packed projection, in place
+# ----------------------------------------------------------------------------
+def qk_norm_plan(M, n_heads, hp):
+    """The launch geometry of both QK-norm kernels for M rows: dict(rows_per_wg, slot_groups, blocks, vpl).  No GPU call."""
+    out = (ctypes.c_int32 * 4)()
+    check(lib.sfcvit_qk_norm_plan(M, n_heads, hp, out), "sfcvit_qk_norm_plan")
+    return dict(rows_per_wg=out[0], slot_groups=out[1], blocks=out[2], vpl=out[3])
+
+
+def _qk_norm_args(what, qkv, params, n_heads, head_dim):
+    """-> (M, hp) of a packed buffer [.., 3 * H * hp] and its parameters [4, head_dim], checked."""
+    if qkv.dim() not in (2, 3):
+        raise ValueError(f"{what}: [M, 3 * H * hp] or [B, N, 3 * H * hp] expected, got shape {tuple(qkv.shape)}")
+    _need(qkv, _BF16, f"{what} qkv")
+    _need(params, _BF16, f"{what} params", 2)
+    D3 = qkv.shape[-1]
+    if n_heads <= 0 or D3 % (3 * n_heads):
+        raise ValueError(f"{what}: packed width {D3} is not 3 * n_heads * head_dim for n_heads = {n_heads}")
+    hp = D3 // (3 * n_heads)
+    if tuple(params.shape) != (4, head_dim):
+        raise ValueError(f"{what}: params must be [4, head_dim] = [4, {head_dim}] (q_weight, q_bias, k_weight, k_bias), got "
+                         f"{tuple(params.shape)}")
+    return qkv.numel() // D3, hp
+
+
+def qk_norm_fwd(qkv, params, n_heads, head_dim, eps=1e-6):
+    """LayerNorm over the head_dim real columns of every query and key head row of qkv [.., 3 * H * hp] bf16, IN PLACE (columns
+    head_dim .. hp - 1, the zero padding of a head dim the kernels do not have, become +0; v is untouched) -> raw [M, 2 * H * hp]:
+    the bits of q | k as they were, which qk_norm_bwd needs.  params: bf16 [4, head_dim], rows q_weight, q_bias, k_weight,
+    k_bias, shared by all heads."""
+    M, hp = _qk_norm_args("qk_norm_fwd", qkv, params, n_heads, head_dim)
+    raw = torch.empty((M, 2 * n_heads * hp), device=qkv.device, dtype=_BF16)
+    check(lib.sfcvit_qk_norm_fwd(_p(qkv), _p(raw), _p(params), M, n_heads, head_dim, hp, eps, _stream()), "sfcvit_qk_norm_fwd")
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append(last_rowwise_kernel())
+    return raw
+
+
+def qk_norm_bwd(dqkv, raw, params, n_heads, head_dim, eps=1e-6, colsum=None, grad_out=None, vsum=None):
+    """The backward of qk_norm_fwd, IN PLACE on the q and k thirds of dqkv as the attention backward left them (v untouched,
+    padded columns +0) -> (dqkv, dparams, colsum or None).  dparams [4, head_dim]: fp32 (new), or -- with grad_out, a bf16
+    [4, head_dim] tensor such as a gradient slot -- written there.  colsum: None; True -> fp32 [2 * H * hp] (new), the column
+    sums of the new dq | dk; or a contiguous fp32 / bf16 tensor to write into.  With vsum (fp32 [H * hp], the v third of
+    attention_bwd's colsum) the colsum tensor is [3 * H * hp] and its last third receives vsum: the whole in_proj bias gradient
+    in one place.  The reductions run now, in a fixed order (never queued: the slot they end in is complete when this returns
+    to the stream)."""
+    M, hp = _qk_norm_args("qk_norm_bwd", dqkv, params, n_heads, head_dim)
+    Da = n_heads * hp
+    _need(raw, _BF16, "qk_norm_bwd raw", 2)
+    if tuple(raw.shape) != (M, 2 * Da):
+        raise ValueError(f"qk_norm_bwd: raw must be [M, 2 * H * hp] = {(M, 2 * Da)}, got {tuple(raw.shape)}")
+    (dP,), dp_bf16 = _grad_outs("qk_norm_bwd", grad_out, ((4, head_dim),), (True,), dqkv.device, "a contiguous bf16 [4, head_dim] tensor",
+                                name="grad_out")
+    width = 3 * Da if vsum is not None else 2 * Da
+    if vsum is not None:
+        _need(vsum, torch.float32, "qk_norm_bwd vsum", 1)
+        if vsum.numel() != Da or colsum is None or colsum is False:
+            raise ValueError(f"qk_norm_bwd: vsum must be fp32 [H * hp] = [{Da}] and needs colsum")
+    cs = None
+    if colsum is not None and colsum is not False:
+        cs = torch.empty(width, device=dqkv.device, dtype=torch.float32) if colsum is True else colsum
+        if not cs.is_cuda or cs.numel() != width or not cs.is_contiguous() or cs.dtype not in (torch.float32, _BF16):
+            raise ValueError(f"qk_norm_bwd colsum: contiguous fp32 or bf16 [{width}] expected")
+    ws = torch.empty(lib.sfcvit_qk_norm_bwd_ws(M, n_heads, hp), device=dqkv.device, dtype=torch.uint8)
+    check(lib.sfcvit_qk_norm_bwd(_p(dqkv), _p(raw), _p(params), _p(dP), int(dp_bf16), _p(cs), int(cs is not None and cs.dtype == _BF16),
+                                 _p(vsum), _p(ws), M, n_heads, head_dim, hp, eps, _stream()), "sfcvit_qk_norm_bwd")
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append(last_rowwise_kernel())
+    return dqkv, dP, cs
+
+
+# ----------------------------------------------------------------------------
 # attention
 # ----------------------------------------------------------------------------
 SUPPORTED_HEAD_DIMS = (64, 128, 192, 256)
