@@ -316,6 +316,8 @@ def test_adamw_and_clip(ops):
                        weight_decay=5e-5, max_norm=1.0, step=step)
         assert torch.allclose(master, ref.detach(), atol=1e-6, rtol=1e-5)
         assert torch.equal(param, bf(master))
+        assert torch.allclose(m, opt.state[ref]["exp_avg"], atol=1e-6, rtol=1e-5)
+        assert torch.allclose(v, opt.state[ref]["exp_avg_sq"], atol=1e-6, rtol=1e-5)
 
 
 def test_transpose_and_gemm_dx(ops):
