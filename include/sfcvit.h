@@ -494,6 +494,32 @@ int64_t sfcvit_qk_norm_bwd_ws(int M, int H, int hp);
  * row, out[2] = workgroups = out[1] * ceil(M / out[0]), out[3] = 16-byte vectors per lane. */
 int sfcvit_qk_norm_plan(int M, int H, int hp, int32_t *out);
 
+/* RoPE (rotary position embedding; RoPE-ViT, EVA-02, timm's rope blocks) on the queries and keys of every head of a packed
+ * projection qkv [M = B * N, 3 * H * hp] bf16 (q | k | v thirds, head h at columns h * hp .. of each third), IN PLACE, after
+ * QK-norm and before q k^T.  Channel pairs are interleaved: pair p of a head row is its columns (2 p, 2 p + 1).
+ *   table [N, hd / 2, 2] fp32: row n, pair p holds (c, s); shared by the heads, the batch, q and k; row m uses n = m mod N
+ *   y0 = x0 * c - x1 * s,  y1 = x0 * s + x1 * c          (fp32 from the bf16 inputs, one rounding to bf16)
+ * The map [c -s; s c] is applied as given: c * c + s * s = 1 is not assumed.  hp: the kernel head dim (64 / 128 / 192 / 256);
+ * hd: the model's head dim, EVEN, 2 <= hd <= hp; columns hd .. hp - 1 are padding and are written +0 whatever they held.  v is
+ * neither read nor written and nothing is saved for the backward.  Notes its kernel ("rope_fwd_kernel<64>") for
+ * sfcvit_last_rowwise_kernel. */
+int sfcvit_rope_fwd(void *qkv, const float *table, int B, int N, int H, int hd, int hp, void *stream);
+/* Its backward, in place on the q and k thirds of dqkv [B * N, 3 * H * hp] as the attention backward left them (v untouched):
+ * the transposed map, dx0 = g0 * c + g1 * s, dx1 = -g0 * s + g1 * c; padded columns are written +0 even when they held NaN.
+ * colsum (optional; fp32, or bf16 with colsum_is_bf16) [2 * H * hp]: the column sums of the stored dq | dk over the M rows, the q
+ * and k part of the in_proj bias gradient; needs ws (sfcvit_rope_bwd_ws(B, N, H, hp) bytes).  vsum (optional, needs colsum):
+ * fp32 [H * hp], the v third's column sums from the attention backward; colsum is then [3 * H * hp] and its last third
+ * receives them.  Deterministic: per-workgroup fp32 partials, one fixed-order second-stage launch, no atomics, a grid that
+ * depends on the shape alone.  Without colsum: one launch, no workspace, the same dq | dk bits.  Never queued under
+ * sfcvit_reduce_defer.  Notes "rope_bwd_kernel<64>". */
+int sfcvit_rope_bwd(void *dqkv, const float *table, void *colsum, int colsum_is_bf16, const float *vsum, void *ws, int B, int N,
+                    int H, int hd, int hp, void *stream);
+int64_t sfcvit_rope_bwd_ws(int B, int N, int H, int hp);
+/* HOST: the launch geometry of both directions: out[0] = tokens per workgroup (one per wave), out[1] = images per workgroup (a
+ * wave walks them), out[2] = slot groups (of 8 head slots) per row, out[3] = workgroups = out[2] * ceil(N / out[0]) *
+ * ceil(B / out[1]), out[4] = 16-byte vectors per lane. */
+int sfcvit_rope_plan(int B, int N, int H, int hp, int32_t *out);
+
 /* ------------------------------------------------------------------------
  * Multi-head self-attention core (no mask; the masked form is the next section) on the packed projection
  *   replaces F.scaled_dot_product_attention as reached from nn.MultiheadAttention

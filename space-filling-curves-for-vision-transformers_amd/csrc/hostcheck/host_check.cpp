@@ -4,7 +4,7 @@
 //   host part), the error path of common.cpp, the mask validation and block map of attention_masked.cpp (check_mask_blocks),
 //   the index validation, inverted index, workspace and argument checks of attention_bias.cpp (check_attention_bias),
 //   the plans and refusals of pos_embed.cpp (check_pos_embed), token_pool.cpp (check_token_pool), token_agg.cpp (check_dwconv),
-//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), tokenizer.cpp (check_tokenizer), drop_path.cpp (check_drop_path), layer_scale.cpp (check_layer_scale), qk_norm.cpp (check_qk_norm), model_ema.cpp (check_model_ema) and grad_accum.cpp (check_grad_accum), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
+//   token_mix.cpp (check_tokmix), rowwise.cpp (check_rowwise), tokenizer.cpp (check_tokenizer), drop_path.cpp (check_drop_path), layer_scale.cpp (check_layer_scale), qk_norm.cpp (check_qk_norm), rope.cpp (check_rope), model_ema.cpp (check_model_ema) and grad_accum.cpp (check_grad_accum), and the kernel selection of dispatch.cpp (check_dispatch: which kernel, grid, splits
 //   and post passes each GEMM / attention shape of the benchmarked models gets).
 // Every buffer is a heap block of EXACTLY the documented size, so that an off-by-one in a generator or in the descriptor
 // writer is a heap-buffer-overflow report instead of silent corruption.
@@ -27,6 +27,7 @@
 #include "../model_ema.h"
 #include "../pos_embed.h"
 #include "../qk_norm.h"
+#include "../rope.h"
 #include "../rowwise.h"
 #include "../token_agg.h"
 #include "../token_mix.h"
@@ -1161,6 +1162,88 @@ static void check_qk_norm() {
     CHECK(qk_norm_fwd_plan(qkv, raw, P, 10, 4, 64, 64, 0.f).err == SFCVIT_OK, "qk_norm: eps = 0 refused");
 }
 
+// rope_fwd_plan / rope_bwd_plan (rope.cpp): the grid and the workspace per shape, and every refusal.
+static void check_rope() {
+    void *qkv = ptr(8), *cs = ptr(5), *ws = ptr(6);
+    const float *tab = static_cast<const float *>(ptr(3)), *vs = static_cast<const float *>(ptr(7));
+    struct R { int B, N, H, hd, hp; };
+    for (const R &r : {R{2, 5, 4, 64, 64}, R{2, 5, 3, 64, 64}, R{2, 197, 12, 64, 64}, R{67, 3, 1, 64, 64}, R{1, 9, 2, 64, 64},
+                       R{3, 1, 2, 64, 64}, R{2, 5, 4, 48, 64}, R{2, 5, 4, 20, 64}, R{1, 3, 1, 2, 64}, R{1, 7, 2, 128, 128},
+                       R{1, 7, 2, 96, 128}, R{1, 7, 1, 192, 192}, R{1, 7, 1, 256, 256}, R{256, 196, 12, 64, 64}, R{64, 576, 16, 64, 64},
+                       R{INT_MAX, 1, 1, 64, 64}, R{1, INT_MAX, 1, 64, 64}}) {
+        const RopePlan f = rope_fwd_plan(qkv, tab, r.B, r.N, r.H, r.hd, r.hp);
+        const RopePlan b = rope_bwd_plan(qkv, tab, cs, vs, ws, r.B, r.N, r.H, r.hd, r.hp);
+        CHECK(f.err == SFCVIT_OK && b.err == SFCVIT_OK, "rope %d %d %d %d %d refused: %s %s", r.B, r.N, r.H, r.hd, r.hp, f.msg, b.msg);
+        const int sgs = (2 * r.H + 7) / 8, tbs = int((int64_t(r.N) + ROPE_WAVES - 1) / ROPE_WAVES);
+        const int bcs = int((int64_t(r.B) + ROPE_BATCH_PER_WG - 1) / ROPE_BATCH_PER_WG);
+        CHECK(f.vpl == r.hp / 64 && f.slot_groups == sgs && f.token_blocks == tbs && f.batch_chunks == bcs &&
+                  int64_t(f.blocks) == int64_t(sgs) * tbs * bcs,
+              "rope fwd %d %d %d %d: vpl %d groups %d token blocks %d batch chunks %d blocks %d", r.B, r.N, r.H, r.hp, f.vpl,
+              f.slot_groups, f.token_blocks, f.batch_chunks, f.blocks);
+        CHECK(b.blocks == f.blocks && b.part_ld == 8 * r.hp && b.ws_bytes == int64_t(b.blocks) * 8 * r.hp * 4 && b.sums,
+              "rope bwd %d %d %d %d: blocks %d ws %lld", r.B, r.N, r.H, r.hp, b.blocks, (long long)b.ws_bytes);
+        CHECK(int64_t(tbs) * ROPE_WAVES >= r.N && int64_t(tbs - 1) * ROPE_WAVES < r.N, "rope token blocks %d for %d tokens", tbs, r.N);
+        CHECK(int64_t(bcs) * ROPE_BATCH_PER_WG >= r.B && int64_t(bcs - 1) * ROPE_BATCH_PER_WG < r.B, "rope batch chunks %d for %d images", bcs, r.B);
+        CHECK(rope_geometry(r.B, r.N, r.H, r.hp, "t").ws_bytes == b.ws_bytes, "rope: the workspace query disagrees");
+        const int Da = r.H * r.hp;
+        CHECK(b.reduce_blocks == 2 * Da / 16 + (Da + 1023) / 1024, "rope bwd reduce blocks %d", b.reduce_blocks);
+        const RopePlan c = rope_bwd_plan(qkv, tab, cs, nullptr, ws, r.B, r.N, r.H, r.hd, r.hp);
+        CHECK(c.err == SFCVIT_OK && c.sums && c.reduce_blocks == 2 * Da / 16, "rope bwd without vsum: %s, %d reduce blocks", c.msg, c.reduce_blocks);
+        const RopePlan n = rope_bwd_plan(qkv, tab, nullptr, nullptr, nullptr, r.B, r.N, r.H, r.hd, r.hp);
+        CHECK(n.err == SFCVIT_OK && !n.sums && n.reduce_blocks == 0, "rope bwd without sums: %s, %d reduce blocks", n.msg, n.reduce_blocks);
+        const RopePlan w = rope_bwd_plan(qkv, tab, nullptr, nullptr, ws, r.B, r.N, r.H, r.hd, r.hp);     // a workspace nobody needs is no error
+        CHECK(w.err == SFCVIT_OK && !w.sums, "rope bwd with a spare workspace: %s", w.msg);
+    }
+    // ViT-B/16 at batch 256 fills 256 CUs several times over
+    CHECK(rope_geometry(256, 196, 12, 64, "t").blocks == 3 * 49 * 16, "rope: ViT-B grid %d", rope_geometry(256, 196, 12, 64, "t").blocks);
+    auto fwd = [&](const char *what, const char *frag, void *q_, const void *t_, int B, int N, int H, int hd, int hp) {
+        const RopePlan r = rope_fwd_plan(q_, t_, B, N, H, hd, hp);
+        CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag), "rope fwd %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
+    };
+    auto bwd = [&](const char *what, const char *frag, void *q_, const void *t_, void *c_, const float *v_, void *w_, int B, int N, int H,
+                   int hd, int hp) {
+        const RopePlan r = rope_bwd_plan(q_, t_, c_, v_, w_, B, N, H, hd, hp);
+        CHECK(r.err == SFCVIT_EINVAL && std::strstr(r.msg, frag), "rope bwd %s: want '%s', got %d '%s'", what, frag, r.err, r.msg);
+    };
+    auto off8 = [](const void *p) { return reinterpret_cast<void *>(reinterpret_cast<uintptr_t>(p) + 8); };
+    fwd("null qkv", "null", nullptr, tab, 2, 5, 4, 64, 64);
+    fwd("null table", "null", qkv, nullptr, 2, 5, 4, 64, 64);
+    fwd("qkv + 8", "aligned", off8(qkv), tab, 2, 5, 4, 64, 64);
+    fwd("table + 8", "aligned", qkv, off8(tab), 2, 5, 4, 64, 64);
+    bwd("null dqkv", "null", nullptr, tab, cs, vs, ws, 2, 5, 4, 64, 64);
+    bwd("null table", "null", qkv, nullptr, cs, vs, ws, 2, 5, 4, 64, 64);
+    bwd("null ws", "colsum without a workspace", qkv, tab, cs, vs, nullptr, 2, 5, 4, 64, 64);
+    bwd("null ws, no vsum", "colsum without a workspace", qkv, tab, cs, nullptr, nullptr, 2, 5, 4, 64, 64);
+    bwd("vsum alone", "vsum without colsum", qkv, tab, nullptr, vs, ws, 2, 5, 4, 64, 64);
+    bwd("dqkv + 8", "aligned", off8(qkv), tab, cs, vs, ws, 2, 5, 4, 64, 64);
+    bwd("table + 8", "aligned", qkv, off8(tab), cs, vs, ws, 2, 5, 4, 64, 64);
+    bwd("colsum + 8", "aligned", qkv, tab, off8(cs), vs, ws, 2, 5, 4, 64, 64);
+    bwd("vsum + 8", "aligned", qkv, tab, cs, static_cast<const float *>(off8(vs)), ws, 2, 5, 4, 64, 64);
+    bwd("ws + 8", "aligned", qkv, tab, cs, vs, off8(ws), 2, 5, 4, 64, 64);
+    for (int hp : {0, 32, 96, 65, 512, -64}) {
+        fwd("hp", "not a kernel head dim", qkv, tab, 2, 5, 4, 8, hp);
+        bwd("hp", "not a kernel head dim", qkv, tab, cs, vs, ws, 2, 5, 4, 8, hp);
+    }
+    for (int hd : {0, -2, 1, 3, 63, 66, 1000}) {                                            // odd, < 2, > hp
+        fwd("hd", "hd=", qkv, tab, 2, 5, 4, hd, 64);
+        bwd("hd", "hd=", qkv, tab, cs, vs, ws, 2, 5, 4, hd, 64);
+    }
+    fwd("hd > hp", "hd=130", qkv, tab, 2, 5, 4, 130, 128);
+    for (int z : {0, -5}) {
+        fwd("B", "B=", qkv, tab, z, 5, 4, 64, 64);
+        fwd("N", "N=", qkv, tab, 2, z, 4, 64, 64);
+        fwd("H", "H=", qkv, tab, 2, 5, z, 64, 64);
+        bwd("B", "B=", qkv, tab, cs, vs, ws, z, 5, 4, 64, 64);
+        bwd("N", "N=", qkv, tab, cs, vs, ws, 2, z, 4, 64, 64);
+        bwd("H", "H=", qkv, tab, cs, vs, ws, 2, 5, z, 64, 64);
+    }
+    fwd("row width", "leaves int", qkv, tab, 2, 5, 11184811, 64, 64);                       // 3 * H * 64 = 2^31 + 64
+    bwd("row width", "leaves int", qkv, tab, cs, vs, ws, 2, 5, INT_MAX, 64, 256);
+    CHECK(rope_fwd_plan(qkv, tab, 2, 5, 11184810, 64, 64).err == SFCVIT_OK, "rope: the widest row that fits is refused");
+    fwd("rows", "leaves int", qkv, tab, 65536, 32768, 1, 64, 64);                           // B * N = 2^31
+    fwd("grid", "leaves int", qkv, tab, 1, INT_MAX, 64, 64, 64);                            // 16 slot groups * 2^29 token blocks
+}
+
 static void check_model_ema() {
     using namespace sfcvit;
     const RowwiseKnobs k0;
@@ -1970,6 +2053,7 @@ int main() {
     check_drop_path();
     check_layer_scale();
     check_qk_norm();
+    check_rope();
     check_model_ema();
     check_grad_accum();
     if (g_fail) { std::fprintf(stderr, "host_check: %d check(s) failed\n", g_fail); return 1; }

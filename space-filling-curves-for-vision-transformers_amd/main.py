@@ -149,6 +149,17 @@ def build_parser():
                          "bias, k weight, k bias).  Works with post- and pre-norm layers, --rel-pos-bias, --attn-window*, "
                          "--drop-path, --layer-scale, --graph, --accum-steps, --model-ema, --pool, --pos-embed and "
                          "--attention-report")
+    ap.add_argument("--rope", choices=("curve", "image"), default=None,
+                    help="rotary position embedding (RoPE-ViT, EVA-02, timm's rope blocks) on the queries and keys of every "
+                         "encoder layer, after QK-norm: channel pairs are rotated by an angle that grows with the token's index "
+                         "along the curve ('curve') or, half of the pairs each, with the column and the row of its centre in the "
+                         "image ('image': the same whatever curve orders the tokens), so q . k depends on the offset only.  A "
+                         "fixed table, no parameter and no checkpoint key; the kind and base are stored in the checkpoint and "
+                         "--resume rebuilds the same table.  Works with post- and pre-norm layers, --qk-norm, --layer-scale, "
+                         "--rel-pos-bias, --attn-window*, --pos-embed, --pool, --drop-path, --graph, --accum-steps, --model-ema "
+                         "and --attention-report")
+    ap.add_argument("--rope-base", type=float, default=None, metavar="X",
+                    help="the base of the --rope frequencies (default: 10000 for 'curve', 100 for 'image')")
     ap.add_argument("--model-ema", type=float, nargs="?", const=0.9999, default=None, metavar="DECAY",
                     help="keep an exponential moving average of the weights (timm's --model-ema; DECAY defaults to 0.9999): "
                          "averaged in fp32 inside the AdamW kernel, evaluated after every epoch next to the raw weights (one "
@@ -204,6 +215,8 @@ def build_model(a, patch_embed, attn_mask=None):
         rel.update(norm_first=a.pre_norm, activation=a.activation, layer_scale=a.layer_scale)
     if getattr(a, "qk_norm", None) is not None:
         rel.update(qk_norm=True, qk_norm_eps=a.qk_norm)
+    if getattr(a, "rope", None) is not None:
+        rel.update(rope=a.rope, rope_base=getattr(a, "rope_base", None))
     return VisionTransformer1D(patch_embed=patch_embed, depth=a.depth, n_heads=a.heads, mlp_dim=a.mlp_dim,
                                num_classes=a.classes,
                                token_aggregator=a.token_aggregator or False, token_mix=a.token_mix,
@@ -223,6 +236,10 @@ def parse_args(argv=None):
         ap.error("--layer-scale needs --pre-norm: the post-norm layer has no LayerScale")
     if a.qk_norm is not None and not (a.qk_norm >= 0.0 and a.qk_norm < float("inf")):
         ap.error(f"--qk-norm {a.qk_norm}: a finite epsilon >= 0 expected")
+    if a.rope_base is not None and a.rope is None:
+        ap.error("--rope-base needs --rope curve or --rope image")
+    if a.rope_base is not None and not (a.rope_base > 0.0 and a.rope_base < float("inf")):
+        ap.error(f"--rope-base {a.rope_base}: a finite base > 0 expected")
     if a.graph and a.accum_steps > 1:
         ap.error("--graph cannot be combined with --accum-steps > 1: a captured step does not accumulate (graphs serve "
                  "launch-bound small models, accumulation serves models too large for the batch)")
@@ -315,6 +332,14 @@ def main():
         # the reference saves the torch.compile wrapper's state_dict: same keys behind an "_orig_mod." prefix
         msd = {(k[len("_orig_mod."):] if k.startswith("_orig_mod.") else k): v for k, v in ck["model_state_dict"].items()}
         model.load_state_dict(msd)
+        saved = ck.get("rope")                                  # {"kind", "base"} of the run that wrote it: the table is a function of them
+        if saved and a.rope is None:
+            model.encoder.attach_rope(saved["kind"], saved["base"])
+            if rank == 0:
+                print(f"rotary position embedding ({saved['kind']}, base {saved['base']:g}): taken from the checkpoint")
+        elif saved and (saved["kind"], saved["base"]) != (model.encoder.rope_kind, model.encoder.rope_base):
+            raise SystemExit(f"--resume: the checkpoint was trained with --rope {saved['kind']} --rope-base {saved['base']:g}, "
+                             f"this run asks for --rope {model.encoder.rope_kind} --rope-base {model.encoder.rope_base:g}")
         osd = ck.get("optimizer_state_dict") or {}
         if osd and not a.resume_model_only:
             # this repository's flat fp32 state (FusedAdamW.state_dict), or a torch.optim.AdamW state_dict as the reference's
@@ -385,6 +410,8 @@ def main():
                       "scheduler_state_dict": {"n": scheduler.n},
                       "augment_state_dict": augment.state_dict() if augment is not None else {}, "train_loss": tr_loss, "train_acc": tr_acc,
                       "test_loss": te_loss, "test_acc": te_acc}                  # main.py:345-354 keys
+                if getattr(model.encoder, "rope", None) is not None:
+                    ck["rope"] = {"kind": model.encoder.rope_kind, "base": model.encoder.rope_base}
                 if a.model_ema is not None:            # the averaged weights under the reference's keys: model.load_state_dict takes them
                     ck.update(model_ema_state_dict=optimizer.ema_state_dict(model), ema_test_acc=ema_acc)
                 torch.save(ck, ckpt)

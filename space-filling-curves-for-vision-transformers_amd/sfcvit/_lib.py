@@ -162,6 +162,11 @@ SIGNATURES = {
                                    c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "sfcvit_qk_norm_bwd_ws": (c_int64, [c_int, c_int, c_int]),
     "sfcvit_qk_norm_plan": (c_int, [c_int, c_int, c_int, c_void_p]),
+    "sfcvit_rope_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "sfcvit_rope_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                c_void_p]),
+    "sfcvit_rope_bwd_ws": (c_int64, [c_int, c_int, c_int, c_int]),
+    "sfcvit_rope_plan": (c_int, [c_int, c_int, c_int, c_int, c_void_p]),
     "sfcvit_gelu_drop_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, ctypes.c_uint32, c_void_p, c_void_p]),
     "sfcvit_gelu_drop_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, ctypes.c_uint32, c_void_p, c_void_p]),
     "sfcvit_step_advance": (c_int, [c_void_p, c_float, c_float, ctypes.c_uint32, c_void_p]),

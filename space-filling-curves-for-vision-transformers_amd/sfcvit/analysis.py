@@ -98,6 +98,8 @@ def _vit_layers(model, images):
         a = layer.self_attn
         # QK-norm: the probe returns the normalised q, k -- what the attention kernels consumed
         qk = dict(qk_norm=enc.qk_norm[l], qk_norm_eps=enc.qk_norm_eps) if hasattr(enc, "qk_norm") else {}
+        if getattr(enc, "rope", None) is not None:              # RoPE: likewise the rotated q, k
+            qk["rope"] = enc.rope
         x, qkv, lse, scale = F.encoder_layer_probe(x, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
                                                    layer.norm1.weight, layer.norm1.bias, layer.linear1.weight,
                                                    layer.linear1.bias, layer.linear2.weight, layer.linear2.bias,

@@ -496,6 +496,90 @@ def _qk_norm_arg(qk_norm, qk_norm_eps, hd, what):
     return _c(_bf(qk_norm)), eps
 
 
+def _rope_fwd(qkv, cfg):
+    """RoPE of a layer, after QK-norm and before the attention core: with cfg.rope (an ops.RopeTable) the channel pairs of the q
+    and k thirds of qkv [M, 3 * H * hp] are rotated per token IN PLACE; nothing is kept for the backward.  With cfg.rope = None
+    nothing is launched.  This and _rope_bwd are the only place that decides."""
+    if cfg.rope is not None:
+        ops.rope_fwd(qkv, cfg.rope, cfg.n_heads)
+
+
+def _rope_bwd(attn_bwd, in_b, cfg):
+    """attn_bwd(fp32_sums) -- _attn_bwd with the layer's arguments -- with the mirror of _rope_fwd behind it, in the same form, so
+    that _qk_norm_bwd takes either.  Without RoPE it is attn_bwd itself.  With it, the attention backward's column sums are
+    the bias gradient for the v third alone: they come back as fp32, never into the slot.  Asked for fp32 sums (QK-norm follows
+    and owns the q | k sums) the transposed rotation runs in its no-sums form, one launch; otherwise ops.rope_bwd writes the
+    column sums of the dq | dk it stores and carries the v sums over, into in_b's slot when it has one."""
+    if cfg.rope is None:
+        return attn_bwd
+
+    def run(fp32_sums):
+        dqkv, sums, dtable = attn_bwd(True)
+        if fp32_sums:
+            ops.rope_bwd(dqkv, cfg.rope, cfg.n_heads)
+            return dqkv, sums, dtable
+        Da = sums.numel() // 3
+        bi_slot = _slot(in_b)
+        dbi = bi_slot if bi_slot is not None else torch.empty(3 * Da, device=dqkv.device, dtype=_BF16)
+        ops.rope_bwd(dqkv, cfg.rope, cfg.n_heads, colsum=dbi, vsum=sums[2 * Da:])
+        return dqkv, dbi, dtable
+    return run
+
+
+def _rope_arg(rope, n_tokens, hd, what):
+    """A layer call's rope = None, an ops.RopeTable or a CPU fp32 [N, head_dim / 2, 2] table (sfcvit.rope builds them; head_dim
+    = the model's head dim, not the padded one) -> ops.RopeTable or None, matching n_tokens and hd where the caller knows them
+    (None: not known here; ops checks the table against the buffer).  Refused under tracing: the torch.library ops have no RoPE
+    form."""
+    if rope is None:
+        return None
+    if _traced():
+        raise NotImplementedError(f"{what}: rope is not supported under torch.compile / tracing (the torch.library ops have "
+                                  "no RoPE form); run the model eagerly")
+    if isinstance(rope, torch.Tensor):
+        rope = ops.RopeTable(rope)
+    if not isinstance(rope, ops.RopeTable):
+        raise ValueError(f"{what}: rope must be an ops.RopeTable or a CPU fp32 [N, head_dim / 2, 2] table, got {type(rope).__name__}")
+    if hd is not None and hd % 2:
+        raise ValueError(f"{what}: rope needs an even head dim, got {hd}: channels rotate in pairs")
+    if (n_tokens is not None and rope.n_tokens != n_tokens) or (hd is not None and rope.head_dim != hd):
+        raise ValueError(f"{what}: rope table for {rope.n_tokens} tokens and head dim {rope.head_dim} on a sequence of {n_tokens} "
+                         f"tokens with head dim {hd}")
+    return rope
+
+
+class _Rope(Function):
+    """rope: the stand-alone differentiable form on a copy of the packed projection (the layers use the in-place kernels)."""
+
+    @staticmethod
+    def forward(ctx, qkv, table, n_heads):
+        ctx.table, ctx.n_heads = table, n_heads
+        return ops.rope_fwd(qkv.clone(memory_format=torch.contiguous_format), table, n_heads)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dqkv, _ = ops.rope_bwd(dout.clone(memory_format=torch.contiguous_format), ctx.table, ctx.n_heads)
+        return dqkv, None, None
+
+
+def rope(qkv, table, n_heads):
+    """Rotary position embedding of a packed projection qkv [B, N, 3 * H * hp] (or [B * N, ..]; q | k | v thirds, head h at
+    columns h * hp .. of each third): the channel pairs (2 p, 2 p + 1) of every query and key head row are rotated by the
+    table's (cos, sin) of the row's token, v unchanged -> a new tensor.  table: an ops.RopeTable, or a CPU fp32
+    [N, head_dim / 2, 2] table (sfcvit.rope.curve_table / image_table); head_dim <= hp, the columns above it come out +0; hp
+    must be 64, 128, 192 or 256.  The table receives no gradient."""
+    qkv = _bf(qkv)
+    if n_heads <= 0 or qkv.shape[-1] % (3 * n_heads):
+        raise ValueError(f"rope: packed width {qkv.shape[-1]} is not 3 * n_heads * head_dim for n_heads = {n_heads}")
+    hp = qkv.shape[-1] // (3 * n_heads)
+    if hp not in ops.SUPPORTED_HEAD_DIMS:
+        raise ValueError(f"rope: packed head width {hp} must be one of {ops.SUPPORTED_HEAD_DIMS}")
+    if table is None:
+        raise ValueError("rope: table must be an ops.RopeTable or a CPU fp32 [N, head_dim / 2, 2] table")
+    table = _rope_arg(table, qkv.shape[1] if qkv.dim() == 3 else None, None, "rope")
+    return _Rope.apply(qkv, table, n_heads)
+
+
 class _QkNorm(Function):
     """qk_norm: the stand-alone differentiable form on a copy of the packed projection (the layers use the in-place kernels)."""
 
@@ -935,9 +1019,10 @@ class _LayerCfg:
     """The non-tensor arguments of _EncoderLayer and _PreNormLayer, one object so that apply() has a fixed argument list.
     seeds: the four dropout seeds (attention, dropout1, the MLP's, dropout2); drop_path: None or (rate, (seed1, seed2))."""
 
-    def __init__(self, n_heads, eps, p, seeds, scale, act, attn_mask=None, drop_path=None, rel_index=None, qk_eps=1e-6):
+    def __init__(self, n_heads, eps, p, seeds, scale, act, attn_mask=None, drop_path=None, rel_index=None, qk_eps=1e-6, rope=None):
         self.n_heads, self.eps, self.p, self.seeds, self.scale, self.act = n_heads, eps, p, seeds, scale, act
         self.attn_mask, self.drop_path, self.rel_index, self.qk_eps = attn_mask, drop_path, rel_index, qk_eps
+        self.rope = rope                                        # None or an ops.RopeTable: not differentiable, like the mask
 
 
 _PreNormCfg = _LayerCfg     # the name callers that build a _PreNormLayer by hand knew it by: same constructor
@@ -1047,6 +1132,7 @@ class _EncoderLayer(Function):
         x2 = _c(x).view(B * N, D)
         qkv = ops.gemm(x2, in_w, bias=in_b)
         raw = _qk_norm_fwd(qkv, qk, cfg)
+        _rope_fwd(qkv, cfg)
         o, lse = _attn_fwd(qkv.view(B, N, 3 * Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask, rel_bias)
         _, s1, x1, mean1, rstd1 = _site_fwd(o.view(B * N, Da), out_w, out_b, x2, None, n1_w, n1_b, B, cfg.eps, p, s1_, cfg.drop_path, 0)
         hbits, _, h = _mlp_fwd(x1, w1, b1, cfg.act, p, sf)
@@ -1088,9 +1174,9 @@ class _EncoderLayer(Function):
         dwo = wg(da, o.view(B * N, Da), out_w)
         do = ops.gemm_dx(da, out_w)
         want = ctx.rel_bias is not None and ctx.needs_input_grad[13]        # a frozen table costs nothing
-        dqkv, dbi, dtable, dqk = _qk_norm_bwd(
+        dqkv, dbi, dtable, dqk = _qk_norm_bwd(_rope_bwd(
             lambda fp32: _attn_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask,
-                                   ctx.rel_bias, True, in_b, ctx.rel_table, want, fp32), raw, qk, getattr(ctx, "qk_param", None), in_b, cfg)
+                                   ctx.rel_bias, True, in_b, ctx.rel_table, want, fp32), in_b, cfg), raw, qk, getattr(ctx, "qk_param", None), in_b, cfg)
         dqkv = dqkv.view(B * N, 3 * Da)
         dwi = wg(dqkv, x2, in_w)
         dx = ops.gemm_dx(dqkv, in_w, residual=ds1)
@@ -1116,15 +1202,17 @@ def _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2,
 
 
 def encoder_layer_probe(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5, qk_norm=None,
-                        qk_norm_eps=1e-6):
+                        qk_norm_eps=1e-6, rope=None):
     """The eval-mode (dropout 0) encoder layer with its attention inputs exposed: (y, qkv [B, N, 3 * H * kernel head dim],
     lse [B, H, N], softmax scale or None).  Same launches as encoder_layer(dropout_p=0): y has its bits.  With qk_norm the
-    qkv returned is the NORMALISED one: what the attention kernels consumed.  For sfcvit.analysis; no autograd graph is built."""
+    qkv returned is the NORMALISED one, with rope the ROTATED one: what the attention kernels consumed.  For sfcvit.analysis; no
+    autograd graph is built."""
     with torch.no_grad():
         args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
         B, N, D = args[0].shape
         qk, qk_eps = _qk_norm_arg(qk_norm, qk_norm_eps, D // n_heads, "encoder_layer_probe")
-        t = _EncoderLayer.launches(*args, None, _LayerCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, "relu", qk_eps=qk_eps), qk)
+        rope = _rope_arg(rope, N, D // n_heads, "encoder_layer_probe")
+        t = _EncoderLayer.launches(*args, None, _LayerCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, "relu", qk_eps=qk_eps, rope=rope), qk)
         return t["y"].view(B, N, D), t["qkv"].view(B, N, -1), t["lse"], scale
 
 
@@ -1145,17 +1233,17 @@ def _layer_options(what, n_tokens, n_heads, attn_mask, rel_bias, no_traced_form=
     return _attention_mask(attn_mask, n_tokens, what), rel_bias
 
 
-def _layer_cfg(n_heads, eps, dropout_p, scale, act, attn_mask, drop_path, rel_bias, qk_eps=1e-6):
+def _layer_cfg(n_heads, eps, dropout_p, scale, act, attn_mask, drop_path, rel_bias, qk_eps=1e-6, rope=None):
     """An eager layer call's (_LayerCfg, bias table or None).  The seeds are drawn here, on the host, in this order: four dropout
-    seeds when dropout_p > 0, then two path seeds when drop_path > 0.  (QK-norm draws nothing.)"""
+    seeds when dropout_p > 0, then two path seeds when drop_path > 0.  (QK-norm and RoPE draw nothing.)"""
     seeds = tuple(ops.next_seed() for _ in range(4)) if dropout_p > 0 else (0, 0, 0, 0)
     path = (drop_path, (ops.next_seed(), ops.next_seed())) if drop_path > 0 else None
     table, index = rel_bias if rel_bias is not None else (None, None)
-    return _LayerCfg(n_heads, eps, float(dropout_p), seeds, scale, act, attn_mask, path, index, qk_eps), table
+    return _LayerCfg(n_heads, eps, float(dropout_p), seeds, scale, act, attn_mask, path, index, qk_eps, rope), table
 
 
 def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads, eps=1e-5,
-                  dropout_p=0.0, attn_mask=None, drop_path=0.0, rel_bias=None, qk_norm=None, qk_norm_eps=1e-6):
+                  dropout_p=0.0, attn_mask=None, drop_path=0.0, rel_bias=None, qk_norm=None, qk_norm_eps=1e-6, rope=None):
     """dropout_p > 0 = training-mode nn.TransformerEncoderLayer (fresh masks every call).
     attn_mask = nn.TransformerEncoderLayer's src_mask: None, or an additive [N, N] mask as in `attention` (build an
     ops.AttentionMask once when the layer runs more than once).  With None the launches and the bits are those of a call
@@ -1177,17 +1265,22 @@ def encoder_layer(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w,
     heads; head_dim = embed_dim / n_heads, not the padded one): QK-norm, a LayerNorm(head_dim, eps=qk_norm_eps) on the queries
     and keys of every head before q k^T, one in-place kernel between the projection GEMM and the attention core and its mirror
     in the backward; the softmax scale, mask, bias and dropout are untouched and the tensor receives its gradient (in its slot
-    when it has one).  Combines with every other option; not under tracing.  None runs the call as it is without the argument."""
+    when it has one).  Combines with every other option; not under tracing.  None runs the call as it is without the argument.
+    rope = an ops.RopeTable (or a CPU fp32 [N, head_dim / 2, 2] table; sfcvit.rope builds them): rotary position embedding, the
+    channel pairs of the queries and keys of every head rotated by the table's (cos, sin) of their token, after QK-norm and
+    before q k^T; one in-place kernel and its transposed mirror in the backward, nothing saved, no gradient to the table.
+    Needs an even head_dim.  Combines with every other option; not under tracing.  None runs the call as it is without it."""
     drop_path = _path_rate("encoder_layer", drop_path)
     args, scale = _encoder_layer_args(x, in_w, in_b, out_w, out_b, n1_w, n1_b, w1, b1, w2, b2, n2_w, n2_b, n_heads)
     qk, qk_eps = _qk_norm_arg(qk_norm, qk_norm_eps, args[0].shape[-1] // n_heads, "encoder_layer")
+    rope = _rope_arg(rope, args[0].shape[1], args[0].shape[-1] // n_heads, "encoder_layer")
     attn_mask, rel_bias = _layer_options("encoder_layer", args[0].shape[1], n_heads, attn_mask, rel_bias)
     if drop_path > 0 and _traced():
         raise NotImplementedError("encoder_layer: drop_path > 0 has no traced form (torch.compile); run the layer eagerly")
     if _traced():
         from . import library      # (dropout seeds are drawn inside the op: nothing data-dependent in the traced graph)
         return library.encoder_layer(args, n_heads, eps, float(dropout_p), scale)
-    cfg, table = _layer_cfg(n_heads, eps, dropout_p, scale, "relu", attn_mask, drop_path, rel_bias, qk_eps)
+    cfg, table = _layer_cfg(n_heads, eps, dropout_p, scale, "relu", attn_mask, drop_path, rel_bias, qk_eps, rope)
     return _EncoderLayer.apply(*args, table, cfg) if qk is None else _EncoderLayer.apply(*args, table, cfg, qk)
 
 
@@ -1213,6 +1306,7 @@ class _PreNormLayer(Function):
         s0, n0 = _c(s).view(B * N, D), _c(n).view(B * N, D)
         qkv = ops.gemm(n0, in_w, bias=in_b)
         raw = _qk_norm_fwd(qkv, qk, cfg)
+        _rope_fwd(qkv, cfg)
         o, lse = _attn_fwd(qkv.view(B, N, 3 * Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask, rel_bias)
         lam1, lam2 = (lam[0], lam[1]) if lam is not None else (None, None)
         a, s1, n1, mean1, rstd1 = _site_fwd(o.view(B * N, Da), out_w, out_b, s0, lam1, n2_w, n2_b, B, cfg.eps, p, s1_, cfg.drop_path, 0)
@@ -1267,9 +1361,9 @@ class _PreNormLayer(Function):
         dwo = wg(da, o.view(B * N, Da), out_w)
         do = ops.gemm_dx(da, out_w)
         want = ctx.rel_bias is not None and ctx.needs_input_grad[15]        # a frozen table costs nothing
-        dqkv, dbi, dtable, dqk = _qk_norm_bwd(
+        dqkv, dbi, dtable, dqk = _qk_norm_bwd(_rope_bwd(
             lambda fp32: _attn_bwd(qkv.view(B, N, 3 * Da), o, lse, do.view(B, N, Da), cfg.n_heads, p, sa, cfg.scale, cfg.attn_mask,
-                                   ctx.rel_bias, True, in_b, ctx.rel_table, want, fp32), raw, qk, getattr(ctx, "qk_param", None), in_b, cfg)
+                                   ctx.rel_bias, True, in_b, ctx.rel_table, want, fp32), in_b, cfg), raw, qk, getattr(ctx, "qk_param", None), in_b, cfg)
         dqkv = dqkv.view(B * N, 3 * Da)
         dwi = wg(dqkv, n0, in_w)
         dn_in = ops.gemm_dx(dqkv, in_w)
@@ -1315,7 +1409,8 @@ def _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, n
 
 
 def pre_norm_layer(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads, eps=1e-5, dropout_p=0.0,
-                   attn_mask=None, drop_path=0.0, rel_bias=None, activation="relu", layer_scale=None, qk_norm=None, qk_norm_eps=1e-6):
+                   attn_mask=None, drop_path=0.0, rel_bias=None, activation="relu", layer_scale=None, qk_norm=None, qk_norm_eps=1e-6,
+                   rope=None):
     """One pre-norm encoder layer (nn.TransformerEncoderLayer(norm_first=True)) on the HIP path, as "residual site + the
     LayerNorm after it": takes the residual stream s [B, N, D] and n = norm1(s), returns (s', n') with n' = LayerNorm(s') by
     the FOLLOWING norm (next_w, next_b): the next layer's norm1, or the encoder's final norm after the last layer.  The first
@@ -1323,31 +1418,34 @@ def pre_norm_layer(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, n
     activation: "relu" or "gelu" (erf).  layer_scale: None, or (lam1, lam2) / a [2, D] tensor: the per-channel scales of the
     attention and MLP branches (CaiT / DeiT-III), s1 = s + c1[b] lam1 * a.  dropout_p, attn_mask, drop_path, rel_bias and the
     zero padding of head dims the kernels do not have: as in encoder_layer, with its masks, flags and seeds; qk_norm, qk_norm_eps
-    (QK-norm) as there too.  Not under tracing."""
+    (QK-norm) and rope (rotary position embedding) as there too.  Not under tracing."""
     what = "pre_norm_layer"
     drop_path = _path_rate(what, drop_path)
     args, scale, n, lam = _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads,
                                          activation, layer_scale, what)
     qk, qk_eps = _qk_norm_arg(qk_norm, qk_norm_eps, args[0].shape[-1] // n_heads, what)
+    rope = _rope_arg(rope, args[0].shape[1], args[0].shape[-1] // n_heads, what)
     attn_mask, rel_bias = _layer_options(what, args[0].shape[1], n_heads, attn_mask, rel_bias,
                                          no_traced_form="the pre-norm layer has no traced form (torch.compile); run the model eagerly")
-    cfg, table = _layer_cfg(n_heads, eps, dropout_p, scale, activation, attn_mask, drop_path, rel_bias, qk_eps)
+    cfg, table = _layer_cfg(n_heads, eps, dropout_p, scale, activation, attn_mask, drop_path, rel_bias, qk_eps, rope)
     if qk is None:
         return _PreNormLayer.apply(args[0], n, *args[1:], lam, table, cfg)
     return _PreNormLayer.apply(args[0], n, *args[1:], lam, table, cfg, qk)
 
 
 def pre_norm_layer_probe(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads, eps=1e-5,
-                         activation="relu", layer_scale=None, qk_norm=None, qk_norm_eps=1e-6):
+                         activation="relu", layer_scale=None, qk_norm=None, qk_norm_eps=1e-6, rope=None):
     """The eval-mode (dropout 0) pre-norm layer with its attention inputs exposed: (s', n', qkv [B, N, 3 * H * kernel head dim],
     lse [B, H, N], softmax scale or None).  Same launches as pre_norm_layer(dropout_p=0): s' and n' have its bits.  With qk_norm
-    the qkv returned is the NORMALISED one: what the attention kernels consumed.  For sfcvit.analysis; no autograd graph is built."""
+    the qkv returned is the NORMALISED one, with rope the ROTATED one: what the attention kernels consumed.  For sfcvit.analysis;
+    no autograd graph is built."""
     with torch.no_grad():
         args, scale, n, lam = _pre_norm_args(s, n, in_w, in_b, out_w, out_b, n2_w, n2_b, w1, b1, w2, b2, next_w, next_b, n_heads,
                                              activation, layer_scale, "pre_norm_layer_probe")
         B, N, D = args[0].shape
         qk, qk_eps = _qk_norm_arg(qk_norm, qk_norm_eps, D // n_heads, "pre_norm_layer_probe")
-        cfg = _LayerCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, activation, qk_eps=qk_eps)
+        rope = _rope_arg(rope, N, D // n_heads, "pre_norm_layer_probe")
+        cfg = _LayerCfg(n_heads, eps, 0.0, (0, 0, 0, 0), scale, activation, qk_eps=qk_eps, rope=rope)
         t = _PreNormLayer.launches(args[0], n, *args[1:], lam, None, cfg, qk)
         return t["s2"].view(B, N, D), t["n2"].view(B, N, D), t["qkv"].view(B, N, -1), t["lse"], scale
 

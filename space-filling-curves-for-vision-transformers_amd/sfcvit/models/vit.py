@@ -134,7 +134,7 @@ class TransformerSeqEncoder(nn.Module):
 
     def __init__(self, input_dim, max_len, n_head, hidden_dim, method, dropout_p=0.1, n_layers=1, cls_token=False,
                  drop_path_rate=0.0, rel_pos_bias=None, norm_first=False, activation="relu", layer_scale=None, qk_norm=False,
-                 qk_norm_eps=1e-6):
+                 qk_norm_eps=1e-6, rope=None, rope_base=None):
         """norm_first=True: pre-norm layers, x + f(LN(x)), and a final LayerNorm after the last one -- torch's
         nn.TransformerEncoderLayer(norm_first=True, activation=...) under nn.TransformerEncoder(norm=nn.LayerNorm(D)), so the
         state_dict keys are torch's own (`transformer.layers.<l>.*`, `transformer.norm.weight|bias`); F.pre_norm_layer runs them.
@@ -147,6 +147,9 @@ class TransformerSeqEncoder(nn.Module):
         layer with rows q_weight, q_bias, k_weight, k_bias = 1, 0, 1, 0 (timm's blocks.<l>.attn.q_norm.weight | .bias and
         k_norm.weight | .bias), shared by the heads of a layer.  Constructed after everything else of the encoder, no draw;
         False: the encoder as it is without the keyword.
+        rope: None (the encoder as it is without the keyword), "curve" or "image": rotary position embedding on the queries and
+        keys of every layer, after QK-norm (attach_rope, which the models call after everything else is constructed); rope_base:
+        None for the kind's default.  No parameter and no state_dict key.
         rel_pos_bias: None, or an ops.AttentionBiasIndex (or (index, init_std)): every layer adds a learned relative
         position bias per head to its attention scores, one table `rel_pos_bias.<l>` [n_head, T] per layer in a ParameterList
         (attach_rel_pos_bias; the models call it after everything else is constructed).
@@ -206,6 +209,46 @@ class TransformerSeqEncoder(nn.Module):
         if qk_norm:
             row = torch.tensor([1.0, 0.0, 1.0, 0.0]).unsqueeze(1)
             self.qk_norm = nn.ParameterList(nn.Parameter(row.expand(4, input_dim // n_head).clone()) for _ in range(n_layers))
+        self.input_dim = input_dim
+        if rope is not None and rope is not False:
+            self.attach_rope(rope, rope_base)
+
+    def attach_rope(self, kind, base=None):
+        """Rotary position embedding for every layer.  "curve": the angle grows with the index along the token sequence
+        (sfcvit.rope.curve_table, base 10000 by default), so q_i . k_j depends on the offset j - i along the curve; "image":
+        half of the channel pairs turn with the column and half with the row of the token's centre in the image, in cells of
+        sqrt(pixels per token) pixels (sfcvit.rope.image_table, base 100 by default; a hierarchical tokenizer answers with level
+        0), whatever the curve.  With a CLS token the table gets an identity row in front: the CLS token is not rotated.  The
+        table is fixed: `rope_table`, a NON-persistent buffer [N, head_dim / 2, 2] -- no state_dict key, so checkpoints load with
+        and without the option -- and `rope`, the validated ops.RopeTable whose device copy the kernels read."""
+        from .. import rope as rope_tables
+        if kind not in ROPE_KINDS:
+            raise ValueError(f"rope={kind!r}: None, {', '.join(map(repr, ROPE_KINDS))} expected")
+        D, H = self.input_dim, self.n_head
+        if D % H:
+            raise ValueError(f"rope={kind!r}: input_dim={D} is not a multiple of n_head={H}")
+        hd = D // H
+        if hd % 2:
+            raise ValueError(f"rope={kind!r}: head dim {hd} must be even: channels rotate in pairs")
+        if kind == "image" and hd % 4:
+            raise ValueError(f"rope='image': head dim {hd} must be a multiple of 4: half of the pairs turn with the column, half "
+                             "with the row")
+        if ops.padded_head_dim(hd) is None:
+            raise ValueError(f"rope={kind!r}: head dim {hd} exceeds the largest supported one, {max(ops.SUPPORTED_HEAD_DIMS)}")
+        base = rope_tables.DEFAULT_BASE[kind] if base is None else float(base)
+        if not (math.isfinite(base) and base > 0):
+            raise ValueError(f"rope_base={base} must be finite and > 0")
+        pe = self.to_patch_embedding
+        if kind == "curve":
+            table = rope_tables.curve_table(self.max_len, hd, base)
+        else:
+            from ..analysis import token_positions              # (analysis imports this module: resolved at call time)
+            table = rope_tables.image_table(token_positions(pe), rel_pos_cell(pe), hd, base)
+        if hasattr(self, "cls_token"):
+            table = rope_tables.with_cls_token(table)
+        self.rope_kind, self.rope_base = kind, base
+        self.rope = ops.RopeTable(table)
+        self.register_buffer("rope_table", self.rope.table.clone(), persistent=False)
 
     def attach_rel_pos_bias(self, bias_index, init_std=0.0):
         """One table [n_head, T] per layer, zeros or randn * init_std (init_std = 0 draws nothing: the model then computes
@@ -233,7 +276,7 @@ class TransformerSeqEncoder(nn.Module):
     def forward(self, x, mask=None):
         p = self.dropout_p if self.training else 0.0
         mask = self._mask(mask)
-        tables, qks = getattr(self, "rel_pos_bias", None), getattr(self, "qk_norm", None)
+        tables, qks, rope = getattr(self, "rel_pos_bias", None), getattr(self, "qk_norm", None), getattr(self, "rope", None)
         if tables is not None and mask is not None:
             raise ValueError("TransformerSeqEncoder: rel_pos_bias and a mask cannot be combined; the window belongs in the "
                              "bias index (rel_pos_window)")
@@ -250,6 +293,8 @@ class TransformerSeqEncoder(nn.Module):
                 path["rel_bias"] = (tables[l], self.rel_pos_index)
             if qks is not None:
                 path["qk_norm"], path["qk_norm_eps"] = qks[l], self.qk_norm_eps
+            if rope is not None:
+                path["rope"] = rope
             x = F.encoder_layer(x, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
                                 layer.norm1.weight, layer.norm1.bias, layer.linear1.weight, layer.linear1.bias,
                                 layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias,
@@ -275,6 +320,8 @@ class TransformerSeqEncoder(nn.Module):
             kw = dict(activation=self.activation, layer_scale=scales[l] if scales is not None else None)
             if hasattr(self, "qk_norm"):
                 kw["qk_norm"], kw["qk_norm_eps"] = self.qk_norm[l], self.qk_norm_eps
+            if getattr(self, "rope", None) is not None:
+                kw["rope"] = self.rope
             if probe:
                 out = F.pre_norm_layer_probe(s, n, *w, self.n_head, layer.norm2.eps, **kw)
             else:
@@ -423,6 +470,7 @@ def _model_mask(attn_mask, n_patches, pool):
 
 
 REL_POS_KINDS = ("curve", "image")
+ROPE_KINDS = ("curve", "image")
 
 
 def _attach_rel_pos_bias(model, kind, window, init_std, attn_mask, pool):
@@ -454,6 +502,16 @@ def _attach_rel_pos_bias(model, kind, window, init_std, attn_mask, pool):
     model.encoder.attach_rel_pos_bias(ops.AttentionBiasIndex(index, T), float(init_std))
 
 
+def _attach_rope(model, kind, base):
+    """The models' `rope` keyword, on request only and constructed LAST, after `ta`, `pos_embed`, `cls_token` and the relative
+    position bias: no parameter, no draw, no state_dict key (TransformerSeqEncoder.attach_rope)."""
+    if kind is None or kind is False:
+        if base is not None:
+            raise ValueError("rope_base needs rope='curve' or 'image'")
+        return
+    model.encoder.attach_rope(kind, base)
+
+
 def rel_pos_cell(patch_embed):
     """The pixel pitch image offsets are counted in: the square root of the pixels per token."""
     levels = getattr(patch_embed, "levels", None)               # hierarchical: level 0 is the sequence (analysis.token_positions)
@@ -476,7 +534,8 @@ class VisionTransformer(nn.Module):
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, attn_mask=None,
                  pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0, rel_pos_bias=None, rel_pos_window=None,
-                 rel_pos_init_std=0.0, norm_first=False, activation="relu", layer_scale=None, qk_norm=False, qk_norm_eps=1e-6):
+                 rel_pos_init_std=0.0, norm_first=False, activation="relu", layer_scale=None, qk_norm=False, qk_norm_eps=1e-6,
+                 rope=None, rope_base=None):
         """rel_pos_bias: None (the model as it is without the keyword), "curve" or "image": every encoder layer adds a learned
         relative position bias per head to its attention scores, softmax(q k^T / sqrt(hd) + b_h[offset(i, j)]), the offset taken
         along the token sequence (j - i) or in the image (the displacement of the token centres in cells of sqrt(pixels per
@@ -490,6 +549,10 @@ class VisionTransformer(nn.Module):
         (TransformerSeqEncoder: the DeiT / timm block; `encoder.transformer.norm`, `encoder.layer_scale.<l>` [2, D]).
         qk_norm, qk_norm_eps: QK-norm, a LayerNorm over the head dim on the queries and keys of every head
         (TransformerSeqEncoder; `encoder.qk_norm.<l>` [4, head_dim]).
+        rope, rope_base: None (the model as it is without the keyword), "curve" or "image": rotary position embedding on the
+        queries and keys of every encoder layer, the angle taken from the index along the token sequence or from the token's
+        centre in the image (TransformerSeqEncoder.attach_rope); rope_base None = the kind's default (10000 / 100).  Built last;
+        a fixed table in a non-persistent buffer, so state_dict is unchanged by it; with pool="cls" the CLS token is not rotated.
         attn_mask: None, or a mask for every encoder layer (ops.as_attention_mask's forms; sfcvit.masks builds windows).
         Held outside state_dict: checkpoint keys are the reference's with or without it.
         pos_embed: None / False (the reference as shipped), "learned" (vit.py:360-361: a Parameter [1, N, D] = randn *
@@ -515,6 +578,7 @@ class VisionTransformer(nn.Module):
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)
         _attach_rel_pos_bias(self, rel_pos_bias, rel_pos_window, rel_pos_init_std, self.attn_mask, pool)
+        _attach_rope(self, rope, rope_base)
 
     def forward(self, x, mix=None):
         """mix: a sfcvit.training.BatchMix applied to the image batch by the tokenizer, or None."""
@@ -535,8 +599,9 @@ class VisionTransformer1D(nn.Module):
     def __init__(self, patch_embed: BasePatchEmbedding, embed_dim=128, depth=6, n_heads=4, mlp_dim=256,
                  num_classes=10, dropout_p=0.1, head_dropout_p=0.5, token_aggregator=False, token_mix=False, attn_mask=None,
                  pos_embed=None, pos_embed_std=1.0, pool=None, drop_path_rate=0.0, rel_pos_bias=None, rel_pos_window=None,
-                 rel_pos_init_std=0.0, norm_first=False, activation="relu", layer_scale=None, qk_norm=False, qk_norm_eps=1e-6):
-        """attn_mask, pos_embed, pos_embed_std, pool, drop_path_rate, rel_pos_bias, rel_pos_window, rel_pos_init_std, norm_first, activation, layer_scale, qk_norm, qk_norm_eps: as in VisionTransformer (the table is added directly after the tokenizer
+                 rel_pos_init_std=0.0, norm_first=False, activation="relu", layer_scale=None, qk_norm=False, qk_norm_eps=1e-6,
+                 rope=None, rope_base=None):
+        """attn_mask, pos_embed, pos_embed_std, pool, drop_path_rate, rel_pos_bias, rel_pos_window, rel_pos_init_std, norm_first, activation, layer_scale, qk_norm, qk_norm_eps, rope, rope_base: as in VisionTransformer (the table is added directly after the tokenizer
         and, if present, `ta`: before `mlp_mixer`; with pool="cls" the token joins after `mlp_mixer`, whose weights stay sized
         for the N patch tokens)."""
         super().__init__()
@@ -555,6 +620,7 @@ class VisionTransformer1D(nn.Module):
         _attach_aggregator(self, token_aggregator, embed_dim)
         _attach_pos_embed(self, pos_embed, pos_embed_std)
         _attach_rel_pos_bias(self, rel_pos_bias, rel_pos_window, rel_pos_init_std, self.attn_mask, pool)
+        _attach_rope(self, rope, rope_base)
 
     def forward(self, x, mix=None):
         """mix: a sfcvit.training.BatchMix applied to the image batch by the tokenizer, or None."""

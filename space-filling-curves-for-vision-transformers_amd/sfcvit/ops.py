@@ -598,6 +598,105 @@ def qk_norm_bwd(dqkv, raw, params, n_heads, head_dim, eps=1e-6, colsum=None, gra
 
 
 # ----------------------------------------------------------------------------
+# RoPE: rotary position embedding on the q and k thirds of a packed projection, in place
+# ----------------------------------------------------------------------------
+class RopeTable:
+    """The (cos, sin) table of a rotary position embedding: fp32 [N, head_dim / 2, 2] (CPU; row n, pair p holds (c, s);
+    sfcvit.rope builds them), shared by the heads, the batch, and q and k.  Validated once on the host -- shape, dtype, every
+    entry finite -- and uploaded once per device, where the copy stays put (graph capture replays it).  Not a parameter: it
+    receives no gradient and enters no state_dict."""
+
+    def __init__(self, table):
+        if not isinstance(table, torch.Tensor) or table.is_cuda or table.dtype != torch.float32 or table.dim() != 3 \
+                or table.shape[2] != 2 or table.shape[0] < 1 or table.shape[1] < 1:
+            raise ValueError("RopeTable: a CPU fp32 [N, head_dim / 2, 2] tensor of (cos, sin) pairs is expected "
+                             "(sfcvit.rope builds them)")
+        if not bool(torch.isfinite(table).all()):
+            raise ValueError("RopeTable: the table holds a non-finite entry")
+        self.table = table.detach().contiguous().clone()
+        self.n_tokens, self.head_dim = int(table.shape[0]), 2 * int(table.shape[1])
+        self._dev = {}
+
+    def on(self, device):
+        """The table on `device`, uploaded at the first request."""
+        key = torch.device(device)
+        if key.type == "cuda" and key.index is None:
+            key = torch.device("cuda", torch.cuda.current_device())
+        if key not in self._dev:
+            self._dev[key] = self.table.to(key)
+        return self._dev[key]
+
+    def __repr__(self):
+        return f"RopeTable(N={self.n_tokens}, head_dim={self.head_dim})"
+
+
+def rope_plan(B, N, n_heads, hp):
+    """The launch geometry of both RoPE kernels for B images of N tokens: dict(tokens_per_wg, batch_per_wg, rows_per_wg,
+    slot_groups, blocks, vpl).  No GPU call."""
+    out = (ctypes.c_int32 * 5)()
+    check(lib.sfcvit_rope_plan(B, N, n_heads, hp, out), "sfcvit_rope_plan")
+    return dict(tokens_per_wg=out[0], batch_per_wg=out[1], rows_per_wg=out[0] * out[1], slot_groups=out[2], blocks=out[3], vpl=out[4])
+
+
+def _rope_args(what, qkv, table, n_heads):
+    """-> (device table, B, N, hd, hp) of a packed buffer [M, 3 * H * hp] or [B, N, 3 * H * hp] and a RopeTable, checked."""
+    if qkv.dim() not in (2, 3):
+        raise ValueError(f"{what}: [M, 3 * H * hp] or [B, N, 3 * H * hp] expected, got shape {tuple(qkv.shape)}")
+    _need(qkv, _BF16, f"{what} qkv")
+    if not isinstance(table, RopeTable):
+        raise ValueError(f"{what}: table must be an ops.RopeTable")
+    D3 = qkv.shape[-1]
+    if n_heads <= 0 or D3 % (3 * n_heads):
+        raise ValueError(f"{what}: packed width {D3} is not 3 * n_heads * head_dim for n_heads = {n_heads}")
+    hp, M, N = D3 // (3 * n_heads), qkv.numel() // D3, table.n_tokens
+    if qkv.dim() == 3 and qkv.shape[1] != N:
+        raise ValueError(f"{what}: table for {N} tokens on a sequence of {qkv.shape[1]}")
+    if M % N:
+        raise ValueError(f"{what}: {M} rows are no whole number of sequences of the table's {N} tokens")
+    if table.head_dim > hp:
+        raise ValueError(f"{what}: table for head dim {table.head_dim} on a packed head width of {hp}")
+    return table.on(qkv.device), M // N, N, table.head_dim, hp
+
+
+def rope_fwd(qkv, table, n_heads):
+    """Rotates the channel pairs (2 p, 2 p + 1) of every query and key head row of qkv [.., 3 * H * hp] bf16 IN PLACE by the
+    table's (c, s) of the row's token, y0 = x0 c - x1 s, y1 = x0 s + x1 c (columns head_dim .. hp - 1, the zero padding of a head
+    dim the kernels do not have, become +0; v is untouched) -> qkv.  table: an ops.RopeTable for N tokens; row m uses its row
+    m mod N.  Nothing is kept for the backward."""
+    t, B, N, hd, hp = _rope_args("rope_fwd", qkv, table, n_heads)
+    check(lib.sfcvit_rope_fwd(_p(qkv), _p(t), B, N, n_heads, hd, hp, _stream()), "sfcvit_rope_fwd")
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append(last_rowwise_kernel())
+    return qkv
+
+
+def rope_bwd(dqkv, table, n_heads, colsum=None, vsum=None):
+    """The backward of rope_fwd, the transposed rotation, IN PLACE on the q and k thirds of dqkv as the attention backward left
+    them (v untouched, padded columns +0) -> (dqkv, colsum or None).  colsum: None -- one launch, no workspace; True -> fp32
+    [2 * H * hp] (new), the column sums of the new dq | dk; or a contiguous fp32 / bf16 tensor to write into.  With vsum (fp32
+    [H * hp], the v third of attention_bwd's colsum) the colsum tensor is [3 * H * hp] and its last third receives vsum: the
+    whole in_proj bias gradient in one place.  The reduction runs now, in a fixed order (never queued)."""
+    t, B, N, hd, hp = _rope_args("rope_bwd", dqkv, table, n_heads)
+    Da = n_heads * hp
+    width = 3 * Da if vsum is not None else 2 * Da
+    if vsum is not None:
+        _need(vsum, torch.float32, "rope_bwd vsum", 1)
+        if vsum.numel() != Da or colsum is None or colsum is False:
+            raise ValueError(f"rope_bwd: vsum must be fp32 [H * hp] = [{Da}] and needs colsum")
+    cs = ws = None
+    if colsum is not None and colsum is not False:
+        cs = torch.empty(width, device=dqkv.device, dtype=torch.float32) if colsum is True else colsum
+        if not cs.is_cuda or cs.numel() != width or not cs.is_contiguous() or cs.dtype not in (torch.float32, _BF16):
+            raise ValueError(f"rope_bwd colsum: contiguous fp32 or bf16 [{width}] expected")
+        ws = torch.empty(lib.sfcvit_rope_bwd_ws(B, N, n_heads, hp), device=dqkv.device, dtype=torch.uint8)
+    check(lib.sfcvit_rope_bwd(_p(dqkv), _p(t), _p(cs), int(cs is not None and cs.dtype == _BF16), _p(vsum), _p(ws), B, N, n_heads,
+                              hd, hp, _stream()), "sfcvit_rope_bwd")
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append(last_rowwise_kernel())
+    return dqkv, cs
+
+
+# ----------------------------------------------------------------------------
 # attention
 # ----------------------------------------------------------------------------
 SUPPORTED_HEAD_DIMS = (64, 128, 192, 256)
