@@ -122,11 +122,14 @@ def build(design, B, H, N, hd, scale=None, tag=0):
     return c
 
 
-def _off_mass(qs, k, sel, gain, scale):
-    """Largest total softmax probability outside the selected keys at this gain, fp64."""
+def _off_mass(qs, k, sel, gain, scale, term=None):
+    """Largest total softmax probability outside the selected keys at this gain, fp64.  term: an additive [items, N, N] term of
+    the scores (tests/attn_masked_exact_ref.py), finite or -inf."""
     worst = 0.0
     for lo in range(0, qs.shape[0], CHUNK):
         s = gain * scale * (qs[lo:lo + CHUNK] @ k[lo:lo + CHUNK].transpose(1, 2))
+        if term is not None:
+            s = s + term[lo:lo + CHUNK]
         sl = sel[lo:lo + CHUNK]
         top = torch.where(sl, s, torch.full_like(s, -math.inf)).amax(-1, keepdim=True)
         assert bool((torch.where(sl, s, top) == top).all()), "the selected keys of a row do not tie"
@@ -159,6 +162,9 @@ def ideal_p(c, rounded=True):
 
 def expect(c, keep=None, p=0.0, rounded=True):
     """fp64 expectations from the ideal probabilities.  keep: bool [items, N, N], the keys dropout keeps (p > 0).
+    c["term"] (optional, [items, N, N], finite or -inf; tests/attn_masked_exact_ref.py): an additive term of the scores -- it moves
+    lse and the leak, the ideal probabilities come from c["sel"] as ever; with c["table_terms"] the un-scaled P (keep dP - delta)
+    of every pair is kept as well (g, and g_leak: what the off-selection probability can add to it).
     -> out, lse, delta, dq, dk, dv [items, N, hd] (lse, delta [items, N]); ds (what the kernels round to bf16, scale included),
     pm (P keep / (1 - p)); terms_dq, terms_dk, terms_dv (sum of |terms| of each output); leak (per output, see the docstring)."""
     q, k, v, do, scale = c["q"], c["k"], c["v"], c["do"], c["scale"]
@@ -172,6 +178,8 @@ def expect(c, keep=None, p=0.0, rounded=True):
         sl = slice(lo, lo + CHUNK)
         kk = keep[sl].to(F64) * ks if keep is not None else torch.ones(1, dtype=F64)
         s = scale * (q[sl] @ k[sl].transpose(1, 2))
+        if c.get("term") is not None:
+            s = s + c["term"][sl]
         pm = P[sl] * kk
         # the forward sums the un-normalised exp (1 on the ideal keys) times keep / (1 - p), then divides by l = their number
         unn = (c["sel"][sl].to(F64) if c["sel"] is not None else torch.ones(N, N, dtype=F64).expand(s.shape)) * kk
@@ -205,6 +213,9 @@ def expect(c, keep=None, p=0.0, rounded=True):
             for name, val in (("out", l_out), ("dq", e @ k[sl].abs()), ("dk", e.transpose(1, 2) @ q[sl].abs()),
                               ("dv", off.transpose(1, 2) @ do[sl].abs())):
                 leak[name] = max(leak[name], 2.0 * float(val.max()))            # x 2: the bf16 and fp32 roundings on the way
+            if c.get("table_terms"):
+                r.setdefault("g", torch.empty(I, N, N, dtype=F64))[sl] = ds0
+                r.setdefault("g_leak", torch.empty(I, N, N, dtype=F64))[sl] = 2.0 * e / scale
         else:
             r["sums_exact"] &= _sum_exact(unn, v[sl]) and _sum_exact(do[sl], v[sl].transpose(1, 2)) and (not rounded or _sum_exact(pm.transpose(1, 2), do[sl]))
             r["sums_exact"] &= _sum_exact(do[sl], rb(out).transpose(1, 2))
@@ -232,6 +243,8 @@ def truth(c, keep=None, p=0.0):
     """Plain fp64 softmax attention and its autograd gradient, with the keep mask applied to the probabilities."""
     q, k, v = (c[n].clone().requires_grad_(True) for n in "qkv")
     s = c["scale"] * (q @ k.transpose(1, 2))
+    if c.get("term") is not None:
+        s = s + c["term"]
     pr = torch.softmax(s, -1)
     if keep is not None:
         pr = pr * keep.to(F64) / (1.0 - p)

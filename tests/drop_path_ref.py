@@ -32,6 +32,18 @@ def keep_flags(seed, rate, B):
     return h >= (thresh << np.uint64(16))
 
 
+def dropout_keep(seed, p, rows, cols):
+    """bool [rows, cols]: the whole dropout mask of `seed` at rate p for rows < 2^32, as csrc/device_common.h states it:
+    keep(row, col) = ((drop_row_key(seed, row) ^ col * G) * C mod 2^32) >= (thresh << 16), thresh = uint32(p * 65536.f + 0.5f).
+    `rows` is a count (rows 0 .. rows - 1) or an array of row numbers."""
+    thresh = np.uint64(int(np.float32(p) * np.float32(65536.0) + np.float32(0.5)))
+    rows = np.arange(rows, dtype=np.uint64) if np.isscalar(rows) else np.asarray(rows, dtype=np.uint64)
+    assert rows.size == 0 or int(rows.max()) < 2 ** 32
+    col_g = (np.arange(cols, dtype=np.uint64) * DROP_G) & M32
+    h = ((row_key(seed, rows)[:, None] ^ col_g[None, :]) * DROP_C) & M32
+    return h >= (thresh << np.uint64(16))
+
+
 def layer_rates(rate, L):
     return [rate * l / (L - 1) if L > 1 else rate for l in range(L)]
 
